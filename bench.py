@@ -7,7 +7,8 @@
 
 One step = zero_grad -> forward -> cross entropy -> backward -> (bucketed RCCL all-reduce,
 overlapped) -> Adam, on synthetic token ids resident in HBM, random-init weights, fp32.
-Per-GPU batch is fixed (weak scaling).  Prints ONE compact JSON line (< 4 KB) on rank 0 and writes the
+Per-GPU batch is fixed (weak scaling); `--dump-outputs DIR` saves what the last timed step computed (dump_outputs).
+Prints ONE compact JSON line (< 4 KB) on rank 0 and writes the
 full record (per-family GEMM tables, the other configs, memory) to bench_detail.json, which the line names.  The launcher only has to
 provide RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT; this script itself uses no
 PyTorch -- device memory, streams, events and RCCL all come from libpdnhip.so.
@@ -542,6 +543,33 @@ def write_detail(full):
     return os.path.relpath(written, ROOT) if written else None
 
 
+DUMP_LIMIT = 64 * 10 ** 6                                   # bytes --dump-outputs may write, all files together
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, loss, params):
+    """`--dump-outputs DIR`: what the last timed step handed its caller -- the loss, every gradient the backward pass left
+    and every parameter after the Adam update -- as float32 DIR/<name>.npy, so that two builds can be compared output for
+    output on the same seeded inputs.  A tensor that does not fit the byte budget is written as a fixed sample of its
+    flattened entries: the indices are drawn without replacement (sorted) from default_rng(DUMP_SEED), so they depend on the
+    tensor's size only.  Small tensors are written whole; the largest share what is left equally."""
+    fetch = {"loss": lambda: np.float32(loss)}
+    sizes = {"loss": 1}
+    for n, p in params:
+        fetch[f"grad.{n}"], fetch[f"param.{n}"] = p.grad.get, p.data.get
+        sizes[f"grad.{n}"] = sizes[f"param.{n}"] = int(p.size)
+    budget, cap = (DUMP_LIMIT - 256 * len(sizes)) // 4, {}          # (256 bytes: at least one .npy header)
+    for i, k in enumerate(sorted(sizes, key=sizes.get)):    # ascending: each takes min(size, a fair share of the rest)
+        cap[k] = min(sizes[k], budget // (len(sizes) - i))
+        budget -= cap[k]
+    os.makedirs(out_dir, exist_ok=True)
+    for k in fetch:
+        a = np.asarray(fetch[k](), dtype=np.float32)
+        if cap[k] < sizes[k]:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(DUMP_SEED).choice(sizes[k], cap[k], replace=False))]
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def _pick(d, keys):
     return None if d is None else {k: d.get(k) for k in keys if k in d}
 
@@ -622,7 +650,14 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short runs of BASELINE configs 2 / 3 (MLP, LeNet), the GRU and greedy decode that the "
                          "default single-GPU line carries in `other_configs`")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one computed (loss, gradients, updated parameters) "
+                         "as DIR/<name>.npy, at most 64 MB in all (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != "llama":
+        ap.error("--dump-outputs is implemented for the llama config only")
 
     if args.config != "llama":
         import bench_other
@@ -804,6 +839,8 @@ def main():
                 "traffic_stale": traffic.get("_stale")}
         roof["hbm_bound_kernels"] = hbm_kernels(adam_events, traffic,
                                                 sum(int(p.size) for p in model.parameters())) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses[-1], list(model.named_parameters()))
     per_rank = [B * args.steps / dt]
     if world > 1:
         mine = np.zeros((world,), np.float32)

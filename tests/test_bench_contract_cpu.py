@@ -159,6 +159,54 @@ def test_whole_bench_main_prints_one_compact_line_and_a_detail_file(emulated_hip
     assert d["other_configs"]["lenet_b4096"]["roofline"]
 
 
+def test_dump_outputs_writes_the_last_timed_step(emulated_hip, monkeypatch, tmp_path, capsys):
+    """`bench.py --dump-outputs DIR` on the emulated ABI (model shrunk as above): the loss, every gradient and every updated
+    parameter of the last timed step as float32 .npy files; the same arguments give the same files; under a byte budget
+    too small for everything, the largest tensors are written as the fixed seeded sample of their entries and the rest
+    whole, within the budget."""
+    import json
+    import numpy as np
+    import bench
+    for k, v in dict(V=192, D=96, H=2, F_=128, L=32, LAYERS=2).items():
+        monkeypatch.setattr(bench, k, v)
+    monkeypatch.setenv("PDN_BENCH_DETAIL", str(tmp_path / "detail.json"))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+
+    def run(name):
+        out = tmp_path / name
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1", "--batch", "2", "--no-parity-gate",
+                                          "--no-cpu-baseline", "--no-other-configs", "--dump-outputs", str(out)])
+        bench.main()
+        line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        return line, {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+
+    line, a = run("a")
+    _, b = run("b")
+    names = {"loss"} | {f"{kind}.{n}" for n in ("lm_head.weight", "tok_embedding.weight", "norm.weight",
+                                                "layers.1.ffn.down.weight") for kind in ("grad", "param")}
+    assert names <= set(a) and set(a) == set(b)
+    assert all(x.dtype == np.float32 for x in a.values())
+    assert float(a["loss"]) == line["final_loss"]
+    assert a["param.tok_embedding.weight"].shape == (192, 96)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+    whole = sum(x.nbytes for x in a.values())
+    monkeypatch.setattr(bench, "DUMP_LIMIT", whole // 2)
+    _, c = run("c")
+    assert sum(os.path.getsize(tmp_path / "c" / f"{k}.npy") for k in c) <= whole // 2
+    sampled = [k for k in c if c[k].size < a[k].size]
+    assert sampled and all(a[k].size >= max(a[j].size for j in c if j not in sampled) for k in sampled)
+    for k in c:
+        if k in sampled:
+            idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(a[k].size, c[k].size, replace=False))
+            assert np.array_equal(c[k], a[k].reshape(-1)[idx]), k
+        else:
+            assert np.array_equal(c[k], a[k]), k
+
+
 def test_gpus_n_beyond_the_visible_devices_fails_fast():
     """`bench.py --gpus 8` on a box with fewer GPUs: refused before any rank is started (no RCCL peer left hanging)."""
     import subprocess
