@@ -164,7 +164,7 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
                               int64_t ldx, void* stream);
 /* Launch counters per kernel: which kernel the entry points really launched since the last reset -- bench.py's parity
  * gates and the tests assert on them (a dispatch that silently falls back to a slower kernel must not stay green).
- * Copies min(n, 24) counters to `out` (may be null), clears all of them when `reset` != 0.  Slots:
+ * Copies min(n, 28) counters to `out` (may be null), clears all of them when `reset` != 0.  Slots:
  *   0 gemm_rowres_kernel (chunk kernel, any)      1 gemm_rowtile_kernel plain        2 ... + SwiGLU forward (gate | up)
  *   3 ... + SwiGLU backward (dh)                  4 ... + RoPE (q | k | v)           5 ... + row maxima (lm_head forward)
  *   6 gemm_rowres_kernel with a fused epilogue    7 attention_p forward (persistent) 8 attention_p backward (dQ + dK/dV)
@@ -173,7 +173,9 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  14 gemm_outres_kernel plain                   15 gemm_outres_tn_kernel plain
  *  16 pdn_linear_relu_fwd_f32                    17 pdn_linear_dx_masked_f32        18 cross entropy over <= 32 classes
  *  19 pdn_gateup_swiglu_tiled_fwd_f32            20 pdn_swiglu_bwd_tiled_f32
- *  21 conv_quad_fwd_kernel (csrc/conv_quad.hip)  22 conv_quad_dgrad_kernel          23 conv_quad_wgrad_kernel */
+ *  21 conv_quad_fwd_kernel (csrc/conv_quad.hip)  22 conv_quad_dgrad_kernel          23 conv_quad_wgrad_kernel
+ *  24 pdn_patch_embed_fwd_f32 (csrc/patch_embed.hip)                                25 pdn_patch_embed_bwd_f32
+ *  26 pdn_l2norm_rows_fwd_f32                     27 pdn_l2norm_rows_bwd_f32 */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -339,6 +341,24 @@ int pdn_layernorm_bwd_f32(const float* x, const float* w, const float* mean, con
                           int cols, void* workspace, int64_t workspace_bytes, void* stream);
 int64_t pdn_layernorm_bwd_workspace_bytes(int64_t rows, int cols);
 int pdn_gated_sigmoid_fwd_f32(const float* x, float* y, float alpha, int64_t n, void* stream);
+/* ---- CLIP's patch embedding (csrc/patch_embed.hip; llm/clip/model.py:17-32 patch_project + :129-130 concat with the
+ * class embedding + position embedding): out (N, P+1, D), P = (H/p)(W/p), from img (N, C, H, W) NCHW, kernel (D, C, p, p),
+ * cls (D), pos (P+1, D):  out[n][0] = cls + pos[0];  out[n][1+g] = sum_k patch(n, g)[k] kernel[d][k] + pos[1+g], k = (c, py, px)
+ * in the reference's order.  fp32-MFMA GEMM whose A tile is gathered straight from the image (no transposed copy).
+ * bwd: dkernel (D x C p p) = dOut[:, 1:]^T @ patches (the patches gathered from the image again), dcls = sum_n dOut[n][0],
+ * dpos = sum_n dOut[n]; each output nullable, `acc_*` selects += vs = (straight into the leaves' gradient buffers).
+ * `pdn_patch_embed_supported` is 1 for the shapes both take (p % 4 == 0, H % p == W % p == 0, D % 4 == 0); img, kernel and
+ * dout 16-byte aligned, everything contiguous.  Others return PDN_EUNSUPPORTED. */
+int pdn_patch_embed_supported(int N, int C, int H, int W, int p, int D);
+int pdn_patch_embed_fwd_f32(const float* img, const float* kernel, const float* cls, const float* pos, float* out, int N,
+                            int C, int H, int W, int p, int D, void* stream);
+int pdn_patch_embed_bwd_f32(const float* img, const float* dout, float* dkernel, int acc_kernel, float* dcls, int acc_cls,
+                            float* dpos, int acc_pos, int N, int C, int H, int W, int p, int D, void* stream);
+/* ---- L2 row normalisation of CLIP's contrastive head (llm/clip/model.py:198-203): y = x / n, n = sqrt(sum x^2 + 1e-12)
+ * per row (rows, cols contiguous), n (rows,) saved; bwd dx = (dy - y (y . dy)) / n.  One wave per row. */
+int pdn_l2norm_rows_fwd_f32(const float* x, float* y, float* norm, int64_t rows, int cols, void* stream);
+int pdn_l2norm_rows_bwd_f32(const float* y, const float* norm, const float* dy, float* dx, int64_t rows, int cols,
+                            void* stream);
 int pdn_gated_sigmoid_bwd_f32(const float* x, const float* dy, float* dx, float alpha, int64_t n, void* stream);
 
 /* ---- SiLU / SwiGLU (nn/functional.py:39-40; llm/llama/model.py:56-58):

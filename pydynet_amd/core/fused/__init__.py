@@ -20,6 +20,8 @@ expression.  Reference chains replaced:
     linear_cross_entropy  llm/llama/model.py:179 + :239-249 (lm_head -> reshape -> cross entropy as one node); the same
                                                     three calls written with plain operators are taken over as they are
                                                     built (chain.py: loss_chain)
+    patch_embed     llm/clip/model.py:17-32, 129-130 (6-D transposed copy, GEMM, concat with the class token, + positions)
+    clip_logits     llm/clip/model.py:195-205       (two L2 normalisations, transpose, scale, product)
 """
 from ._common import (_hip, _L, _contig, hip_f32, _require_f32, _foldable, two_stream, _beside, _is_leaf_f32, _Deferred, _pack_columns, _dx_of_shared_input, _gemm_raw)
 from .dense import linear, linear_relu, embedding, cross_entropy, linear_cross_entropy
@@ -29,6 +31,7 @@ from .attn import _attn_layout, _attn_mask_args, _attn_kernel, attention, qkv_at
 from .ffn import gate_up_swiglu, ffn_swiglu
 from .conv import relu, conv2d, conv2d_relu_pool, pool2d
 from .recurrent import _cell_grads, rnn_cell, lstm_cell, gru_cell, gru_sequence
+from .vision import patch_project, patch_embed, clip_logits
 from . import chain as _chain_mod
 from .chain import attn_link
 from .. import tensor as _tensor

@@ -42,7 +42,7 @@ extern "C" int pdn_stream_synchronize(void* stream) {
   return PDN_OK;
 }
 
-// Launch counters per kernel (slots: PDN_CNT_* in common.h, listed in include/pdn_hip.h).  Copies min(n, 16) counters
+// Launch counters per kernel (slots: PDN_CNT_* in common.h, listed in include/pdn_hip.h).  Copies min(n, PDN_CNT_SLOTS) counters
 // to `out` (may be null) and clears them when `reset` is non-zero.
 static std::atomic<int64_t> g_counters[PDN_CNT_SLOTS];
 void pdn_count(int slot) {

@@ -45,7 +45,11 @@ enum {
   PDN_CNT_CONV_QUAD_FWD = 21,     // conv_quad_fwd_kernel (conv + relu + max_pool of the LeNet shapes, csrc/conv_quad.hip)
   PDN_CNT_CONV_QUAD_DGRAD = 22,   // conv_quad_dgrad_kernel (col2im-style data gradient)
   PDN_CNT_CONV_QUAD_WGRAD = 23,   // conv_quad_wgrad_kernel (shifted image copies)
-  PDN_CNT_SLOTS = 24
+  PDN_CNT_PATCH_EMBED_FWD = 24,   // pe_fwd_kernel (csrc/patch_embed.hip: CLIP patch projection + class row + positions)
+  PDN_CNT_PATCH_EMBED_BWD = 25,   // pdn_patch_embed_bwd_f32 (kernel-gradient GEMM and / or class / position column sums)
+  PDN_CNT_L2NORM_FWD = 26,        // l2norm_fwd_kernel (CLIP's contrastive head)
+  PDN_CNT_L2NORM_BWD = 27,        // l2norm_bwd_kernel
+  PDN_CNT_SLOTS = 28
 };
 void pdn_count(int slot);
 

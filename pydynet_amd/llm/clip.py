@@ -1,4 +1,4 @@
-"""CLIP transformer blocks (llm/clip/model.py:8-113 of the reference) on this package's fused nodes.
+"""CLIP (llm/clip/model.py of the reference) on this package's fused nodes: the transformer blocks and the whole model.
 
 Same class names, constructor signatures and registered parameter names as the reference
 (`mha.QKV.weight`, `mha.O.bias`, `layer_norm1.scale`, `mlp.fc1.weight`, ...), so weights map by name.
@@ -8,14 +8,21 @@ What differs is the node count: the reference's block is ~45 generic tape nodes;
                       causal mask tensor), one biased output GEMM
   CLIPLayerNorm       one last-axis LayerNorm node (9 generic nodes in the reference)
   MLP                 GEMM, one `x * sigmoid(1.702 x)` node, GEMM
-The weights of the full CLIP model (patch projection, encoders, tokenizer, image preprocessing) are not in
-the reference tree (downloaded at run time), so the encoders themselves stay out of scope; these blocks
-are what its attention / normalisation / MLP hot path is made of.
+  ImageEncoder        ONE patch-embedding node (patch projection + class token + position embedding, fused.patch_embed)
+                      instead of a transposed image copy and four generic nodes; post_norm on the class rows only
+  TextEncoder         the end-of-text rows gathered BEFORE post_norm (LayerNorm is per row: the same values, 77x fewer
+                      rows normalised); their positions found on the host when the token ids are host data
+  CLIP                the contrastive head as ONE node (fused.clip_logits: two L2 normalisations and the product)
+The one deliberate extension: the reference's ImageEncoder concatenates a (1, 1, D) class token to (N, P, D) patches and
+so only takes N = 1; here the class token is broadcast over the batch, row n being the single-image result for image n.
+Weights: `pydynet_amd.llm.clip_io.load_model` maps an OpenAI ViT-B/32 state dict (any key -> array mapping) by the
+reference's keys.  The tokenizer and the image preprocessing stay out of scope.
 """
 import numpy as np
 
 from .. import nn
 from ..core import Tensor, fused, function as fn
+from ..core.fused import patch_project  # noqa: F401  (llm/clip/model.py:17-32, on the generic operators)
 
 
 def build_attention_mask(context_length: int):
@@ -83,3 +90,97 @@ class Transformer(nn.Module):
     def forward(self, x, mask):
         x = x + self.mha(self.layer_norm1(x), mask)
         return x + self.mlp(self.layer_norm2(x))
+
+
+class ImageEncoder(nn.Module):
+    def __init__(self, n_dim, n_head, mlp_dim, kernel_size, n_layer, final_dim):
+        super().__init__()
+        self.kernel = nn.Parameter(Tensor(np.random.randn(n_dim, 3, kernel_size, kernel_size), dtype=np.float32))
+        self.pre_norm = CLIPLayerNorm((n_dim,), 1e-5, dtype=np.float32)
+        self.transformers = nn.ModuleList([Transformer(n_dim, n_head, mlp_dim) for _ in range(n_layer)])
+        self.post_norm = CLIPLayerNorm((n_dim,), 1e-5, dtype=np.float32)
+        self.proj = nn.Linear(n_dim, final_dim, bias=False, dtype=np.float32)
+
+    def forward(self, x, class_emb, position_emb):
+        x = fused.patch_embed(x, self.kernel, class_emb, position_emb)        # (N, P + 1, D)
+        x = self.pre_norm(x)
+        for block in self.transformers:
+            x = block(x, None)
+        return self.proj(self.post_norm(x[:, 0]))
+
+
+class TextEncoder(nn.Module):
+    def __init__(self, n_dim, n_head, mlp_dim, n_layer, final_dim, vocab_size):
+        super().__init__()
+        self.token_embed = nn.Embedding(vocab_size, n_dim, dtype=np.float32)
+        self.transformers = nn.ModuleList([Transformer(n_dim, n_head, mlp_dim) for _ in range(n_layer)])
+        self.post_norm = CLIPLayerNorm((n_dim,), 1e-5, dtype=np.float32)
+        self.proj = nn.Linear(n_dim, final_dim, bias=False, dtype=np.float32)
+        self._masks = {}
+
+    def forward(self, idx, position_emb):
+        """idx (B, L): token ids as a NumPy array or a Tensor on any device; the end-of-text token is the largest id."""
+        ids = idx.data if isinstance(idx, Tensor) else np.asarray(idx)
+        x = self.token_embed(idx) + position_emb
+        B, L, D = x.shape
+        mask = self._masks.get(L)
+        if mask is None:
+            mask = self._masks[L] = build_attention_mask(L)
+        for block in self.transformers:
+            x = block(x, mask)
+        if isinstance(ids, np.ndarray):                  # host ids: the rows are known without touching the device
+            rows = np.arange(B) * L + np.argmax(ids, axis=-1)
+        else:                                            # device ids: found and used on the device (the library's
+            # argmax reduces floating-point arrays; token ids < 2^24 are exact in float32)
+            rows = ids.astype(np.float32).argmax(-1) + Tensor(np.arange(B) * L, dtype=np.int64, device=x.device).data
+        return self.proj(self.post_norm(x.reshape(B * L, D)[rows]))
+
+
+class CLIP(nn.Module):
+    def __init__(self, image_dim: int = 768, image_heads: int = 12, image_mlp_dim: int = 3072, image_patch: int = 32,
+                 image_layers: int = 12, text_dim: int = 512, text_heads: int = 8, text_mlp_dim: int = 2048,
+                 text_layers: int = 12, final_dim: int = 512, vocab_size: int = 49408, vision_tokens: int = 50,
+                 text_tokens: int = 77):
+        super().__init__()
+        self.class_embed = nn.Parameter(Tensor(np.random.randn(1, 1, image_dim), dtype=np.float32))
+        self.v_pos_emb = nn.Parameter(Tensor(np.random.randn(vision_tokens, image_dim), dtype=np.float32))
+        self.t_pos_emb = nn.Parameter(Tensor(np.random.randn(text_tokens, text_dim), dtype=np.float32))
+        self.image_encoder = ImageEncoder(image_dim, image_heads, image_mlp_dim, image_patch, image_layers, final_dim)
+        self.text_encoder = TextEncoder(text_dim, text_heads, text_mlp_dim, text_layers, final_dim, vocab_size)
+        self.scale = 1                  # a Python number, or (load_model) a one-element Tensor
+
+    def forward(self, img, idx):
+        img_feature = self.image_encoder(img, self.class_embed, self.v_pos_emb)
+        txt_feature = self.text_encoder(idx, self.t_pos_emb)
+        scale = self.scale
+        if isinstance(scale, Tensor) and scale.device != img_feature.device:
+            scale = self.scale = scale.to(img_feature.device)      # moved once, not uploaded every step
+        return fused.clip_logits(img_feature, txt_feature, scale)
+
+    def set_trainable_parameters(self, trainable_prefixes=("text_encoder",)):
+        """requires_grad = (the name starts with one of the prefixes) for every registered parameter, running statistics
+        included, as the reference does (llm/clip/model.py:207-217); returns (trainable, frozen) counts."""
+        trainable_count, frozen_count = 0, 0
+        for name, param in self._parameters.items():
+            is_trainable = any(name.startswith(prefix) for prefix in trainable_prefixes)
+            param.requires_grad = is_trainable
+            if is_trainable:
+                trainable_count += 1
+            else:
+                frozen_count += 1
+        return trainable_count, frozen_count
+
+    def finetune_step(self, image, text_tokens, target_ids, optimizer, criterion=None):
+        """zero_grad -> forward -> cross entropy over the (images, texts) logits -> backward -> optimizer step; returns the
+        loss (llm/clip/model.py:219-243)."""
+        if criterion is None:
+            criterion = nn.CrossEntropyLoss()
+        self.train(True)
+        optimizer.zero_grad()
+        logits = self(image, text_tokens)
+        B, K = logits.shape
+        targets = Tensor(np.asarray(target_ids).reshape(-1), dtype=np.int64, device=logits.device)
+        loss = criterion(logits.reshape(B, K), targets)
+        loss.backward()
+        optimizer.step()
+        return loss.item()
