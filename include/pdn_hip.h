@@ -164,7 +164,8 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
                               int64_t ldx, void* stream);
 /* Launch counters per kernel: which kernel the entry points really launched since the last reset -- bench.py's parity
  * gates and the tests assert on them (a dispatch that silently falls back to a slower kernel must not stay green).
- * Copies min(n, 28) counters to `out` (may be null), clears all of them when `reset` != 0.  Slots:
+ * Copies min(n, 28) counters of slots 0-27 to `out` (may be null) and slot 28 as well when n > 28; clears all of them
+ * when `reset` != 0.  Slots:
  *   0 gemm_rowres_kernel (chunk kernel, any)      1 gemm_rowtile_kernel plain        2 ... + SwiGLU forward (gate | up)
  *   3 ... + SwiGLU backward (dh)                  4 ... + RoPE (q | k | v)           5 ... + row maxima (lm_head forward)
  *   6 gemm_rowres_kernel with a fused epilogue    7 attention_p forward (persistent) 8 attention_p backward (dQ + dK/dV)
@@ -175,7 +176,8 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  19 pdn_gateup_swiglu_tiled_fwd_f32            20 pdn_swiglu_bwd_tiled_f32
  *  21 conv_quad_fwd_kernel (csrc/conv_quad.hip)  22 conv_quad_dgrad_kernel          23 conv_quad_wgrad_kernel
  *  24 pdn_patch_embed_fwd_f32 (csrc/patch_embed.hip)                                25 pdn_patch_embed_bwd_f32
- *  26 pdn_l2norm_rows_fwd_f32                     27 pdn_l2norm_rows_bwd_f32 */
+ *  26 pdn_l2norm_rows_fwd_f32                     27 pdn_l2norm_rows_bwd_f32
+ *  28 pdn_sample_rows_f32 / pdn_decode_sample_tick_f32 (csrc/sample.hip) */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -471,6 +473,29 @@ int pdn_decode_pick_tick_f32(const float* blk_max, const int* blk_arg, int B, in
                              void* stream);
 int pdn_decode_argmax_tick_f32(const float* logits, int64_t row_stride, int B, int V, int64_t* next_ids, int* pos,
                                void* stream);
+/* Sampled decode (csrc/sample.hip): the greedy pick of llm/llama/model.py:258-269 (argmax(-1)) generalised to temperature,
+ * top-k and top-p.  For each fp32 logit row z (V <= 2^23) and params->temperature T > 0: keep z_i >= the k-th largest
+ * value counting repeats (top_k = 0 or >= V: all); p_i = exp((z_i - max z) / T) over the kept tokens, normalised; keep
+ * z_i >= theta, the largest kept value whose mass of {z_i >= theta} is >= top_p (top_p >= 1: all); draw with
+ * u = (w >> 40) * 2^-24, w the first word of Philox4x64-10(counter (t, b, 0, 0), key (seed, 0)): the token is the
+ * smallest kept id whose inclusive cumulative probability (ascending ids) is > u.  Deterministic: the same input gives
+ * the same ids (the probability mass is summed as integers, 2^-40 units of the largest weight).  T <= 0: the argmax.
+ * `params` is a DEVICE pointer, so a captured step can be replayed with new values.
+ *   pdn_sample_rows_f32         row b -> out_ids[b] (int64) with counter (t, b); one workgroup per row.
+ *   pdn_decode_sample_tick_f32  pdn_decode_pick_tick_f32 with full logit rows in place of the candidates: row b is
+ *                               drawn with counter (*pos, b), stored to next_ids[b] and the history slot, its embedding
+ *                               row copied to x_next; then *pos += 1 (one workgroup walks the B rows). */
+typedef struct pdn_sample_params {
+  float temperature;
+  int top_k;
+  float top_p;
+  uint64_t seed;
+} pdn_sample_params;
+int pdn_sample_rows_f32(const float* logits, int64_t row_stride, int B, int V, const pdn_sample_params* params, int64_t t,
+                        int64_t* out_ids, void* stream);
+int pdn_decode_sample_tick_f32(const float* logits, int64_t row_stride, int B, int V, const pdn_sample_params* params,
+                               int64_t* next_ids, int* pos, int64_t* const* history, const float* emb,
+                               int64_t emb_row_stride, int D, float* x_next, void* stream);
 /* Fused decode layer (csrc/decode_layer.hip, decode_stage.h): three launches per TransformerBlock (model.py:118-121)
  * instead of five.  An output projection is a sum over heads / hidden units, so its producer stops one step early:
  * every workgroup leaves the contribution of ITS head / 32 hidden units to the projected row as a record, and every

@@ -49,7 +49,8 @@ enum {
   PDN_CNT_PATCH_EMBED_BWD = 25,   // pdn_patch_embed_bwd_f32 (kernel-gradient GEMM and / or class / position column sums)
   PDN_CNT_L2NORM_FWD = 26,        // l2norm_fwd_kernel (CLIP's contrastive head)
   PDN_CNT_L2NORM_BWD = 27,        // l2norm_bwd_kernel
-  PDN_CNT_SLOTS = 28
+  PDN_CNT_SAMPLE = 28,            // sample_rows_kernel / decode_sample_tick_kernel (csrc/sample.hip: temperature, top-k, top-p)
+  PDN_CNT_SLOTS = 29
 };
 void pdn_count(int slot);
 

@@ -20,6 +20,7 @@ from .. import nn
 from ..autograd import is_grad_enable
 from ..core import Tensor, fused
 from ..special import zeros
+from .sampling import check_args as check_sampling_args, params_bytes, params_buffer, sample_next
 
 
 def compute_cos_sin_cache(head_dim: int, max_seq_len: int, base: int = 10000, dtype=None):
@@ -217,20 +218,30 @@ class Llama(nn.Module):
 
     fast_decode = True      # class switch: False keeps every decode step on the generic tape-node path
 
-    def generate(self, input_ids, max_new_tokens: int):
+    def generate(self, input_ids, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0):
+        """Yield the next ids, (B, 1) int64, for positions L .. max_new_tokens - 1.  temperature 0 (the default): the
+        greedy pick of the reference (model.py:258-269); temperature > 0: drawn with top-k / top-p and the seeded
+        counter-based generator of llm/sampling.py (token at position t of row b: Philox counter (t, b)).  The arguments
+        are checked here, before anything runs."""
+        temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
+        return self._generate(input_ids, max_new_tokens, (temperature, top_k, top_p, seed) if temperature > 0 else None)
+
+    def _generate(self, input_ids, max_new_tokens, sampling):
         B, L = input_ids.shape
         next_id = None
         for i, pos in enumerate(range(L, max_new_tokens)):
             if i == 0:
                 logits = self(input_ids, 0)                       # prompt pass: fills the KV caches
-                next_id = logits[:, -1, :].argmax(-1, True)
+                next_id = (logits[:, -1, :].argmax(-1, True) if sampling is None
+                           else sample_next(logits[:, -1, :], pos, *sampling))
             elif (Llama.fast_decode and next_id.device.is_hip and not self._train
                   and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0):
                 # (`more`: another token will be asked for -- the step after this one may be queued ahead)
-                next_id = Tensor(self._decode_step_hip(next_id.data, pos, more=pos + 1 < max_new_tokens), dtype=np.int64,
-                                 device=next_id.device, copy=False)
+                next_id = Tensor(self._decode_step_hip(next_id.data, pos, more=pos + 1 < max_new_tokens,
+                                                       sampling=sampling), dtype=np.int64, device=next_id.device, copy=False)
             else:
-                next_id = self(next_id, pos)[:, -1, :].argmax(-1, True)
+                logits = self(next_id, pos)[:, -1, :]
+                next_id = logits.argmax(-1, True) if sampling is None else sample_next(logits, pos, *sampling)
             yield next_id
 
     # -- decode fast path (SURVEY 8f-1) -----------------------------------------------------------
@@ -238,9 +249,11 @@ class Llama(nn.Module):
     decode_ahead = True     # class switch: False never queues the next step before the caller asked for it
     fused_decode = 2        # class switch: launches per layer = 2 (q|k|v inside the attention kernel), 1 -> 3, 0 / False -> 5
 
-    def _decode_plan(self, B):
+    def _decode_plan(self, B, sampling=False):
         """Buffers and weight views of the graph-replayable decode step (csrc/decode.hip), or None when the
-        model's shapes / layout are outside what those kernels take (then the generic launches below run)."""
+        model's shapes / layout are outside what those kernels take (then the generic launches below run).
+        `sampling`: the step ends in the sample tick (csrc/sample.hip) instead of the greedy pick; its parameters live in
+        the plan's `params` buffer, so new values never re-capture."""
         from .. import hipnp as hp, _lib
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
         st = getattr(self, "_decode_st", None)
@@ -256,7 +269,7 @@ class Llama(nn.Module):
                                             f.gate.weight, f.up.weight, f.down.weight, layer.input_norm.weight,
                                             layer.post_attn_norm.weight)]
         key = (B, hp._state["device"], int(Llama.fused_decode or 0), os.environ.get("PDN_DECODE_SPLITS", ""),
-               self.layers[0].attention.cache_k.shape[1], tuple(ptrs))      # (the addresses themselves: no hash to collide)
+               self.layers[0].attention.cache_k.shape[1], tuple(ptrs), bool(sampling))   # (the addresses: no hash to collide)
         if st is not None and st["key"] == key:
             return st if st["ok"] else None
         if st is not None:
@@ -276,7 +289,7 @@ class Llama(nn.Module):
                     break
                 packs.append((qkv, gu))
             ok = ok and self.lm_head.weight.data.is_contiguous() and self.tok_embedding.weight.data.is_contiguous()
-        st = {"B": B, "key": key, "ok": ok}
+        st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling)}
         if ok:
             nblk = _lib.lib().query("pdn_decode_gemv_blocks", V)
             # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
@@ -288,6 +301,8 @@ class Llama(nn.Module):
                       # the caller; a fresh history per generation (the pointer lives on the device, the graph holds
                       # only ITS address), so arrays returned earlier are never rewritten
                       hist_ptr=hp.zeros((1,), np.int64), hist=None,
+                      # pdn_sample_params of the current generation (written before its first step; sampling plans only)
+                      params=hp.zeros((3,), np.int64) if sampling else None, params_val=None,
                       **{n: hp.empty((B, w), np.float32) for n, w in
                          (("x", D), ("qkv", 3 * D), ("att", ns * H * (4 + D // H)), ("gu", 2 * F), ("logits", V))})
             # three launches per layer (csrc/decode_layer.hip): the output / down projections leave per-head /
@@ -380,10 +395,10 @@ class Llama(nn.Module):
                 L.call("pdn_decode_mlp_f32", x if li == 0 else xa, D, recs, rrs, ns, H, xb, D, nrm.weight.data._ptr,
                        nrm.eps, f.gate.weight.data._ptr, f.up.weight.data._ptr, F, f.down.weight.data._ptr, D, dparts,
                        J * D, B, D, F, s)
+            cv, ci = (None, None) if st["sampling"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
             L.call("pdn_decode_gemv_sum_f32", xb, D, dparts, J, J * D, None, 0, self.norm.weight.data._ptr, self.norm.eps,
-                   head.weight.data._ptr, V, V, 0, bias, logits, V, B, D, V, st["cand_v"]._ptr, st["cand_i"]._ptr, s)
-            L.call("pdn_decode_pick_tick_f32", st["cand_v"]._ptr, st["cand_i"]._ptr, B, st["cand_v"].shape[1],
-                   st["ids"]._ptr, pos, st["hist_ptr"]._ptr, emb._ptr, emb._strides[0], D, x, s)
+                   head.weight.data._ptr, V, V, 0, bias, logits, V, B, D, V, cv, ci, s)
+            self._decode_tick(st, s)
             return
         for layer, (wqkv, wgu) in zip(self.layers, st["packs"]):
             a, f = layer.attention, layer.ffn
@@ -406,10 +421,22 @@ class Llama(nn.Module):
                    None, None, s)
         # vocabulary projection; every workgroup also leaves the first maximum of its columns, the pick kernel
         # finishes the argmax over those candidates (model.py:262-268) and advances the position
+        cv, ci = (None, None) if st["sampling"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
         L.call("pdn_decode_gemv_f32", x, D, self.norm.weight.data._ptr, self.norm.eps, head.weight.data._ptr, V, V, 0,
-               bias, None, 0, logits, V, B, D, V, 0, 0, 0, st["cand_v"]._ptr, st["cand_i"]._ptr, s)
+               bias, None, 0, logits, V, B, D, V, 0, 0, 0, cv, ci, s)
+        self._decode_tick(st, s)
+
+    def _decode_tick(self, st, s):
+        """The last launch of a step: the greedy pick over the projection's candidates, or (sampling plans) the sample
+        tick over the full logit rows with counter (*pos, b); either stores the token and its embedding row, *pos += 1."""
+        from .. import _lib
+        L, emb, D, B = _lib.lib(), self.tok_embedding.weight.data, self.embed_dim, st["B"]
+        if st["sampling"]:
+            L.call("pdn_decode_sample_tick_f32", st["logits"]._ptr, self.vocab_size, B, self.vocab_size, st["params"]._ptr,
+                   st["ids"]._ptr, st["pos"]._ptr, st["hist_ptr"]._ptr, emb._ptr, emb._strides[0], D, st["x"]._ptr, s)
+            return
         L.call("pdn_decode_pick_tick_f32", st["cand_v"]._ptr, st["cand_i"]._ptr, B, st["cand_v"].shape[1],
-               st["ids"]._ptr, pos, st["hist_ptr"]._ptr, emb._ptr, emb._strides[0], D, x, s)
+               st["ids"]._ptr, st["pos"]._ptr, st["hist_ptr"]._ptr, emb._ptr, emb._strides[0], D, st["x"]._ptr, s)
 
     def _decode_gather(self, st):
         """x = tok_embedding[ids] for ids that did not come out of the previous step's pick kernel."""
@@ -418,11 +445,12 @@ class Llama(nn.Module):
         _lib.lib().call("pdn_embedding_gather_f32", emb._ptr, self.vocab_size, self.embed_dim, emb._strides[0],
                         st["ids"]._ptr, st["B"], st["x"]._ptr, hp.err_flag_ptr(), hp.stream())
 
-    def _decode_step_hip(self, ids, pos: int, more: bool = False):
-        """One greedy decode step (one new token per sequence) without building tape nodes.  ids: (B, 1) int64
+    def _decode_step_hip(self, ids, pos: int, more: bool = False, sampling=None):
+        """One decode step (one new token per sequence) without building tape nodes.  ids: (B, 1) int64
         device array; returns the next ids, (B, 1) int64.  The step is ONE hipGraph replay: norm + projection,
         RoPE + cache append, decode attention, SwiGLU + down projection and the greedy pick all read the position
-        from device memory (csrc/decode.hip), so nothing changes between replays but the data."""
+        from device memory (csrc/decode.hip), so nothing changes between replays but the data.  `sampling`: None =
+        greedy, else (temperature, top_k, top_p, seed) and the step ends in the sample tick (csrc/sample.hip)."""
         from .. import hipnp as hp, _lib
         B = ids.shape[0]
         cache = self.layers[0].attention.cache_k
@@ -433,12 +461,12 @@ class Llama(nn.Module):
                              f"(max_seq_len {cache.shape[1]}, {self.freqs_cos.shape[0]} RoPE rows)")
         if B > cache.shape[0]:
             raise ValueError(f"batch {B} exceeds the KV cache's max_batch_size {cache.shape[0]}")
-        st = self._decode_plan(B)
+        st = self._decode_plan(B, sampling is not None)
         if st is None:
-            return self._decode_step_generic(ids, pos)
+            return self._decode_step_generic(ids, pos, sampling)
         ahead, st["ahead"] = st.get("ahead"), None
         if ahead is not None:
-            if ahead[0] == pos and ahead[1] is ids:              # the step queued ahead is exactly this one
+            if ahead[0] == pos and ahead[1] is ids and st["params_val"] == sampling:   # exactly this step, queued ahead
                 out = st["last_out"] = ahead[2]
                 if more and Llama.decode_ahead and pos + 1 < min(cache.shape[1], self.freqs_cos.shape[0]):
                     self._decode_ahead(st, pos + 1)
@@ -450,12 +478,16 @@ class Llama(nn.Module):
             # a new generation: its own history -- slots in mapped host memory the pick kernel stores into directly
             st["hist"] = hp.Mailbox(cache.shape[1], (B, 1))
             st["hist_ptr"][...] = np.int64(st["hist"]._ptr)
+        if st["params_val"] != sampling:
+            if sampling is not None:
+                st["params"][...] = params_bytes(*sampling)      # (stream-ordered: earlier steps read the old values)
+            st["params_val"] = sampling
         fresh = ids is not st["ids"] and ids is not st.get("last_out")
         if fresh:
             st["ids"][...] = ids                                 # (not the array the previous step returned: that
             self._decode_gather(st)                              # one's embedding row is already in x)
         ns = self._decode_ns(st, pos)
-        g = False if st["nograph"] else st["graphs"].get(ns)
+        g = False if st["nograph"] else st["graphs"].get((ns, st["sampling"]))
         if g is None and Llama.graph_decode and pos + 2 < min(cache.shape[1], self.freqs_cos.shape[0]):
             # capture once: hipnp.Graph runs the step twice for real (pool warm-up + first replay), which writes the
             # cache rows of positions pos and pos + 1 with exactly what the real steps will write there; the
@@ -469,7 +501,7 @@ class Llama(nn.Module):
             try:
                 g = hp.Graph()
                 g.capture(lambda: self._decode_launches(st, ns))
-                st["graphs"][ns] = g
+                st["graphs"][(ns, st["sampling"])] = g
             except _lib.HipLibraryError as e:
                 if e.code != -2:                                 # PDN_EUNSUPPORTED: no graph support (the emulated
                     raise                                        # ABI) -> plain launches; anything else is a bug
@@ -497,7 +529,7 @@ class Llama(nn.Module):
         gather reads them -- so the GPU does not idle while the host hands the previous token to the caller.  The
         result is kept for the next `_decode_step_hip(last_out, pos)` call; any other call discards it."""
         ns = self._decode_ns(st, pos)
-        g = False if st["nograph"] else st["graphs"].get(ns)
+        g = False if st["nograph"] else st["graphs"].get((ns, st["sampling"]))
         if g is None:
             return                                               # (a new range count: its step is captured by the next call)
         if g:
@@ -508,7 +540,7 @@ class Llama(nn.Module):
         prev = st["last_out"]
         st["ahead"] = (pos, prev, st["hist"].slot(pos))
 
-    def _decode_step_generic(self, ids, pos: int):
+    def _decode_step_generic(self, ids, pos: int, sampling=None):
         """The same step from the library's generic entry points (skinny `pdn_gemm_f32`, RMSNorm, RoPE, decode
         attention, SwiGLU), ~77 launches from preallocated buffers: for shapes / layouts the graph path does not take."""
         from .. import hipnp as hp, _lib
@@ -556,4 +588,8 @@ class Llama(nn.Module):
         L.call("pdn_rmsnorm_fwd_f32", x, self.norm.weight.data._ptr, h, None, B, D, self.norm.eps, st)
         gemv(h, D, self.lm_head.weight, logits, V,
              bias=self.lm_head.bias.data._ptr if getattr(self.lm_head, "bias", None) is not None else None)
-        return ws["logits"].argmax(-1, keepdims=True)
+        if sampling is None:
+            return ws["logits"].argmax(-1, keepdims=True)
+        out = hp.empty((B, 1), np.int64)              # (the sampled form of the pick: counter (pos, b))
+        L.call("pdn_sample_rows_f32", logits, V, B, V, params_buffer(*sampling)._ptr, pos, out._ptr, st)
+        return out

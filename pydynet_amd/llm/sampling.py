@@ -1,0 +1,143 @@
+"""Sampled next tokens for `Llama.generate`: temperature, top-k and top-p (nucleus), seeded and reproducible.
+
+The reference's `generate` (llm/llama/model.py:258-269) only takes the argmax.  This module states the sampled pick and
+runs it: on a HIP device through `pdn_sample_rows_f32` (csrc/sample.hip), elsewhere through the NumPy statement below,
+which IS the contract (the kernel computes the same in fp32 / integer mass units).
+
+For one row of logits z (length V) and temperature T > 0:
+  1. top-k (k = 0 or k >= V: off): keep every token with z_i >= z_(k), the k-th largest value counting repeats;
+  2. p_i = exp((z_i - max z) / T) over the kept tokens, normalised;
+  3. top-p (top_p = 1: off): theta = the largest kept value such that the mass of {kept i : z_i >= theta} is at least
+     top_p; keep exactly those (ties at theta are all kept);
+  4. renormalise; u = (w >> 40) * 2^-24 with w the first 64-bit word of Philox4x64-10 for counter (t, b, 0, 0) and key
+     (seed, 0); the token is the smallest kept id whose inclusive cumulative probability (ascending ids) is > u.
+`t` is the position of the generate-loop iteration that yields the token, `b` the batch row.
+"""
+import numpy as np
+
+_M0, _M1 = 0xD2E7470EE14C6C93, 0xCA5A826395121157
+_W0, _W1 = 0x9E3779B97F4A7C15, 0xBB67AE8584CAA73B
+_MASK32 = np.uint64(0xFFFFFFFF)
+
+
+def check_args(temperature, top_k, top_p, seed):
+    """Validate the sampling arguments of `generate`; returns them normalised (float, int, float, int)."""
+    temperature, top_p = float(temperature), float(top_p)
+    if not temperature >= 0.0:
+        raise ValueError(f"temperature must be >= 0, got {temperature}")
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k must be a non-negative integer, got {top_k}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must lie in (0, 1], got {top_p}")
+    if int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed}")
+    return temperature, int(top_k), top_p, int(seed)
+
+
+def _mulhilo(a, b):
+    """(hi, lo) 64-bit halves of the 128-bit products a * b of uint64 arrays (b a scalar constant)."""
+    b = np.uint64(b)
+    a_lo, a_hi = a & _MASK32, a >> np.uint64(32)
+    b_lo, b_hi = b & _MASK32, b >> np.uint64(32)
+    ll, lh, hl, hh = a_lo * b_lo, a_lo * b_hi, a_hi * b_lo, a_hi * b_hi
+    mid = (ll >> np.uint64(32)) + (lh & _MASK32) + (hl & _MASK32)
+    hi = hh + (lh >> np.uint64(32)) + (hl >> np.uint64(32)) + (mid >> np.uint64(32))
+    return hi, a * b
+
+
+def philox4x64(counter, key):
+    """Philox4x64-10 blocks: counter (..., 4) and key (..., 2) uint64 -> (..., 4) uint64 (Salmon et al., SC'11)."""
+    c = np.array(np.broadcast_to(np.asarray(counter, np.uint64), np.broadcast_shapes(np.shape(counter)[:-1] + (4,),
+                                                                                    np.shape(key)[:-1] + (4,))))
+    k = np.array(np.broadcast_to(np.asarray(key, np.uint64), c.shape[:-1] + (2,)))
+    with np.errstate(over="ignore"):
+        for r in range(10):
+            if r:
+                k[..., 0] += np.uint64(_W0)
+                k[..., 1] += np.uint64(_W1)
+            hi0, lo0 = _mulhilo(c[..., 0], _M0)
+            hi1, lo1 = _mulhilo(c[..., 2], _M1)
+            c = np.stack([hi1 ^ c[..., 1] ^ k[..., 0], lo1, hi0 ^ c[..., 3] ^ k[..., 1], lo0], axis=-1)
+    return c
+
+
+def uniforms(t, rows, seed):
+    """u in [0, 1) for counters (t, b, 0, 0), b in `rows`, key (seed, 0): (w >> 40) * 2^-24 of the block's first word."""
+    rows = np.asarray(rows, np.uint64).reshape(-1)
+    ctr = np.zeros((rows.size, 4), np.uint64)
+    ctr[:, 0], ctr[:, 1] = np.uint64(t), rows
+    w = philox4x64(ctr, np.array([seed, 0], np.uint64))[:, 0]
+    return (w >> np.uint64(40)).astype(np.float64) * 2.0 ** -24
+
+
+def kept_mask(z, top_k, top_p, temperature):
+    """Steps 1-3 for one float64 row: the kept tokens and their renormalised probabilities (0 elsewhere)."""
+    V = z.shape[0]
+    kept = np.ones(V, bool)
+    if 0 < top_k < V:
+        kept = z >= np.partition(z, V - top_k)[V - top_k]
+    w = np.where(kept, np.exp((z - z.max()) / temperature), 0.0)
+    p = w / w.sum()
+    if top_p < 1.0:
+        vals, grp = np.unique(z[kept], return_inverse=True)
+        cum = np.cumsum(np.bincount(grp.reshape(-1), weights=p[kept], minlength=vals.size)[::-1])   # largest value first
+        theta = vals[::-1][min(int(np.searchsorted(cum, top_p, side="left")), vals.size - 1)]
+        kept &= z >= theta
+        p = np.where(kept, p, 0.0)
+        p /= p.sum()
+    return kept, p
+
+
+def sample_rows_np(logits, t, temperature, top_k=0, top_p=1.0, seed=0, rows=None):
+    """The NumPy statement of the contract: (B, V) logits -> (B,) int64 ids, row b drawn with counter (t, rows[b])."""
+    z = np.asarray(logits, np.float64)
+    B = z.shape[0]
+    rows = np.arange(B) if rows is None else np.asarray(rows)
+    if temperature == 0.0:
+        return z.argmax(-1).astype(np.int64)
+    u = uniforms(t, rows, seed)
+    out = np.empty(B, np.int64)
+    for b in range(B):
+        _, p = kept_mask(z[b], top_k, top_p, temperature)
+        cdf = np.cumsum(p)
+        i = int(np.searchsorted(cdf, u[b], side="right"))     # first inclusive prefix > u
+        out[b] = i if i < z.shape[1] and p[i] > 0 else int(np.flatnonzero(p)[-1])
+    return out
+
+
+def params_bytes(temperature, top_k, top_p, seed):
+    """pdn_sample_params (include/pdn_hip.h) as three int64 words: {float T; int top_k; float top_p; uint64_t seed}."""
+    raw = np.zeros(24, np.uint8)
+    raw[0:4] = np.frombuffer(np.float32(temperature).tobytes(), np.uint8)
+    raw[4:8] = np.frombuffer(np.int32(top_k).tobytes(), np.uint8)
+    raw[8:12] = np.frombuffer(np.float32(top_p).tobytes(), np.uint8)
+    raw[16:24] = np.frombuffer(np.uint64(seed).tobytes(), np.uint8)
+    return raw.view(np.int64)
+
+
+def params_buffer(temperature, top_k, top_p, seed):
+    """A device copy of pdn_sample_params on the current HIP device (the allocator orders its reuse on the stream)."""
+    from .. import hipnp as hp
+    return hp.asarray(params_bytes(temperature, top_k, top_p, seed))
+
+
+def sample_next(logits, t, temperature, top_k=0, top_p=1.0, seed=0):
+    """Sampled next ids of a (B, V) logits Tensor: (B, 1) int64 on the logits' device.  temperature 0 = argmax."""
+    from ..core import Tensor
+    temperature, top_k, top_p, seed = check_args(temperature, top_k, top_p, seed)
+    if temperature == 0.0:
+        return logits.argmax(-1, True)
+    B, V = logits.shape
+    if logits.device.is_hip:
+        from .. import hipnp as hp, _lib
+        x = logits.data
+        if x.dtype != np.float32:
+            raise TypeError(f"sampling takes float32 logits on the GPU, got {x.dtype}")
+        if x._strides[1] != 1 or x._strides[0] < V:
+            x = x.copy()
+        out = hp.empty((B, 1), np.int64)
+        _lib.lib().call("pdn_sample_rows_f32", x._ptr, x._strides[0], B, V,
+                        params_buffer(temperature, top_k, top_p, seed)._ptr, int(t), out._ptr, hp.stream())
+        return Tensor(out, dtype=np.int64, device=logits.device, copy=False)
+    ids = sample_rows_np(np.asarray(logits.numpy()), t, temperature, top_k, top_p, seed)
+    return Tensor(ids.reshape(B, 1), dtype=np.int64, device=logits.device)
