@@ -164,7 +164,8 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
                               int64_t ldx, void* stream);
 /* Launch counters per kernel: which kernel the entry points really launched since the last reset -- bench.py's parity
  * gates and the tests assert on them (a dispatch that silently falls back to a slower kernel must not stay green).
- * Copies min(n, 28) counters of slots 0-27 to `out` (may be null) and slot 28 as well when n > 28; clears all of them
+ * Copies min(n, 28) counters of slots 0-27 to `out` (may be null), slot 28 as well when n > 28 and slot 29 when n > 29;
+ * clears all of them
  * when `reset` != 0.  Slots:
  *   0 gemm_rowres_kernel (chunk kernel, any)      1 gemm_rowtile_kernel plain        2 ... + SwiGLU forward (gate | up)
  *   3 ... + SwiGLU backward (dh)                  4 ... + RoPE (q | k | v)           5 ... + row maxima (lm_head forward)
@@ -177,7 +178,10 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  21 conv_quad_fwd_kernel (csrc/conv_quad.hip)  22 conv_quad_dgrad_kernel          23 conv_quad_wgrad_kernel
  *  24 pdn_patch_embed_fwd_f32 (csrc/patch_embed.hip)                                25 pdn_patch_embed_bwd_f32
  *  26 pdn_l2norm_rows_fwd_f32                     27 pdn_l2norm_rows_bwd_f32
- *  28 pdn_sample_rows_f32 / pdn_decode_sample_tick_f32 (csrc/sample.hip) */
+ *  28 pdn_sample_rows_f32 / pdn_decode_sample_tick_f32 (csrc/sample.hip)
+ *  29 decode with a position per row: pdn_decode_block_rows_f32, pdn_decode_attention_rows_f32,
+ *     pdn_decode_attention_oproj_rows_f32, pdn_decode_pick_tick_rows_f32, pdn_decode_sample_tick_rows_f32 (which also
+ *     counts in 28) and pdn_attention_decode_rows_f32 */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -538,6 +542,42 @@ int pdn_decode_gemv_sum_f32(const float* base, int64_t base_row_stride, const fl
                             float eps, const float* W, int64_t w_row_stride, int blk_cols, int64_t w_block_stride,
                             const float* bias, float* y, int64_t y_row_stride, int B, int K, int N, float* blk_max,
                             int* blk_arg, void* stream);
+/* Ragged decode (Llama.generate_ragged): every row at its own position.  The *_rows_f32 entries take the arguments of
+ * the entries above, but `pos` is a (B,) int32 device array: row b's new token is rotated by the angle of position
+ * pos[b], its k / v go to cache slot pos[b] of row b and it attends to [0, pos[b]] (the keys of row b cut into ranges
+ * of ceil(pos[b] / n) each).  pos[b] < 0 marks a stopped row: it is computed at position 0 and writes no cache slot.
+ *   pdn_decode_pick_tick_rows_f32 / pdn_decode_sample_tick_rows_f32  the ticks with a position per row: the history is
+ *                            indexed by the STEP, (*history)[*step * B + b] (the host reads step i of every row at one
+ *                            place), -1 for a stopped row, which is otherwise left alone (ids, x_next, pos); a sampled
+ *                            row is drawn with counter (pos[b], b); a live row whose token t has bit t set in
+ *                            stop_mask ((V + 31) / 32 words, may be NULL) stops (pos[b] = -1), else pos[b] += 1; then
+ *                            *step += 1.  One workgroup walks the B rows.
+ *   pdn_attention_decode_rows_f32  pdn_attention_decode_f32 with a length per row: row b attends to [0, lens[b])
+ *                            (lens: (B,) int32 device array, values in [1, max_T]). */
+int pdn_decode_block_rows_f32(const float* base, int64_t base_row_stride, const float* parts, int n_parts,
+                              int64_t parts_row_stride, float* x_out, int64_t x_out_row_stride, const float* norm_w,
+                              float eps, const float* Wqkv, int64_t w_row_stride, int64_t w_block_stride,
+                              const float* cos_table, const float* sin_table, float* k_cache, float* v_cache,
+                              int64_t cache_batch_stride, const int* pos, int max_len, const float* Wo,
+                              int64_t wo_row_stride, float* records, int B, int H, int head_dim, int n_ranges,
+                              void* stream);
+int pdn_decode_attention_rows_f32(const float* qkv, int64_t qkv_row_stride, const float* cos_table,
+                                  const float* sin_table, float* k_cache, float* v_cache, float* partials, int B, int H,
+                                  int head_dim, int n_splits, int64_t cache_batch_stride, const int* pos, int max_len,
+                                  void* stream);
+int pdn_decode_attention_oproj_rows_f32(const float* qkv, int64_t qkv_row_stride, const float* cos_table,
+                                        const float* sin_table, float* k_cache, float* v_cache, const float* Wo,
+                                        int64_t wo_row_stride, float* records, int B, int H, int head_dim, int n_splits,
+                                        int64_t cache_batch_stride, const int* pos, int max_len, void* stream);
+int pdn_decode_pick_tick_rows_f32(const float* blk_max, const int* blk_arg, int B, int n_blocks, int64_t* next_ids,
+                                  int* pos, int* step, const unsigned* stop_mask, int64_t* const* history,
+                                  const float* emb, int64_t emb_row_stride, int D, float* x_next, void* stream);
+int pdn_decode_sample_tick_rows_f32(const float* logits, int64_t row_stride, int B, int V,
+                                    const pdn_sample_params* params, int64_t* next_ids, int* pos, int* step,
+                                    const unsigned* stop_mask, int64_t* const* history, const float* emb,
+                                    int64_t emb_row_stride, int D, float* x_next, void* stream);
+int pdn_attention_decode_rows_f32(const float* q, const float* k_cache, const float* v_cache, float* o, int B, int H,
+                                  const int* lens, int max_T, int head_dim, int64_t cache_batch_stride, void* stream);
 /* shapes the resident (K / V of a head chunk-wise in LDS) kernels above take: head_dim 48 or 64, L a multiple of 32 up
  * to 1024 -- sequences beyond 256 pass through LDS in 256-row chunks (forward: one online rescale per chunk) -- and
  * (round 6, csrc/attention_hd128.hip) head_dim 128 at ANY length 1 .. 1024, no RoPE inside: the shape of

@@ -150,15 +150,18 @@ class Mailbox:
     """(n, *shape) int64 slots in host memory the GPU writes directly: a kernel stores slot i (system scope), the host
     reads it by polling -- no copy command, no event, nothing queued between two graph replays.  Slots start at -1
     (the kernels store non-negative values: token ids); `slot(i)` is slot i as a device array (its address is the
-    mapped one: kernels may read it) whose `get()` / `item()` wait until the GPU has filled it."""
+    mapped one: kernels may read it) whose `get()` / `item()` wait until the GPU has filled it.
+    `unset`: the value that marks a slot as not written yet, for kernels that store negative values themselves (the
+    ragged decode stores -1 for a stopped row); None = any negative value."""
 
-    def __init__(self, n, shape):
+    def __init__(self, n, shape, unset=None):
         self.shape = tuple(int(s) for s in shape)
+        self.unset = unset
         self.n, self.per = int(n), int(math.prod(self.shape))
         self._mem = _MappedHost(8 * self.n * self.per)
         buf = (ctypes.c_char * self._mem.nbytes).from_address(self._mem.host)
         self.host = np.frombuffer(buf, dtype=np.int64).reshape((self.n,) + self.shape)
-        self.host[...] = -1
+        self.host[...] = -1 if unset is None else unset
         self._ptr = self._mem.ptr
 
     def slot(self, i):
@@ -167,19 +170,19 @@ class Mailbox:
             strides.append(acc); acc *= d
         out = readback_array(self._mem, self._ptr + 8 * self.per * int(i), self.shape, tuple(reversed(strides)), np.int64)
         out._host = None
-        out._rb = _Polled(self.host[int(i)])
+        out._rb = _Polled(self.host[int(i)], self.unset)
         return out
 
 
 class _Polled:
-    __slots__ = ("view",)
+    __slots__ = ("view", "unset")
 
-    def __init__(self, view):
-        self.view = view
+    def __init__(self, view, unset=None):
+        self.view, self.unset = view, unset
 
     def _finish(self, arr):
         v, spins = self.view, 0
-        while (v < 0).any():                       # the GPU's store has not landed yet
+        while (v < 0).any() if self.unset is None else (v == self.unset).any():   # the GPU's store has not landed yet
             spins += 1
             if spins == 200000:                    # far beyond any decode step: make sure the stream is still alive
                 synchronize()

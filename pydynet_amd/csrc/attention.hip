@@ -1032,13 +1032,16 @@ extern "C" int pdn_attention_bwd_rotated_f32(const float* q, const float* k, con
 // probability-weighted sum of the value rows.  Tiny and latency-bound; it replaces two batched GEMMs,
 // a softmax and the cache slicing of the generic path.
 // ======================================================================================
+// ROWS: row b attends to positions [0, lens[b]) (lens clamped to [1, T], T = the longest).
+template <bool ROWS>
 __global__ __launch_bounds__(256) void attention_decode_kernel(const float* __restrict__ q, const float* __restrict__ kc,
                                                                const float* __restrict__ vc, float* __restrict__ o,
                                                                int H, int T, int hd, int64_t cache_batch_stride,
-                                                               float inv_sqrt) {
+                                                               float inv_sqrt, const int* __restrict__ lens) {
   extern __shared__ __attribute__((aligned(16))) float sc[];      // [T] scores, then [21][hd] partial sums
   __shared__ float red[16];
   const int b = blockIdx.x / H, h = blockIdx.x % H, tid = threadIdx.x;
+  if (ROWS) T = min(max(lens[b], 1), T);
   const int D = H * hd, f4 = hd / 4;
   const float4* q4 = reinterpret_cast<const float4*>(q + ((int64_t)b * H + h) * hd);
   const float* kb = kc + (int64_t)b * cache_batch_stride + (int64_t)h * hd;
@@ -1099,8 +1102,28 @@ extern "C" int pdn_attention_decode_f32(const float* q, const float* k_cache, co
   const int f4 = head_dim / 4, groups = 256 / f4;
   const size_t shm = sizeof(float) * (size_t)(T > groups * head_dim ? T : groups * head_dim);
   PDN_CHECK_ARG(shm <= 64 * 1024, "pdn_attention_decode_f32: T=%d too long", T);
-  hipLaunchKernelGGL(attention_decode_kernel, dim3(B * H), dim3(256), shm, (hipStream_t)stream, q, k_cache,
-                     v_cache, o, H, T, head_dim, cache_batch_stride, 1.f / sqrtf((float)head_dim));
+  hipLaunchKernelGGL(attention_decode_kernel<false>, dim3(B * H), dim3(256), shm, (hipStream_t)stream, q, k_cache,
+                     v_cache, o, H, T, head_dim, cache_batch_stride, 1.f / sqrtf((float)head_dim), nullptr);
   PDN_LAUNCH_CHECK();
+  return PDN_OK;
+}
+
+// The same with a length per row: row b attends to positions [0, lens[b]) (lens: (B,) int32 device array, each in
+// [1, max_T]; max_T sizes the launch).
+extern "C" int pdn_attention_decode_rows_f32(const float* q, const float* k_cache, const float* v_cache, float* o, int B,
+                                             int H, const int* lens, int max_T, int head_dim, int64_t cache_batch_stride,
+                                             void* stream) {
+  if (B == 0 || H == 0) return PDN_OK;
+  PDN_CHECK_ARG(q && k_cache && v_cache && o && lens && max_T > 0, "pdn_attention_decode_rows_f32: bad arguments");
+  PDN_CHECK_ARG(head_dim % 4 == 0 && head_dim <= 256 && (cache_batch_stride % 4) == 0 &&
+                    ((((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)o) & 15) == 0),
+                "pdn_attention_decode_rows_f32: head_dim %% 4, 16-byte alignment required");
+  const int f4 = head_dim / 4, groups = 256 / f4;
+  const size_t shm = sizeof(float) * (size_t)(max_T > groups * head_dim ? max_T : groups * head_dim);
+  PDN_CHECK_ARG(shm <= 64 * 1024, "pdn_attention_decode_rows_f32: T=%d too long", max_T);
+  hipLaunchKernelGGL(attention_decode_kernel<true>, dim3(B * H), dim3(256), shm, (hipStream_t)stream, q, k_cache,
+                     v_cache, o, H, max_T, head_dim, cache_batch_stride, 1.f / sqrtf((float)head_dim), lens);
+  PDN_LAUNCH_CHECK();
+  pdn_count(PDN_CNT_DECODE_ROWS);
   return PDN_OK;
 }

@@ -50,7 +50,9 @@ enum {
   PDN_CNT_L2NORM_FWD = 26,        // l2norm_fwd_kernel (CLIP's contrastive head)
   PDN_CNT_L2NORM_BWD = 27,        // l2norm_bwd_kernel
   PDN_CNT_SAMPLE = 28,            // sample_rows_kernel / decode_sample_tick_kernel (csrc/sample.hip: temperature, top-k, top-p)
-  PDN_CNT_SLOTS = 29
+  PDN_CNT_DECODE_ROWS = 29,       // decode kernels with a position per row (the *_rows_f32 entries of csrc/decode*.hip,
+                                  // sample.hip, pdn_attention_decode_rows_f32)
+  PDN_CNT_SLOTS = 30
 };
 void pdn_count(int slot);
 

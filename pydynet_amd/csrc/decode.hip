@@ -378,7 +378,9 @@ extern "C" int pdn_decode_gemv_sum_f32(const float* base, int64_t base_row_strid
 // workgroups share a (range, head): each repeats the attention (the K / V rows come out of L2) and owns D / C columns.
 // KPRE / VPRE: float4s of the thread's K row / V rows of the thread held in registers from the start (head_dim 48:
 // 12 / 13, 64: 16 / 16 -- a 256-key range completely; 0 / 0: any head_dim, loads where they are used).
-template <int KPRE, int VPRE, bool OPROJ>
+// ROWS: pos_ptr is a (B,) array, row b at its own position pos_ptr[b]; pos_ptr[b] < 0 = a stopped row: computed at
+// position 0 (its one key is the new one, kept in LDS) and its cache rows are not written.
+template <int KPRE, int VPRE, bool OPROJ, bool ROWS>
 __global__ __launch_bounds__(256) void decode_attention_kernel(const int* __restrict__ pos_ptr, int H, int hd, int NS, int C,
                                                                const float* __restrict__ qkv, float* __restrict__ kc,
                                                                float* __restrict__ vc, const float* __restrict__ cs,
@@ -390,7 +392,9 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(const int* __rest
   __shared__ __attribute__((aligned(16))) float qs[256], ks[256], vs[256];
   __shared__ float red[16];
   DEC_T_BEGIN(1);
-  const int pos = *pos_ptr, T = pos + 1;
+  const int pos_u = ROWS ? pos_ptr[blockIdx.x / (C * NS * H)] : *pos_ptr;
+  const bool keep = !ROWS || pos_u >= 0;
+  const int pos = ROWS ? max(pos_u, 0) : pos_u, T = pos + 1;
   const int ci = blockIdx.x % C, sp = (blockIdx.x / C) % NS, bh = blockIdx.x / (C * NS), b = bh / H, h = bh % H;
   const int tid = threadIdx.x;
   const int chunk = (T + NS - 1) / NS, t0 = sp * chunk, t1 = min(T, t0 + chunk);
@@ -456,7 +460,7 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(const int* __rest
       const float2 kr = make_float2(nk.x * rc - nk.y * rs, nk.x * rs + nk.y * rc);
       *reinterpret_cast<float2*>(ks + 2 * tid) = kr;
       *reinterpret_cast<float2*>(vs + 2 * tid) = nv;
-      if (ci == 0) {
+      if (ci == 0 && keep) {
         *reinterpret_cast<float2*>(kb + (int64_t)pos * D + 2 * tid) = kr;
         *reinterpret_cast<float2*>(vb + (int64_t)pos * D + 2 * tid) = nv;
       }
@@ -573,7 +577,7 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(const int* __rest
 static int decode_attention_impl(const float* qkv, int64_t qkv_row_stride, const float* cos_table, const float* sin_table,
                                  float* k_cache, float* v_cache, float* partials, int B, int H, int head_dim, int n_splits,
                                  int64_t cache_batch_stride, const int* pos, int max_len, const float* Wo,
-                                 int64_t wo_row_stride, bool oproj, void* stream) {
+                                 int64_t wo_row_stride, bool oproj, void* stream, bool rows = false) {
   if (B == 0 || H == 0) return PDN_OK;
   PDN_CHECK_ARG(qkv && cos_table && sin_table && k_cache && v_cache && partials && pos && max_len > 0,
                 "pdn_decode_attention_f32: bad arguments");
@@ -599,14 +603,18 @@ static int decode_attention_impl(const float* qkv, int64_t qkv_row_stride, const
   const dim3 grid(B * H * NS * C);
   hipStream_t st = (hipStream_t)stream;
 #define ATT_GO(KP, VP, OP)                                                                                              \
-  hipLaunchKernelGGL((decode_attention_kernel<KP, VP, OP>), grid, dim3(256), shm, st, pos, H, head_dim, NS, C, qkv,      \
+  if (rows) ATT_GO_R(KP, VP, OP, true); else ATT_GO_R(KP, VP, OP, false)
+#define ATT_GO_R(KP, VP, OP, R)                                                                                         \
+  hipLaunchKernelGGL((decode_attention_kernel<KP, VP, OP, R>), grid, dim3(256), shm, st, pos, H, head_dim, NS, C, qkv,      \
                      k_cache, v_cache, cos_table, sin_table, Wo, partials, qkv_row_stride, cache_batch_stride, inv_sqrt, \
                      (int)wo_row_stride)
   if (head_dim == 48) { if (oproj) ATT_GO(12, 13, true); else ATT_GO(12, 13, false); }
   else if (head_dim == 64) { if (oproj) ATT_GO(16, 16, true); else ATT_GO(16, 16, false); }
   else { if (oproj) ATT_GO(0, 0, true); else ATT_GO(0, 0, false); }
+#undef ATT_GO_R
 #undef ATT_GO
   PDN_LAUNCH_CHECK();
+  if (rows) pdn_count(PDN_CNT_DECODE_ROWS);
   return PDN_OK;
 }
 
@@ -628,6 +636,24 @@ extern "C" int pdn_decode_attention_oproj_f32(const float* qkv, int64_t qkv_row_
                                               void* stream) {
   return decode_attention_impl(qkv, qkv_row_stride, cos_table, sin_table, k_cache, v_cache, records, B, H, head_dim,
                                n_splits, cache_batch_stride, pos, max_len, Wo, wo_row_stride, true, stream);
+}
+
+// Both with a position per row: pos (B,) int32, row b's new token at position pos[b]; pos[b] < 0: a stopped row
+// (computed at position 0, no cache row written).
+extern "C" int pdn_decode_attention_rows_f32(const float* qkv, int64_t qkv_row_stride, const float* cos_table,
+                                             const float* sin_table, float* k_cache, float* v_cache, float* partials,
+                                             int B, int H, int head_dim, int n_splits, int64_t cache_batch_stride,
+                                             const int* pos, int max_len, void* stream) {
+  return decode_attention_impl(qkv, qkv_row_stride, cos_table, sin_table, k_cache, v_cache, partials, B, H, head_dim,
+                               n_splits, cache_batch_stride, pos, max_len, nullptr, 0, false, stream, true);
+}
+extern "C" int pdn_decode_attention_oproj_rows_f32(const float* qkv, int64_t qkv_row_stride, const float* cos_table,
+                                                   const float* sin_table, float* k_cache, float* v_cache, const float* Wo,
+                                                   int64_t wo_row_stride, float* records, int B, int H, int head_dim,
+                                                   int n_splits, int64_t cache_batch_stride, const int* pos, int max_len,
+                                                   void* stream) {
+  return decode_attention_impl(qkv, qkv_row_stride, cos_table, sin_table, k_cache, v_cache, records, B, H, head_dim,
+                               n_splits, cache_batch_stride, pos, max_len, Wo, wo_row_stride, true, stream, true);
 }
 
 // ---- greedy pick + position tick (model.py:262-268: logits[:, -1, :].argmax(-1, keepdims=True)) ------------------
@@ -677,19 +703,29 @@ extern "C" int pdn_decode_argmax_tick_f32(const float* logits, int64_t row_strid
 // the host can fetch -- and hand to the caller as that token's own array -- while later steps already run.
 // With an embedding table the picked token's row is copied to x_next[b] right away: the next step then starts at its
 // first projection (one launch less per token; model.py:254-256 feeds next_id straight back into the embedding).
+// ROWS: pos is a (B,) array (row b at position pos[b], < 0 = stopped) and the history is indexed by the step counter
+// *step: row b's token goes to (*hist)[*step * B + b], -1 for a stopped row (which is otherwise left alone); a live
+// row whose token is in the stop bitmask (bit tok of stop[], may be null) stops: pos[b] = -1, else pos[b] += 1.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void decode_pick_tick_kernel(const float* __restrict__ vals, const int* __restrict__ args,
                                                                int B, int n, int64_t* __restrict__ ids, int* __restrict__ pos,
                                                                int64_t* const* __restrict__ hist,
                                                                const float* __restrict__ emb, int64_t emb_rs, int D,
-                                                               float* __restrict__ x_next) {
+                                                               float* __restrict__ x_next, int* __restrict__ step,
+                                                               const unsigned* __restrict__ stop) {
   __shared__ float bv[4];
   __shared__ int bi[4];
   __shared__ int64_t chosen;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   DEC_T_BEGIN(2);
-  const int p = pos ? *pos : 0;
+  const int p = ROWS ? *step : (pos ? *pos : 0);
   int64_t* hrow = hist ? *hist + (int64_t)p * B : nullptr;
   for (int b = 0; b < B; ++b) {
+    const int pb = ROWS ? pos[b] : 0;      // (read by every thread before tid 0 rewrites it after the barrier below)
+    if (ROWS && pb < 0) {                  // (uniform)
+      if (tid == 0 && hrow) __hip_atomic_store(hrow + b, (int64_t)-1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      continue;
+    }
     float best = -INFINITY;
     int idx = 0x7fffffff;
     // the first four candidates of the thread with ONE round of loads (n <= 1024: all of them), the rest in a loop
@@ -722,6 +758,7 @@ __global__ __launch_bounds__(256) void decode_pick_tick_kernel(const float* __re
       ids[b] = tok;
       if (hrow) __hip_atomic_store(hrow + b, tok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (may be host memory)
       chosen = tok;
+      if (ROWS) pos[b] = (stop && ((stop[tok >> 5] >> (tok & 31)) & 1u)) ? -1 : pb + 1;
     }
     lds_barrier();
     DEC_T(1);
@@ -731,7 +768,12 @@ __global__ __launch_bounds__(256) void decode_pick_tick_kernel(const float* __re
       lds_barrier();                       // `chosen` is rewritten for the next row
     }
   }
-  if (tid == 0 && pos) *pos = p + 1;
+  if (ROWS) {
+    __syncthreads();                       // (every thread has read *step)
+    if (tid == 0) *step = p + 1;
+  } else if (tid == 0 && pos) {
+    *pos = p + 1;
+  }
   DEC_T(2);
   DEC_T_END();
 }
@@ -744,8 +786,26 @@ extern "C" int pdn_decode_pick_tick_f32(const float* blk_max, const int* blk_arg
   PDN_CHECK_ARG(blk_max && blk_arg && next_ids && n_blocks > 0, "pdn_decode_pick_tick_f32: bad arguments");
   PDN_CHECK_ARG(!history || pos, "pdn_decode_pick_tick_f32: a history needs the position");
   PDN_CHECK_ARG(!emb || (x_next && D > 0), "pdn_decode_pick_tick_f32: an embedding table needs x_next and D");
-  hipLaunchKernelGGL(decode_pick_tick_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, blk_max, blk_arg, B, n_blocks,
-                     next_ids, pos, history, emb, emb_row_stride, D, x_next);
+  hipLaunchKernelGGL(decode_pick_tick_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, blk_max, blk_arg, B,
+                     n_blocks, next_ids, pos, history, emb, emb_row_stride, D, x_next, nullptr, nullptr);
   PDN_LAUNCH_CHECK();
+  return PDN_OK;
+}
+
+// The same with a position per row (see decode_pick_tick_kernel): pos (B,) int32 and step (1,) int32 are required; the
+// history slot is (*history)[*step * B + b]; stop_mask: (V + 31) / 32 words, bit t set = token t stops its row (may be
+// null: no stop ids); then *step += 1.
+extern "C" int pdn_decode_pick_tick_rows_f32(const float* blk_max, const int* blk_arg, int B, int n_blocks,
+                                             int64_t* next_ids, int* pos, int* step, const unsigned* stop_mask,
+                                             int64_t* const* history, const float* emb, int64_t emb_row_stride, int D,
+                                             float* x_next, void* stream) {
+  if (B == 0) return PDN_OK;
+  PDN_CHECK_ARG(blk_max && blk_arg && next_ids && n_blocks > 0 && pos && step,
+                "pdn_decode_pick_tick_rows_f32: bad arguments");
+  PDN_CHECK_ARG(!emb || (x_next && D > 0), "pdn_decode_pick_tick_rows_f32: an embedding table needs x_next and D");
+  hipLaunchKernelGGL(decode_pick_tick_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, blk_max, blk_arg, B,
+                     n_blocks, next_ids, pos, history, emb, emb_row_stride, D, x_next, step, stop_mask);
+  PDN_LAUNCH_CHECK();
+  pdn_count(PDN_CNT_DECODE_ROWS);
   return PDN_OK;
 }

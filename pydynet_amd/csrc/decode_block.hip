@@ -24,7 +24,9 @@
 // same registers hold the K / V rows of a range role), PW = rows of Wo per thread.  EXACT: the shape needs exactly QP
 // steps and PW rows -- every weight load is unconditional (a zero-initialised register overwritten by a conditional
 // load costs a copy that WAITS for the load: the compiler's phi).
-template <int F4, int VPRE, int QP, int PW, bool EXACT>
+// ROWS: pos_ptr is a (B,) array, row b at its own position pos_ptr[b]; a row with pos_ptr[b] < 0 has stopped: it is
+// computed at position 0 (one key, nothing cached is read) and its cache rows are not written.
+template <int F4, int VPRE, int QP, int PW, bool EXACT, bool ROWS>
 __global__ __launch_bounds__(256) void decode_block_kernel(
     const int* __restrict__ pos_ptr, const float* __restrict__ base, const float* __restrict__ parts, int D, int R,
     const float* __restrict__ norm_w, const float* __restrict__ Wqkv, int64_t w_bs,
@@ -41,7 +43,8 @@ __global__ __launch_bounds__(256) void decode_block_kernel(
   DEC_T_BEGIN(5);
   // (the position: requested FIRST and as a vector load -- a scalar load would be sunk to its first use by the
   //  compiler and cost a whole round trip in the middle of the issue phase; everything about the keys waits for it)
-  const int pos_v = __hip_atomic_load(pos_ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int pos_v = __hip_atomic_load(ROWS ? pos_ptr + blockIdx.x / (C * (NS + 1) * H) : pos_ptr, __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT);
   const int ci = blockIdx.x % C, role = (blockIdx.x / C) % (NS + 1), bh = blockIdx.x / (C * (NS + 1)), b = bh / H, h = bh % H;
   const bool isnew = role == NS;           // (uniform)
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -68,7 +71,9 @@ __global__ __launch_bounds__(256) void decode_block_kernel(
     if (!EXACT) wa[i] = z4;
     if (EXACT || i < nsteps) wa[i] = *reinterpret_cast<const float4*>(wq_t + ((i < nsteps - 1 || k < D) ? (unsigned)(i * SL * w_rs) : 0u));
   }
-  const int pos = __builtin_amdgcn_readfirstlane(pos_v);           // (first use: by now the load is back)
+  const int pos_u = __builtin_amdgcn_readfirstlane(pos_v);         // (first use: by now the load is back)
+  const bool keep = !ROWS || pos_u >= 0;   // (ROWS: a stopped row writes no cache row)
+  const int pos = ROWS ? max(pos_u, 0) : pos_u;
   const int chunk = (pos + NS - 1) / NS, t0 = isnew ? 0 : role * chunk, t1 = isnew ? 0 : min(pos, t0 + chunk);
   float* kb = kc + (int64_t)b * cbs + (unsigned)(h * HD);
   float* vb = vc + (int64_t)b * cbs + (unsigned)(h * HD);
@@ -181,7 +186,7 @@ __global__ __launch_bounds__(256) void decode_block_kernel(
       const float2 k = *reinterpret_cast<const float2*>(ks + 2 * tid);
       const float2 kr = make_float2(k.x * rc - k.y * rs, k.x * rs + k.y * rc);
       *reinterpret_cast<float2*>(ks + 2 * tid) = kr;
-      if (ci == 0) {
+      if (ci == 0 && keep) {
         *reinterpret_cast<float2*>(kb + (unsigned)(pos * D + 2 * tid)) = kr;
         *reinterpret_cast<float2*>(vb + (unsigned)(pos * D + 2 * tid)) = *reinterpret_cast<const float2*>(vs + 2 * tid);
       }
@@ -345,13 +350,14 @@ extern "C" int64_t pdn_decode_block_lds_bytes(int D, int H, int head_dim, int n_
 // to x_out; Wqkv: three (D, D) matrices (in, out) w_block_stride floats apart, rows w_row_stride apart; cos / sin
 // tables (max_len, head_dim / 2); caches (B, max_len, H, head_dim) with cache_batch_stride between sequences; Wo (D, D).
 // records: (B, n_ranges + 1, H, 4 + D), the last one per head being the new token's own partial.
-extern "C" int pdn_decode_block_f32(const float* base, int64_t base_row_stride, const float* parts, int n_parts,
-                                    int64_t parts_row_stride, float* x_out, int64_t x_out_row_stride, const float* norm_w,
-                                    float eps, const float* Wqkv, int64_t w_row_stride, int64_t w_block_stride,
-                                    const float* cos_table, const float* sin_table, float* k_cache, float* v_cache,
-                                    int64_t cache_batch_stride, const int* pos, int max_len, const float* Wo,
-                                    int64_t wo_row_stride, float* records, int B, int H, int head_dim, int n_ranges,
-                                    void* stream) {
+template <bool ROWS>
+static int decode_block_impl(const float* base, int64_t base_row_stride, const float* parts, int n_parts,
+                             int64_t parts_row_stride, float* x_out, int64_t x_out_row_stride, const float* norm_w,
+                             float eps, const float* Wqkv, int64_t w_row_stride, int64_t w_block_stride,
+                             const float* cos_table, const float* sin_table, float* k_cache, float* v_cache,
+                             int64_t cache_batch_stride, const int* pos, int max_len, const float* Wo,
+                             int64_t wo_row_stride, float* records, int B, int H, int head_dim, int n_ranges,
+                             void* stream) {
   if (B == 0) return PDN_OK;
   const int D = H * head_dim, NS = n_ranges;
   PDN_CHECK_ARG(base && x_out && norm_w && Wqkv && cos_table && sin_table && k_cache && v_cache && pos && Wo && records &&
@@ -388,7 +394,7 @@ extern "C" int pdn_decode_block_f32(const float* base, int64_t base_row_stride, 
   hipStream_t st = (hipStream_t)stream;
   const float inv_sqrt = 1.f / sqrtf((float)head_dim);
 #define BLK_GO(F4, VP, QP, PW, EX)                                                                                      \
-  hipLaunchKernelGGL((decode_block_kernel<F4, VP, QP, PW, EX>), grid, dim3(256), shm, st, pos, base, parts, D, n_parts,  \
+  hipLaunchKernelGGL((decode_block_kernel<F4, VP, QP, PW, EX, ROWS>), grid, dim3(256), shm, st, pos, base, parts, D, n_parts,  \
                      norm_w, Wqkv, w_block_stride, (int)w_row_stride, H, NS, C, eps, x_out, cos_table, sin_table,       \
                      k_cache, v_cache, cache_batch_stride, Wo, (int)wo_row_stride, records, (int)base_row_stride,       \
                      (int)parts_row_stride, (int)x_out_row_stride, inv_sqrt, scf)
@@ -404,5 +410,34 @@ extern "C" int pdn_decode_block_f32(const float* base, int64_t base_row_stride, 
   }
 #undef BLK_GO
   PDN_LAUNCH_CHECK();
+  if (ROWS) pdn_count(PDN_CNT_DECODE_ROWS);
   return PDN_OK;
+}
+
+extern "C" int pdn_decode_block_f32(const float* base, int64_t base_row_stride, const float* parts, int n_parts,
+                                    int64_t parts_row_stride, float* x_out, int64_t x_out_row_stride, const float* norm_w,
+                                    float eps, const float* Wqkv, int64_t w_row_stride, int64_t w_block_stride,
+                                    const float* cos_table, const float* sin_table, float* k_cache, float* v_cache,
+                                    int64_t cache_batch_stride, const int* pos, int max_len, const float* Wo,
+                                    int64_t wo_row_stride, float* records, int B, int H, int head_dim, int n_ranges,
+                                    void* stream) {
+  return decode_block_impl<false>(base, base_row_stride, parts, n_parts, parts_row_stride, x_out, x_out_row_stride,
+                                  norm_w, eps, Wqkv, w_row_stride, w_block_stride, cos_table, sin_table, k_cache, v_cache,
+                                  cache_batch_stride, pos, max_len, Wo, wo_row_stride, records, B, H, head_dim, n_ranges,
+                                  stream);
+}
+
+// The same with a position per row: pos (B,) int32, row b's new token at position pos[b] (keys [0, pos[b]], its own
+// cache slot and RoPE row); pos[b] < 0: a stopped row -- its records are those of position 0 and no cache row is written.
+extern "C" int pdn_decode_block_rows_f32(const float* base, int64_t base_row_stride, const float* parts, int n_parts,
+                                         int64_t parts_row_stride, float* x_out, int64_t x_out_row_stride,
+                                         const float* norm_w, float eps, const float* Wqkv, int64_t w_row_stride,
+                                         int64_t w_block_stride, const float* cos_table, const float* sin_table,
+                                         float* k_cache, float* v_cache, int64_t cache_batch_stride, const int* pos,
+                                         int max_len, const float* Wo, int64_t wo_row_stride, float* records, int B, int H,
+                                         int head_dim, int n_ranges, void* stream) {
+  return decode_block_impl<true>(base, base_row_stride, parts, n_parts, parts_row_stride, x_out, x_out_row_stride,
+                                 norm_w, eps, Wqkv, w_row_stride, w_block_stride, cos_table, sin_table, k_cache, v_cache,
+                                 cache_batch_stride, pos, max_len, Wo, wo_row_stride, records, B, H, head_dim, n_ranges,
+                                 stream);
 }

@@ -236,25 +236,40 @@ extern "C" int pdn_sample_rows_f32(const float* logits, int64_t row_stride, int 
 // ONE workgroup walks the B rows (B <= 8 on the graph path), so that "read *pos, then advance it" is race free; each row
 // is drawn with counter (*pos, b).  Token b goes to ids[b], to the history slot (*hist)[*pos * B + b] and its embedding
 // row to x_next[b], exactly as the greedy pick does.
+// ROWS: the per-row form of decode_pick_tick_kernel<true> (csrc/decode.hip): row b is drawn with counter (pos[b], b),
+// the history slot is (*hist)[*step * B + b] (-1 for a stopped row, pos[b] < 0, which is otherwise left alone), a
+// token in the stop bitmask stops its row (pos[b] = -1), else pos[b] += 1; then *step += 1.
+template <bool ROWS>
 __global__ __launch_bounds__(SMP_THREADS) void decode_sample_tick_kernel(
     const float* __restrict__ logits, int64_t rs, int B, int V, const SampleParams* __restrict__ prm,
     int64_t* __restrict__ ids, int* __restrict__ pos, int64_t* const* __restrict__ hist, const float* __restrict__ emb,
-    int64_t emb_rs, int D, float* __restrict__ x_next) {
+    int64_t emb_rs, int D, float* __restrict__ x_next, int* __restrict__ step, const unsigned* __restrict__ stop) {
   __shared__ SmpShared s;
   const int tid = threadIdx.x;
-  const int p = pos ? *pos : 0;
+  const int p = ROWS ? *step : (pos ? *pos : 0);
   const SampleParams pr = *prm;
   int64_t* hrow = hist ? *hist + (int64_t)p * B : nullptr;
   for (int b = 0; b < B; ++b) {
-    const int64_t tok = smp_row(logits + (int64_t)b * rs, V, pr, (uint64_t)p, (uint64_t)b, s);
+    const int pb = ROWS ? pos[b] : p;      // (read by every thread before the barriers of smp_row)
+    if (ROWS && pb < 0) {                  // (uniform)
+      if (tid == 0 && hrow) __hip_atomic_store(hrow + b, (int64_t)-1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      continue;
+    }
+    const int64_t tok = smp_row(logits + (int64_t)b * rs, V, pr, (uint64_t)pb, (uint64_t)b, s);
     if (tid == 0) {
       ids[b] = tok;
       if (hrow) __hip_atomic_store(hrow + b, tok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (may be host memory)
+      if (ROWS) pos[b] = (stop && ((stop[tok >> 5] >> (tok & 31)) & 1u)) ? -1 : pb + 1;
     }
     if (emb) {
       const float* er = emb + tok * emb_rs;
       for (int d = tid; d < D; d += SMP_THREADS) x_next[(int64_t)b * D + d] = er[d];
     }
+  }
+  if (ROWS) {
+    __syncthreads();                       // (every thread has read *step)
+    if (tid == 0) *step = p + 1;
+    return;
   }
   // every thread read *pos before the first barrier of smp_row
   if (tid == 0 && pos) *pos = p + 1;
@@ -268,9 +283,28 @@ extern "C" int pdn_decode_sample_tick_f32(const float* logits, int64_t row_strid
                 "pdn_decode_sample_tick_f32: bad arguments (B %d, V %d)", B, V);
   PDN_CHECK_ARG(!history || pos, "pdn_decode_sample_tick_f32: a history needs the position");
   PDN_CHECK_ARG(!emb || (x_next && D > 0), "pdn_decode_sample_tick_f32: an embedding table needs x_next and D");
-  hipLaunchKernelGGL(decode_sample_tick_kernel, dim3(1), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits, row_stride, B,
-                     V, (const SampleParams*)params, next_ids, pos, history, emb, emb_row_stride, D, x_next);
+  hipLaunchKernelGGL(decode_sample_tick_kernel<false>, dim3(1), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
+                     row_stride, B, V, (const SampleParams*)params, next_ids, pos, history, emb, emb_row_stride, D, x_next,
+                     nullptr, nullptr);
   PDN_LAUNCH_CHECK();
   pdn_count(PDN_CNT_SAMPLE);
+  return PDN_OK;
+}
+
+// The same with a position per row (decode_sample_tick_kernel<true>): pos (B,) and step (1,) int32 are required.
+extern "C" int pdn_decode_sample_tick_rows_f32(const float* logits, int64_t row_stride, int B, int V, const void* params,
+                                               int64_t* next_ids, int* pos, int* step, const unsigned* stop_mask,
+                                               int64_t* const* history, const float* emb, int64_t emb_row_stride, int D,
+                                               float* x_next, void* stream) {
+  if (B == 0) return PDN_OK;
+  PDN_CHECK_ARG(logits && params && next_ids && pos && step && B > 0 && V > 0 && V <= (1 << 23) && row_stride >= V,
+                "pdn_decode_sample_tick_rows_f32: bad arguments (B %d, V %d)", B, V);
+  PDN_CHECK_ARG(!emb || (x_next && D > 0), "pdn_decode_sample_tick_rows_f32: an embedding table needs x_next and D");
+  hipLaunchKernelGGL(decode_sample_tick_kernel<true>, dim3(1), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
+                     row_stride, B, V, (const SampleParams*)params, next_ids, pos, history, emb, emb_row_stride, D, x_next,
+                     step, stop_mask);
+  PDN_LAUNCH_CHECK();
+  pdn_count(PDN_CNT_SAMPLE);
+  pdn_count(PDN_CNT_DECODE_ROWS);
   return PDN_OK;
 }

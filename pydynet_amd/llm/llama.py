@@ -20,7 +20,8 @@ from .. import nn
 from ..autograd import is_grad_enable
 from ..core import Tensor, fused
 from ..special import zeros
-from .sampling import check_args as check_sampling_args, params_bytes, params_buffer, sample_next
+from .sampling import (check_args as check_sampling_args, params_bytes, params_buffer, sample_next,
+                       sample_next_rows)
 
 
 def compute_cos_sin_cache(head_dim: int, max_seq_len: int, base: int = 10000, dtype=None):
@@ -135,6 +136,32 @@ class Attention(nn.Module):
         return fused.linear(out, self.O.weight, None, residual)
 
 
+    def step_rows(self, x, pos, freqs_cos, freqs_sin, residual=None):
+        """One new token per row, row b at its own position pos[b] (Llama.generate_ragged; pos[b] < 0: a stopped row,
+        computed at position 0 and its cache left alone).  Built from the operators above: RoPE with the cos / sin row of
+        each row's position, the cache written at (b, pos[b]), attention over the cache with -inf for keys j > pos[b]."""
+        B = x.shape[0]
+        H, hd = self.n_heads, self.head_dim
+        p = np.maximum(pos, 0)
+        xq = self.Q(x).reshape(B, 1, H, hd)
+        xk = self.K(x).reshape(B, 1, H, hd)
+        xv = self.V(x).reshape(B, 1, H, hd)
+        # the B rows as one sequence of B positions: RoPE takes one (cos, sin) row per position
+        cos, sin = freqs_cos[p], freqs_sin[p]
+        xq = fused.rope(xq.reshape(1, B, H, hd), cos, sin).reshape(B, 1, H, hd)
+        xk = fused.rope(xk.reshape(1, B, H, hd), cos, sin).reshape(B, 1, H, hd)
+        for b in np.flatnonzero(pos >= 0):
+            self.cache_k[int(b), int(p[b])] = xk[int(b), 0]
+            self.cache_v[int(b), int(p[b])] = xv[int(b), 0]
+        T = int(p.max()) + 1
+        mask = np.where(np.arange(T)[None, :] > p[:, None], -np.inf, 0.0).astype(xq.dtype).reshape(B, 1, 1, T)
+        out = fused.attention(xq, self.cache_k[:B, :T], self.cache_v[:B, :T], causal=False, mask=mask)
+        out = out.reshape(B, 1, -1)
+        if residual is None:
+            return self.O(out)
+        return fused.linear(out, self.O.weight, None, residual)
+
+
 class TransformerBlock(nn.Module):
     def __init__(self, dim, n_heads, ffn_dim, max_seq_len, max_batch_size=None, dtype=None):
         super().__init__()
@@ -146,6 +173,10 @@ class TransformerBlock(nn.Module):
     def forward(self, x, start_pos, mask, freqs_cos, freqs_sin):
         # z = x + attn(norm(x)); out = z + ffn(norm(z)) -- both adds ride in the GEMM epilogues
         z = self.attention(self.input_norm(x), start_pos, mask, freqs_cos, freqs_sin, residual=x)
+        return self.ffn(self.post_attn_norm(z), residual=z)
+
+    def step_rows(self, x, pos, freqs_cos, freqs_sin):
+        z = self.attention.step_rows(self.input_norm(x), pos, freqs_cos, freqs_sin, residual=x)
         return self.ffn(self.post_attn_norm(z), residual=z)
 
 
@@ -244,16 +275,131 @@ class Llama(nn.Module):
                 next_id = logits.argmax(-1, True) if sampling is None else sample_next(logits, pos, *sampling)
             yield next_id
 
+    def generate_ragged(self, prompts, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=()):
+        """Generation for B prompts of different lengths, every row at its own position.  Yields a (B, 1) int64 Tensor
+        per step: step i holds, for row b, the token at position len_b + i.  `max_new_tokens` is the number of NEW tokens
+        per row -- `generate`'s second argument is an end position instead: for equal lengths L,
+        `generate_ragged(rows, n)` yields what `generate(ids, L + n)` yields.  Sampling follows llm/sampling.py with
+        the row's own position as the counter: row b's token at position t is drawn with counter (t, b).
+        `stop_ids`: once row b yields one of them it yields -1 at every later step and its position stops advancing
+        (its KV cache is no longer written); the iterator ends after the step at which every row has stopped, or after
+        `max_new_tokens` steps.  Every argument is checked here (ValueError), before anything runs."""
+        temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
+        V = self.vocab_size
+        if int(max_new_tokens) != max_new_tokens or max_new_tokens < 0:
+            raise ValueError(f"max_new_tokens must be a non-negative integer, got {max_new_tokens}")
+        max_new_tokens = int(max_new_tokens)
+        rows = [np.asarray(p.numpy() if isinstance(p, Tensor) else p).reshape(-1) for p in prompts]
+        cache = self.layers[0].attention.cache_k
+        if not rows:
+            raise ValueError("generate_ragged needs at least one prompt")
+        if len(rows) > cache.shape[0]:
+            raise ValueError(f"batch {len(rows)} exceeds the KV cache's max_batch_size {cache.shape[0]}")
+        limit = min(cache.shape[1], self.freqs_cos.shape[0])     # positions the cache / RoPE table hold
+        for b, r in enumerate(rows):
+            if r.size == 0:
+                raise ValueError(f"prompt {b} is empty")
+            if r.dtype.kind not in "iu" or r.min() < 0 or r.max() >= V:
+                raise ValueError(f"prompt {b}: token ids must be integers in [0, {V})")
+            last = r.size + max_new_tokens - 1                   # (the position of the row's last decode step)
+            if r.size > cache.shape[1] or (max_new_tokens > 1 and last >= limit):
+                raise ValueError(f"prompt {b}: its last position {last} is outside the KV cache / RoPE table "
+                                 f"(max_seq_len {cache.shape[1]}, {self.freqs_cos.shape[0]} RoPE rows)")
+        stops = np.asarray(sorted({int(t) for t in stop_ids}), np.int64)
+        if stops.size and (stops.min() < 0 or stops.max() >= V):
+            raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
+        sampling = (temperature, top_k, top_p, seed) if temperature > 0 else None
+        return self._generate_ragged([r.astype(np.int64) for r in rows], max_new_tokens, sampling, stops)
+
+    def _generate_ragged(self, rows, n, sampling, stops):
+        B = len(rows)
+        lens = np.array([r.size for r in rows], np.int64)
+        if n == 0:
+            return
+        nxt = self._prompt_rows(rows, lens, sampling)
+        live = np.ones(B, bool)
+        if stops.size:
+            live = ~np.isin(nxt.numpy().reshape(-1), stops)
+        yield nxt
+        fast = (Llama.fast_decode and nxt.device.is_hip and not self._train
+                and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
+        if fast:
+            from .. import hipnp as hp
+            mask = np.zeros(-(-self.vocab_size // 32), np.uint32)
+            np.bitwise_or.at(mask, stops >> 5, np.uint32(1) << (stops & 31).astype(np.uint32))
+            # tokens by STEP: slot i holds step i of every row (-1 for a stopped row), so "not written yet" is its own
+            # value; two slots beyond the last step for the runs of a graph capture
+            run = {"lens": lens, "live": live, "sampling": sampling, "stop_mask": mask.view(np.int32),
+                   "hist": hp.Mailbox(n + 2, (B, 1), unset=np.iinfo(np.int64).min)}
+        ids = nxt.data
+        for i in range(1, n):
+            if not live.any():
+                return
+            if fast:
+                run["live"] = live
+                ids = self._decode_step_rows(ids, run, i, more=i + 1 < n)
+                nxt = Tensor(ids, dtype=np.int64, device=nxt.device, copy=False)
+            else:
+                nxt = self._step_module_rows(nxt, np.where(live, lens + i, -1), sampling)
+            if stops.size:
+                yield nxt
+                tok = nxt.numpy().reshape(-1)                    # (fast path: a poll of the mapped history slot)
+                live = live & (tok >= 0) & ~np.isin(tok, stops)
+                continue
+            yield nxt
+
+    def _prompt_rows(self, rows, lens, sampling):
+        """The prompt pass of a ragged generation: the prompts right-padded to the longest and run as one batched
+        causal pass from position 0 (no real token attends to a pad after it); each row's logits at its last real token,
+        gathered before lm_head.  The cache slots the pads wrote, [len_b, L_max) of row b, are put back as they were: a
+        row's cache is written at its own positions only.  Returns the first token of every row, (B, 1) int64."""
+        B, Lm, lo = len(rows), int(lens.max()), int(lens.min())
+        ids = np.zeros((B, Lm), np.int64)
+        for b, r in enumerate(rows):
+            ids[b, :r.size] = r
+        caches = [c for layer in self.layers for c in (layer.attention.cache_k, layer.attention.cache_v)]
+        saved = [c.data[:B, lo:Lm].copy() for c in caches] if lo < Lm else []
+        dev = self.tok_embedding.weight.device
+        h = self._forward_hidden(Tensor(ids, dtype=np.int64, device=dev), 0)
+        last = h.reshape(B * Lm, self.embed_dim)[np.arange(B) * Lm + lens - 1].reshape(B, 1, self.embed_dim)
+        logits = self.lm_head(last)[:, -1, :]
+        for c, keep in zip(caches, saved):
+            for b in np.flatnonzero(lens < Lm):
+                c.data[int(b), int(lens[b]):Lm] = keep[int(b), int(lens[b]) - lo:]
+        if sampling is None:
+            return logits.argmax(-1, True)
+        return sample_next_rows(logits, lens, *sampling)
+
+    def _step_module_rows(self, ids, pos, sampling):
+        """One ragged decode step on the tape-node operators (the `cpu` device, fast_decode = False, training mode,
+        other dtypes): row b's token at position pos[b] (-1: a stopped row, which yields -1).  The NumPy statement of what
+        the per-row kernels compute."""
+        tok = ids.data if pos.min() >= 0 else np.maximum(ids.numpy(), 0)      # (a stopped row's -1 is no token)
+        p = np.maximum(pos, 0)
+        h = self.tok_embedding(Tensor(tok, dtype=np.int64, device=ids.device) if tok is not ids.data else ids)
+        for layer in self.layers:
+            h = layer.step_rows(h, pos, self.freqs_cos, self.freqs_sin)
+        logits = self.lm_head(self.norm(h))[:, -1, :]
+        nxt = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, p, *sampling)
+        if pos.min() >= 0:
+            return nxt
+        out = nxt.numpy().reshape(-1, 1)
+        out[pos < 0] = -1
+        return Tensor(out, dtype=np.int64, device=ids.device)
+
     # -- decode fast path (SURVEY 8f-1) -----------------------------------------------------------
     graph_decode = True     # class switch: False issues the step's launches one by one instead of replaying a hipGraph
     decode_ahead = True     # class switch: False never queues the next step before the caller asked for it
     fused_decode = 2        # class switch: launches per layer = 2 (q|k|v inside the attention kernel), 1 -> 3, 0 / False -> 5
 
-    def _decode_plan(self, B, sampling=False):
+    def _decode_plan(self, B, sampling=False, ragged=False):
         """Buffers and weight views of the graph-replayable decode step (csrc/decode.hip), or None when the
         model's shapes / layout are outside what those kernels take (then the generic launches below run).
         `sampling`: the step ends in the sample tick (csrc/sample.hip) instead of the greedy pick; its parameters live in
-        the plan's `params` buffer, so new values never re-capture."""
+        the plan's `params` buffer, so new values never re-capture.
+        `ragged` (generate_ragged): every row at its own position -- `pos` is (B,) int32 (-1: a stopped row), the
+        *_rows_f32 entries run, the tick indexes the history by the device step counter `step` and stops rows whose
+        token is set in the `stop` bitmask."""
         from .. import hipnp as hp, _lib
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
         st = getattr(self, "_decode_st", None)
@@ -269,7 +415,8 @@ class Llama(nn.Module):
                                             f.gate.weight, f.up.weight, f.down.weight, layer.input_norm.weight,
                                             layer.post_attn_norm.weight)]
         key = (B, hp._state["device"], int(Llama.fused_decode or 0), os.environ.get("PDN_DECODE_SPLITS", ""),
-               self.layers[0].attention.cache_k.shape[1], tuple(ptrs), bool(sampling))   # (the addresses: no hash to collide)
+               self.layers[0].attention.cache_k.shape[1], tuple(ptrs), bool(sampling),   # (the addresses: no hash to collide)
+               bool(ragged))
         if st is not None and st["key"] == key:
             return st if st["ok"] else None
         if st is not None:
@@ -289,7 +436,7 @@ class Llama(nn.Module):
                     break
                 packs.append((qkv, gu))
             ok = ok and self.lm_head.weight.data.is_contiguous() and self.tok_embedding.weight.data.is_contiguous()
-        st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling)}
+        st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged)}
         if ok:
             nblk = _lib.lib().query("pdn_decode_gemv_blocks", V)
             # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
@@ -334,6 +481,9 @@ class Llama(nn.Module):
             if st["fused"]:
                 st.update(J=J, recs=hp.empty((B, (max(ns, st["ns_max"]) + 1) * H * (4 + D)), np.float32), dparts=hp.empty((B, J * D), np.float32),
                           xa=hp.empty((B, D), np.float32), xb=hp.empty((B, D), np.float32))
+            if ragged:
+                st.update(pos=hp.zeros((B,), np.int32), step=hp.zeros((1,), np.int32),
+                          stop=hp.zeros((-(-V // 32),), np.int32), run=None, host_step=None)
             self._decode_ws = {"logits": st["logits"], "x": st["x"]}
         self._decode_st = st
         return st if ok else None
@@ -355,6 +505,8 @@ class Llama(nn.Module):
         hd = D // H
         x, qkv, att, gu, logits = (st[n]._ptr for n in ("x", "qkv", "att", "gu", "logits"))
         pos = st["pos"]._ptr
+        # (ragged plans: the same launches through the entries with a position per row)
+        rows = "rows_" if st["ragged"] else ""
         # (x = embedding rows of the current ids: left there by the previous step's pick kernel, or by
         #  `_decode_gather` when the ids came from outside)
         emb = self.tok_embedding.weight.data
@@ -372,7 +524,7 @@ class Llama(nn.Module):
                 if st["block"]:
                     # x = previous block's h + its feed-forward records (-> xa); q | k | v, RoPE, cache append, attention
                     # and each head's rows of Wo in one launch: records of ns key ranges + the new key
-                    L.call("pdn_decode_block_f32", x if li == 0 else xb, D, None if li == 0 else dparts, 0 if li == 0 else J,
+                    L.call(f"pdn_decode_block_{rows}f32", x if li == 0 else xb, D, None if li == 0 else dparts, 0 if li == 0 else J,
                            J * D, xa, D, nrm.weight.data._ptr, nrm.eps, wqkv._ptr, D, wqkv._strides[0], cos, sin, ck._ptr,
                            cv._ptr, ck._strides[0], pos, ck.shape[1], a.O.weight.data._ptr, D, recs, B, H, hd, ns, s)
                     nrm = layer.post_attn_norm
@@ -388,7 +540,7 @@ class Llama(nn.Module):
                     L.call("pdn_decode_gemv_sum_f32", xb, D, dparts, J, J * D, xa, D, nrm.weight.data._ptr, nrm.eps,
                            wqkv._ptr, D, D, wqkv._strides[0], None, qkv, 3 * D, B, D, 3 * D, None, None, s)
                 # RoPE, cache append, attention over [0, pos], each head times its rows of Wo -> records
-                L.call("pdn_decode_attention_oproj_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, a.O.weight.data._ptr, D,
+                L.call(f"pdn_decode_attention_oproj_{rows}f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, a.O.weight.data._ptr, D,
                        recs, B, H, hd, ns, ck._strides[0], pos, ck.shape[1], s)
                 # h = x + merged records (-> xb); 32 hidden units per workgroup: gate | up, SwiGLU, their rows of Wdown
                 nrm = layer.post_attn_norm
@@ -408,7 +560,7 @@ class Llama(nn.Module):
             L.call("pdn_decode_gemv_f32", x, D, layer.input_norm.weight.data._ptr, layer.input_norm.eps, wqkv._ptr, D, D,
                    wqkv._strides[0], None, None, 0, qkv, 3 * D, B, D, 3 * D, 0, 0, 0, None, None, s)
             # RoPE of q / k, cache append, attention over positions [0, pos]
-            L.call("pdn_decode_attention_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, att, B, H, hd, st["ns"], cbs, pos,
+            L.call(f"pdn_decode_attention_{rows}f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, att, B, H, hd, st["ns"], cbs, pos,
                    ck.shape[1], s)
             wo, wd = a.O.weight.data, f.down.weight.data
             # x += merge(att partials) @ Wo: the key-range partials are merged while the row is staged
@@ -431,6 +583,16 @@ class Llama(nn.Module):
         tick over the full logit rows with counter (*pos, b); either stores the token and its embedding row, *pos += 1."""
         from .. import _lib
         L, emb, D, B = _lib.lib(), self.tok_embedding.weight.data, self.embed_dim, st["B"]
+        if st["ragged"]:
+            pos, step, stop = st["pos"]._ptr, st["step"]._ptr, st["stop"]._ptr
+            if st["sampling"]:
+                L.call("pdn_decode_sample_tick_rows_f32", st["logits"]._ptr, self.vocab_size, B, self.vocab_size,
+                       st["params"]._ptr, st["ids"]._ptr, pos, step, stop, st["hist_ptr"]._ptr, emb._ptr, emb._strides[0], D,
+                       st["x"]._ptr, s)
+            else:
+                L.call("pdn_decode_pick_tick_rows_f32", st["cand_v"]._ptr, st["cand_i"]._ptr, B, st["cand_v"].shape[1],
+                       st["ids"]._ptr, pos, step, stop, st["hist_ptr"]._ptr, emb._ptr, emb._strides[0], D, st["x"]._ptr, s)
+            return
         if st["sampling"]:
             L.call("pdn_decode_sample_tick_f32", st["logits"]._ptr, self.vocab_size, B, self.vocab_size, st["params"]._ptr,
                    st["ids"]._ptr, st["pos"]._ptr, st["hist_ptr"]._ptr, emb._ptr, emb._strides[0], D, st["x"]._ptr, s)
@@ -592,4 +754,160 @@ class Llama(nn.Module):
             return ws["logits"].argmax(-1, keepdims=True)
         out = hp.empty((B, 1), np.int64)              # (the sampled form of the pick: counter (pos, b))
         L.call("pdn_sample_rows_f32", logits, V, B, V, params_buffer(*sampling)._ptr, pos, out._ptr, st)
+        return out
+
+    # -- ragged decode (generate_ragged): every row at its own position ------------------------------
+    def _decode_step_rows(self, ids, run, i: int, more: bool = False):
+        """Step i >= 1 of a ragged generation: row b's token at position lens[b] + i, rows the host knows to have stopped
+        at -1.  ids: (B, 1) int64 device array (the previous step's tokens); returns this step's tokens, (B, 1) int64, -1
+        for rows stopped before it.  The graph path of `_decode_step_hip` with the *_rows_f32 launches: the positions, the
+        step counter and the stop bitmask live on the device, the history is indexed by the step (`run["hist"]`), and the
+        range count follows the furthest row, max_b lens[b] + i, which the host knows without a device read."""
+        from .. import hipnp as hp, _lib
+        lens, live, sampling = run["lens"], run["live"], run["sampling"]
+        B, top = len(lens), int(lens.max()) + i
+        cache = self.layers[0].attention.cache_k
+        limit = min(cache.shape[1], self.freqs_cos.shape[0])
+        pos = np.where(live, lens + i, -1).astype(np.int32)
+        st = self._decode_plan(B, sampling is not None, ragged=True)
+        if st is None:
+            out = self._decode_step_generic_rows(ids, pos, sampling)
+            if pos.min() >= 0:
+                return out
+            tok = out.get().reshape(B, 1)
+            tok[pos < 0] = -1
+            return hp.asarray(tok)
+        ahead, st["ahead"] = st.get("ahead"), None
+        if ahead is not None:
+            if ahead[0] == (id(run), i) and ahead[1] is ids and st["run"] is run:   # exactly this step, queued ahead
+                out = st["last_out"] = ahead[2]
+                if more and Llama.decode_ahead and top + 1 < limit:
+                    self._decode_ahead_rows(st, run, i + 1)
+                return out
+            hp.synchronize()                                     # a different request: the queued step is void
+            st["host_step"] = st["last_out"] = None
+        if st["run"] is not run or st["host_step"] != i:
+            st["run"] = run                                      # (later steps: the device advances pos and step itself)
+            st["pos"][...] = pos
+            st["step"][...] = np.int32(i)
+            st["stop"][...] = run["stop_mask"]
+            st["hist_ptr"][...] = np.int64(run["hist"]._ptr)
+        if st["params_val"] != sampling:
+            if sampling is not None:
+                st["params"][...] = params_bytes(*sampling)
+            st["params_val"] = sampling
+        if ids is not st["ids"] and ids is not st.get("last_out"):
+            # (a stopped row's -1 is no token: any valid id stands in, its row computes nothing that is kept)
+            st["ids"][...] = np.maximum(ids.get(), 0) if isinstance(ids, hp.readback_array) else ids
+            self._decode_gather(st)
+        ns = self._decode_ns(st, top)
+        g = False if st["nograph"] else st["graphs"].get((ns, st["sampling"]))
+        if g is None and Llama.graph_decode and top + 2 < limit:
+            # capture once, as in `_decode_step_hip`: the capture's two real runs store into a scratch history; the
+            # positions, the step counter and the ids are put back afterwards
+            keep = st["ids"].copy()
+            scratch = hp.Mailbox(run["hist"].n, (B, 1), unset=run["hist"].unset)
+            st["hist_ptr"][...] = np.int64(scratch._ptr)
+            try:
+                g = hp.Graph()
+                g.capture(lambda: self._decode_launches(st, ns))
+                st["graphs"][(ns, st["sampling"])] = g
+            except _lib.HipLibraryError as e:
+                if e.code != -2:
+                    raise
+                st["nograph"], g = True, False
+            hp.synchronize()
+            st["hist_ptr"][...] = np.int64(run["hist"]._ptr)
+            st["pos"][...] = pos
+            st["step"][...] = np.int32(i)
+            st["ids"][...] = keep
+            self._decode_gather(st)
+        if g:
+            g.replay()
+        else:
+            self._decode_launches(st, ns)
+        st["host_step"] = i + 1
+        out = st["last_out"] = run["hist"].slot(i)
+        if more and Llama.decode_ahead and (st["graphs"] or st["nograph"]) and top + 1 < limit:
+            self._decode_ahead_rows(st, run, i + 1)
+        return out
+
+    def _decode_ahead_rows(self, st, run, i):
+        """`_decode_ahead` for a ragged plan: queue step i right behind the one just issued."""
+        ns = self._decode_ns(st, int(run["lens"].max()) + i)
+        g = False if st["nograph"] else st["graphs"].get((ns, st["sampling"]))
+        if g is None:
+            return
+        if g:
+            g.replay()
+        else:
+            self._decode_launches(st, ns)
+        st["host_step"] = i + 1
+        st["ahead"] = ((id(run), i), st["last_out"], run["hist"].slot(i))
+
+    def _decode_step_generic_rows(self, ids, pos, sampling=None):
+        """`_decode_step_generic` with a position per row (pos: host int32, -1 = a stopped row: computed at position 0,
+        no cache slot written): k / v are projected into scratch rows and written to each row's own slot, RoPE takes
+        each row's own cos / sin row, and the attention runs over each row's own key count (pdn_attention_decode_rows_f32).
+        Returns the ids of every row, (B, 1) int64."""
+        from .. import hipnp as hp, _lib
+        L, st = _lib.lib(), hp.stream()
+        D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
+        hd, half = D // H, D // H // 2
+        B = ids.shape[0]
+        p = np.maximum(pos, 0)
+        ws = getattr(self, "_decode_ws_rows", None)
+        if ws is None or ws["x"].device_index != hp._state["device"] or ws["x"].shape[0] != B:
+            ws = {n: hp.empty((B, w), np.float32) for n, w in
+                  (("x", D), ("h", D), ("q", D), ("k", D), ("v", D), ("att", D), ("g", F), ("u", F), ("sw", F),
+                   ("logits", V))}
+            ws["lens"] = hp.zeros((B,), np.int32)
+            self._decode_ws_rows = ws
+        ws["lens"][...] = (p + 1).astype(np.int32)
+        x, h, q, k, v, att, g, u, sw, logits = (ws[n]._ptr for n in ("x", "h", "q", "k", "v", "att", "g", "u", "sw", "logits"))
+
+        def gemv(a_ptr, K, w, c_ptr, N, beta=0.0, bias=None):
+            wd = w.data
+            L.call("pdn_gemm_f32", B, N, K, 1.0, a_ptr, K, 1, wd._ptr, wd._strides[0], wd._strides[1], beta, c_ptr,
+                   N, bias, 1, 1, 0, 0, 0, 0, 0, 0, None, None, 0, None, 0, st)
+
+        emb = self.tok_embedding.weight.data
+        idc = ids if ids.is_contiguous() else ids.copy()
+        if pos.min() < 0:                                                 # (a stopped row's -1 is no token)
+            idc = hp.asarray(np.maximum(idc.get(), 0))
+        L.call("pdn_embedding_gather_f32", emb._ptr, V, D, emb._strides[0], idc._ptr, B, x, hp.err_flag_ptr(), st)
+        cos, sin = self.freqs_cos.data._ptr, self.freqs_sin.data._ptr
+        for layer in self.layers:
+            a, f = layer.attention, layer.ffn
+            ck, cv = a.cache_k.data, a.cache_v.data
+            cbs = ck._strides[0]                                          # floats between sequences in the cache
+            L.call("pdn_rmsnorm_fwd_f32", x, layer.input_norm.weight.data._ptr, h, None, B, D, layer.input_norm.eps, st)
+            gemv(h, D, a.Q.weight, q, D)
+            gemv(h, D, a.K.weight, k, D)
+            gemv(h, D, a.V.weight, v, D)
+            for b in range(B):
+                row, ang = b * D * 4, int(p[b]) * half * 4
+                L.call("pdn_rope_f32", q + row, cos + ang, sin + ang, q + row, 1, 1, H, hd, 0, st)
+                if pos[b] >= 0:
+                    slot = (b * cbs + int(p[b]) * D) * 4
+                    L.call("pdn_rope_f32", k + row, cos + ang, sin + ang, ck._ptr + slot, 1, 1, H, hd, 0, st)
+                    L.call("pdn_memcpy_d2d", cv._ptr + slot, v + row, D * 4, st)
+            L.call("pdn_attention_decode_rows_f32", q, ck._ptr, cv._ptr, att, B, H, ws["lens"]._ptr, int(p.max()) + 1,
+                   hd, cbs, st)
+            gemv(att, D, a.O.weight, x, D, beta=1.0)                      # x += att @ Wo
+            L.call("pdn_rmsnorm_fwd_f32", x, layer.post_attn_norm.weight.data._ptr, h, None, B, D,
+                   layer.post_attn_norm.eps, st)
+            gemv(h, D, f.gate.weight, g, F)
+            gemv(h, D, f.up.weight, u, F)
+            L.call("pdn_swiglu_fwd_f32", g, u, sw, B * F, st)
+            gemv(sw, F, f.down.weight, x, D, beta=1.0)                    # x += swiglu @ Wdown
+        L.call("pdn_rmsnorm_fwd_f32", x, self.norm.weight.data._ptr, h, None, B, D, self.norm.eps, st)
+        gemv(h, D, self.lm_head.weight, logits, V,
+             bias=self.lm_head.bias.data._ptr if getattr(self.lm_head, "bias", None) is not None else None)
+        if sampling is None:
+            return ws["logits"].argmax(-1, keepdims=True)
+        out = hp.empty((B, 1), np.int64)              # (counter (pos[b], b): the per-row tick on scratch copies)
+        pd, step = hp.asarray(p.astype(np.int32)), hp.zeros((1,), np.int32)
+        L.call("pdn_decode_sample_tick_rows_f32", logits, V, B, V, params_buffer(*sampling)._ptr, out._ptr, pd._ptr,
+               step._ptr, None, None, None, 0, 0, None, st)
         return out

@@ -141,3 +141,31 @@ def sample_next(logits, t, temperature, top_k=0, top_p=1.0, seed=0):
         return Tensor(out, dtype=np.int64, device=logits.device, copy=False)
     ids = sample_rows_np(np.asarray(logits.numpy()), t, temperature, top_k, top_p, seed)
     return Tensor(ids.reshape(B, 1), dtype=np.int64, device=logits.device)
+
+
+def sample_next_rows(logits, positions, temperature, top_k=0, top_p=1.0, seed=0):
+    """`sample_next` with a counter per row: row b of the (B, V) logits Tensor drawn with counter (positions[b], b)
+    (Llama.generate_ragged: every row at its own position).  (B, 1) int64 on the logits' device."""
+    from ..core import Tensor
+    temperature, top_k, top_p, seed = check_args(temperature, top_k, top_p, seed)
+    if temperature == 0.0:
+        return logits.argmax(-1, True)
+    B, V = logits.shape
+    positions = np.asarray(positions, np.int64).reshape(B)
+    if logits.device.is_hip:
+        from .. import hipnp as hp, _lib
+        x = logits.data
+        if x.dtype != np.float32:
+            raise TypeError(f"sampling takes float32 logits on the GPU, got {x.dtype}")
+        if x._strides[1] != 1 or x._strides[0] < V:
+            x = x.copy()
+        out = hp.empty((B, 1), np.int64)
+        pos, step = hp.asarray(positions.astype(np.int32)), hp.zeros((1,), np.int32)   # (the tick advances these copies)
+        _lib.lib().call("pdn_decode_sample_tick_rows_f32", x._ptr, x._strides[0], B, V,
+                        params_buffer(temperature, top_k, top_p, seed)._ptr, out._ptr, pos._ptr, step._ptr, None, None,
+                        None, 0, 0, None, hp.stream())
+        return Tensor(out, dtype=np.int64, device=logits.device, copy=False)
+    z = np.asarray(logits.numpy())
+    ids = np.array([sample_rows_np(z[b:b + 1], int(positions[b]), temperature, top_k, top_p, seed, rows=[b])[0]
+                    for b in range(B)], np.int64)
+    return Tensor(ids.reshape(B, 1), dtype=np.int64, device=logits.device)
