@@ -164,8 +164,8 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
                               int64_t ldx, void* stream);
 /* Launch counters per kernel: which kernel the entry points really launched since the last reset -- bench.py's parity
  * gates and the tests assert on them (a dispatch that silently falls back to a slower kernel must not stay green).
- * Copies min(n, 28) counters of slots 0-27 to `out` (may be null), slot 28 as well when n > 28 and slot 29 when n > 29;
- * clears all of them
+ * Copies min(n, 28) counters of slots 0-27 to `out` (may be null), slot 28 as well when n > 28, slot 29 when n > 29 and
+ * slot 30 when n > 30; clears all of them
  * when `reset` != 0.  Slots:
  *   0 gemm_rowres_kernel (chunk kernel, any)      1 gemm_rowtile_kernel plain        2 ... + SwiGLU forward (gate | up)
  *   3 ... + SwiGLU backward (dh)                  4 ... + RoPE (q | k | v)           5 ... + row maxima (lm_head forward)
@@ -181,7 +181,9 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  28 pdn_sample_rows_f32 / pdn_decode_sample_tick_f32 (csrc/sample.hip)
  *  29 decode with a position per row: pdn_decode_block_rows_f32, pdn_decode_attention_rows_f32,
  *     pdn_decode_attention_oproj_rows_f32, pdn_decode_pick_tick_rows_f32, pdn_decode_sample_tick_rows_f32 (which also
- *     counts in 28) and pdn_attention_decode_rows_f32 */
+ *     counts in 28) and pdn_attention_decode_rows_f32
+ *  30 continuous batching: pdn_decode_pick_tick_slots_f32, pdn_decode_sample_tick_slots_f32 (which also counts in 28)
+ *     and pdn_kv_store_slots_f32 (csrc/serve.hip) */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -578,6 +580,35 @@ int pdn_decode_sample_tick_rows_f32(const float* logits, int64_t row_stride, int
                                     int64_t emb_row_stride, int D, float* x_next, void* stream);
 int pdn_attention_decode_rows_f32(const float* q, const float* k_cache, const float* v_cache, float* o, int B, int H,
                                   const int* lens, int max_T, int head_dim, int64_t cache_batch_stride, void* stream);
+/* Continuous batching (Llama.serve): a finished row takes the next waiting request while the other rows go on decoding.
+ * The step launches are the *_rows_f32 entries above; only the last launch and the admission differ.
+ *   pdn_decode_pick_tick_slots_f32 / pdn_decode_sample_tick_slots_f32  the ragged ticks with two more (B,) int32 device
+ *                            arrays.  req[b]: the id of the request in row b -- a sampled row is drawn with counter
+ *                            (pos[b], req[b]), so a token does not depend on the row its request runs in (the greedy
+ *                            pick does not read req; may be NULL there).  left[b]: the tokens row b may still produce --
+ *                            a live row stores left[b] - 1 after its token and stops (pos[b] = -1) once that is 0, as a
+ *                            stop id stops it, so a step queued ahead never writes past a request's end.  The history is
+ *                            a ring of `ring` steps: row b's token goes to (*history)[(*step % ring) * B + b].
+ *   pdn_kv_store_slots_f32   the keys / values of a batched prompt pass into the rows of the cache that take those
+ *                            prompts.  For each of the n_tensors pointer pairs (src[j], dst[j]: device arrays of pointers,
+ *                            e.g. every layer's k and v) and each input i < n_inputs: positions [0, lens[i]) of src[j]
+ *                            row i (batch stride src_batch_stride floats, 0 allowed; position stride D) go to dst[j] row
+ *                            slots[i] (batch stride dst_batch_stride >= max_len * D), positions start[i] + [0, lens[i])
+ *                            (start may be NULL: 0).  lens[i] is clamped to max_src_len and to the cache length max_len;
+ *                            a row outside [0, n_rows) is skipped.  The pad positions [lens[i], max_src_len) and every
+ *                            other row are never written.  One launch for all tensors. */
+int pdn_decode_pick_tick_slots_f32(const float* blk_max, const int* blk_arg, int B, int n_blocks, int64_t* next_ids,
+                                   int* pos, int* step, const int* req, int* left, int ring, const unsigned* stop_mask,
+                                   int64_t* const* history, const float* emb, int64_t emb_row_stride, int D,
+                                   float* x_next, void* stream);
+int pdn_decode_sample_tick_slots_f32(const float* logits, int64_t row_stride, int B, int V,
+                                     const pdn_sample_params* params, int64_t* next_ids, int* pos, int* step,
+                                     const int* req, int* left, int ring, const unsigned* stop_mask,
+                                     int64_t* const* history, const float* emb, int64_t emb_row_stride, int D,
+                                     float* x_next, void* stream);
+int pdn_kv_store_slots_f32(const float* const* src, int64_t src_batch_stride, float* const* dst,
+                           int64_t dst_batch_stride, int n_tensors, int n_inputs, int max_src_len, int D,
+                           const int* slots, const int* lens, const int* start, int n_rows, int max_len, void* stream);
 /* shapes the resident (K / V of a head chunk-wise in LDS) kernels above take: head_dim 48 or 64, L a multiple of 32 up
  * to 1024 -- sequences beyond 256 pass through LDS in 256-row chunks (forward: one online rescale per chunk) -- and
  * (round 6, csrc/attention_hd128.hip) head_dim 128 at ANY length 1 .. 1024, no RoPE inside: the shape of

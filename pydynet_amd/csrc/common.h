@@ -52,7 +52,8 @@ enum {
   PDN_CNT_SAMPLE = 28,            // sample_rows_kernel / decode_sample_tick_kernel (csrc/sample.hip: temperature, top-k, top-p)
   PDN_CNT_DECODE_ROWS = 29,       // decode kernels with a position per row (the *_rows_f32 entries of csrc/decode*.hip,
                                   // sample.hip, pdn_attention_decode_rows_f32)
-  PDN_CNT_SLOTS = 30
+  PDN_CNT_DECODE_SLOTS = 30,      // continuous batching (Llama.serve): the *_tick_slots_f32 ticks, pdn_kv_store_slots_f32
+  PDN_CNT_SLOTS = 31
 };
 void pdn_count(int slot);
 

@@ -706,20 +706,23 @@ extern "C" int pdn_decode_argmax_tick_f32(const float* logits, int64_t row_strid
 // ROWS: pos is a (B,) array (row b at position pos[b], < 0 = stopped) and the history is indexed by the step counter
 // *step: row b's token goes to (*hist)[*step * B + b], -1 for a stopped row (which is otherwise left alone); a live
 // row whose token is in the stop bitmask (bit tok of stop[], may be null) stops: pos[b] = -1, else pos[b] += 1.
-template <bool ROWS>
+// SLOTS (with ROWS; Llama.serve): the history is a ring of `ring` steps, (*hist)[(*step % ring) * B + b], and left[b]
+// counts the tokens row b may still produce: a live row stores left[b] - 1 and stops once it reaches 0.
+template <bool ROWS, bool SLOTS = false>
 __global__ __launch_bounds__(256) void decode_pick_tick_kernel(const float* __restrict__ vals, const int* __restrict__ args,
                                                                int B, int n, int64_t* __restrict__ ids, int* __restrict__ pos,
                                                                int64_t* const* __restrict__ hist,
                                                                const float* __restrict__ emb, int64_t emb_rs, int D,
                                                                float* __restrict__ x_next, int* __restrict__ step,
-                                                               const unsigned* __restrict__ stop) {
+                                                               const unsigned* __restrict__ stop, int* __restrict__ left,
+                                                               int ring) {
   __shared__ float bv[4];
   __shared__ int bi[4];
   __shared__ int64_t chosen;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   DEC_T_BEGIN(2);
   const int p = ROWS ? *step : (pos ? *pos : 0);
-  int64_t* hrow = hist ? *hist + (int64_t)p * B : nullptr;
+  int64_t* hrow = hist ? *hist + (int64_t)(SLOTS ? p % ring : p) * B : nullptr;
   for (int b = 0; b < B; ++b) {
     const int pb = ROWS ? pos[b] : 0;      // (read by every thread before tid 0 rewrites it after the barrier below)
     if (ROWS && pb < 0) {                  // (uniform)
@@ -758,7 +761,13 @@ __global__ __launch_bounds__(256) void decode_pick_tick_kernel(const float* __re
       ids[b] = tok;
       if (hrow) __hip_atomic_store(hrow + b, tok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (may be host memory)
       chosen = tok;
-      if (ROWS) pos[b] = (stop && ((stop[tok >> 5] >> (tok & 31)) & 1u)) ? -1 : pb + 1;
+      if (SLOTS) {
+        const int lb = left[b] - 1;
+        left[b] = lb;
+        pos[b] = (lb <= 0 || (stop && ((stop[tok >> 5] >> (tok & 31)) & 1u))) ? -1 : pb + 1;
+      } else if (ROWS) {
+        pos[b] = (stop && ((stop[tok >> 5] >> (tok & 31)) & 1u)) ? -1 : pb + 1;
+      }
     }
     lds_barrier();
     DEC_T(1);
@@ -787,7 +796,7 @@ extern "C" int pdn_decode_pick_tick_f32(const float* blk_max, const int* blk_arg
   PDN_CHECK_ARG(!history || pos, "pdn_decode_pick_tick_f32: a history needs the position");
   PDN_CHECK_ARG(!emb || (x_next && D > 0), "pdn_decode_pick_tick_f32: an embedding table needs x_next and D");
   hipLaunchKernelGGL(decode_pick_tick_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, blk_max, blk_arg, B,
-                     n_blocks, next_ids, pos, history, emb, emb_row_stride, D, x_next, nullptr, nullptr);
+                     n_blocks, next_ids, pos, history, emb, emb_row_stride, D, x_next, nullptr, nullptr, nullptr, 0);
   PDN_LAUNCH_CHECK();
   return PDN_OK;
 }
@@ -804,8 +813,27 @@ extern "C" int pdn_decode_pick_tick_rows_f32(const float* blk_max, const int* bl
                 "pdn_decode_pick_tick_rows_f32: bad arguments");
   PDN_CHECK_ARG(!emb || (x_next && D > 0), "pdn_decode_pick_tick_rows_f32: an embedding table needs x_next and D");
   hipLaunchKernelGGL(decode_pick_tick_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, blk_max, blk_arg, B,
-                     n_blocks, next_ids, pos, history, emb, emb_row_stride, D, x_next, step, stop_mask);
+                     n_blocks, next_ids, pos, history, emb, emb_row_stride, D, x_next, step, stop_mask, nullptr, 0);
   PDN_LAUNCH_CHECK();
   pdn_count(PDN_CNT_DECODE_ROWS);
+  return PDN_OK;
+}
+
+// The per-row tick of a served batch (decode_pick_tick_kernel<true, true>): as pdn_decode_pick_tick_rows_f32, plus
+// left (B,) int32, the tokens row b may still produce (a live row stops once its count reaches 0), and a history ring
+// of `ring` steps: row b's token goes to (*history)[(*step % ring) * B + b].  `req` (the counter id of each row in the
+// sampled form) is not read by the greedy pick and may be null.
+extern "C" int pdn_decode_pick_tick_slots_f32(const float* blk_max, const int* blk_arg, int B, int n_blocks,
+                                              int64_t* next_ids, int* pos, int* step, const int* req, int* left, int ring,
+                                              const unsigned* stop_mask, int64_t* const* history, const float* emb,
+                                              int64_t emb_row_stride, int D, float* x_next, void* stream) {
+  if (B == 0) return PDN_OK;
+  PDN_CHECK_ARG(blk_max && blk_arg && next_ids && n_blocks > 0 && pos && step && left && ring > 0,
+                "pdn_decode_pick_tick_slots_f32: bad arguments (ring %d)", ring);
+  PDN_CHECK_ARG(!emb || (x_next && D > 0), "pdn_decode_pick_tick_slots_f32: an embedding table needs x_next and D");
+  hipLaunchKernelGGL((decode_pick_tick_kernel<true, true>), dim3(1), dim3(256), 0, (hipStream_t)stream, blk_max, blk_arg,
+                     B, n_blocks, next_ids, pos, history, emb, emb_row_stride, D, x_next, step, stop_mask, left, ring);
+  PDN_LAUNCH_CHECK();
+  pdn_count(PDN_CNT_DECODE_SLOTS);
   return PDN_OK;
 }

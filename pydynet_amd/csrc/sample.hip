@@ -239,27 +239,37 @@ extern "C" int pdn_sample_rows_f32(const float* logits, int64_t row_stride, int 
 // ROWS: the per-row form of decode_pick_tick_kernel<true> (csrc/decode.hip): row b is drawn with counter (pos[b], b),
 // the history slot is (*hist)[*step * B + b] (-1 for a stopped row, pos[b] < 0, which is otherwise left alone), a
 // token in the stop bitmask stops its row (pos[b] = -1), else pos[b] += 1; then *step += 1.
-template <bool ROWS>
+// SLOTS (with ROWS; Llama.serve): row b is drawn with counter (pos[b], req[b]) -- the request it holds, not the row --,
+// the history is a ring of `ring` steps, (*hist)[(*step % ring) * B + b], and left[b] counts the tokens row b may still
+// produce: a live row stores left[b] - 1 and stops once it reaches 0.
+template <bool ROWS, bool SLOTS = false>
 __global__ __launch_bounds__(SMP_THREADS) void decode_sample_tick_kernel(
     const float* __restrict__ logits, int64_t rs, int B, int V, const SampleParams* __restrict__ prm,
     int64_t* __restrict__ ids, int* __restrict__ pos, int64_t* const* __restrict__ hist, const float* __restrict__ emb,
-    int64_t emb_rs, int D, float* __restrict__ x_next, int* __restrict__ step, const unsigned* __restrict__ stop) {
+    int64_t emb_rs, int D, float* __restrict__ x_next, int* __restrict__ step, const unsigned* __restrict__ stop,
+    const int* __restrict__ req, int* __restrict__ left, int ring) {
   __shared__ SmpShared s;
   const int tid = threadIdx.x;
   const int p = ROWS ? *step : (pos ? *pos : 0);
   const SampleParams pr = *prm;
-  int64_t* hrow = hist ? *hist + (int64_t)p * B : nullptr;
+  int64_t* hrow = hist ? *hist + (int64_t)(SLOTS ? p % ring : p) * B : nullptr;
   for (int b = 0; b < B; ++b) {
     const int pb = ROWS ? pos[b] : p;      // (read by every thread before the barriers of smp_row)
     if (ROWS && pb < 0) {                  // (uniform)
       if (tid == 0 && hrow) __hip_atomic_store(hrow + b, (int64_t)-1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       continue;
     }
-    const int64_t tok = smp_row(logits + (int64_t)b * rs, V, pr, (uint64_t)pb, (uint64_t)b, s);
+    const int64_t tok = smp_row(logits + (int64_t)b * rs, V, pr, (uint64_t)pb, (uint64_t)(SLOTS ? req[b] : b), s);
     if (tid == 0) {
       ids[b] = tok;
       if (hrow) __hip_atomic_store(hrow + b, tok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (may be host memory)
-      if (ROWS) pos[b] = (stop && ((stop[tok >> 5] >> (tok & 31)) & 1u)) ? -1 : pb + 1;
+      if (SLOTS) {
+        const int lb = left[b] - 1;
+        left[b] = lb;
+        pos[b] = (lb <= 0 || (stop && ((stop[tok >> 5] >> (tok & 31)) & 1u))) ? -1 : pb + 1;
+      } else if (ROWS) {
+        pos[b] = (stop && ((stop[tok >> 5] >> (tok & 31)) & 1u)) ? -1 : pb + 1;
+      }
     }
     if (emb) {
       const float* er = emb + tok * emb_rs;
@@ -285,7 +295,7 @@ extern "C" int pdn_decode_sample_tick_f32(const float* logits, int64_t row_strid
   PDN_CHECK_ARG(!emb || (x_next && D > 0), "pdn_decode_sample_tick_f32: an embedding table needs x_next and D");
   hipLaunchKernelGGL(decode_sample_tick_kernel<false>, dim3(1), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
                      row_stride, B, V, (const SampleParams*)params, next_ids, pos, history, emb, emb_row_stride, D, x_next,
-                     nullptr, nullptr);
+                     nullptr, nullptr, nullptr, nullptr, 0);
   PDN_LAUNCH_CHECK();
   pdn_count(PDN_CNT_SAMPLE);
   return PDN_OK;
@@ -302,9 +312,31 @@ extern "C" int pdn_decode_sample_tick_rows_f32(const float* logits, int64_t row_
   PDN_CHECK_ARG(!emb || (x_next && D > 0), "pdn_decode_sample_tick_rows_f32: an embedding table needs x_next and D");
   hipLaunchKernelGGL(decode_sample_tick_kernel<true>, dim3(1), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
                      row_stride, B, V, (const SampleParams*)params, next_ids, pos, history, emb, emb_row_stride, D, x_next,
-                     step, stop_mask);
+                     step, stop_mask, nullptr, nullptr, 0);
   PDN_LAUNCH_CHECK();
   pdn_count(PDN_CNT_SAMPLE);
   pdn_count(PDN_CNT_DECODE_ROWS);
+  return PDN_OK;
+}
+
+// The per-row tick of a served batch (decode_sample_tick_kernel<true, true>): as pdn_decode_sample_tick_rows_f32, but
+// row b is drawn with counter (pos[b], req[b]), left (B,) int32 counts the tokens row b may still produce and the
+// history is a ring of `ring` steps, (*history)[(*step % ring) * B + b].
+extern "C" int pdn_decode_sample_tick_slots_f32(const float* logits, int64_t row_stride, int B, int V, const void* params,
+                                                int64_t* next_ids, int* pos, int* step, const int* req, int* left,
+                                                int ring, const unsigned* stop_mask, int64_t* const* history,
+                                                const float* emb, int64_t emb_row_stride, int D, float* x_next,
+                                                void* stream) {
+  if (B == 0) return PDN_OK;
+  PDN_CHECK_ARG(logits && params && next_ids && pos && step && req && left && ring > 0 && B > 0 && V > 0 &&
+                    V <= (1 << 23) && row_stride >= V,
+                "pdn_decode_sample_tick_slots_f32: bad arguments (B %d, V %d, ring %d)", B, V, ring);
+  PDN_CHECK_ARG(!emb || (x_next && D > 0), "pdn_decode_sample_tick_slots_f32: an embedding table needs x_next and D");
+  hipLaunchKernelGGL((decode_sample_tick_kernel<true, true>), dim3(1), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
+                     row_stride, B, V, (const SampleParams*)params, next_ids, pos, history, emb, emb_row_stride, D, x_next,
+                     step, stop_mask, req, left, ring);
+  PDN_LAUNCH_CHECK();
+  pdn_count(PDN_CNT_SAMPLE);
+  pdn_count(PDN_CNT_DECODE_SLOTS);
   return PDN_OK;
 }

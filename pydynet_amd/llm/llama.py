@@ -370,17 +370,17 @@ class Llama(nn.Module):
             return logits.argmax(-1, True)
         return sample_next_rows(logits, lens, *sampling)
 
-    def _step_module_rows(self, ids, pos, sampling):
+    def _step_module_rows(self, ids, pos, sampling, req=None):
         """One ragged decode step on the tape-node operators (the `cpu` device, fast_decode = False, training mode,
         other dtypes): row b's token at position pos[b] (-1: a stopped row, which yields -1).  The NumPy statement of what
-        the per-row kernels compute."""
+        the per-row kernels compute.  `req`: the counter id of each row (Llama.serve; default: the row)."""
         tok = ids.data if pos.min() >= 0 else np.maximum(ids.numpy(), 0)      # (a stopped row's -1 is no token)
         p = np.maximum(pos, 0)
         h = self.tok_embedding(Tensor(tok, dtype=np.int64, device=ids.device) if tok is not ids.data else ids)
         for layer in self.layers:
             h = layer.step_rows(h, pos, self.freqs_cos, self.freqs_sin)
         logits = self.lm_head(self.norm(h))[:, -1, :]
-        nxt = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, p, *sampling)
+        nxt = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, p, *sampling, rows=req)
         if pos.min() >= 0:
             return nxt
         out = nxt.numpy().reshape(-1, 1)
@@ -392,14 +392,16 @@ class Llama(nn.Module):
     decode_ahead = True     # class switch: False never queues the next step before the caller asked for it
     fused_decode = 2        # class switch: launches per layer = 2 (q|k|v inside the attention kernel), 1 -> 3, 0 / False -> 5
 
-    def _decode_plan(self, B, sampling=False, ragged=False):
+    def _decode_plan(self, B, sampling=False, ragged=False, serve=False):
         """Buffers and weight views of the graph-replayable decode step (csrc/decode.hip), or None when the
         model's shapes / layout are outside what those kernels take (then the generic launches below run).
         `sampling`: the step ends in the sample tick (csrc/sample.hip) instead of the greedy pick; its parameters live in
         the plan's `params` buffer, so new values never re-capture.
         `ragged` (generate_ragged): every row at its own position -- `pos` is (B,) int32 (-1: a stopped row), the
         *_rows_f32 entries run, the tick indexes the history by the device step counter `step` and stops rows whose
-        token is set in the `stop` bitmask."""
+        token is set in the `stop` bitmask.
+        `serve` (Llama.serve, with `ragged`): the step ends in the slot ticks -- `req` (B,) int32 holds the counter id of
+        each row, `left` (B,) int32 the tokens it may still produce -- and the history is a ring of `ring` steps."""
         from .. import hipnp as hp, _lib
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
         st = getattr(self, "_decode_st", None)
@@ -416,7 +418,7 @@ class Llama(nn.Module):
                                             layer.post_attn_norm.weight)]
         key = (B, hp._state["device"], int(Llama.fused_decode or 0), os.environ.get("PDN_DECODE_SPLITS", ""),
                self.layers[0].attention.cache_k.shape[1], tuple(ptrs), bool(sampling),   # (the addresses: no hash to collide)
-               bool(ragged))
+               bool(ragged), bool(serve))
         if st is not None and st["key"] == key:
             return st if st["ok"] else None
         if st is not None:
@@ -436,7 +438,7 @@ class Llama(nn.Module):
                     break
                 packs.append((qkv, gu))
             ok = ok and self.lm_head.weight.data.is_contiguous() and self.tok_embedding.weight.data.is_contiguous()
-        st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged)}
+        st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged), "serve": bool(serve)}
         if ok:
             nblk = _lib.lib().query("pdn_decode_gemv_blocks", V)
             # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
@@ -484,6 +486,8 @@ class Llama(nn.Module):
             if ragged:
                 st.update(pos=hp.zeros((B,), np.int32), step=hp.zeros((1,), np.int32),
                           stop=hp.zeros((-(-V // 32),), np.int32), run=None, host_step=None)
+            if serve:
+                st.update(req=hp.zeros((B,), np.int32), left=hp.zeros((B,), np.int32), ring=4, pending=0, issued=0)
             self._decode_ws = {"logits": st["logits"], "x": st["x"]}
         self._decode_st = st
         return st if ok else None
@@ -583,6 +587,17 @@ class Llama(nn.Module):
         tick over the full logit rows with counter (*pos, b); either stores the token and its embedding row, *pos += 1."""
         from .. import _lib
         L, emb, D, B = _lib.lib(), self.tok_embedding.weight.data, self.embed_dim, st["B"]
+        if st["serve"]:
+            # (the slot ticks: counter (pos[b], req[b]), a token budget per row, a history ring)
+            srv = (st["pos"]._ptr, st["step"]._ptr, st["req"]._ptr, st["left"]._ptr, st["ring"], st["stop"]._ptr,
+                   st["hist_ptr"]._ptr, emb._ptr, emb._strides[0], D, st["x"]._ptr, s)
+            if st["sampling"]:
+                L.call("pdn_decode_sample_tick_slots_f32", st["logits"]._ptr, self.vocab_size, B, self.vocab_size,
+                       st["params"]._ptr, st["ids"]._ptr, *srv)
+            else:
+                L.call("pdn_decode_pick_tick_slots_f32", st["cand_v"]._ptr, st["cand_i"]._ptr, B, st["cand_v"].shape[1],
+                       st["ids"]._ptr, *srv)
+            return
         if st["ragged"]:
             pos, step, stop = st["pos"]._ptr, st["step"]._ptr, st["stop"]._ptr
             if st["sampling"]:
@@ -845,11 +860,12 @@ class Llama(nn.Module):
         st["host_step"] = i + 1
         st["ahead"] = ((id(run), i), st["last_out"], run["hist"].slot(i))
 
-    def _decode_step_generic_rows(self, ids, pos, sampling=None):
+    def _decode_step_generic_rows(self, ids, pos, sampling=None, req=None):
         """`_decode_step_generic` with a position per row (pos: host int32, -1 = a stopped row: computed at position 0,
         no cache slot written): k / v are projected into scratch rows and written to each row's own slot, RoPE takes
         each row's own cos / sin row, and the attention runs over each row's own key count (pdn_attention_decode_rows_f32).
-        Returns the ids of every row, (B, 1) int64."""
+        `req` (Llama.serve): the counter id of each row, drawn by the slot tick (default: the row).  Returns the ids of
+        every row, (B, 1) int64."""
         from .. import hipnp as hp, _lib
         L, st = _lib.lib(), hp.stream()
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
@@ -908,6 +924,281 @@ class Llama(nn.Module):
             return ws["logits"].argmax(-1, keepdims=True)
         out = hp.empty((B, 1), np.int64)              # (counter (pos[b], b): the per-row tick on scratch copies)
         pd, step = hp.asarray(p.astype(np.int32)), hp.zeros((1,), np.int32)
+        if req is not None:                           # (counter (pos[b], req[b]): the slot tick, a budget of one token)
+            rq, left = hp.asarray(np.asarray(req, np.int32).reshape(B)), hp.asarray(np.ones(B, np.int32))
+            L.call("pdn_decode_sample_tick_slots_f32", logits, V, B, V, params_buffer(*sampling)._ptr, out._ptr,
+                   pd._ptr, step._ptr, rq._ptr, left._ptr, 1, None, None, None, 0, 0, None, st)
+            return out
         L.call("pdn_decode_sample_tick_rows_f32", logits, V, B, V, params_buffer(*sampling)._ptr, out._ptr, pd._ptr,
                step._ptr, None, None, None, 0, 0, None, st)
         return out
+
+    # -- continuous batching (serve): a finished row takes the next waiting request -------------------------------
+    def serve(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=()):
+        """Continuous batching: N requests (`prompts`, N may exceed max_batch_size) through `slots` decode rows
+        (default min(N, max_batch_size)).  A row frees when its request yields a stop id or uses up its budget
+        (`max_new_tokens`: one int, or one per request; 0 = the request yields nothing and never takes a row).  Before
+        the next step the freed rows are refilled -- the lowest free row takes the lowest waiting request -- by one
+        batched prompt pass, while the other rows go on decoding.
+        Yields, per step, two (slots,) int64 arrays (requests, tokens): the request in row b (-1: empty) and the token it
+        produced at this step (the prompt pass's token for a row admitted at this step; -1: none).
+        Request r's tokens are the first budget_r tokens of row r of `generate_ragged(prompts, max(budgets), ...)`,
+        cut after its first stop id: a sampled token of request r at position t is drawn with Philox counter (t, r),
+        whichever row it runs in.  Every argument is checked here (ValueError), before anything runs."""
+        temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
+        V = self.vocab_size
+        rows = [np.asarray(p.numpy() if isinstance(p, Tensor) else p).reshape(-1) for p in prompts]
+        if not rows:
+            raise ValueError("serve needs at least one prompt")
+        N = len(rows)
+        budgets = [max_new_tokens] * N if np.ndim(max_new_tokens) == 0 else list(max_new_tokens)
+        if len(budgets) != N:
+            raise ValueError(f"max_new_tokens: {len(budgets)} budgets for {N} prompts")
+        for r, n in enumerate(budgets):
+            if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer, float, np.floating)) \
+                    or int(n) != n or n < 0:
+                raise ValueError(f"max_new_tokens of request {r} must be a non-negative integer, got {n!r}")
+        budgets = np.array([int(n) for n in budgets], np.int64)
+        cache = self.layers[0].attention.cache_k
+        if slots is None:
+            slots = min(N, cache.shape[0])
+        if isinstance(slots, (bool, np.bool_)) or int(slots) != slots or not 1 <= slots <= cache.shape[0]:
+            raise ValueError(f"slots must be an integer in [1, {cache.shape[0]}] (the KV cache's max_batch_size), "
+                             f"got {slots!r}")
+        limit = min(cache.shape[1], self.freqs_cos.shape[0])     # positions the cache / RoPE table hold
+        for r, (p, n) in enumerate(zip(rows, budgets)):
+            if p.size == 0:
+                raise ValueError(f"prompt {r} is empty")
+            if p.dtype.kind not in "iu" or p.min() < 0 or p.max() >= V:
+                raise ValueError(f"prompt {r}: token ids must be integers in [0, {V})")
+            last = p.size + n - 1                                 # (the position of the request's last decode step)
+            if n > 0 and (p.size > cache.shape[1] or (n > 1 and last >= limit)):
+                raise ValueError(f"prompt {r}: its last position {last} is outside the KV cache / RoPE table "
+                                 f"(max_seq_len {cache.shape[1]}, {self.freqs_cos.shape[0]} RoPE rows)")
+        stops = np.asarray(sorted({int(t) for t in stop_ids}), np.int64)
+        if stops.size and (stops.min() < 0 or stops.max() >= V):
+            raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
+        sampling = (temperature, top_k, top_p, seed) if temperature > 0 else None
+        return self._serve([p.astype(np.int64) for p in rows], budgets, int(slots), sampling, stops)
+
+    def serve_all(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=()):
+        """`serve` run to the end: a list of N int64 arrays, request r's generated tokens in order."""
+        it = self.serve(prompts, max_new_tokens, slots, temperature, top_k, top_p, seed, stop_ids)
+        out = [[] for _ in range(len(prompts))]
+        for reqs, toks in it:
+            for r, t in zip(reqs, toks):
+                if r >= 0 and t >= 0:
+                    out[r].append(int(t))
+        return [np.array(o, np.int64) for o in out]
+
+    def _serve(self, rows, budgets, S, sampling, stops):
+        """The scheduler of `serve`.  Per step: the rows holding a request decode one token, then the rows freed by the
+        previous step take the waiting requests in order through one prompt pass (`_serve_prefill`), then the step is
+        yielded.  The host keeps, per row, the request, the position of its next decode step, the tokens it may still
+        produce and its last token; on the graph path the device keeps the same in the served plan (`_serve_begin`) and
+        the host writes it only after an admission, when every queued step has been read."""
+        lens = np.array([r.size for r in rows], np.int64)
+        queue = [r for r in range(len(rows)) if budgets[r] > 0]   # FIFO by index; a budget of 0 never takes a row
+        req = np.full(S, -1, np.int64)
+        pos = np.full(S, -1, np.int64)
+        left = np.zeros(S, np.int64)
+        last = np.zeros(S, np.int64)
+        dev = self.tok_embedding.weight.device
+        hip = (Llama.fast_decode and dev.is_hip and not self._train
+               and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
+        st = self._serve_begin(S, sampling, stops) if hip else None      # None: the plan refuses -> generic HIP step
+        q = 0
+        try:
+            while True:
+                run = req >= 0
+                adm = np.flatnonzero(~run)[:len(queue) - q]      # the lowest free rows take the lowest waiting requests
+                new = np.array(queue[q:q + adm.size], np.int64)
+                q += adm.size
+                if not run.any() and not adm.size:
+                    return
+                p = np.where(run, pos, -1)
+                toks = np.full(S, -1, np.int64)
+                if st is not None:
+                    # (invariant: at most one step is queued here, and it is this step's -- void if no row runs)
+                    if run.any() and not st["pending"]:
+                        self._serve_issue(st, int(p.max()))
+                    if not adm.size:
+                        nxt = np.where(run & (left > 1), p + 1, -1)
+                        if nxt.max() >= 0:
+                            self._serve_ahead(st, int(nxt.max()))    # the next step, queued before this one is read
+                        toks[run] = self._serve_read(st)[run]
+                elif run.any():
+                    ids, rq = last.reshape(S, 1), np.maximum(req, 0)
+                    if hip:
+                        from .. import hipnp as hp
+                        out = self._decode_step_generic_rows(hp.asarray(ids), p.astype(np.int32), sampling, rq).get()
+                    else:
+                        out = self._step_module_rows(Tensor(ids, dtype=np.int64, device=dev), p, sampling, rq).numpy()
+                    toks[run] = out.reshape(-1)[run]
+                shown = req.copy()
+                if adm.size:
+                    first = self._serve_prefill([rows[r] for r in new], adm, new, sampling)
+                    if st is not None and st["pending"]:
+                        d = self._serve_read(st)                 # (stream order: that step ran before the prefill)
+                        toks[run] = d[run]
+                    toks[adm], shown[adm] = first, new
+                    req[adm], pos[adm], left[adm] = new, lens[new], budgets[new]
+                # every row that produced a token: one position further, one token less; a request ends at its budget
+                # or at a stop id, and its row is free for the next step
+                has = shown >= 0
+                left[has] -= 1
+                pos[has] += 1
+                last[has] = toks[has]
+                done = has & ((left <= 0) | np.isin(toks, stops))
+                req[done], pos[done], left[done] = -1, -1, 0
+                if st is not None and adm.size:
+                    self._serve_write(st, req, pos, left, last)
+                    if (req >= 0).any():
+                        self._serve_ahead(st, int(np.where(req >= 0, pos, -1).max()))
+                yield shown, toks
+        finally:
+            if st is not None and st["pending"]:
+                from .. import hipnp as hp
+                hp.synchronize()                                 # (queued steps store into this run's history)
+                st["pending"] = 0
+
+    def _serve_prefill(self, prompts, rows, reqs, sampling):
+        """Admit requests `reqs` (their prompts) into decode rows `rows`: the prompts right-padded to the longest run as one
+        batched causal pass from position 0 into a staging cache (the layers' caches point at it meanwhile), then
+        pdn_kv_store_slots_f32 puts prompt i's keys / values, positions [0, len_i), into cache row rows[i] and zeroes
+        position len_i there -- the slot a decode step attends to but never writes (`generate`'s step at position p feeds
+        the token of position p - 1), which in a fresh cache holds zeros.  No pad position and no other row is written.
+        Returns the first token of each request (counter (len_i, reqs[i]) when sampled), host int64."""
+        A = len(prompts)
+        lens = np.array([p.size for p in prompts], np.int64)
+        Lp = int(lens.max())
+        ids = np.zeros((A, Lp), np.int64)
+        for i, p in enumerate(prompts):
+            ids[i, :p.size] = p
+        dev = self.tok_embedding.weight.device
+        caches = [c for layer in self.layers for c in (layer.attention.cache_k, layer.attention.cache_v)]
+        Bc, T, H, hd = caches[0].shape
+        keep = [c.data for c in caches]
+        with dev:
+            staged = [dev.xp.zeros((A, Lp, H, hd), c.dtype) for c in keep]
+        try:
+            for c, s in zip(caches, staged):
+                c.data = s
+            h = self._forward_hidden(Tensor(ids, dtype=np.int64, device=dev), 0)
+        finally:
+            for c, k in zip(caches, keep):
+                c.data = k
+        last = h.reshape(A * Lp, self.embed_dim)[np.arange(A) * Lp + lens - 1].reshape(A, 1, self.embed_dim)
+        logits = self.lm_head(last)[:, -1, :]
+        D = H * hd
+        if dev.is_hip and keep[0].dtype == np.float32 and all(k.is_contiguous() for k in keep):
+            from .. import hipnp as hp, _lib
+            L, s = _lib.lib(), hp.stream()
+            src = hp.asarray(np.array([a._ptr for a in staged], np.int64))
+            dst = hp.asarray(np.array([k._ptr for k in keep], np.int64))
+            zero = hp.zeros((D,), np.float32)
+            slots, ln, one = (hp.asarray(np.asarray(a, np.int32)) for a in (rows, lens, np.ones(A)))
+            L.call("pdn_kv_store_slots_f32", src._ptr, Lp * D, dst._ptr, keep[0]._strides[0], len(keep), A, Lp, D,
+                   slots._ptr, ln._ptr, None, Bc, T, s)
+            zeros = hp.asarray(np.full(len(keep), zero._ptr, np.int64))
+            L.call("pdn_kv_store_slots_f32", zeros._ptr, 0, dst._ptr, keep[0]._strides[0], len(keep), A, 1, D,
+                   slots._ptr, one._ptr, ln._ptr, Bc, T, s)
+        else:
+            with dev:
+                for k, a in zip(keep, staged):
+                    for i, b in enumerate(rows):
+                        k[int(b), :int(lens[i])] = a[i, :int(lens[i])]
+                        if lens[i] < T:
+                            k[int(b), int(lens[i])] = 0
+        first = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, lens, *sampling, rows=reqs)
+        return np.asarray(first.numpy()).reshape(-1).astype(np.int64)
+
+    # (graph path of `serve`: the served plan holds the rows' state on the device; steps are issued, queued ahead and
+    #  read in order, through a ring of `ring` history slots)
+    def _serve_begin(self, S, sampling, stops):
+        from .. import hipnp as hp
+        st = self._decode_plan(S, sampling is not None, ragged=True, serve=True)
+        if st is None:
+            return None
+        if st["pending"]:
+            hp.synchronize()                                     # (an abandoned run's queued steps)
+        mask = np.zeros(-(-self.vocab_size // 32), np.uint32)
+        np.bitwise_or.at(mask, stops >> 5, np.uint32(1) << (stops & 31).astype(np.uint32))
+        st["hist"] = hp.Mailbox(st["ring"], (S, 1), unset=np.iinfo(np.int64).min)
+        st["hist_ptr"][...] = np.int64(st["hist"]._ptr)
+        st["stop"][...] = mask.view(np.int32)
+        st["pos"][...] = np.full(S, -1, np.int32)
+        st["step"][...] = np.int32(0)
+        st["left"][...] = np.zeros(S, np.int32)
+        st["req"][...] = np.zeros(S, np.int32)
+        if sampling is not None and st["params_val"] != sampling:
+            st["params"][...] = params_bytes(*sampling)
+        st["params_val"] = sampling
+        st["pending"], st["read"] = 0, 0
+        return st
+
+    def _serve_issue(self, st, top):
+        """Issue the next decode step of a served plan (its furthest row at position `top`); captures its graph first
+        when this range count has none -- the capture's two real runs store into a scratch history and the rows' state
+        is put back afterwards."""
+        from .. import hipnp as hp, _lib
+        if self._decode_st is not st:
+            raise RuntimeError("another generation replaced the plan of a running serve() on this model")
+        ns = self._decode_ns(st, top)
+        g = False if st["nograph"] else st["graphs"].get((ns, st["sampling"]))
+        if g is None and Llama.graph_decode:
+            keep = {n: st[n].copy() for n in ("ids", "pos", "step", "left")}
+            scratch = hp.Mailbox(st["ring"], (st["B"], 1), unset=st["hist"].unset)
+            st["hist_ptr"][...] = np.int64(scratch._ptr)
+            try:
+                g = hp.Graph()
+                g.capture(lambda: self._decode_launches(st, ns))
+                st["graphs"][(ns, st["sampling"])] = g
+            except _lib.HipLibraryError as e:
+                if e.code != -2:                                 # PDN_EUNSUPPORTED: no graph support (emulated ABI)
+                    raise
+                st["nograph"], g = True, False
+            hp.synchronize()
+            st["hist_ptr"][...] = np.int64(st["hist"]._ptr)
+            for n, v in keep.items():
+                st[n][...] = v
+            self._decode_gather(st)
+        if g:
+            g.replay()
+        else:
+            self._decode_launches(st, ns)
+        st["pending"] += 1
+
+    def _serve_ahead(self, st, top):
+        """Queue the next step right behind the issued ones (decode_ahead), if its graph exists: a row that ends in the
+        step before computes nothing that is kept (its position is -1 on the device by then)."""
+        if not Llama.decode_ahead or not (st["graphs"] or st["nograph"]):
+            return
+        ns = self._decode_ns(st, top)
+        g = False if st["nograph"] else st["graphs"].get((ns, st["sampling"]))
+        if g is None:
+            return                                               # (a new range count: captured when next issued)
+        if g:
+            g.replay()
+        else:
+            self._decode_launches(st, ns)
+        st["pending"] += 1
+
+    def _serve_read(self, st):
+        """The tokens of the oldest unread step, (B,) host int64 (-1 for rows that computed nothing): a poll of its
+        mapped history slot, which is then marked unwritten for the step `ring` steps later."""
+        h, i = st["hist"], st["read"] % st["ring"]
+        tok = np.array(h.slot(i).get()).reshape(-1)
+        h.host[i] = h.unset
+        st["read"] += 1
+        st["pending"] -= 1
+        return tok
+
+    def _serve_write(self, st, req, pos, left, last):
+        """After an admission (no step queued): the rows' state as the host keeps it -- positions (-1: free), counter
+        ids, budgets and last tokens -- written in stream order, and x = the embedding rows of those tokens."""
+        st["pos"][...] = pos.astype(np.int32)
+        st["req"][...] = np.maximum(req, 0).astype(np.int32)
+        st["left"][...] = left.astype(np.int32)
+        st["ids"][...] = last.reshape(-1, 1)
+        self._decode_gather(st)

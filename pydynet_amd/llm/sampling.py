@@ -143,9 +143,10 @@ def sample_next(logits, t, temperature, top_k=0, top_p=1.0, seed=0):
     return Tensor(ids.reshape(B, 1), dtype=np.int64, device=logits.device)
 
 
-def sample_next_rows(logits, positions, temperature, top_k=0, top_p=1.0, seed=0):
-    """`sample_next` with a counter per row: row b of the (B, V) logits Tensor drawn with counter (positions[b], b)
-    (Llama.generate_ragged: every row at its own position).  (B, 1) int64 on the logits' device."""
+def sample_next_rows(logits, positions, temperature, top_k=0, top_p=1.0, seed=0, rows=None):
+    """`sample_next` with a counter per row: row b of the (B, V) logits Tensor drawn with counter (positions[b], rows[b])
+    (Llama.generate_ragged: every row at its own position; Llama.serve: `rows` = the request each row holds).  `rows`
+    defaults to arange(B).  (B, 1) int64 on the logits' device."""
     from ..core import Tensor
     temperature, top_k, top_p, seed = check_args(temperature, top_k, top_p, seed)
     if temperature == 0.0:
@@ -161,11 +162,17 @@ def sample_next_rows(logits, positions, temperature, top_k=0, top_p=1.0, seed=0)
             x = x.copy()
         out = hp.empty((B, 1), np.int64)
         pos, step = hp.asarray(positions.astype(np.int32)), hp.zeros((1,), np.int32)   # (the tick advances these copies)
-        _lib.lib().call("pdn_decode_sample_tick_rows_f32", x._ptr, x._strides[0], B, V,
-                        params_buffer(temperature, top_k, top_p, seed)._ptr, out._ptr, pos._ptr, step._ptr, None, None,
-                        None, 0, 0, None, hp.stream())
+        prm = params_buffer(temperature, top_k, top_p, seed)
+        if rows is None:
+            _lib.lib().call("pdn_decode_sample_tick_rows_f32", x._ptr, x._strides[0], B, V, prm._ptr, out._ptr, pos._ptr,
+                            step._ptr, None, None, None, 0, 0, None, hp.stream())
+        else:                                      # (the served tick: counter ids per row, a budget of one token)
+            req, left = hp.asarray(np.asarray(rows, np.int32).reshape(B)), hp.asarray(np.ones(B, np.int32))
+            _lib.lib().call("pdn_decode_sample_tick_slots_f32", x._ptr, x._strides[0], B, V, prm._ptr, out._ptr,
+                            pos._ptr, step._ptr, req._ptr, left._ptr, 1, None, None, None, 0, 0, None, hp.stream())
         return Tensor(out, dtype=np.int64, device=logits.device, copy=False)
     z = np.asarray(logits.numpy())
-    ids = np.array([sample_rows_np(z[b:b + 1], int(positions[b]), temperature, top_k, top_p, seed, rows=[b])[0]
+    rows = np.arange(B) if rows is None else np.asarray(rows, np.int64).reshape(B)
+    ids = np.array([sample_rows_np(z[b:b + 1], int(positions[b]), temperature, top_k, top_p, seed, rows=[rows[b]])[0]
                     for b in range(B)], np.int64)
     return Tensor(ids.reshape(B, 1), dtype=np.int64, device=logits.device)
