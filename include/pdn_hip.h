@@ -183,7 +183,9 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *     pdn_decode_attention_oproj_rows_f32, pdn_decode_pick_tick_rows_f32, pdn_decode_sample_tick_rows_f32 (which also
  *     counts in 28) and pdn_attention_decode_rows_f32
  *  30 continuous batching: pdn_decode_pick_tick_slots_f32, pdn_decode_sample_tick_slots_f32 (which also counts in 28)
- *     and pdn_kv_store_slots_f32 (csrc/serve.hip) */
+ *     and pdn_kv_store_slots_f32 (csrc/serve.hip)
+ *  31 wide decode (csrc/decode_wide.hip): pdn_decode_wide_gemm_f32 and the four pdn_decode_wide_*_tick_* entries (the
+ *     ticks also count in 29, the slot forms in 30, the sampled forms in 28) */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -609,6 +611,53 @@ int pdn_decode_sample_tick_slots_f32(const float* logits, int64_t row_stride, in
 int pdn_kv_store_slots_f32(const float* const* src, int64_t src_batch_stride, float* const* dst,
                            int64_t dst_batch_stride, int n_tensors, int n_inputs, int max_src_len, int D,
                            const int* slots, const int* lens, const int* start, int n_rows, int max_len, void* stream);
+/* Wide decode (csrc/decode_wide.hip): the graph-replayed step for 9 <= B <= 256 rows, every row at its own position (the
+ * ragged / served contract above; a rectangular batch passes equal positions).  Per layer: pdn_decode_wide_gemm_f32 for
+ * q | k | v, pdn_decode_attention_rows_f32, the wide product for the output projection, gate | up and down; then the
+ * vocabulary projection and one wide tick.
+ *   pdn_decode_wide_supported  1 when a model of these shapes runs on the wide step with B rows, else 0.
+ *   pdn_decode_wide_gemm_f32   y (B, N) = A(x) (B, K) @ W + bias on fp32 MFMA, B <= 256.  W: N / blk_cols column blocks
+ *                            of blk_cols columns, block j at W + j * w_block_stride, rows w_row_stride floats apart.
+ *                            mode 0: A = x; 1: A = RMSNorm(x) with norm_w, eps; 2: x rows are [gate | up] of width
+ *                            2 K and A = silu(gate) * up; 3: x rows are the act_ns (<= 8) key-range partials of
+ *                            pdn_decode_attention_rows_f32 ((act_ns, K / act_hd, 4 + act_hd) floats) and A merges them.
+ *                            epi 0: y = A @ W + bias; 1: y += A @ W + bias; 2: as 0, and per row and 32-column block
+ *                            the first maximum and its column in cand_v / cand_i (B x pdn_decode_wide_blocks(N)), for
+ *                            the wide pick tick.  pos (B,) int32 may be NULL; rows with pos[b] < 0 are not computed and
+ *                            their y row is not written.  work: pdn_decode_wide_work_floats(B, K, N) floats (0: may be
+ *                            NULL), zeroed once before the first launch.  Its first 192 words are the arrival counters
+ *                            of the split products, at that place for every shape and back at zero after every launch,
+ *                            so products of different shapes may share one workspace of the largest size they need.
+ *                            Every sum runs in a fixed order (no float atomics): two launches give the same bits.
+ *   pdn_decode_wide_pick_tick_rows_f32 / _slots_f32, pdn_decode_wide_sample_tick_rows_f32 / _slots_f32  the ticks of
+ *                            pdn_decode_pick_tick_rows_f32 / _slots_f32 and pdn_decode_sample_tick_rows_f32 / _slots_f32
+ *                            with one workgroup per row (the same tokens, history slots, positions, budgets and stops; the
+ *                            sampled draw is the same code as theirs).  arrive (1,) int32: zero before the first launch,
+ *                            left zero by every launch -- the rows count in there, and the last one advances *step. */
+int pdn_decode_wide_supported(int B, int D, int H, int head_dim, int F, int V, int max_len);
+int pdn_decode_wide_blocks(int N);
+int64_t pdn_decode_wide_work_floats(int B, int K, int N);
+int pdn_decode_wide_gemm_f32(const float* x, int64_t x_row_stride, int mode, const float* norm_w, float eps, int act_ns,
+                             int act_hd, const float* W, int64_t w_row_stride, int blk_cols, int64_t w_block_stride,
+                             const float* bias, float* y, int64_t y_row_stride, int epi, float* cand_v, int* cand_i,
+                             const int* pos, int B, int K, int N, float* work, void* stream);
+int pdn_decode_wide_pick_tick_rows_f32(const float* blk_max, const int* blk_arg, int B, int n_blocks, int64_t* next_ids,
+                                       int* pos, int* step, int* arrive, const unsigned* stop_mask,
+                                       int64_t* const* history, const float* emb, int64_t emb_row_stride, int D,
+                                       float* x_next, void* stream);
+int pdn_decode_wide_pick_tick_slots_f32(const float* blk_max, const int* blk_arg, int B, int n_blocks, int64_t* next_ids,
+                                        int* pos, int* step, int* arrive, const int* req, int* left, int ring,
+                                        const unsigned* stop_mask, int64_t* const* history, const float* emb,
+                                        int64_t emb_row_stride, int D, float* x_next, void* stream);
+int pdn_decode_wide_sample_tick_rows_f32(const float* logits, int64_t row_stride, int B, int V,
+                                         const pdn_sample_params* params, int64_t* next_ids, int* pos, int* step,
+                                         int* arrive, const unsigned* stop_mask, int64_t* const* history,
+                                         const float* emb, int64_t emb_row_stride, int D, float* x_next, void* stream);
+int pdn_decode_wide_sample_tick_slots_f32(const float* logits, int64_t row_stride, int B, int V,
+                                          const pdn_sample_params* params, int64_t* next_ids, int* pos, int* step,
+                                          int* arrive, const int* req, int* left, int ring, const unsigned* stop_mask,
+                                          int64_t* const* history, const float* emb, int64_t emb_row_stride, int D,
+                                          float* x_next, void* stream);
 /* shapes the resident (K / V of a head chunk-wise in LDS) kernels above take: head_dim 48 or 64, L a multiple of 32 up
  * to 1024 -- sequences beyond 256 pass through LDS in 256-row chunks (forward: one online rescale per chunk) -- and
  * (round 6, csrc/attention_hd128.hip) head_dim 128 at ANY length 1 .. 1024, no RoPE inside: the shape of

@@ -95,5 +95,12 @@ def lib() -> _Lib:
     return _LIB
 
 
+def provides(name: str) -> bool:
+    """Whether the installed library answers entry point `name` (an ABI stand-in may implement only part of the header)."""
+    L = lib()
+    fn = getattr(L, "fn", None)
+    return name in fn if fn is not None else hasattr(L, name)
+
+
 def is_built() -> bool:
     return os.path.exists(LIB_PATH)

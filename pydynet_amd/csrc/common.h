@@ -53,7 +53,8 @@ enum {
   PDN_CNT_DECODE_ROWS = 29,       // decode kernels with a position per row (the *_rows_f32 entries of csrc/decode*.hip,
                                   // sample.hip, pdn_attention_decode_rows_f32)
   PDN_CNT_DECODE_SLOTS = 30,      // continuous batching (Llama.serve): the *_tick_slots_f32 ticks, pdn_kv_store_slots_f32
-  PDN_CNT_SLOTS = 31
+  PDN_CNT_DECODE_WIDE = 31,       // wide decode (9..256 rows, csrc/decode_wide.hip): the MFMA product and the wide ticks
+  PDN_CNT_SLOTS = 32
 };
 void pdn_count(int slot);
 

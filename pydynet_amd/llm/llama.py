@@ -24,6 +24,12 @@ from .sampling import (check_args as check_sampling_args, params_bytes, params_b
                        sample_next_rows)
 
 
+# the entry points of the wide step: a library (or ABI stand-in) without them keeps B > 8 on the generic step
+_WIDE_ENTRIES = ("pdn_decode_wide_supported", "pdn_decode_wide_blocks", "pdn_decode_wide_work_floats",
+                 "pdn_decode_wide_gemm_f32", "pdn_decode_wide_pick_tick_rows_f32", "pdn_decode_wide_pick_tick_slots_f32",
+                 "pdn_decode_wide_sample_tick_rows_f32", "pdn_decode_wide_sample_tick_slots_f32")
+
+
 def compute_cos_sin_cache(head_dim: int, max_seq_len: int, base: int = 10000, dtype=None):
     """cos/sin(outer(arange(max_seq_len), base^(-2i/head_dim))) -> two (max_seq_len, head_dim/2) tensors."""
     inv_freq = 1.0 / (base ** (np.arange(0, head_dim, 2)[: head_dim // 2] / head_dim))
@@ -391,6 +397,7 @@ class Llama(nn.Module):
     graph_decode = True     # class switch: False issues the step's launches one by one instead of replaying a hipGraph
     decode_ahead = True     # class switch: False never queues the next step before the caller asked for it
     fused_decode = 2        # class switch: launches per layer = 2 (q|k|v inside the attention kernel), 1 -> 3, 0 / False -> 5
+    wide_decode = True      # class switch: 9 .. 256 rows on the wide step (csrc/decode_wide.hip); False -> the generic step
 
     def _decode_plan(self, B, sampling=False, ragged=False, serve=False):
         """Buffers and weight views of the graph-replayable decode step (csrc/decode.hip), or None when the
@@ -401,7 +408,9 @@ class Llama(nn.Module):
         *_rows_f32 entries run, the tick indexes the history by the device step counter `step` and stops rows whose
         token is set in the `stop` bitmask.
         `serve` (Llama.serve, with `ragged`): the step ends in the slot ticks -- `req` (B,) int32 holds the counter id of
-        each row, `left` (B,) int32 the tokens it may still produce -- and the history is a ring of `ring` steps."""
+        each row, `left` (B,) int32 the tokens it may still produce -- and the history is a ring of `ring` steps.
+        More than 8 rows (`wide_decode`): the wide step of csrc/decode_wide.hip, always in the per-row form (`rows`; a
+        rectangular batch holds equal positions and a step counter equal to the position)."""
         from .. import hipnp as hp, _lib
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
         st = getattr(self, "_decode_st", None)
@@ -416,8 +425,10 @@ class Llama(nn.Module):
             ptrs += [t.data._ptr for t in (a.Q.weight, a.K.weight, a.V.weight, a.O.weight, a.cache_k, a.cache_v,
                                             f.gate.weight, f.up.weight, f.down.weight, layer.input_norm.weight,
                                             layer.post_attn_norm.weight)]
+        cache_len = self.layers[0].attention.cache_k.shape[1]
+        wide = B > 8 and Llama.wide_decode and self._decode_wide_ok(B, cache_len)
         key = (B, hp._state["device"], int(Llama.fused_decode or 0), os.environ.get("PDN_DECODE_SPLITS", ""),
-               self.layers[0].attention.cache_k.shape[1], tuple(ptrs), bool(sampling),   # (the addresses: no hash to collide)
+               cache_len, tuple(ptrs), bool(sampling), wide,   # (the addresses: no hash to collide)
                bool(ragged), bool(serve))
         if st is not None and st["key"] == key:
             return st if st["ok"] else None
@@ -426,6 +437,9 @@ class Llama(nn.Module):
                 g.destroy()
         ok = (B <= 8 and B * max(D, F) <= 16384 and D % 4 == 0 and F % 4 == 0 and V % 4 == 0 and (D // H) % 4 == 0
               and self.layers[0].attention.cache_k.shape[1] * 4 <= 60 * 1024 and D // H <= 256)
+        if wide:
+            # (the merge of the key-range partials happens in the output projection's load: at most 8 ranges)
+            ok = int(os.environ.get("PDN_DECODE_SPLITS", "0") or 0) <= 8
         packs = []
         if ok:
             for layer in self.layers:
@@ -438,9 +452,10 @@ class Llama(nn.Module):
                     break
                 packs.append((qkv, gu))
             ok = ok and self.lm_head.weight.data.is_contiguous() and self.tok_embedding.weight.data.is_contiguous()
-        st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged), "serve": bool(serve)}
+        st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged), "serve": bool(serve),
+              "wide": wide, "rows": bool(ragged or wide)}
         if ok:
-            nblk = _lib.lib().query("pdn_decode_gemv_blocks", V)
+            nblk = _lib.lib().query("pdn_decode_wide_blocks" if wide else "pdn_decode_gemv_blocks", V)
             # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
             ns = int(os.environ.get("PDN_DECODE_SPLITS", "0")) or (1 if self.layers[0].attention.cache_k.shape[1] <= 256 else 4)
             st.update(packs=packs, graphs={}, nograph=False, host_pos=None, ns=ns,
@@ -457,7 +472,7 @@ class Llama(nn.Module):
             # three launches per layer (csrc/decode_layer.hip): the output / down projections leave per-head /
             # per-32-hidden-unit records that the next kernel's staging adds to the residual row
             J = _lib.lib().query("pdn_decode_mlp_slices", F)
-            st["fused"] = bool(Llama.fused_decode and J and D <= 1024 and ns * H <= 256 and len(self.layers) > 0 and all(
+            st["fused"] = bool(not wide and Llama.fused_decode and J and D <= 1024 and ns * H <= 256 and len(self.layers) > 0 and all(
                 l.ffn.gate.weight.data.is_contiguous() and l.ffn.up.weight.data.is_contiguous() for l in self.layers))
             # two launches per layer (csrc/decode_block.hip): the q | k | v projection inside the attention kernel, one
             # more record per head for the new key
@@ -483,14 +498,33 @@ class Llama(nn.Module):
             if st["fused"]:
                 st.update(J=J, recs=hp.empty((B, (max(ns, st["ns_max"]) + 1) * H * (4 + D)), np.float32), dparts=hp.empty((B, J * D), np.float32),
                           xa=hp.empty((B, D), np.float32), xb=hp.empty((B, D), np.float32))
-            if ragged:
+            if ragged or wide:
                 st.update(pos=hp.zeros((B,), np.int32), step=hp.zeros((1,), np.int32),
                           stop=hp.zeros((-(-V // 32),), np.int32), run=None, host_step=None)
+            if wide:
+                # the wide ticks count their rows in at `arrive`; the split products keep partial tiles and arrival
+                # counters in `work` (both zero between launches)
+                work = max(_lib.lib().query("pdn_decode_wide_work_floats", B, k, n)
+                           for k, n in ((D, 3 * D), (D, D), (F, D), (D, 2 * F), (D, V)))
+                st.update(arrive=hp.zeros((1,), np.int32), work=hp.zeros((max(work, 4),), np.float32))
             if serve:
                 st.update(req=hp.zeros((B,), np.int32), left=hp.zeros((B,), np.int32), ring=4, pending=0, issued=0)
             self._decode_ws = {"logits": st["logits"], "x": st["x"]}
         self._decode_st = st
         return st if ok else None
+
+    def _decode_wide_ok(self, B, cache_len):
+        """Whether the library provides the wide step and takes this model with B rows; asked once per (library, B,
+        cache length), not at every step."""
+        from .. import _lib
+        L, D, H, F, V = _lib.lib(), self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
+        memo = getattr(self, "_wide_memo", None)
+        if memo is not None and memo[0] is L and memo[1] == (B, D, H, F, V, cache_len):
+            return memo[2]
+        ok = bool(all(_lib.provides(n) for n in _WIDE_ENTRIES)
+                  and L.query("pdn_decode_wide_supported", B, D, H, D // H, F, V, cache_len))
+        self._wide_memo = (L, (B, D, H, F, V, cache_len), ok)
+        return ok
 
     def _decode_ns(self, st, pos):
         """Key ranges per head for the step at position `pos`."""
@@ -510,13 +544,16 @@ class Llama(nn.Module):
         x, qkv, att, gu, logits = (st[n]._ptr for n in ("x", "qkv", "att", "gu", "logits"))
         pos = st["pos"]._ptr
         # (ragged plans: the same launches through the entries with a position per row)
-        rows = "rows_" if st["ragged"] else ""
+        rows = "rows_" if st["rows"] else ""
         # (x = embedding rows of the current ids: left there by the previous step's pick kernel, or by
         #  `_decode_gather` when the ids came from outside)
         emb = self.tok_embedding.weight.data
         cos, sin = self.freqs_cos.data._ptr, self.freqs_sin.data._ptr
         head = self.lm_head
         bias = head.bias.data._ptr if getattr(head, "bias", None) is not None else None
+        if st["wide"]:
+            self._decode_launches_wide(st, s)
+            return
         if st["fused"]:
             J, ns = st["J"], (st["ns"] if ns is None else ns)
             recs, dparts, xa, xb = (st[n]._ptr for n in ("recs", "dparts", "xa", "xb"))
@@ -582,11 +619,56 @@ class Llama(nn.Module):
                bias, None, 0, logits, V, B, D, V, 0, 0, 0, cv, ci, s)
         self._decode_tick(st, s)
 
+    def _decode_launches_wide(self, st, s):
+        """The wide step (9 .. 256 rows, csrc/decode_wide.hip): 5 launches per layer -- q | k | v with RMSNorm in the load,
+        the per-row attention, x += merge(partials) @ Wo, gate | up with RMSNorm in the load, x += SwiGLU(gate | up) @
+        Wdown -- then the vocabulary projection (+ candidates of the greedy pick) and the wide tick."""
+        from .. import _lib
+        L = _lib.lib()
+        D, H, F, V, B = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size, st["B"]
+        hd, ns = D // H, st["ns"]
+        x, qkv, att, gu, logits, pos, work = (st[n]._ptr for n in ("x", "qkv", "att", "gu", "logits", "pos", "work"))
+        cos, sin = self.freqs_cos.data._ptr, self.freqs_sin.data._ptr
+        for layer, (wqkv, wgu) in zip(self.layers, st["packs"]):
+            a, f = layer.attention, layer.ffn
+            ck, cv = a.cache_k.data, a.cache_v.data
+            nrm = layer.input_norm
+            L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wqkv._ptr, D, D,
+                   wqkv._strides[0], None, qkv, 3 * D, 0, None, None, pos, B, D, 3 * D, work, s)
+            L.call("pdn_decode_attention_rows_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, att, B, H, hd, ns,
+                   ck._strides[0], pos, ck.shape[1], s)
+            L.call("pdn_decode_wide_gemm_f32", att, st["att"].shape[1], 3, None, 0.0, ns, hd, a.O.weight.data._ptr, D, D,
+                   0, None, x, D, 1, None, None, pos, B, D, D, work, s)
+            nrm = layer.post_attn_norm
+            L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wgu._ptr, F, F,
+                   wgu._strides[0], None, gu, 2 * F, 0, None, None, pos, B, D, 2 * F, work, s)
+            L.call("pdn_decode_wide_gemm_f32", gu, 2 * F, 2, None, 0.0, 0, 0, f.down.weight.data._ptr, D, D, 0, None,
+                   x, D, 1, None, None, pos, B, F, D, work, s)
+        head = self.lm_head
+        bias = head.bias.data._ptr if getattr(head, "bias", None) is not None else None
+        cv, ci = (None, None) if st["sampling"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
+        L.call("pdn_decode_wide_gemm_f32", x, D, 1, self.norm.weight.data._ptr, self.norm.eps, 0, 0, head.weight.data._ptr,
+               V, V, 0, bias, logits, V, 0 if st["sampling"] else 2, cv, ci, pos, B, D, V, work, s)
+        self._decode_tick(st, s)
+
     def _decode_tick(self, st, s):
         """The last launch of a step: the greedy pick over the projection's candidates, or (sampling plans) the sample
         tick over the full logit rows with counter (*pos, b); either stores the token and its embedding row, *pos += 1."""
         from .. import _lib
         L, emb, D, B = _lib.lib(), self.tok_embedding.weight.data, self.embed_dim, st["B"]
+        if st["wide"]:
+            # (one workgroup per row: the last row to finish advances the step counter, csrc/decode_wide.hip)
+            cnt = (st["pos"]._ptr, st["step"]._ptr, st["arrive"]._ptr)
+            out = (st["hist_ptr"]._ptr, emb._ptr, emb._strides[0], D, st["x"]._ptr, s)
+            src = ((st["logits"]._ptr, self.vocab_size, B, self.vocab_size, st["params"]._ptr) if st["sampling"] else
+                   (st["cand_v"]._ptr, st["cand_i"]._ptr, B, st["cand_v"].shape[1]))
+            kind = "sample" if st["sampling"] else "pick"
+            if st["serve"]:
+                L.call(f"pdn_decode_wide_{kind}_tick_slots_f32", *src, st["ids"]._ptr, *cnt, st["req"]._ptr,
+                       st["left"]._ptr, st["ring"], st["stop"]._ptr, *out)
+            else:
+                L.call(f"pdn_decode_wide_{kind}_tick_rows_f32", *src, st["ids"]._ptr, *cnt, st["stop"]._ptr, *out)
+            return
         if st["serve"]:
             # (the slot ticks: counter (pos[b], req[b]), a token budget per row, a history ring)
             srv = (st["pos"]._ptr, st["step"]._ptr, st["req"]._ptr, st["left"]._ptr, st["ring"], st["stop"]._ptr,
@@ -652,6 +734,9 @@ class Llama(nn.Module):
             st["host_pos"] = st["last_out"] = None               # (position and ids are uploaded again below)
         if st["host_pos"] != pos:
             st["pos"][...] = np.int32(pos)                       # (later steps: the device advances it itself)
+            if st["rows"]:                                       # (the wide step: equal positions, history by step)
+                st["step"][...] = np.int32(pos)
+                st["stop"][...] = np.int32(0)
             # a new generation: its own history -- slots in mapped host memory the pick kernel stores into directly
             st["hist"] = hp.Mailbox(cache.shape[1], (B, 1))
             st["hist_ptr"][...] = np.int64(st["hist"]._ptr)
@@ -686,6 +771,8 @@ class Llama(nn.Module):
             hp.synchronize()                                     # the capture's runs are done with the scratch history
             st["hist_ptr"][...] = np.int64(st["hist"]._ptr)
             st["pos"][...] = np.int32(pos)
+            if st["rows"]:
+                st["step"][...] = np.int32(pos)
             st["ids"][...] = keep
             self._decode_gather(st)
         if g:
