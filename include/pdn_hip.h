@@ -185,7 +185,8 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  30 continuous batching: pdn_decode_pick_tick_slots_f32, pdn_decode_sample_tick_slots_f32 (which also counts in 28)
  *     and pdn_kv_store_slots_f32 (csrc/serve.hip)
  *  31 wide decode (csrc/decode_wide.hip): pdn_decode_wide_gemm_f32 and the four pdn_decode_wide_*_tick_* entries (the
- *     ticks also count in 29, the slot forms in 30, the sampled forms in 28) */
+ *     ticks also count in 29, the slot forms in 30, the sampled forms in 28)
+ *  32 beam search (csrc/beam.hip): pdn_beam_topk_rows_f32, pdn_beam_select_f32, pdn_kv_reorder_rows_f32 */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -658,6 +659,42 @@ int pdn_decode_wide_sample_tick_slots_f32(const float* logits, int64_t row_strid
                                           int* arrive, const int* req, int* left, int ring, const unsigned* stop_mask,
                                           int64_t* const* history, const float* emb, int64_t emb_row_stride, int D,
                                           float* x_next, void* stream);
+/* Beam search (csrc/beam.hip; Llama.beam_search, the NumPy statement is pydynet_amd/llm/beam.py): G groups of W <= 16 beam
+ * rows, rows g * W .. g * W + W - 1 holding the beams of prompt g.  A step's launches are the *_rows_f32 step with full
+ * logit rows, then these three instead of a tick.  Every sum runs in a fixed order (no float atomics): two runs give the
+ * same bits.
+ *   pdn_beam_topk_rows_f32   one workgroup per row r with pos[r] >= 0 (pos may be NULL: every row): lse = the row's
+ *                            log-sum-exp (double, fixed order); the W best tokens that are not among the n_stops <= 16
+ *                            (distinct) stop ids, by (logit desc, id asc), as (float(z - lse), id) in cand_lp / cand_id
+ *                            (B, W); float(z[stops[j]] - lse) in stop_lp (B, n_stops).  first != 0 (the prompt pass):
+ *                            only rows r % W == 0 run, reading logit row r / W (the B / W prompt rows).  A row of up to
+ *                            36864 tokens is staged once in LDS; longer rows (up to 2^20) are re-read from memory.
+ *   pdn_beam_select_f32      one workgroup per group g whose pos[g * W] >= 0 (else done: it only counts in).  Candidates
+ *                            (beam j, token v): the W non-stop and the n_stops stop candidates of each row g * W + j
+ *                            (first: beam 0 only, score 0), score float(scores[g * W + j] + logp), ordered by (score
+ *                            desc, j asc, v asc).  The first W non-stop candidates become beams 0 .. W - 1: next_ids,
+ *                            scores, parent (row index), (*step, row) -> (token, parent beam) into hist (n_hist, B, 2)
+ *                            int32 (NULL: none; steps >= n_hist are not stored), the token's embedding row into x_next
+ *                            (may be NULL), pos += 1.  A stop candidate among the first W of the whole order is appended
+ *                            to the group's finished list, fin (G, 2 W - 1, 4) int32 (step, parent beam, stop id, score
+ *                            bits), count fin_n (G,).  A group holding >= W finished entries is done: pos = -1 and
+ *                            parent = the row itself on all its rows.  arrive and live_acc (1,) int32: zero before the
+ *                            first launch, left zero by every launch; the last group to count in stores the number of
+ *                            groups still live into live_out[*step] (int64, may be host memory; NULL: none; only when
+ *                            *step < n_live) and advances *step.
+ *   pdn_kv_reorder_rows_f32  for each of the n_tensors caches (a device array of pointers, each (B', max_len, D) with
+ *                            batch stride batch_stride floats, 16-byte aligned) and every row r < B <= 256 with
+ *                            parent[r] != r and pos[r] > 0: positions [0, min(pos[r], max_len)) of row r take row
+ *                            parent[r]'s contents as they were before the launch (an in-place gather: swaps and cycles
+ *                            are allowed).  Rows with parent[r] == r or pos[r] <= 0 are not touched.  D % 4 == 0. */
+int pdn_beam_topk_rows_f32(const float* logits, int64_t row_stride, int B, int V, int W, int first, const int* pos,
+                           const int* stops, int n_stops, float* cand_lp, int* cand_id, float* stop_lp, void* stream);
+int pdn_beam_select_f32(const float* cand_lp, const int* cand_id, const float* stop_lp, const int* stops, int n_stops,
+                        int G, int W, int first, float* scores, int64_t* next_ids, int* parent, int* pos, int* step,
+                        int* arrive, int* live_acc, int* hist, int n_hist, int* fin_n, int* fin, int64_t* live_out,
+                        int n_live, const float* emb, int64_t emb_row_stride, int D, float* x_next, void* stream);
+int pdn_kv_reorder_rows_f32(float* const* caches, int n_tensors, int64_t batch_stride, int B, int max_len, int D,
+                            const int* parent, const int* pos, void* stream);
 /* shapes the resident (K / V of a head chunk-wise in LDS) kernels above take: head_dim 48 or 64, L a multiple of 32 up
  * to 1024 -- sequences beyond 256 pass through LDS in 256-row chunks (forward: one online rescale per chunk) -- and
  * (round 6, csrc/attention_hd128.hip) head_dim 128 at ANY length 1 .. 1024, no RoPE inside: the shape of

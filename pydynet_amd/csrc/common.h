@@ -54,7 +54,8 @@ enum {
                                   // sample.hip, pdn_attention_decode_rows_f32)
   PDN_CNT_DECODE_SLOTS = 30,      // continuous batching (Llama.serve): the *_tick_slots_f32 ticks, pdn_kv_store_slots_f32
   PDN_CNT_DECODE_WIDE = 31,       // wide decode (9..256 rows, csrc/decode_wide.hip): the MFMA product and the wide ticks
-  PDN_CNT_SLOTS = 32
+  PDN_CNT_BEAM = 32,              // beam search (csrc/beam.hip): top-k, select and the KV-cache reorder
+  PDN_CNT_SLOTS = 33
 };
 void pdn_count(int slot);
 

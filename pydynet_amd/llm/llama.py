@@ -20,6 +20,7 @@ from .. import nn
 from ..autograd import is_grad_enable
 from ..core import Tensor, fused
 from ..special import zeros
+from . import beam as beam_np
 from .sampling import (check_args as check_sampling_args, params_bytes, params_buffer, sample_next,
                        sample_next_rows)
 
@@ -380,12 +381,8 @@ class Llama(nn.Module):
         """One ragged decode step on the tape-node operators (the `cpu` device, fast_decode = False, training mode,
         other dtypes): row b's token at position pos[b] (-1: a stopped row, which yields -1).  The NumPy statement of what
         the per-row kernels compute.  `req`: the counter id of each row (Llama.serve; default: the row)."""
-        tok = ids.data if pos.min() >= 0 else np.maximum(ids.numpy(), 0)      # (a stopped row's -1 is no token)
         p = np.maximum(pos, 0)
-        h = self.tok_embedding(Tensor(tok, dtype=np.int64, device=ids.device) if tok is not ids.data else ids)
-        for layer in self.layers:
-            h = layer.step_rows(h, pos, self.freqs_cos, self.freqs_sin)
-        logits = self.lm_head(self.norm(h))[:, -1, :]
+        logits = self._step_logits_rows(ids, pos)
         nxt = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, p, *sampling, rows=req)
         if pos.min() >= 0:
             return nxt
@@ -393,13 +390,21 @@ class Llama(nn.Module):
         out[pos < 0] = -1
         return Tensor(out, dtype=np.int64, device=ids.device)
 
+    def _step_logits_rows(self, ids, pos):
+        """The logits (B, V) of `_step_module_rows`' step: row b fed ids[b] at position pos[b] (-1: stopped)."""
+        tok = ids.data if pos.min() >= 0 else np.maximum(ids.numpy(), 0)      # (a stopped row's -1 is no token)
+        h = self.tok_embedding(Tensor(tok, dtype=np.int64, device=ids.device) if tok is not ids.data else ids)
+        for layer in self.layers:
+            h = layer.step_rows(h, pos, self.freqs_cos, self.freqs_sin)
+        return self.lm_head(self.norm(h))[:, -1, :]
+
     # -- decode fast path (SURVEY 8f-1) -----------------------------------------------------------
     graph_decode = True     # class switch: False issues the step's launches one by one instead of replaying a hipGraph
     decode_ahead = True     # class switch: False never queues the next step before the caller asked for it
     fused_decode = 2        # class switch: launches per layer = 2 (q|k|v inside the attention kernel), 1 -> 3, 0 / False -> 5
     wide_decode = True      # class switch: 9 .. 256 rows on the wide step (csrc/decode_wide.hip); False -> the generic step
 
-    def _decode_plan(self, B, sampling=False, ragged=False, serve=False):
+    def _decode_plan(self, B, sampling=False, ragged=False, serve=False, beam=0, n_stops=0):
         """Buffers and weight views of the graph-replayable decode step (csrc/decode.hip), or None when the
         model's shapes / layout are outside what those kernels take (then the generic launches below run).
         `sampling`: the step ends in the sample tick (csrc/sample.hip) instead of the greedy pick; its parameters live in
@@ -409,6 +414,8 @@ class Llama(nn.Module):
         token is set in the `stop` bitmask.
         `serve` (Llama.serve, with `ragged`): the step ends in the slot ticks -- `req` (B,) int32 holds the counter id of
         each row, `left` (B,) int32 the tokens it may still produce -- and the history is a ring of `ring` steps.
+        `beam` (Llama.beam_search, with `ragged`): W beams per group and `n_stops` stop ids; the projection writes full
+        logit rows and the tick is replaced by top-k -> select -> KV-cache reorder (csrc/beam.hip, buffers in `bm`).
         More than 8 rows (`wide_decode`): the wide step of csrc/decode_wide.hip, always in the per-row form (`rows`; a
         rectangular batch holds equal positions and a step counter equal to the position)."""
         from .. import hipnp as hp, _lib
@@ -429,7 +436,7 @@ class Llama(nn.Module):
         wide = B > 8 and Llama.wide_decode and self._decode_wide_ok(B, cache_len)
         key = (B, hp._state["device"], int(Llama.fused_decode or 0), os.environ.get("PDN_DECODE_SPLITS", ""),
                cache_len, tuple(ptrs), bool(sampling), wide,   # (the addresses: no hash to collide)
-               bool(ragged), bool(serve))
+               (int(beam), int(n_stops)), bool(ragged), bool(serve))
         if st is not None and st["key"] == key:
             return st if st["ok"] else None
         if st is not None:
@@ -453,7 +460,7 @@ class Llama(nn.Module):
                 packs.append((qkv, gu))
             ok = ok and self.lm_head.weight.data.is_contiguous() and self.tok_embedding.weight.data.is_contiguous()
         st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged), "serve": bool(serve),
-              "wide": wide, "rows": bool(ragged or wide)}
+              "wide": wide, "rows": bool(ragged or wide), "beam": int(beam), "full": bool(sampling or beam)}
         if ok:
             nblk = _lib.lib().query("pdn_decode_wide_blocks" if wide else "pdn_decode_gemv_blocks", V)
             # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
@@ -509,6 +516,8 @@ class Llama(nn.Module):
                 st.update(arrive=hp.zeros((1,), np.int32), work=hp.zeros((max(work, 4),), np.float32))
             if serve:
                 st.update(req=hp.zeros((B,), np.int32), left=hp.zeros((B,), np.int32), ring=4, pending=0, issued=0)
+            if beam:
+                st["bm"] = self._beam_buffers(B, int(beam), int(n_stops), cache_len + 2)
             self._decode_ws = {"logits": st["logits"], "x": st["x"]}
         self._decode_st = st
         return st if ok else None
@@ -588,7 +597,7 @@ class Llama(nn.Module):
                 L.call("pdn_decode_mlp_f32", x if li == 0 else xa, D, recs, rrs, ns, H, xb, D, nrm.weight.data._ptr,
                        nrm.eps, f.gate.weight.data._ptr, f.up.weight.data._ptr, F, f.down.weight.data._ptr, D, dparts,
                        J * D, B, D, F, s)
-            cv, ci = (None, None) if st["sampling"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
+            cv, ci = (None, None) if st["full"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
             L.call("pdn_decode_gemv_sum_f32", xb, D, dparts, J, J * D, None, 0, self.norm.weight.data._ptr, self.norm.eps,
                    head.weight.data._ptr, V, V, 0, bias, logits, V, B, D, V, cv, ci, s)
             self._decode_tick(st, s)
@@ -614,7 +623,7 @@ class Llama(nn.Module):
                    None, None, s)
         # vocabulary projection; every workgroup also leaves the first maximum of its columns, the pick kernel
         # finishes the argmax over those candidates (model.py:262-268) and advances the position
-        cv, ci = (None, None) if st["sampling"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
+        cv, ci = (None, None) if st["full"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
         L.call("pdn_decode_gemv_f32", x, D, self.norm.weight.data._ptr, self.norm.eps, head.weight.data._ptr, V, V, 0,
                bias, None, 0, logits, V, B, D, V, 0, 0, 0, cv, ci, s)
         self._decode_tick(st, s)
@@ -646,9 +655,9 @@ class Llama(nn.Module):
                    x, D, 1, None, None, pos, B, F, D, work, s)
         head = self.lm_head
         bias = head.bias.data._ptr if getattr(head, "bias", None) is not None else None
-        cv, ci = (None, None) if st["sampling"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
+        cv, ci = (None, None) if st["full"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
         L.call("pdn_decode_wide_gemm_f32", x, D, 1, self.norm.weight.data._ptr, self.norm.eps, 0, 0, head.weight.data._ptr,
-               V, V, 0, bias, logits, V, 0 if st["sampling"] else 2, cv, ci, pos, B, D, V, work, s)
+               V, V, 0, bias, logits, V, 0 if st["full"] else 2, cv, ci, pos, B, D, V, work, s)
         self._decode_tick(st, s)
 
     def _decode_tick(self, st, s):
@@ -656,6 +665,10 @@ class Llama(nn.Module):
         tick over the full logit rows with counter (*pos, b); either stores the token and its embedding row, *pos += 1."""
         from .. import _lib
         L, emb, D, B = _lib.lib(), self.tok_embedding.weight.data, self.embed_dim, st["B"]
+        if st["beam"]:
+            self._beam_launches(st["bm"], st["logits"]._ptr, self.vocab_size, st["pos"]._ptr, st["step"]._ptr,
+                                st["ids"]._ptr, st["x"]._ptr, first=False)
+            return
         if st["wide"]:
             # (one workgroup per row: the last row to finish advances the step counter, csrc/decode_wide.hip)
             cnt = (st["pos"]._ptr, st["step"]._ptr, st["arrive"]._ptr)
@@ -1156,6 +1169,14 @@ class Llama(nn.Module):
         position len_i there -- the slot a decode step attends to but never writes (`generate`'s step at position p feeds
         the token of position p - 1), which in a fresh cache holds zeros.  No pad position and no other row is written.
         Returns the first token of each request (counter (len_i, reqs[i]) when sampled), host int64."""
+        logits = self._prefill_rows(prompts, rows)
+        lens = np.array([p.size for p in prompts], np.int64)
+        first = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, lens, *sampling, rows=reqs)
+        return np.asarray(first.numpy()).reshape(-1).astype(np.int64)
+
+    def _prefill_rows(self, prompts, rows):
+        """The prompt pass of `_serve_prefill` (and of `beam_search`): prompt i's keys / values into cache row rows[i],
+        positions [0, len_i), position len_i zeroed.  Returns the logits of each prompt's last real position, (A, V)."""
         A = len(prompts)
         lens = np.array([p.size for p in prompts], np.int64)
         Lp = int(lens.max())
@@ -1197,8 +1218,7 @@ class Llama(nn.Module):
                         k[int(b), :int(lens[i])] = a[i, :int(lens[i])]
                         if lens[i] < T:
                             k[int(b), int(lens[i])] = 0
-        first = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, lens, *sampling, rows=reqs)
-        return np.asarray(first.numpy()).reshape(-1).astype(np.int64)
+        return logits
 
     # (graph path of `serve`: the served plan holds the rows' state on the device; steps are issued, queued ahead and
     #  read in order, through a ring of `ring` history slots)
@@ -1289,3 +1309,232 @@ class Llama(nn.Module):
         st["left"][...] = left.astype(np.int32)
         st["ids"][...] = last.reshape(-1, 1)
         self._decode_gather(st)
+
+    # -- beam search: the W most probable continuations of each prompt (statement: llm/beam.py) ----------------------
+    def beam_search(self, prompts, max_new_tokens, num_beams, length_penalty=1.0, stop_ids=()):
+        """Beam search over B prompts (ragged lengths allowed) with `num_beams` = W beams each: rows g * W .. g * W + W - 1
+        of the KV cache hold prompt g's beams.  Returns a list of B lists of W (tokens: int64 array, score: float) pairs,
+        best first: the W best hypotheses of each prompt by score / n_gen ** length_penalty (llm/beam.py states the rules).
+        A hypothesis ends at a stop id (included) or after `max_new_tokens` tokens; a prompt is done once it holds W
+        hypotheses ended by a stop id.  Every argument is checked here (ValueError), before anything runs."""
+        V = self.vocab_size
+        if isinstance(num_beams, (bool, np.bool_)) or int(num_beams) != num_beams or not 1 <= num_beams <= beam_np.MAX_BEAMS:
+            raise ValueError(f"num_beams must be an integer in [1, {beam_np.MAX_BEAMS}], got {num_beams!r}")
+        W = int(num_beams)
+        if isinstance(max_new_tokens, (bool, np.bool_)) or int(max_new_tokens) != max_new_tokens or max_new_tokens < 1:
+            raise ValueError(f"max_new_tokens must be a positive integer, got {max_new_tokens!r}")
+        n = int(max_new_tokens)
+        length_penalty = float(length_penalty)
+        if not np.isfinite(length_penalty):
+            raise ValueError(f"length_penalty must be finite, got {length_penalty}")
+        rows = [np.asarray(p.numpy() if isinstance(p, Tensor) else p).reshape(-1) for p in prompts]
+        if not rows:
+            raise ValueError("beam_search needs at least one prompt")
+        cache = self.layers[0].attention.cache_k
+        B = len(rows) * W
+        if B > cache.shape[0] or B > 256:
+            raise ValueError(f"{len(rows)} prompts x {W} beams = {B} rows exceed the KV cache's max_batch_size "
+                             f"{cache.shape[0]} or 256")
+        limit = min(cache.shape[1], self.freqs_cos.shape[0])
+        for g, r in enumerate(rows):
+            if r.size == 0:
+                raise ValueError(f"prompt {g} is empty")
+            if r.dtype.kind not in "iu" or r.min() < 0 or r.max() >= V:
+                raise ValueError(f"prompt {g}: token ids must be integers in [0, {V})")
+            last = r.size + n - 1
+            if r.size > cache.shape[1] or (n > 1 and last >= limit):
+                raise ValueError(f"prompt {g}: its last position {last} is outside the KV cache / RoPE table "
+                                 f"(max_seq_len {cache.shape[1]}, {self.freqs_cos.shape[0]} RoPE rows)")
+        stops = np.asarray(sorted({int(t) for t in stop_ids}), np.int64)
+        if stops.size and (stops.min() < 0 or stops.max() >= V):
+            raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
+        if stops.size > beam_np.MAX_STOPS:
+            raise ValueError(f"at most {beam_np.MAX_STOPS} distinct stop ids, got {stops.size}")
+        if V - stops.size < W:
+            raise ValueError(f"{V} tokens minus {stops.size} stop ids leave fewer than num_beams = {W}")
+        rows = [r.astype(np.int64) for r in rows]
+        dev = self.tok_embedding.weight.device
+        if (Llama.fast_decode and dev.is_hip and not self._train and self.lm_head.weight.dtype == np.float32
+                and (self.embed_dim // self.n_heads) % 4 == 0):
+            out = self._beam_device(rows, n, W, length_penalty, stops)
+        else:
+            out = self._beam_module(rows, n, W, length_penalty, stops)
+        # the rows' caches back to zeros, as a fresh model holds them: a later generation reads the slot after its prompt
+        # before writing it (the reference's decode positions), so nothing of this search may stay there
+        T = min(cache.shape[1], max(r.size for r in rows) + n + 1)
+        for c in (c for layer in self.layers for c in (layer.attention.cache_k, layer.attention.cache_v)):
+            c.data[:B, :T] = 0
+        return out
+
+    def _beam_module(self, rows, n, W, lp, stops):
+        """The NumPy statement on the tape-node operators (the `cpu` device, training mode, fast_decode = False): logits of
+        `_step_logits_rows`, top-k / select of llm/beam.py, the cache reorder by indexing."""
+        G, B = len(rows), len(rows) * W
+        lens = np.array([r.size for r in rows], np.int64)
+        dev = self.tok_embedding.weight.device
+        caches = [c for layer in self.layers for c in (layer.attention.cache_k, layer.attention.cache_v)]
+        z = np.asarray(self._prefill_rows(rows, np.arange(G) * W).numpy(), np.float32)
+        hist = np.zeros((n, B, 2), np.int64)
+        fins = [[] for _ in range(G)]
+        scores = np.zeros(B, np.float32)
+        pos = np.repeat(lens, W)                      # (the position just fed: the prompt's pass counts as len)
+        ids = np.zeros(B, np.int64)
+        last = 0
+        for s in range(n):
+            if s:
+                logits = self._step_logits_rows(Tensor(ids.reshape(B, 1), dtype=np.int64, device=dev), pos)
+                z = np.asarray(logits.numpy(), np.float32)
+            cl, ci, sl = beam_np.topk_rows(z, W, stops)
+            parent = np.arange(B)
+            for g in range(G):
+                r0 = g * W
+                if pos[r0] < 0:
+                    continue
+                k, nb = (slice(g, g + 1), 1) if s == 0 else (slice(r0, r0 + W), W)
+                tok, par, sc, fin = beam_np.select_group(scores[r0:r0 + W], cl[k], ci[k], sl[k].reshape(nb, stops.size),
+                                                         stops, W, first=s == 0)
+                hist[s, r0:r0 + W, 0], hist[s, r0:r0 + W, 1] = tok, par
+                scores[r0:r0 + W], ids[r0:r0 + W] = sc, tok
+                fins[g] += [(s, p, t, raw) for p, t, raw in fin]
+                if len(fins[g]) >= W:
+                    pos[r0:r0 + W] = -1
+                else:
+                    pos[r0:r0 + W] += 1
+                    parent[r0:r0 + W] = r0 + par
+            last = s
+            move = np.flatnonzero((parent != np.arange(B)) & (pos > 0))
+            for c in caches:                          # (every source read before any row is written)
+                src = [c.data[int(parent[r]), :int(pos[r])].copy() for r in move]
+                for r, v in zip(move, src):
+                    c.data[int(r), :int(pos[r])] = v
+            if (pos < 0).all():
+                break
+        live = [None if pos[g * W] < 0 else scores[g * W:(g + 1) * W] for g in range(G)]
+        return beam_np.results(hist[:last + 1], fins, live, last, W, lp)
+
+    def _beam_buffers(self, B, W, S, n_hist):
+        """Device state of a beam search over B = G * W rows (csrc/beam.hip): candidates, scores, parents, the (token,
+        parent beam) history of n_hist steps, the finished lists, the counters and the live-group mailbox."""
+        from .. import hipnp as hp
+        caches = [c.data for layer in self.layers for c in (layer.attention.cache_k, layer.attention.cache_v)]
+        G = B // W
+        return dict(W=W, S=S, n_hist=n_hist, cand_lp=hp.empty((B, W), np.float32), cand_id=hp.empty((B, W), np.int32),
+                    stop_lp=hp.empty((B, max(S, 1)), np.float32), stops=hp.zeros((max(S, 1),), np.int32),
+                    scores=hp.zeros((B,), np.float32), parent=hp.zeros((B,), np.int32),
+                    arrive=hp.zeros((1,), np.int32), live_acc=hp.zeros((1,), np.int32),
+                    hist=hp.zeros((n_hist, B, 2), np.int32), fin_n=hp.zeros((G,), np.int32),
+                    fin=hp.zeros((G, 2 * W - 1, 4), np.int32), live=hp.Mailbox(n_hist, (1,), unset=np.iinfo(np.int64).min),
+                    caches=hp.asarray(np.array([c._ptr for c in caches], np.int64)), n_caches=len(caches),
+                    cache_bs=caches[0]._strides[0], cache_len=caches[0].shape[1])
+
+    def _beam_launches(self, bm, logits, rs, pos, step, ids, x, first):
+        """top-k -> select -> KV-cache reorder of one beam step over the logit rows at `logits` (first: the B / W prompt
+        rows of the prompt pass)."""
+        from .. import hipnp as hp, _lib
+        L, s = _lib.lib(), hp.stream()
+        W, S, V, D = bm["W"], bm["S"], self.vocab_size, self.embed_dim
+        B = bm["scores"].shape[0]
+        emb = self.tok_embedding.weight.data
+        cl, ci, sl, stops = (bm[k]._ptr for k in ("cand_lp", "cand_id", "stop_lp", "stops"))
+        L.call("pdn_beam_topk_rows_f32", logits, rs, B, V, W, int(first), pos, stops, S, cl, ci, sl, s)
+        L.call("pdn_beam_select_f32", cl, ci, sl, stops, S, B // W, W, int(first), bm["scores"]._ptr, ids,
+               bm["parent"]._ptr, pos, step, bm["arrive"]._ptr, bm["live_acc"]._ptr, bm["hist"]._ptr, bm["n_hist"],
+               bm["fin_n"]._ptr, bm["fin"]._ptr, bm["live"]._ptr, bm["n_hist"], emb._ptr, emb._strides[0], D, x, s)
+        L.call("pdn_kv_reorder_rows_f32", bm["caches"]._ptr, bm["n_caches"], bm["cache_bs"], B, bm["cache_len"], D,
+               bm["parent"]._ptr, pos, s)
+
+    def _beam_device(self, rows, n, W, lp, stops):
+        """beam_search on a HIP device: the prompt pass (`_prefill_rows`, into rows g * W) and its beam launches, then one
+        decode step per generated token -- a replay of the captured beam plan (or, where the plan refuses the shapes, the
+        generic per-row step and the beam launches one by one).  The host polls the live-group count of each step,
+        queuing the next step first; at the end it reads the history and backtracks."""
+        from .. import hipnp as hp
+        G, B = len(rows), len(rows) * W
+        lens = np.array([r.size for r in rows], np.int64)
+        st = self._decode_plan(B, ragged=True, beam=W, n_stops=stops.size)
+        if st is not None:
+            bm, pos, step, ids, x = st["bm"], st["pos"], st["step"], st["ids"], st["x"]
+        else:
+            bm = self._beam_buffers(B, W, stops.size, n + 2)
+            pos, step, ids, x = hp.zeros((B,), np.int32), hp.zeros((1,), np.int32), hp.zeros((B, 1), np.int64), None
+        bm["live"].host[...] = bm["live"].unset
+        if stops.size:
+            bm["stops"][...] = stops.astype(np.int32)
+        bm["scores"][...] = np.float32(0)
+        bm["fin_n"][...] = np.int32(0)
+        step[...] = np.int32(0)
+        pos[...] = np.repeat(lens, W).astype(np.int32)
+        logits = self._prefill_rows(rows, np.arange(G) * W).data
+        if not logits.is_contiguous():
+            logits = logits.copy()
+        self._beam_launches(bm, logits._ptr, self.vocab_size, pos._ptr, step._ptr, ids._ptr, x._ptr if x is not None else None,
+                            first=True)
+        last = 0
+        live = int(bm["live"].slot(0).get().reshape(-1)[0])
+        queued = False
+        for s in range(1, n):
+            if live == 0:
+                break
+            top = int(lens.max()) + s
+            if st is None:
+                p = pos.get().astype(np.int32)
+                self._decode_step_generic_rows(ids, p)
+                ws = self._decode_ws_rows
+                self._beam_launches(bm, ws["logits"]._ptr, self.vocab_size, pos._ptr, step._ptr, ids._ptr, None, False)
+            else:
+                if not queued:
+                    self._beam_issue(st, top)
+                queued = s + 1 < n and self._beam_ahead(st, top + 1)
+            last = s
+            live = int(bm["live"].slot(s).get().reshape(-1)[0])
+        hp.synchronize()                                 # (a step queued ahead: all its rows had stopped)
+        hist = bm["hist"].get()[:last + 1].astype(np.int64)
+        fin_n, fin, sc, p = bm["fin_n"].get(), bm["fin"].get(), bm["scores"].get(), pos.get()
+        fins = [[(int(e[0]), int(e[1]), int(e[2]), np.int32(e[3]).view(np.float32)) for e in fin[g, :fin_n[g]]]
+                for g in range(G)]
+        live_sc = [None if p[g * W] < 0 else sc[g * W:(g + 1) * W] for g in range(G)]
+        return beam_np.results(hist, fins, live_sc, last, W, lp)
+
+    def _beam_issue(self, st, top):
+        """Issue the next step of a beam plan (its furthest row at position `top`); captures its graph first when this
+        range count has none.  The capture's two real runs see every row stopped -- no cache, score or history is
+        written -- and the rows' state is put back afterwards."""
+        from .. import hipnp as hp, _lib
+        ns = self._decode_ns(st, top)
+        g = False if st["nograph"] else st["graphs"].get((ns, "beam"))
+        if g is None and Llama.graph_decode:
+            keep = {n: st[n].copy() for n in ("ids", "pos", "step")}
+            k = int(keep["step"].get()[0])
+            st["pos"][...] = np.int32(-1)
+            try:
+                g = hp.Graph()
+                g.capture(lambda: self._decode_launches(st, ns))
+                st["graphs"][(ns, "beam")] = g
+            except _lib.HipLibraryError as e:
+                if e.code != -2:                                 # PDN_EUNSUPPORTED: no graph support (emulated ABI)
+                    raise
+                st["nograph"], g = True, False
+            hp.synchronize()
+            live = st["bm"]["live"]
+            live.host[k:min(k + 2, live.n)] = live.unset         # (the capture's runs counted no live group there)
+            for n_, v in keep.items():
+                st[n_][...] = v
+            self._decode_gather(st)
+        if g:
+            g.replay()
+        else:
+            self._decode_launches(st, ns)
+
+    def _beam_ahead(self, st, top):
+        """Queue the next beam step right behind the issued one if its graph exists (decode_ahead); True if queued."""
+        if not Llama.decode_ahead:
+            return False
+        ns = self._decode_ns(st, top)
+        g = False if st["nograph"] else st["graphs"].get((ns, "beam"))
+        if g is None:
+            return False
+        if g:
+            g.replay()
+        else:
+            self._decode_launches(st, ns)
+        return True
