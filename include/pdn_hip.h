@@ -186,7 +186,8 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *     and pdn_kv_store_slots_f32 (csrc/serve.hip)
  *  31 wide decode (csrc/decode_wide.hip): pdn_decode_wide_gemm_f32 and the four pdn_decode_wide_*_tick_* entries (the
  *     ticks also count in 29, the slot forms in 30, the sampled forms in 28)
- *  32 beam search (csrc/beam.hip): pdn_beam_topk_rows_f32, pdn_beam_select_f32, pdn_kv_reorder_rows_f32 */
+ *  32 beam search (csrc/beam.hip): pdn_beam_topk_rows_f32, pdn_beam_select_f32, pdn_kv_reorder_rows_f32
+ *  33 chunked prefill (csrc/extend.hip): pdn_kv_append_rows_f32, pdn_decode_extend_attention_f32 */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -695,6 +696,39 @@ int pdn_beam_select_f32(const float* cand_lp, const int* cand_id, const float* s
                         int n_live, const float* emb, int64_t emb_row_stride, int D, float* x_next, void* stream);
 int pdn_kv_reorder_rows_f32(float* const* caches, int n_tensors, int64_t batch_stride, int B, int max_len, int D,
                             const int* parent, const int* pos, void* stream);
+/* Chunked prefill (csrc/extend.hip; Llama.serve(prefill_chunk=C), the schedule's NumPy statement is
+ * pydynet_amd/llm/chunked.py): the mixed step runs the decode queries of the slots and up to C prompt tokens as n_q query
+ * rows of the wide product (pdn_decode_wide_gemm_f32 takes 1 .. 256 rows).  Its attention is a layout of runs, runs
+ * (n_runs, 4) int32, one per cache row r < n_runs: [q0, n, start, ends] = query rows q0 .. q0 + n - 1 of the packed
+ * q | k | v rows (qkv_row_stride floats apart, [q | k | v] of width 3 H head_dim) at positions start .. start + n - 1 of
+ * cache row r; n = 0: the row is not in the layout.  A run is taken only if 1 <= n <= max_run, q0 + n <= n_q and start
+ * + n <= max_len (else nothing of it is written).  Caches (>= n_runs, max_len, H, head_dim) with batch stride
+ * cache_batch_stride floats; cos / sin tables (max_len, head_dim / 2); head_dim % 4 == 0, <= 256.  Every sum runs in a
+ * fixed order (no float atomics): two launches give the same bits.
+ *   pdn_decode_mixed_supported       1 when the mixed step takes a model of these shapes at any row count: the shape
+ *                                    conditions of pdn_decode_wide_supported without the row count, and the extend
+ *                                    attention's LDS within 64 KB.
+ *   pdn_kv_append_rows_f32           k of query q0 + j rotated by position start + j (interleaved pairs, as the decode
+ *                                    kernels), stored with v into cache row r at that position; ends != 0 also zeroes
+ *                                    position start + n of the row when it is < max_len (the slot the first decode step
+ *                                    attends to but never writes).  No other position or row is written.
+ *   pdn_decode_extend_attention_f32  reads only the caches (run the append first): query q0 + j, rotated by position
+ *                                    start + j, attends keys [0, start + j] of cache row r.  The keys of a run are cut
+ *                                    into n_splits ranges of ceil((start + n) / n_splits) keys (for n = 1 the ranges of
+ *                                    pdn_decode_attention_rows_f32), and each (query row, range, head) gets the record
+ *                                    of that kernel, [m, l, 0, 0 | sum exp(s - m) v]: partials (n_q, n_splits, H, 4 +
+ *                                    head_dim) floats, merged by mode 3 of pdn_decode_wide_gemm_f32 (a range without
+ *                                    keys: m = -inf, l = 0, zeros).  Query rows outside every run are not written.  A
+ *                                    workgroup takes 16 queries of one (run, head, range) and reads each key of the
+ *                                    range once for all of them. */
+int pdn_decode_mixed_supported(int D, int H, int head_dim, int F, int V, int max_len);
+int pdn_kv_append_rows_f32(const float* qkv, int64_t qkv_row_stride, const float* cos_table, const float* sin_table,
+                           float* k_cache, float* v_cache, int64_t cache_batch_stride, const int* runs, int n_runs,
+                           int max_run, int n_q, int H, int head_dim, int max_len, void* stream);
+int pdn_decode_extend_attention_f32(const float* qkv, int64_t qkv_row_stride, const float* cos_table,
+                                    const float* sin_table, const float* k_cache, const float* v_cache,
+                                    int64_t cache_batch_stride, const int* runs, int n_runs, int max_run, int n_q, int H,
+                                    int head_dim, int n_splits, int max_len, float* partials, void* stream);
 /* shapes the resident (K / V of a head chunk-wise in LDS) kernels above take: head_dim 48 or 64, L a multiple of 32 up
  * to 1024 -- sequences beyond 256 pass through LDS in 256-row chunks (forward: one online rescale per chunk) -- and
  * (round 6, csrc/attention_hd128.hip) head_dim 128 at ANY length 1 .. 1024, no RoPE inside: the shape of

@@ -21,6 +21,7 @@ from ..autograd import is_grad_enable
 from ..core import Tensor, fused
 from ..special import zeros
 from . import beam as beam_np
+from . import chunked
 from .sampling import (check_args as check_sampling_args, params_bytes, params_buffer, sample_next,
                        sample_next_rows)
 
@@ -29,6 +30,8 @@ from .sampling import (check_args as check_sampling_args, params_bytes, params_b
 _WIDE_ENTRIES = ("pdn_decode_wide_supported", "pdn_decode_wide_blocks", "pdn_decode_wide_work_floats",
                  "pdn_decode_wide_gemm_f32", "pdn_decode_wide_pick_tick_rows_f32", "pdn_decode_wide_pick_tick_slots_f32",
                  "pdn_decode_wide_sample_tick_rows_f32", "pdn_decode_wide_sample_tick_slots_f32")
+# ... and of the mixed step of chunked prefill (csrc/extend.hip), which runs on the wide product at any row count
+_MIXED_ENTRIES = _WIDE_ENTRIES + ("pdn_decode_mixed_supported", "pdn_kv_append_rows_f32", "pdn_decode_extend_attention_f32")
 
 
 def compute_cos_sin_cache(head_dim: int, max_seq_len: int, base: int = 10000, dtype=None):
@@ -1034,7 +1037,8 @@ class Llama(nn.Module):
         return out
 
     # -- continuous batching (serve): a finished row takes the next waiting request -------------------------------
-    def serve(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=()):
+    def serve(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
+              prefill_chunk=None):
         """Continuous batching: N requests (`prompts`, N may exceed max_batch_size) through `slots` decode rows
         (default min(N, max_batch_size)).  A row frees when its request yields a stop id or uses up its budget
         (`max_new_tokens`: one int, or one per request; 0 = the request yields nothing and never takes a row).  Before
@@ -1044,7 +1048,11 @@ class Llama(nn.Module):
         produced at this step (the prompt pass's token for a row admitted at this step; -1: none).
         Request r's tokens are the first budget_r tokens of row r of `generate_ragged(prompts, max(budgets), ...)`,
         cut after its first stop id: a sampled token of request r at position t is drawn with Philox counter (t, r),
-        whichever row it runs in.  Every argument is checked here (ValueError), before anything runs."""
+        whichever row it runs in.  Every argument is checked here (ValueError), before anything runs.
+        `prefill_chunk` = C (chunked prefill, the schedule of llm/chunked.py): no prompt pass stalls the other rows;
+        every step feeds at most C prompt tokens in total to the rows still prefilling, in request order, and a row yields
+        -1 until the step that feeds its last prompt token, which yields its first token.  The tokens of each request are
+        those of `serve`; only the step at which they appear changes.  slots + C <= 256."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
         V = self.vocab_size
         rows = [np.asarray(p.numpy() if isinstance(p, Tensor) else p).reshape(-1) for p in prompts]
@@ -1079,11 +1087,15 @@ class Llama(nn.Module):
         if stops.size and (stops.min() < 0 or stops.max() >= V):
             raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
         sampling = (temperature, top_k, top_p, seed) if temperature > 0 else None
+        C = chunked.check_chunk(prefill_chunk, slots)
+        if C is not None:
+            return self._serve_chunked([p.astype(np.int64) for p in rows], budgets, int(slots), C, sampling, stops)
         return self._serve([p.astype(np.int64) for p in rows], budgets, int(slots), sampling, stops)
 
-    def serve_all(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=()):
+    def serve_all(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
+                  prefill_chunk=None):
         """`serve` run to the end: a list of N int64 arrays, request r's generated tokens in order."""
-        it = self.serve(prompts, max_new_tokens, slots, temperature, top_k, top_p, seed, stop_ids)
+        it = self.serve(prompts, max_new_tokens, slots, temperature, top_k, top_p, seed, stop_ids, prefill_chunk)
         out = [[] for _ in range(len(prompts))]
         for reqs, toks in it:
             for r, t in zip(reqs, toks):
@@ -1309,6 +1321,223 @@ class Llama(nn.Module):
         st["left"][...] = left.astype(np.int32)
         st["ids"][...] = last.reshape(-1, 1)
         self._decode_gather(st)
+
+    # -- chunked prefill (serve(prefill_chunk=C)): prompts fed C tokens per step (statement: llm/chunked.py) -----------
+    def _serve_chunked(self, rows, budgets, S, C, sampling, stops):
+        """The scheduler of `serve` with a chunk: llm/chunked.Schedule decides, per step, which rows decode and which
+        prompt tokens are fed.  Graph path (`_mixed_begin`): a step with prompt tokens runs the mixed step (the decode
+        rows and the chunks as query rows of the wide product, csrc/extend.hip), a step without runs the served step.
+        Every other path decodes as `_serve` does, and a prompt pass runs when the schedule completes prompts: one
+        `_serve_prefill` for the requests whose prompts complete in that step."""
+        lens = np.array([r.size for r in rows], np.int64)
+        sch = chunked.Schedule(lens, budgets, S, C)
+        dev = self.tok_embedding.weight.device
+        hip = (Llama.fast_decode and dev.is_hip and not self._train
+               and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
+        st = self._mixed_begin(S, C, sampling, stops) if hip else None
+        dirty = False                                           # (the device's row state differs from the host's)
+        try:
+            while True:
+                sch.admit()
+                if not sch.busy():
+                    return
+                n, dec, comp = sch.plan()
+                toks = np.full(S, -1, np.int64)
+                if st is not None:
+                    got = np.zeros(S, bool)
+                    if st["pending"]:                            # a served step queued ahead: this step's decode rows
+                        toks[dec] = self._serve_read(st)[dec]
+                        got |= dec
+                    if n.any():
+                        inc = dec & ~got
+                        self._mixed_issue(st, sch, n, inc, comp, rows)
+                        t = self._serve_read(st)
+                        toks[inc | comp] = t[inc | comp]
+                        dirty = True
+                    elif not got.any() and dec.any():
+                        p = np.where(dec, sch.pos, -1)
+                        if dirty:
+                            self._serve_write(st, sch.req, p, np.where(dec, sch.left, 0), sch.last)
+                            dirty = False
+                        self._serve_issue(st, int(p.max()))
+                        # the next step queued before this one is read, when it is a served step for sure: no prompt
+                        # left to feed, and no admission unless a stop id frees a row
+                        nxt = np.where(dec & (sch.left > 1), p + 1, -1)
+                        if (nxt.max() >= 0 and not (sch.fed < sch.row_lens()).any()
+                                and (sch.q >= len(sch.queue) or not (dec & (sch.left <= 1)).any())):
+                            self._serve_ahead(st, int(nxt.max()))
+                        toks[dec] = self._serve_read(st)[dec]
+                else:
+                    if dec.any():
+                        p, rq = np.where(dec, sch.pos, -1), np.maximum(sch.req, 0)
+                        ids = sch.last.reshape(S, 1)
+                        if hip:
+                            from .. import hipnp as hp
+                            out = self._decode_step_generic_rows(hp.asarray(ids), p.astype(np.int32), sampling, rq).get()
+                        else:
+                            out = self._step_module_rows(Tensor(ids, dtype=np.int64, device=dev), p, sampling, rq).numpy()
+                        toks[dec] = out.reshape(-1)[dec]
+                    if comp.any():
+                        b = np.flatnonzero(comp)
+                        toks[b] = self._serve_prefill([rows[r] for r in sch.req[b]], b, sch.req[b], sampling)
+                shown = sch.finish(n, toks, stops)
+                yield shown, toks
+        finally:
+            if st is not None and st["pending"]:
+                from .. import hipnp as hp
+                hp.synchronize()
+                st["pending"] = 0
+
+    def _mixed_ok(self, S, C):
+        """Whether the library provides the mixed step and takes this model (any row count up to 256 query rows)."""
+        from .. import _lib
+        L, D, H, F, V = _lib.lib(), self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
+        cache_len = self.layers[0].attention.cache_k.shape[1]
+        return bool(Llama.wide_decode and S + C <= 256 and all(_lib.provides(n) for n in _MIXED_ENTRIES)
+                    and L.query("pdn_decode_mixed_supported", D, H, D // H, F, V, cache_len))
+
+    def _mixed_begin(self, S, C, sampling, stops):
+        """The served plan (`_serve_begin`) plus the buffers of the mixed step (`mixed`), or None when either refuses."""
+        from .. import hipnp as hp, _lib
+        if not self._mixed_ok(S, C):
+            return None
+        st = self._serve_begin(S, sampling, stops)
+        if st is None or st["ns"] > 8:
+            return None
+        M = st.get("mixed")
+        if M is None or M["C"] != C:
+            D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
+            R, ns, L = S + C, st["ns"], _lib.lib()
+            work = max([L.query("pdn_decode_wide_work_floats", R, k, n) for k, n in ((D, 3 * D), (D, D), (F, D), (D, 2 * F))]
+                       + [L.query("pdn_decode_wide_work_floats", S, D, V)])
+            nblk = L.query("pdn_decode_wide_blocks", V)
+            M = {"C": C, "R": R, "arrive": hp.zeros((1,), np.int32), "work": hp.zeros((max(work, 4),), np.float32),
+                 "cand_v": hp.empty((S, nblk), np.float32), "cand_i": hp.empty((S, nblk), np.int32),
+                 # the per-step layout (uploaded before each replay): query-row positions (-1: masked), one run per cache
+                 # row [first query row, count, start, ends the prompt], the prompt tokens, each slot's emitting row
+                 "qpos": hp.zeros((R,), np.int32), "runs": hp.zeros((S, 4), np.int32), "tok": hp.zeros((C,), np.int64),
+                 "emit": hp.zeros((S,), np.int64), "xe": hp.empty((S, D), np.float32),
+                 **{n: hp.zeros((R, w), np.float32) for n, w in
+                    (("x", D), ("qkv", 3 * D), ("att", ns * H * (4 + D // H)), ("gu", 2 * F))}}
+            for k in [k for k in st["graphs"] if len(k) > 2 and k[2] == "mixed"]:
+                st["graphs"].pop(k).destroy()
+            st["mixed"] = M
+        return st
+
+    def _mixed_layout(self, st, sch, n, inc, comp, rows):
+        """Upload one mixed step: the rows' state (decode rows `inc` at their positions, rows completing their prompt at
+        position len for the tick, every other row -1) and the layout of its query rows."""
+        M, S, C = st["mixed"], sch.S, sch.C
+        lens = sch.row_lens()
+        qpos = np.full(S + C, -1, np.int32)
+        runs = np.zeros((S, 4), np.int32)
+        tok = np.zeros(C, np.int64)
+        emit = np.arange(S, dtype=np.int64)
+        qpos[:S][inc] = sch.pos[inc]
+        for b in np.flatnonzero(inc):
+            runs[b] = (b, 1, sch.pos[b], 0)
+        q = S
+        for b in sorted(np.flatnonzero(n > 0).tolist(), key=lambda b: int(sch.req[b])):
+            f, k = int(sch.fed[b]), int(n[b])
+            runs[b] = (q, k, f, int(f + k == lens[b]))
+            qpos[q:q + k] = np.arange(f, f + k)
+            tok[q - S:q - S + k] = rows[int(sch.req[b])][f:f + k]
+            emit[b] = q + k - 1
+            q += k
+        pos = np.where(inc, sch.pos, -1)
+        pos[comp] = lens[comp]
+        st["pos"][...] = pos.astype(np.int32)
+        st["req"][...] = np.maximum(sch.req, 0).astype(np.int32)
+        st["left"][...] = np.where(inc | comp, sch.left, 0).astype(np.int32)
+        M["qpos"][...] = qpos
+        M["runs"][...] = runs
+        M["tok"][...] = tok
+        M["emit"][...] = emit
+
+    def _mixed_issue(self, st, sch, n, inc, comp, rows):
+        """Issue one mixed step (no step queued): upload its layout, capture its graph first when there is none."""
+        from .. import hipnp as hp, _lib
+        if self._decode_st is not st:
+            raise RuntimeError("another generation replaced the plan of a running serve() on this model")
+        self._mixed_layout(st, sch, n, inc, comp, rows)
+        ns = st["ns"]
+        gk = (ns, st["sampling"], "mixed", st["mixed"]["C"])
+        g = False if st["nograph"] else st["graphs"].get(gk)
+        if g is None and Llama.graph_decode:
+            keep = {n: st[n].copy() for n in ("ids", "pos", "step", "left")}
+            scratch = hp.Mailbox(st["ring"], (st["B"], 1), unset=st["hist"].unset)
+            st["hist_ptr"][...] = np.int64(scratch._ptr)
+            try:
+                g = hp.Graph()
+                g.capture(lambda: self._mixed_launches(st, ns))
+                st["graphs"][gk] = g
+            except _lib.HipLibraryError as e:
+                if e.code != -2:                                 # PDN_EUNSUPPORTED: no graph support (emulated ABI)
+                    raise
+                st["nograph"], g = True, False
+            hp.synchronize()
+            st["hist_ptr"][...] = np.int64(st["hist"]._ptr)
+            for k, v in keep.items():
+                st[k][...] = v
+            self._decode_gather(st)
+        if g:
+            g.replay()
+        else:
+            self._mixed_launches(st, ns)
+        st["pending"] += 1
+
+    def _mixed_launches(self, st, ns):
+        """The mixed step: S decode query rows (st["x"]) and C prompt rows (their embedding rows) through the layers on
+        the wide product -- q | k | v, the KV append and the extend attention, the output projection (mode 3 merge),
+        gate | up, down -- then each slot's emitting row gathered, the vocabulary projection and the wide slot tick on
+        the S rows of the served plan."""
+        from .. import hipnp as hp, _lib
+        L, s = _lib.lib(), hp.stream()
+        M = st["mixed"]
+        D, H, F, V, S, C, R = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size, st["B"], M["C"], M["R"]
+        hd = D // H
+        x, qkv, att, gu, work, qpos, runs = (M[n]._ptr for n in ("x", "qkv", "att", "gu", "work", "qpos", "runs"))
+        cos, sin = self.freqs_cos.data._ptr, self.freqs_sin.data._ptr
+        cache = self.layers[0].attention.cache_k
+        max_len = min(cache.shape[1], self.freqs_cos.shape[0])
+        emb = self.tok_embedding.weight.data
+        L.call("pdn_memcpy_d2d", x, st["x"]._ptr, S * D * 4, s)
+        L.call("pdn_embedding_gather_f32", emb._ptr, V, D, emb._strides[0], M["tok"]._ptr, C, x + S * D * 4,
+               hp.err_flag_ptr(), s)
+        for layer, (wqkv, wgu) in zip(self.layers, st["packs"]):
+            a, f = layer.attention, layer.ffn
+            ck, cv = a.cache_k.data, a.cache_v.data
+            nrm = layer.input_norm
+            L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wqkv._ptr, D, D,
+                   wqkv._strides[0], None, qkv, 3 * D, 0, None, None, qpos, R, D, 3 * D, work, s)
+            L.call("pdn_kv_append_rows_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, ck._strides[0], runs, S, C, R, H, hd,
+                   max_len, s)
+            L.call("pdn_decode_extend_attention_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, ck._strides[0], runs, S, C,
+                   R, H, hd, ns, max_len, att, s)
+            L.call("pdn_decode_wide_gemm_f32", att, M["att"].shape[1], 3, None, 0.0, ns, hd, a.O.weight.data._ptr, D, D,
+                   0, None, x, D, 1, None, None, qpos, R, D, D, work, s)
+            nrm = layer.post_attn_norm
+            L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wgu._ptr, F, F,
+                   wgu._strides[0], None, gu, 2 * F, 0, None, None, qpos, R, D, 2 * F, work, s)
+            L.call("pdn_decode_wide_gemm_f32", gu, 2 * F, 2, None, 0.0, 0, 0, f.down.weight.data._ptr, D, D, 0, None,
+                   x, D, 1, None, None, qpos, R, F, D, work, s)
+        xe = M["xe"]._ptr
+        L.call("pdn_embedding_gather_f32", x, R, D, D, M["emit"]._ptr, S, xe, hp.err_flag_ptr(), s)
+        head = self.lm_head
+        bias = head.bias.data._ptr if getattr(head, "bias", None) is not None else None
+        full = st["sampling"]
+        cv, ci = (None, None) if full else (M["cand_v"]._ptr, M["cand_i"]._ptr)
+        L.call("pdn_decode_wide_gemm_f32", xe, D, 1, self.norm.weight.data._ptr, self.norm.eps, 0, 0,
+               head.weight.data._ptr, V, V, 0, bias, st["logits"]._ptr, V, 0 if full else 2, cv, ci, st["pos"]._ptr, S,
+               D, V, work, s)
+        cnt = (st["pos"]._ptr, st["step"]._ptr, M["arrive"]._ptr)
+        out = (st["hist_ptr"]._ptr, emb._ptr, emb._strides[0], D, st["x"]._ptr, s)
+        if full:
+            L.call("pdn_decode_wide_sample_tick_slots_f32", st["logits"]._ptr, V, S, V, st["params"]._ptr,
+                   st["ids"]._ptr, *cnt, st["req"]._ptr, st["left"]._ptr, st["ring"], st["stop"]._ptr, *out)
+        else:
+            L.call("pdn_decode_wide_pick_tick_slots_f32", M["cand_v"]._ptr, M["cand_i"]._ptr, S, M["cand_v"].shape[1],
+                   st["ids"]._ptr, *cnt, st["req"]._ptr, st["left"]._ptr, st["ring"], st["stop"]._ptr, *out)
 
     # -- beam search: the W most probable continuations of each prompt (statement: llm/beam.py) ----------------------
     def beam_search(self, prompts, max_new_tokens, num_beams, length_penalty=1.0, stop_ids=()):
