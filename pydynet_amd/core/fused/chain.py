@@ -18,12 +18,37 @@ import math
 
 import numpy as np
 
+from ...autograd import enable_grad, no_grad
 from ..tensor import (Graph, Tensor, _Operator, transpose, matmul as _matmul, div as _div, add as _add, sub as _sub, mul as _mul,
                       reshape as _reshape, concat as _concat, _get_slice)
 from ._common import _Deferred
 from .attn import attention, _attn_layout
 from .dense import linear as _linear, linear_cross_entropy as _linear_ce
 from .pointwise import softmax as _softmax, rope as _rope, silu as _silu, swiglu as _swiglu
+
+
+def _materialise(link, op, ins):
+    """The array of a pending `link` that somebody reads: `op(*ins)` builds the ordinary operator over the link's inputs
+    (previous links materialise the same way), and on the tape the link becomes an identity over it.
+
+    The operator is built with grad enabled whenever the link is on the tape, whatever the ambient mode (a read under
+    no_grad() must not leave the link over its original inputs).  It takes the place in creation order right BELOW the
+    link (`Graph._place_below`): the engine walks reverse creation order, and a consumer created before this read -- a
+    deferred `silu`, `linear`, `rms_norm` -- has to stay ahead of the link.  A link no longer on the tape (its graph was
+    walked or cleared) just computes its values."""
+    track = link.requires_grad and Graph.contains(link)
+    with enable_grad() if track else no_grad():
+        inner = op(*ins)
+    if track:
+        Graph._place_below(inner, link)
+        link.last = [inner]
+    return inner.data
+
+
+def _cat_plain(*ins):
+    inner = object.__new__(_concat)                   # (constructed past concat.__new__'s own hook)
+    inner.__init__(list(ins), axis=-1)
+    return inner
 
 
 class attn_link(_Deferred, _Operator):
@@ -41,21 +66,12 @@ class attn_link(_Deferred, _Operator):
     def forward_(self, *ins):
         # somebody wants this link's array: build the ordinary operator over the (then materialised) previous link
         if self.stage == "qk":
-            inner = _matmul(ins[0], ins[1])
-        elif self.stage == "scaled":
-            inner = _div(ins[0], self.operand)
-        elif self.stage == "masked":
-            inner = _add(ins[0], ins[1])
-        else:
-            inner = _softmax(ins[0])
-        if self.requires_grad and inner.requires_grad:
-            # the engine walks ancestors in reverse CREATION order: this node now stands behind `inner`, which was
-            # created after it -- it takes a fresh place in the registry
-            self.last = [inner]
-            Graph._free_node(self)
-            self.last = [inner]
-            Graph._add_node(self)
-        return inner.data
+            return _materialise(self, _matmul, ins)
+        if self.stage == "scaled":
+            return _materialise(self, lambda s: _div(s, self.operand), ins)
+        if self.stage == "masked":
+            return _materialise(self, _add, ins)
+        return _materialise(self, _softmax, ins)
 
     def grad_fn(self, x, grad):
         return grad
@@ -311,8 +327,8 @@ def on_mul(a, b):
 #     -> diff = prod - prod, sum = prod + prod -> unsq = unsqueeze(., -1) -> cat = concat([unsq, unsq], -1) -> reshape(x.shape)
 # and the last reshape, finding exactly `concat([r c - i s, r s + i c])` over ONE x and two tables without gradient, builds ONE
 # `fused.rope` node (one kernel forward, one backward) instead of thirteen.  A link somebody reads builds its ordinary
-# operator then (over the previous link, which does the same) and becomes an identity over it, with a fresh place in the
-# tape -- programs that look at the pairs or the products behave as before.
+# operator then (over the previous link, which does the same) and becomes an identity over it (`_materialise`) -- programs
+# that look at the pairs or the products behave as before.  A read after the concat leaves the final reshape plain.
 class rope_link(_Deferred, _Operator):
     _rope_link = True
     _mul_hook = True
@@ -327,24 +343,16 @@ class rope_link(_Deferred, _Operator):
     def forward_(self, *ins):
         st = self.stage
         if st == "pairs" or st == "unsq":
-            inner = _reshape(ins[0], self._shape)
-        elif st == "comp":
-            inner = _get_slice(ins[0], (Ellipsis, self.info["which"]))
-        elif st == "prod":
-            inner = _mul(ins[0], ins[1])
-        elif st == "diff":
-            inner = _sub(ins[0], ins[1])
-        elif st == "sum":
-            inner = _add(ins[0], ins[1])
-        else:                                            # "cat" (constructed past concat.__new__'s own hook)
-            inner = object.__new__(_concat)
-            inner.__init__(list(ins), axis=-1)
-        if self.requires_grad and inner.requires_grad:
-            self.last = [inner]                          # (see attn_link.forward_: a fresh place in the registry)
-            Graph._free_node(self)
-            self.last = [inner]
-            Graph._add_node(self)
-        return inner.data
+            return _materialise(self, lambda t: _reshape(t, self._shape), ins)
+        if st == "comp":
+            return _materialise(self, lambda t: _get_slice(t, (Ellipsis, self.info["which"])), ins)
+        if st == "prod":
+            return _materialise(self, _mul, ins)
+        if st == "diff":
+            return _materialise(self, _sub, ins)
+        if st == "sum":
+            return _materialise(self, _add, ins)
+        return _materialise(self, _cat_plain, ins)
 
     def grad_fn(self, x, grad):
         return grad
@@ -415,12 +423,19 @@ def _rope_reshape(t, new_shape):
     if not (_link(t, "cat") and len(new_shape) == 4):
         return None
     shape = _resolve(new_shape, t.size)
+    # every link under the cat was pending when it was joined; one read since then has run its operator: plain reshape
     u_re, u_im = t._pending
-    d, a = u_re._pending[0], u_im._pending[0]                                     # (all links of a pending cat are pending)
-    if shape is None or d.stage != "diff" or a.stage != "sum":
+    if shape is None or u_re._pending is None or u_im._pending is None:
+        return None
+    d, a = u_re._pending[0], u_im._pending[0]
+    if d.stage != "diff" or a.stage != "sum" or d._pending is None or a._pending is None:
         return None
     (rc, is_), (rs, ic) = d._pending, a._pending
+    if any(p._pending is None for p in (rc, is_, rs, ic)):
+        return None
     r, i = rc.info["comp"], is_.info["comp"]
+    if r._pending is None or i._pending is None or r._pending[0]._pending is None:
+        return None
     cos, sin = rc.info["table"], is_.info["table"]
     if not (rs.info["comp"] is r and ic.info["comp"] is i and rs.info["table"] is sin and ic.info["table"] is cos and
             cos is not sin and r.info["which"] == 0 and i.info["which"] == 1 and r._pending[0] is i._pending[0]):

@@ -37,6 +37,15 @@ class Graph:
         cls._nodes[node._gid] = node
 
     @classmethod
+    def _place_below(cls, node, anchor):
+        """Move `node`, created just now, to the place right below `anchor` in creation order (gid `anchor - 0.5`):
+        for a node that stands in for `anchor`'s inputs from now on (core/fused/chain.py: a pending link that somebody
+        read).  Valid while every input of `node` was created before `anchor`."""
+        cls._nodes.pop(node._gid, None)
+        node._gid = anchor._gid - 0.5
+        cls._nodes[node._gid] = node
+
+    @classmethod
     def _free_node(cls, node):
         node.last = []
         cls._nodes.pop(node._gid, None)
@@ -74,7 +83,10 @@ class Tensor:
     _rope_link = False      # True on the pending links of a rotary embedding written with plain operators (chain.py: rope_link)
     _mul_hook = False       # True on core/fused/pointwise.py's `silu` (pending activation: `silu(gate) * up` becomes one node)
     _reshape_hook = False   # True where core/fused/chain.py wants to see `reshape`: pending projections, the tail of a rotary embedding
-    _causal_mask = False    # True on a Tensor built from exactly the additive causal mask of llm/llama/model.py:199-203
+    # True on a Tensor built from exactly the additive causal mask of llm/llama/model.py:199-203.  Cleared by the writes
+    # the Tensor sees (`t[...] = `, `+=`, `*=`, ...); a write through the array itself (`t.data[...] = `, `t.data = `)
+    # is not seen: the flag would keep the attention chain on the causal schedule.
+    _causal_mask = False
 
     def __init__(self, data, dtype=None, copy=True, device=None, requires_grad=False) -> None:
         if isinstance(data, Tensor):
@@ -239,6 +251,7 @@ class Tensor:
         if self.requires_grad and is_grad_enable():
             raise ValueError("In-place operation is forbidden in node requires grad.")
         others = tuple(o.data if isinstance(o, Tensor) else o for o in others)
+        self._causal_mask = False
         with self.device:
             r = func(*others)
         if r is not None and r is not NotImplemented and _is_array(r):
@@ -252,6 +265,7 @@ class Tensor:
             key = key.data
         if self.requires_grad and is_grad_enable():
             raise ValueError("In-place operation is forbidden in node requires grad.")
+        self._causal_mask = False
         with self.device:
             self.data[key] = value.data if isinstance(value, Tensor) else value
 
@@ -327,7 +341,8 @@ class Tensor:
 
 def _ancestors(root):
     """Grad-tracked ancestors of `root` in reverse creation order (a valid reverse topological
-    order: inputs are always created before their consumers) + edge counts of the leaves."""
+    order: inputs are always created before their consumers, `Graph._place_below` keeps it so) +
+    edge counts of the leaves."""
     seen = {root._gid: root}
     pending = {}
     stack = [root]
