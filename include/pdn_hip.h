@@ -187,7 +187,8 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  31 wide decode (csrc/decode_wide.hip): pdn_decode_wide_gemm_f32 and the four pdn_decode_wide_*_tick_* entries (the
  *     ticks also count in 29, the slot forms in 30, the sampled forms in 28)
  *  32 beam search (csrc/beam.hip): pdn_beam_topk_rows_f32, pdn_beam_select_f32, pdn_kv_reorder_rows_f32
- *  33 chunked prefill (csrc/extend.hip): pdn_kv_append_rows_f32, pdn_decode_extend_attention_f32 */
+ *  33 chunked prefill (csrc/extend.hip): pdn_kv_append_rows_f32, pdn_decode_extend_attention_f32
+ *  34 speculative decoding (csrc/speculative.hip): pdn_spec_draft_rows and the two pdn_spec_verify_*_tick_f32 entries */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -729,6 +730,39 @@ int pdn_decode_extend_attention_f32(const float* qkv, int64_t qkv_row_stride, co
                                     const float* sin_table, const float* k_cache, const float* v_cache,
                                     int64_t cache_batch_stride, const int* runs, int n_runs, int max_run, int n_q, int H,
                                     int head_dim, int n_splits, int max_len, float* partials, void* stream);
+/* Prompt-lookup speculative decoding (csrc/speculative.hip; Llama.generate_ragged(speculate=k), the NumPy statement is
+ * pydynet_amd/llm/speculative.py).  A target pass runs B (k + 1) query rows through the mixed step's layers: rows
+ * b (k + 1) .. b (k + 1) + k belong to row b.  The row state lives on the device: hist (B, hist_stride) int32 holds each
+ * row's tokens (prompt + yielded), hist_len (B,) their count T, pos (B,) the position at which the next pass feeds the
+ * row's last token (-1: stopped), left (B,) the tokens it may still yield.  0 <= k <= 16, B (k + 1) <= 65535.
+ *   pdn_spec_draft_rows            one workgroup per row: the draft rule (for n = 3 .. 1, the largest j with j + n < T and
+ *                                  hist[j:j+n] == hist[T-n:T]; draft hist[j+n : min(j+n+k, T)], at most left - 1
+ *                                  tokens, d of them) -> tokens (B (k + 1),) int64: the last token, the draft, 0 after it;
+ *                                  qpos (B (k + 1),) int32: pos + j for j <= d, else -1; runs (B, 4) int32: [b (k + 1),
+ *                                  d + 1, pos, 0] (the layout of pdn_kv_append_rows_f32).  A stopped row: n = 0, every
+ *                                  qpos -1.
+ *   pdn_spec_verify_pick_tick_f32  each query row with qpos >= 0 picks its token from the block candidates of mode 2 of
+ *                                  pdn_decode_wide_gemm_f32 (n_blocks per row; the lowest index among equal maxima)
+ *                                  into picks (B (k + 1),) int64; then ONE workgroup settles every row: a = the leading
+ *                                  picks that equal the next fed token, the row yields picks 0 .. a, at most left, cut
+ *                                  after the first token set in stop_mask (may be null); it appends them to hist,
+ *                                  advances hist_len / pos / left (pos = -1 once it stops or its budget is used), and
+ *                                  stores [count, d, min(a, count), token 0 .. token k (-1 past count)] for every row
+ *                                  into slot *step of *mailbox ((passes, B, k + 4) int64, may be mapped host memory;
+ *                                  skipped when null); *step += 1.
+ *   pdn_spec_verify_sample_tick_f32  the same with the draw of pdn_sample_rows_f32 (params: pdn_sample_params) from the
+ *                                  full logit rows (row_stride floats apart), counter (qpos[r], r / (k + 1)).
+ * Two launches of either tick give the same bits (no float atomics). */
+int pdn_spec_draft_rows(const int* hist, int hist_stride, const int* hist_len, const int* pos, const int* left, int B,
+                        int k, int64_t* tokens, int* qpos, int* runs, void* stream);
+int pdn_spec_verify_pick_tick_f32(const float* blk_max, const int* blk_arg, int n_blocks, const int64_t* tokens,
+                                  const int* qpos, int B, int k, int64_t* picks, int* hist, int hist_stride,
+                                  int* hist_len, int* pos, int* left, const int* stop_mask, int* step,
+                                  int64_t* const* mailbox, void* stream);
+int pdn_spec_verify_sample_tick_f32(const float* logits, int64_t row_stride, int V, const void* params,
+                                    const int64_t* tokens, const int* qpos, int B, int k, int64_t* picks, int* hist,
+                                    int hist_stride, int* hist_len, int* pos, int* left, const int* stop_mask,
+                                    int* step, int64_t* const* mailbox, void* stream);
 /* shapes the resident (K / V of a head chunk-wise in LDS) kernels above take: head_dim 48 or 64, L a multiple of 32 up
  * to 1024 -- sequences beyond 256 pass through LDS in 256-row chunks (forward: one online rescale per chunk) -- and
  * (round 6, csrc/attention_hd128.hip) head_dim 128 at ANY length 1 .. 1024, no RoPE inside: the shape of

@@ -56,7 +56,8 @@ enum {
   PDN_CNT_DECODE_WIDE = 31,       // wide decode (9..256 rows, csrc/decode_wide.hip): the MFMA product and the wide ticks
   PDN_CNT_BEAM = 32,              // beam search (csrc/beam.hip): top-k, select and the KV-cache reorder
   PDN_CNT_EXTEND = 33,            // chunked prefill (csrc/extend.hip): the KV append and the multi-query extend attention
-  PDN_CNT_SLOTS = 34
+  PDN_CNT_SPECULATE = 34,         // speculative decoding (csrc/speculative.hip): the draft kernel and the verify ticks
+  PDN_CNT_SLOTS = 35
 };
 void pdn_count(int slot);
 

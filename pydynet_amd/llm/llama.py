@@ -22,6 +22,7 @@ from ..core import Tensor, fused
 from ..special import zeros
 from . import beam as beam_np
 from . import chunked
+from . import speculative as spec_np
 from .sampling import (check_args as check_sampling_args, params_bytes, params_buffer, sample_next,
                        sample_next_rows)
 
@@ -32,6 +33,8 @@ _WIDE_ENTRIES = ("pdn_decode_wide_supported", "pdn_decode_wide_blocks", "pdn_dec
                  "pdn_decode_wide_sample_tick_rows_f32", "pdn_decode_wide_sample_tick_slots_f32")
 # ... and of the mixed step of chunked prefill (csrc/extend.hip), which runs on the wide product at any row count
 _MIXED_ENTRIES = _WIDE_ENTRIES + ("pdn_decode_mixed_supported", "pdn_kv_append_rows_f32", "pdn_decode_extend_attention_f32")
+# ... and of the speculative pass (csrc/speculative.hip), which runs the mixed step's layers
+_SPEC_ENTRIES = _MIXED_ENTRIES + ("pdn_spec_draft_rows", "pdn_spec_verify_pick_tick_f32", "pdn_spec_verify_sample_tick_f32")
 
 
 def compute_cos_sin_cache(head_dim: int, max_seq_len: int, base: int = 10000, dtype=None):
@@ -285,7 +288,8 @@ class Llama(nn.Module):
                 next_id = logits.argmax(-1, True) if sampling is None else sample_next(logits, pos, *sampling)
             yield next_id
 
-    def generate_ragged(self, prompts, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=()):
+    def generate_ragged(self, prompts, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
+                        speculate=0):
         """Generation for B prompts of different lengths, every row at its own position.  Yields a (B, 1) int64 Tensor
         per step: step i holds, for row b, the token at position len_b + i.  `max_new_tokens` is the number of NEW tokens
         per row -- `generate`'s second argument is an end position instead: for equal lengths L,
@@ -293,7 +297,13 @@ class Llama(nn.Module):
         the row's own position as the counter: row b's token at position t is drawn with counter (t, b).
         `stop_ids`: once row b yields one of them it yields -1 at every later step and its position stops advancing
         (its KV cache is no longer written); the iterator ends after the step at which every row has stopped, or after
-        `max_new_tokens` steps.  Every argument is checked here (ValueError), before anything runs."""
+        `max_new_tokens` steps.  `speculate` = k > 0: prompt-lookup speculative decoding (llm/speculative.py) -- up to k
+        draft tokens per row per target pass, each checked against the token the model picks at its position.  On `cpu`
+        (and every path that verifies through the one-token rows step) the steps yielded are those of `speculate=0`; the
+        graph-replayed HIP pass computes the logits with other kernels than the plain step (the wide product, the extend
+        attention), so there they agree up to fp32 near-ties, as the plain step and the wide step do.  The counts of the
+        run are in `last_speculation` (None after a call with speculate=0, which runs the plain decode).
+        Every argument is checked here (ValueError), before anything runs."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
         V = self.vocab_size
         if int(max_new_tokens) != max_new_tokens or max_new_tokens < 0:
@@ -303,6 +313,7 @@ class Llama(nn.Module):
         cache = self.layers[0].attention.cache_k
         if not rows:
             raise ValueError("generate_ragged needs at least one prompt")
+        k = spec_np.check_speculate(speculate, len(rows))
         if len(rows) > cache.shape[0]:
             raise ValueError(f"batch {len(rows)} exceeds the KV cache's max_batch_size {cache.shape[0]}")
         limit = min(cache.shape[1], self.freqs_cos.shape[0])     # positions the cache / RoPE table hold
@@ -319,6 +330,9 @@ class Llama(nn.Module):
         if stops.size and (stops.min() < 0 or stops.max() >= V):
             raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
         sampling = (temperature, top_k, top_p, seed) if temperature > 0 else None
+        self.last_speculation = None if k == 0 else spec_np.counts()
+        if k:
+            return self._speculate([r.astype(np.int64) for r in rows], max_new_tokens, k, sampling, stops)
         return self._generate_ragged([r.astype(np.int64) for r in rows], max_new_tokens, sampling, stops)
 
     def _generate_ragged(self, rows, n, sampling, stops):
@@ -404,6 +418,7 @@ class Llama(nn.Module):
     # -- decode fast path -----------------------------------------------------------
     graph_decode = True     # class switch: False issues the step's launches one by one instead of replaying a hipGraph
     decode_ahead = True     # class switch: False never queues the next step before the caller asked for it
+    last_speculation = None  # the counts of the last generate_ragged(speculate=k > 0) run (llm/speculative.py)
     fused_decode = 2        # class switch: launches per layer = 2 (q|k|v inside the attention kernel), 1 -> 3, 0 / False -> 5
     wide_decode = True      # class switch: 9 .. 256 rows on the wide step (csrc/decode_wide.hip); False -> the generic step
 
@@ -426,15 +441,7 @@ class Llama(nn.Module):
         st = getattr(self, "_decode_st", None)
         # a captured step (and the stacked weight views) hold the address of EVERY array the launches read: the key
         # covers them all -- rebinding `.data` of any parameter / cache re-plans -- and the switches that shape the plan
-        ptrs = [self.lm_head.weight.data._ptr, self.tok_embedding.weight.data._ptr, self.norm.weight.data._ptr,
-                self.freqs_cos.data._ptr, self.freqs_sin.data._ptr]
-        bias = getattr(self.lm_head, "bias", None)
-        ptrs.append(bias.data._ptr if bias is not None else 0)
-        for layer in self.layers:
-            a, f = layer.attention, layer.ffn
-            ptrs += [t.data._ptr for t in (a.Q.weight, a.K.weight, a.V.weight, a.O.weight, a.cache_k, a.cache_v,
-                                            f.gate.weight, f.up.weight, f.down.weight, layer.input_norm.weight,
-                                            layer.post_attn_norm.weight)]
+        ptrs = self._weight_ptrs()
         cache_len = self.layers[0].attention.cache_k.shape[1]
         wide = B > 8 and Llama.wide_decode and self._decode_wide_ok(B, cache_len)
         key = (B, hp._state["device"], int(Llama.fused_decode or 0), os.environ.get("PDN_DECODE_SPLITS", ""),
@@ -524,6 +531,19 @@ class Llama(nn.Module):
             self._decode_ws = {"logits": st["logits"], "x": st["x"]}
         self._decode_st = st
         return st if ok else None
+
+    def _weight_ptrs(self):
+        """The address of every array a captured step reads (parameters, caches, RoPE tables): part of a plan's key."""
+        ptrs = [self.lm_head.weight.data._ptr, self.tok_embedding.weight.data._ptr, self.norm.weight.data._ptr,
+                self.freqs_cos.data._ptr, self.freqs_sin.data._ptr]
+        bias = getattr(self.lm_head, "bias", None)
+        ptrs.append(bias.data._ptr if bias is not None else 0)
+        for layer in self.layers:
+            a, f = layer.attention, layer.ffn
+            ptrs += [t.data._ptr for t in (a.Q.weight, a.K.weight, a.V.weight, a.O.weight, a.cache_k, a.cache_v,
+                                            f.gate.weight, f.up.weight, f.down.weight, layer.input_norm.weight,
+                                            layer.post_attn_norm.weight)]
+        return ptrs
 
     def _decode_wide_ok(self, B, cache_len):
         """Whether the library provides the wide step and takes this model with B rows; asked once per (library, B,
@@ -1494,33 +1514,13 @@ class Llama(nn.Module):
         from .. import hipnp as hp, _lib
         L, s = _lib.lib(), hp.stream()
         M = st["mixed"]
-        D, H, F, V, S, C, R = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size, st["B"], M["C"], M["R"]
-        hd = D // H
-        x, qkv, att, gu, work, qpos, runs = (M[n]._ptr for n in ("x", "qkv", "att", "gu", "work", "qpos", "runs"))
-        cos, sin = self.freqs_cos.data._ptr, self.freqs_sin.data._ptr
-        cache = self.layers[0].attention.cache_k
-        max_len = min(cache.shape[1], self.freqs_cos.shape[0])
+        D, V, S, C, R = self.embed_dim, self.vocab_size, st["B"], M["C"], M["R"]
+        x, work = M["x"]._ptr, M["work"]._ptr
         emb = self.tok_embedding.weight.data
         L.call("pdn_memcpy_d2d", x, st["x"]._ptr, S * D * 4, s)
         L.call("pdn_embedding_gather_f32", emb._ptr, V, D, emb._strides[0], M["tok"]._ptr, C, x + S * D * 4,
                hp.err_flag_ptr(), s)
-        for layer, (wqkv, wgu) in zip(self.layers, st["packs"]):
-            a, f = layer.attention, layer.ffn
-            ck, cv = a.cache_k.data, a.cache_v.data
-            nrm = layer.input_norm
-            L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wqkv._ptr, D, D,
-                   wqkv._strides[0], None, qkv, 3 * D, 0, None, None, qpos, R, D, 3 * D, work, s)
-            L.call("pdn_kv_append_rows_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, ck._strides[0], runs, S, C, R, H, hd,
-                   max_len, s)
-            L.call("pdn_decode_extend_attention_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, ck._strides[0], runs, S, C,
-                   R, H, hd, ns, max_len, att, s)
-            L.call("pdn_decode_wide_gemm_f32", att, M["att"].shape[1], 3, None, 0.0, ns, hd, a.O.weight.data._ptr, D, D,
-                   0, None, x, D, 1, None, None, qpos, R, D, D, work, s)
-            nrm = layer.post_attn_norm
-            L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wgu._ptr, F, F,
-                   wgu._strides[0], None, gu, 2 * F, 0, None, None, qpos, R, D, 2 * F, work, s)
-            L.call("pdn_decode_wide_gemm_f32", gu, 2 * F, 2, None, 0.0, 0, 0, f.down.weight.data._ptr, D, D, 0, None,
-                   x, D, 1, None, None, qpos, R, F, D, work, s)
+        self._mixed_layers(M, st["packs"], S, C, R, ns, s)
         xe = M["xe"]._ptr
         L.call("pdn_embedding_gather_f32", x, R, D, D, M["emit"]._ptr, S, xe, hp.err_flag_ptr(), s)
         head = self.lm_head
@@ -1538,6 +1538,260 @@ class Llama(nn.Module):
         else:
             L.call("pdn_decode_wide_pick_tick_slots_f32", M["cand_v"]._ptr, M["cand_i"]._ptr, S, M["cand_v"].shape[1],
                    st["ids"]._ptr, *cnt, st["req"]._ptr, st["left"]._ptr, st["ring"], st["stop"]._ptr, *out)
+
+    def _mixed_layers(self, M, packs, n_runs, max_run, R, ns, s):
+        """The layers of the mixed step on R query rows (M["x"] in, M["x"] out): q | k | v with RMSNorm in the load, the KV
+        append and the extend attention over the runs M["runs"] (n_runs of at most max_run queries), the output
+        projection (mode 3 merge), gate | up, down -- every product on the wide kernel, masked by M["qpos"]."""
+        from .. import _lib
+        L = _lib.lib()
+        D, H, F = self.embed_dim, self.n_heads, self.ffn_dim
+        hd = D // H
+        x, qkv, att, gu, work, qpos, runs = (M[n]._ptr for n in ("x", "qkv", "att", "gu", "work", "qpos", "runs"))
+        cos, sin = self.freqs_cos.data._ptr, self.freqs_sin.data._ptr
+        max_len = min(self.layers[0].attention.cache_k.shape[1], self.freqs_cos.shape[0])
+        for layer, (wqkv, wgu) in zip(self.layers, packs):
+            a, f = layer.attention, layer.ffn
+            ck, cv = a.cache_k.data, a.cache_v.data
+            nrm = layer.input_norm
+            L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wqkv._ptr, D, D,
+                   wqkv._strides[0], None, qkv, 3 * D, 0, None, None, qpos, R, D, 3 * D, work, s)
+            L.call("pdn_kv_append_rows_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, ck._strides[0], runs, n_runs, max_run,
+                   R, H, hd, max_len, s)
+            L.call("pdn_decode_extend_attention_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, ck._strides[0], runs, n_runs,
+                   max_run, R, H, hd, ns, max_len, att, s)
+            L.call("pdn_decode_wide_gemm_f32", att, M["att"].shape[1], 3, None, 0.0, ns, hd, a.O.weight.data._ptr, D, D,
+                   0, None, x, D, 1, None, None, qpos, R, D, D, work, s)
+            nrm = layer.post_attn_norm
+            L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wgu._ptr, F, F,
+                   wgu._strides[0], None, gu, 2 * F, 0, None, None, qpos, R, D, 2 * F, work, s)
+            L.call("pdn_decode_wide_gemm_f32", gu, 2 * F, 2, None, 0.0, 0, 0, f.down.weight.data._ptr, D, D, 0, None,
+                   x, D, 1, None, None, qpos, R, F, D, work, s)
+
+    # -- speculative decoding (generate_ragged(speculate=k)): prompt-lookup drafts verified in one target pass
+    #    (statement: llm/speculative.py) --------------------------------------------------------------------------------
+    def _speculate(self, rows, n, k, sampling, stops):
+        """The generator of `generate_ragged(..., speculate=k)`: the prompt pass of `_generate_ragged`, then target passes
+        until every row has its tokens; step i is yielded once every live row has its token i (rows run ahead of each
+        other).  HIP with the library's speculative entries (`_spec_begin`): one graph-replayed pass per target pass,
+        drafted and settled on the device.  Every other path drafts on the host and verifies through the one-token rows
+        step (`_spec_host`)."""
+        if n == 0:
+            return
+        lens = np.array([r.size for r in rows], np.int64)
+        first = self._prompt_rows(rows, lens, sampling)
+        dev = first.device
+        R = spec_np.Rows(rows, first.numpy().reshape(-1), n, stops)
+        self.last_speculation = R.stats
+        yield first
+        if not R.live().any():
+            return
+        hip = (Llama.fast_decode and dev.is_hip and not self._train
+               and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
+        st = self._spec_begin(R, k, sampling) if hip else None
+        passes = self._spec_device(st, R) if st is not None else self._spec_host(R, k, sampling, hip)
+        out = None
+        if dev.is_hip:                                   # (the steps handed out: mapped host memory the host fills)
+            from .. import hipnp as hp
+            out = hp.Mailbox(n, (len(rows), 1), unset=np.iinfo(np.int64).min)
+        try:
+            i = 1
+            while True:
+                while R.live().any() and R.ready() <= i:
+                    next(passes)
+                if i >= R.ready():
+                    return
+                if out is None:
+                    yield Tensor(R.step(i), dtype=np.int64, device=dev)
+                else:
+                    out.host[i] = R.step(i)
+                    yield Tensor(out.slot(i), dtype=np.int64, device=dev, copy=False)
+                i += 1
+        finally:
+            passes.close()
+
+    def _spec_host(self, R, k, sampling, hip):
+        """The statement path: per pass, the drafts of llm/speculative.py on the host, then the fed tokens through the
+        one-token rows step, query j of every row at once (`_step_module_rows`; the generic rows step on HIP)."""
+        dev = self.tok_embedding.weight.device
+        while True:
+            fed = R.plan(k)
+            picks = [[] for _ in fed]
+            for j in range(max(len(f) for f in fed)):
+                ids = np.array([[f[j] if len(f) > j else 0] for f in fed], np.int64)
+                pos = np.array([R.pos[b] + j if len(f) > j else -1 for b, f in enumerate(fed)], np.int64)
+                if hip:
+                    from .. import hipnp as hp
+                    got = self._decode_step_generic_rows(hp.asarray(ids), pos.astype(np.int32), sampling).get()
+                else:
+                    got = self._step_module_rows(Tensor(ids, dtype=np.int64, device=dev), pos, sampling).numpy()
+                for b, f in enumerate(fed):
+                    if len(f) > j:
+                        picks[b].append(int(got.reshape(-1)[b]))
+            R.finish(fed, picks)
+            yield
+
+    def _spec_ok(self, B, k):
+        """Whether the library provides the speculative pass and takes this model with B (k + 1) query rows."""
+        from .. import _lib
+        L, D, H, F, V = _lib.lib(), self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
+        cache_len = self.layers[0].attention.cache_k.shape[1]
+        return bool(Llama.wide_decode and B * (k + 1) <= 256 and all(_lib.provides(n) for n in _SPEC_ENTRIES)
+                    and L.query("pdn_decode_mixed_supported", D, H, D // H, F, V, cache_len))
+
+    def _spec_begin(self, R, k, sampling):
+        """The plan of the speculative pass (buffers, weight views, its graph), kept across calls while the model's arrays
+        and (B, k, sampling) stay; then this run's row state uploaded.  None when the library or the model's layout
+        refuses it."""
+        from .. import hipnp as hp, _lib
+        B = len(R.out)
+        if not self._spec_ok(B, k):
+            return None
+        D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
+        cache_len = self.layers[0].attention.cache_k.shape[1]
+        ns = int(os.environ.get("PDN_DECODE_SPLITS", "0")) or (1 if cache_len <= 256 else 4)
+        if ns > 8:
+            return None
+        key = (B, k, bool(sampling), hp._state["device"], ns, cache_len, tuple(self._weight_ptrs()))
+        st = getattr(self, "_spec_st", None)
+        if st is not None and st["pending"]:
+            hp.synchronize()                             # (an abandoned run's passes: done before its buffers change)
+            st["pending"] = 0
+        if st is None or st["key"] != key:
+            if st is not None and st["graph"]:
+                st["graph"].destroy()
+            self._spec_st = st = None
+            packs = []
+            for layer in self.layers:
+                a, f = layer.attention, layer.ffn
+                qkv = hp.stacked_view([a.Q.weight.data, a.K.weight.data, a.V.weight.data])
+                gu = hp.stacked_view([f.gate.weight.data, f.up.weight.data])
+                if qkv is None or gu is None or not (a.O.weight.data.is_contiguous() and f.down.weight.data.is_contiguous()):
+                    return None
+                packs.append((qkv, gu))
+            if not (self.lm_head.weight.data.is_contiguous() and self.tok_embedding.weight.data.is_contiguous()):
+                return None
+            L, K1 = _lib.lib(), k + 1
+            Rq, hw = B * K1, min(cache_len, self.freqs_cos.shape[0])
+            work = max(L.query("pdn_decode_wide_work_floats", Rq, a, b)
+                       for a, b in ((D, 3 * D), (D, D), (F, D), (D, 2 * F), (D, V)))
+            nblk = L.query("pdn_decode_wide_blocks", V)
+            st = {"key": key, "B": B, "k": k, "R": Rq, "ns": ns, "hw": hw, "packs": packs, "graph": None, "nograph": False,
+                  "pending": 0, "sampling": bool(sampling), "params_val": None,
+                  "work": hp.zeros((max(work, 4),), np.float32),
+                  "cand_v": hp.empty((Rq, nblk), np.float32), "cand_i": hp.empty((Rq, nblk), np.int32),
+                  "logits": hp.empty((Rq, V), np.float32), "params": hp.zeros((3,), np.int64),
+                  # the rows' state (written before a run, then only by the device): history, its length, the position
+                  # of the next pass, the budget; the pass counter and the address of the run's mailbox
+                  "hist": hp.zeros((B, hw), np.int32), "hlen": hp.zeros((B,), np.int32), "pos": hp.zeros((B,), np.int32),
+                  "left": hp.zeros((B,), np.int32), "step": hp.zeros((1,), np.int32), "mbox_ptr": hp.zeros((1,), np.int64),
+                  "stop": hp.zeros((-(-V // 32),), np.int32),
+                  # the pass's layout, made by the draft kernel
+                  "tok": hp.zeros((Rq,), np.int64), "qpos": hp.zeros((Rq,), np.int32), "runs": hp.zeros((B, 4), np.int32),
+                  "picks": hp.zeros((Rq,), np.int64),
+                  **{n: hp.zeros((Rq, w), np.float32) for n, w in
+                     (("x", D), ("qkv", 3 * D), ("att", ns * H * (4 + D // H)), ("gu", 2 * F))}}
+            self._spec_st = st
+        hist = np.zeros((B, st["hw"]), np.int32)
+        for b, h in enumerate(R.hist):
+            hist[b, :h.size] = h
+        mask = np.zeros(-(-V // 32), np.uint32)
+        np.bitwise_or.at(mask, R.stops >> 5, np.uint32(1) << (R.stops & 31).astype(np.uint32))
+        st["hist"][...] = hist
+        st["hlen"][...] = np.array([h.size for h in R.hist], np.int32)
+        st["pos"][...] = R.pos.astype(np.int32)
+        st["left"][...] = R.left.astype(np.int32)
+        st["step"][...] = np.int32(0)
+        st["stop"][...] = mask.view(np.int32)
+        # one mailbox slot per pass: a pass moves every live row at least one token on, so n - 1 passes finish the run
+        st["mbox"] = hp.Mailbox(max(int(R.left.max()), 1), (B, k + 4), unset=np.iinfo(np.int64).min)
+        st["mbox_ptr"][...] = np.int64(st["mbox"]._ptr)
+        if st["params_val"] != sampling:
+            if sampling is not None:
+                st["params"][...] = params_bytes(*sampling)
+            st["params_val"] = sampling
+        return st
+
+    def _spec_launches(self, st):
+        """One target pass: the draft kernel, the embedding rows of the fed tokens, the mixed step's layers on the B (k + 1)
+        query rows, the vocabulary projection (block candidates, or full logit rows when sampling) and the verify tick."""
+        from .. import hipnp as hp, _lib
+        L, s = _lib.lib(), hp.stream()
+        D, V, B, k, Rq = self.embed_dim, self.vocab_size, st["B"], st["k"], st["R"]
+        emb = self.tok_embedding.weight.data
+        p = {n: st[n]._ptr for n in ("hist", "hlen", "pos", "left", "tok", "qpos", "runs", "picks", "stop", "step",
+                                     "mbox_ptr", "x", "work", "logits", "cand_v", "cand_i")}
+        L.call("pdn_spec_draft_rows", p["hist"], st["hw"], p["hlen"], p["pos"], p["left"], B, k, p["tok"], p["qpos"],
+               p["runs"], s)
+        L.call("pdn_embedding_gather_f32", emb._ptr, V, D, emb._strides[0], p["tok"], Rq, p["x"], hp.err_flag_ptr(), s)
+        self._mixed_layers(st, st["packs"], B, k + 1, Rq, st["ns"], s)
+        head = self.lm_head
+        bias = head.bias.data._ptr if getattr(head, "bias", None) is not None else None
+        full = st["sampling"]
+        cv, ci = (None, None) if full else (p["cand_v"], p["cand_i"])
+        L.call("pdn_decode_wide_gemm_f32", p["x"], D, 1, self.norm.weight.data._ptr, self.norm.eps, 0, 0,
+               head.weight.data._ptr, V, V, 0, bias, p["logits"], V, 0 if full else 2, cv, ci, p["qpos"], Rq, D, V,
+               p["work"], s)
+        row = (p["tok"], p["qpos"], B, k, p["picks"], p["hist"], st["hw"], p["hlen"], p["pos"], p["left"], p["stop"],
+               p["step"], p["mbox_ptr"], s)
+        if full:
+            L.call("pdn_spec_verify_sample_tick_f32", p["logits"], V, V, st["params"]._ptr, *row)
+        else:
+            L.call("pdn_spec_verify_pick_tick_f32", p["cand_v"], p["cand_i"], st["cand_v"].shape[1], *row)
+
+    def _spec_issue(self, st):
+        """Queue one target pass; the first one of a plan captures its graph (whose two real runs work on a copy of the
+        row state and a scratch mailbox: the state is put back afterwards)."""
+        from .. import hipnp as hp, _lib
+        g = False if st["nograph"] else st["graph"]
+        if g is None and Llama.graph_decode:
+            keep = {n: st[n].copy() for n in ("hist", "hlen", "pos", "left", "step")}
+            scratch = hp.Mailbox(2, (st["B"], st["k"] + 4), unset=np.iinfo(np.int64).min)
+            st["mbox_ptr"][...] = np.int64(scratch._ptr)
+            try:
+                g = hp.Graph()
+                g.capture(lambda: self._spec_launches(st))
+                st["graph"] = g
+            except _lib.HipLibraryError as e:
+                if e.code != -2:                                 # PDN_EUNSUPPORTED: no graph support (emulated ABI)
+                    raise
+                st["nograph"], g = True, False
+            hp.synchronize()
+            st["mbox_ptr"][...] = np.int64(st["mbox"]._ptr)
+            for n, v in keep.items():
+                st[n][...] = v
+        if g:
+            g.replay()
+        else:
+            self._spec_launches(st)
+        st["pending"] += 1
+
+    def _spec_device(self, st, R):
+        """The device path: passes queued back to back (one ahead of the one being read when `decode_ahead`), each read
+        from its mailbox slot [count, drafted, accepted, tokens...] per row.  A pass is queued only while some live row
+        may still need it: its budget exceeds the passes already queued for it."""
+        from .. import hipnp as hp
+        B, k = st["B"], st["k"]
+        try:
+            while True:
+                depth = 2 if Llama.decode_ahead else 1
+                while st["pending"] < depth and (R.live() & (R.left > st["pending"])).any():
+                    self._spec_issue(st)
+                if not st["pending"]:
+                    raise RuntimeError("speculative decoding: no pass left to read")
+                got = np.array(st["mbox"].slot(R.stats["passes"]).get()).reshape(B, k + 4)
+                st["pending"] -= 1
+                R.stats["passes"] += 1
+                for b in range(B):
+                    c = int(got[b, 0])
+                    if c > 0:
+                        y = got[b, 3:3 + c]
+                        R.take(b, y, int(got[b, 1]), int(got[b, 2]), bool(np.isin(y[-1], R.stops)))
+                yield
+        finally:
+            if st["pending"]:
+                hp.synchronize()
+                st["pending"] = 0
 
     # -- beam search: the W most probable continuations of each prompt (statement: llm/beam.py) ----------------------
     def beam_search(self, prompts, max_new_tokens, num_beams, length_penalty=1.0, stop_ids=()):
