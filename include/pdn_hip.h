@@ -188,7 +188,8 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *     ticks also count in 29, the slot forms in 30, the sampled forms in 28)
  *  32 beam search (csrc/beam.hip): pdn_beam_topk_rows_f32, pdn_beam_select_f32, pdn_kv_reorder_rows_f32
  *  33 chunked prefill (csrc/extend.hip): pdn_kv_append_rows_f32, pdn_decode_extend_attention_f32
- *  34 speculative decoding (csrc/speculative.hip): pdn_spec_draft_rows and the two pdn_spec_verify_*_tick_f32 entries */
+ *  34 speculative decoding (csrc/speculative.hip): pdn_spec_draft_rows and the two pdn_spec_verify_*_tick_f32 entries
+ *  35 decode penalties (csrc/penalty.hip): pdn_penalty_reset, pdn_penalty_step_f32, pdn_penalty_rows_f32 */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -763,6 +764,38 @@ int pdn_spec_verify_sample_tick_f32(const float* logits, int64_t row_stride, int
                                     const int64_t* tokens, const int* qpos, int B, int k, int64_t* picks, int* hist,
                                     int hist_stride, int* hist_len, int* pos, int* left, const int* stop_mask,
                                     int* step, int64_t* const* mailbox, void* stream);
+/* Repetition, presence and frequency penalties (csrc/penalty.hip; Llama.generate / generate_ragged / serve with
+ * penalties, the NumPy statement is pydynet_amd/llm/penalties.py).  Row b's fp32 logits z, c[v] = the tokens v it
+ * generated before this step, P = its prompt's ids: z[v] = z[v] > 0 ? z[v] / r : z[v] * r for v in P or c[v] > 0, then
+ * z[v] -= f * c[v] + p for c[v] > 0 -- one float32 rounding per operation, no FMA, so the bits equal the statement's.
+ * Row state: counts (B, V) int32, seen (B, ceil(V / 32)) uint32 prompt bits (bit v & 31 of word v >> 5), start (B,) int32
+ * the row's prompt length.  The parameters live in device memory (new values never re-capture a graph).
+ *   pdn_penalty_chunks    the vocabulary chunks of a row: ceil(V / 1024), one workgroup each; the width of cand_v /
+ *                         cand_i below.
+ *   pdn_penalty_reset     rows[i] (i < n_rows, rows outside [0, B) skipped) takes prompt ids[offsets[i] ..
+ *                         offsets[i + 1]): its counts zeroed, its prompt bits set, start = the prompt's length.
+ *   pdn_penalty_step_f32  the step's form, between the vocabulary projection and the tick: row b at position pos[b]
+ *                         (pos_per_row; else pos[0] for every row; < 0: untouched) first counts the token it is fed,
+ *                         ids[b], when pos > start[b] (a generated token), then its logits are penalised in place.
+ *                         cand_v / cand_i (B, pdn_penalty_chunks(V), may be null): each chunk's first maximum and its
+ *                         index -- the candidates of the pick ticks, n_blocks = pdn_penalty_chunks(V).
+ *   pdn_penalty_rows_f32  the same without counting and without a plan: counts (may be null: zeros) and seen (may be
+ *                         null: empty prompts) read only; pos (may be null: every row) skips rows < 0. */
+typedef struct pdn_penalty_params {
+  float repetition;
+  float presence;
+  float frequency;
+  int reserved;
+} pdn_penalty_params;
+int pdn_penalty_chunks(int V);
+int pdn_penalty_reset(int* counts, unsigned* seen, int* start, int B, int V, const int* rows, int n_rows,
+                      const int64_t* ids, const int* offsets, void* stream);
+int pdn_penalty_step_f32(float* logits, int64_t row_stride, int B, int V, const pdn_penalty_params* params, int* counts,
+                         const unsigned* seen, const int* start, const int64_t* ids, const int* pos, int pos_per_row,
+                         float* cand_v, int* cand_i, void* stream);
+int pdn_penalty_rows_f32(float* logits, int64_t row_stride, int B, int V, const pdn_penalty_params* params,
+                         const int* counts, const unsigned* seen, const int* pos, float* cand_v, int* cand_i,
+                         void* stream);
 /* shapes the resident (K / V of a head chunk-wise in LDS) kernels above take: head_dim 48 or 64, L a multiple of 32 up
  * to 1024 -- sequences beyond 256 pass through LDS in 256-row chunks (forward: one online rescale per chunk) -- and
  * (round 6, csrc/attention_hd128.hip) head_dim 128 at ANY length 1 .. 1024, no RoPE inside: the shape of

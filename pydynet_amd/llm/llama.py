@@ -22,6 +22,7 @@ from ..core import Tensor, fused
 from ..special import zeros
 from . import beam as beam_np
 from . import chunked
+from . import penalties as pen_np
 from . import speculative as spec_np
 from .sampling import (check_args as check_sampling_args, params_bytes, params_buffer, sample_next,
                        sample_next_rows)
@@ -35,6 +36,8 @@ _WIDE_ENTRIES = ("pdn_decode_wide_supported", "pdn_decode_wide_blocks", "pdn_dec
 _MIXED_ENTRIES = _WIDE_ENTRIES + ("pdn_decode_mixed_supported", "pdn_kv_append_rows_f32", "pdn_decode_extend_attention_f32")
 # ... and of the speculative pass (csrc/speculative.hip), which runs the mixed step's layers
 _SPEC_ENTRIES = _MIXED_ENTRIES + ("pdn_spec_draft_rows", "pdn_spec_verify_pick_tick_f32", "pdn_spec_verify_sample_tick_f32")
+# the entry points of the penalties (csrc/penalty.hip): without them every path applies the statement of llm/penalties.py
+_PEN_ENTRIES = ("pdn_penalty_chunks", "pdn_penalty_reset", "pdn_penalty_step_f32", "pdn_penalty_rows_f32")
 
 
 def compute_cos_sin_cache(head_dim: int, max_seq_len: int, base: int = 10000, dtype=None):
@@ -262,34 +265,72 @@ class Llama(nn.Module):
 
     fast_decode = True      # class switch: False keeps every decode step on the generic tape-node path
 
-    def generate(self, input_ids, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0):
+    def generate(self, input_ids, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0,
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
         """Yield the next ids, (B, 1) int64, for positions L .. max_new_tokens - 1.  temperature 0 (the default): the
         greedy pick of the reference (model.py:258-269); temperature > 0: drawn with top-k / top-p and the seeded
-        counter-based generator of llm/sampling.py (token at position t of row b: Philox counter (t, b)).  The arguments
-        are checked here, before anything runs."""
+        counter-based generator of llm/sampling.py (token at position t of row b: Philox counter (t, b)).
+        `repetition_penalty` / `presence_penalty` / `frequency_penalty` (defaults: off): the penalties of llm/penalties.py
+        on each row's logits -- its prompt's tokens and the tokens it generated -- before the pick or the draw.  The
+        arguments are checked here, before anything runs."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
-        return self._generate(input_ids, max_new_tokens, (temperature, top_k, top_p, seed) if temperature > 0 else None)
+        penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty)
+        return self._generate(input_ids, max_new_tokens, (temperature, top_k, top_p, seed) if temperature > 0 else None,
+                              penalty)
 
-    def _generate(self, input_ids, max_new_tokens, sampling):
+    def _generate(self, input_ids, max_new_tokens, sampling, penalty=None):
         B, L = input_ids.shape
         next_id = None
+        pen = None
+        if penalty is not None:                                   # (the rows' prompts and counts: llm/penalties.py)
+            ids = np.asarray(input_ids.numpy() if isinstance(input_ids, Tensor) else input_ids).reshape(B, L)
+            pen = pen_np.Rows(B, self.vocab_size, penalty, list(ids))
         for i, pos in enumerate(range(L, max_new_tokens)):
             if i == 0:
-                logits = self(input_ids, 0)                       # prompt pass: fills the KV caches
-                next_id = (logits[:, -1, :].argmax(-1, True) if sampling is None
-                           else sample_next(logits[:, -1, :], pos, *sampling))
+                logits = self(input_ids, 0)[:, -1, :]             # prompt pass: fills the KV caches
+                if pen is not None:
+                    logits = self._penalize_prompt(logits, pen.prompts, penalty)
+                next_id = logits.argmax(-1, True) if sampling is None else sample_next(logits, pos, *sampling)
             elif (Llama.fast_decode and next_id.device.is_hip and not self._train
                   and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0):
                 # (`more`: another token will be asked for -- the step after this one may be queued ahead)
                 next_id = Tensor(self._decode_step_hip(next_id.data, pos, more=pos + 1 < max_new_tokens,
-                                                       sampling=sampling), dtype=np.int64, device=next_id.device, copy=False)
+                                                       sampling=sampling, pen=pen),
+                                 dtype=np.int64, device=next_id.device, copy=False)
             else:
                 logits = self(next_id, pos)[:, -1, :]
+                if pen is not None:
+                    logits = self._penalize_step(logits, pen, next_id.numpy(), np.full(B, pos))
                 next_id = logits.argmax(-1, True) if sampling is None else sample_next(logits, pos, *sampling)
             yield next_id
 
+    def _penalize_prompt(self, logits, prompts, penalty):
+        """The logits (A, V) of a prompt pass penalised for prompts[i] (no generated token yet: only the repetition penalty
+        of the prompt's tokens acts).  On a HIP device with the library's entries: pdn_penalty_rows_f32 in place (stream
+        ordered, no plan); elsewhere the statement of llm/penalties.py."""
+        from .. import _lib
+        dev, V = logits.device, self.vocab_size
+        if dev.is_hip and logits.data.dtype == np.float32 and all(_lib.provides(n) for n in _PEN_ENTRIES):
+            from .. import hipnp as hp
+            x = logits.data
+            if x._strides[1] != 1 or x._strides[0] < V:
+                x = x.copy()
+            seen, prm = hp.asarray(pen_np.seen_bits(prompts, V)), hp.asarray(pen_np.params_bytes(*penalty))
+            _lib.lib().call("pdn_penalty_rows_f32", x._ptr, x._strides[0], x.shape[0], V, prm._ptr, None, seen._ptr, None,
+                            None, None, hp.stream())
+            return Tensor(x, dtype=np.float32, device=dev, copy=False)
+        z = pen_np.penalize(logits.numpy(), np.zeros((len(prompts), V), np.int64), pen_np.seen_rows(prompts, V), *penalty)
+        return Tensor(z, dtype=np.float32, device=dev)
+
+    @staticmethod
+    def _penalize_step(logits, pen, ids, pos):
+        """The statement on a step of a path without the device state (host counts in `pen`, llm/penalties.Rows): the
+        generated tokens fed at positions pos (B,) counted, then the (B, V) logits penalised."""
+        pen.feed(ids, pos)
+        return Tensor(pen.apply(np.asarray(logits.numpy(), np.float32)), dtype=np.float32, device=logits.device)
+
     def generate_ragged(self, prompts, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
-                        speculate=0):
+                        speculate=0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
         """Generation for B prompts of different lengths, every row at its own position.  Yields a (B, 1) int64 Tensor
         per step: step i holds, for row b, the token at position len_b + i.  `max_new_tokens` is the number of NEW tokens
         per row -- `generate`'s second argument is an end position instead: for equal lengths L,
@@ -303,6 +344,8 @@ class Llama(nn.Module):
         graph-replayed HIP pass computes the logits with other kernels than the plain step (the wide product, the extend
         attention), so there they agree up to fp32 near-ties, as the plain step and the wide step do.  The counts of the
         run are in `last_speculation` (None after a call with speculate=0, which runs the plain decode).
+        `repetition_penalty` / `presence_penalty` / `frequency_penalty`: as in `generate` (llm/penalties.py), row b's
+        prompt and generated tokens; not with speculate > 0.
         Every argument is checked here (ValueError), before anything runs."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
         V = self.vocab_size
@@ -314,6 +357,7 @@ class Llama(nn.Module):
         if not rows:
             raise ValueError("generate_ragged needs at least one prompt")
         k = spec_np.check_speculate(speculate, len(rows))
+        penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty, k)
         if len(rows) > cache.shape[0]:
             raise ValueError(f"batch {len(rows)} exceeds the KV cache's max_batch_size {cache.shape[0]}")
         limit = min(cache.shape[1], self.freqs_cos.shape[0])     # positions the cache / RoPE table hold
@@ -333,14 +377,15 @@ class Llama(nn.Module):
         self.last_speculation = None if k == 0 else spec_np.counts()
         if k:
             return self._speculate([r.astype(np.int64) for r in rows], max_new_tokens, k, sampling, stops)
-        return self._generate_ragged([r.astype(np.int64) for r in rows], max_new_tokens, sampling, stops)
+        return self._generate_ragged([r.astype(np.int64) for r in rows], max_new_tokens, sampling, stops, penalty)
 
-    def _generate_ragged(self, rows, n, sampling, stops):
+    def _generate_ragged(self, rows, n, sampling, stops, penalty=None):
         B = len(rows)
         lens = np.array([r.size for r in rows], np.int64)
         if n == 0:
             return
-        nxt = self._prompt_rows(rows, lens, sampling)
+        pen = None if penalty is None else pen_np.Rows(B, self.vocab_size, penalty, rows)
+        nxt = self._prompt_rows(rows, lens, sampling, penalty)
         live = np.ones(B, bool)
         if stops.size:
             live = ~np.isin(nxt.numpy().reshape(-1), stops)
@@ -353,7 +398,7 @@ class Llama(nn.Module):
             np.bitwise_or.at(mask, stops >> 5, np.uint32(1) << (stops & 31).astype(np.uint32))
             # tokens by STEP: slot i holds step i of every row (-1 for a stopped row), so "not written yet" is its own
             # value; two slots beyond the last step for the runs of a graph capture
-            run = {"lens": lens, "live": live, "sampling": sampling, "stop_mask": mask.view(np.int32),
+            run = {"lens": lens, "live": live, "sampling": sampling, "stop_mask": mask.view(np.int32), "pen": pen,
                    "hist": hp.Mailbox(n + 2, (B, 1), unset=np.iinfo(np.int64).min)}
         ids = nxt.data
         for i in range(1, n):
@@ -364,7 +409,7 @@ class Llama(nn.Module):
                 ids = self._decode_step_rows(ids, run, i, more=i + 1 < n)
                 nxt = Tensor(ids, dtype=np.int64, device=nxt.device, copy=False)
             else:
-                nxt = self._step_module_rows(nxt, np.where(live, lens + i, -1), sampling)
+                nxt = self._step_module_rows(nxt, np.where(live, lens + i, -1), sampling, pen=pen)
             if stops.size:
                 yield nxt
                 tok = nxt.numpy().reshape(-1)                    # (fast path: a poll of the mapped history slot)
@@ -372,11 +417,12 @@ class Llama(nn.Module):
                 continue
             yield nxt
 
-    def _prompt_rows(self, rows, lens, sampling):
+    def _prompt_rows(self, rows, lens, sampling, penalty=None):
         """The prompt pass of a ragged generation: the prompts right-padded to the longest and run as one batched
         causal pass from position 0 (no real token attends to a pad after it); each row's logits at its last real token,
         gathered before lm_head.  The cache slots the pads wrote, [len_b, L_max) of row b, are put back as they were: a
-        row's cache is written at its own positions only.  Returns the first token of every row, (B, 1) int64."""
+        row's cache is written at its own positions only.  `penalty`: the logits penalised for each row's prompt first.
+        Returns the first token of every row, (B, 1) int64."""
         B, Lm, lo = len(rows), int(lens.max()), int(lens.min())
         ids = np.zeros((B, Lm), np.int64)
         for b, r in enumerate(rows):
@@ -390,16 +436,21 @@ class Llama(nn.Module):
         for c, keep in zip(caches, saved):
             for b in np.flatnonzero(lens < Lm):
                 c.data[int(b), int(lens[b]):Lm] = keep[int(b), int(lens[b]) - lo:]
+        if penalty is not None:
+            logits = self._penalize_prompt(logits, rows, penalty)
         if sampling is None:
             return logits.argmax(-1, True)
         return sample_next_rows(logits, lens, *sampling)
 
-    def _step_module_rows(self, ids, pos, sampling, req=None):
+    def _step_module_rows(self, ids, pos, sampling, req=None, pen=None):
         """One ragged decode step on the tape-node operators (the `cpu` device, fast_decode = False, training mode,
         other dtypes): row b's token at position pos[b] (-1: a stopped row, which yields -1).  The NumPy statement of what
-        the per-row kernels compute.  `req`: the counter id of each row (Llama.serve; default: the row)."""
+        the per-row kernels compute.  `req`: the counter id of each row (Llama.serve; default: the row).  `pen`
+        (llm/penalties.Rows): the fed tokens counted and the logits penalised before the pick."""
         p = np.maximum(pos, 0)
         logits = self._step_logits_rows(ids, pos)
+        if pen is not None:
+            logits = self._penalize_step(logits, pen, ids.numpy(), pos)
         nxt = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, p, *sampling, rows=req)
         if pos.min() >= 0:
             return nxt
@@ -422,7 +473,7 @@ class Llama(nn.Module):
     fused_decode = 2        # class switch: launches per layer = 2 (q|k|v inside the attention kernel), 1 -> 3, 0 / False -> 5
     wide_decode = True      # class switch: 9 .. 256 rows on the wide step (csrc/decode_wide.hip); False -> the generic step
 
-    def _decode_plan(self, B, sampling=False, ragged=False, serve=False, beam=0, n_stops=0):
+    def _decode_plan(self, B, sampling=False, ragged=False, serve=False, beam=0, n_stops=0, penalty=False):
         """Buffers and weight views of the graph-replayable decode step (csrc/decode.hip), or None when the
         model's shapes / layout are outside what those kernels take (then the generic launches below run).
         `sampling`: the step ends in the sample tick (csrc/sample.hip) instead of the greedy pick; its parameters live in
@@ -435,7 +486,11 @@ class Llama(nn.Module):
         `beam` (Llama.beam_search, with `ragged`): W beams per group and `n_stops` stop ids; the projection writes full
         logit rows and the tick is replaced by top-k -> select -> KV-cache reorder (csrc/beam.hip, buffers in `bm`).
         More than 8 rows (`wide_decode`): the wide step of csrc/decode_wide.hip, always in the per-row form (`rows`; a
-        rectangular batch holds equal positions and a step counter equal to the position)."""
+        rectangular batch holds equal positions and a step counter equal to the position).
+        `penalty` (generation with penalties, csrc/penalty.hip): the projection writes full logit rows, and
+        pdn_penalty_step_f32 counts each row's fed token and penalises them before the tick; the rows' counts / prompt
+        bits / prompt lengths live in the plan (`counts`, `seen`, `start`), the values in `pen_params`.  A greedy plan's
+        `cand_v` / `cand_i` then hold the candidates of that kernel.  None when the library lacks the entries."""
         from .. import hipnp as hp, _lib
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
         st = getattr(self, "_decode_st", None)
@@ -446,7 +501,7 @@ class Llama(nn.Module):
         wide = B > 8 and Llama.wide_decode and self._decode_wide_ok(B, cache_len)
         key = (B, hp._state["device"], int(Llama.fused_decode or 0), os.environ.get("PDN_DECODE_SPLITS", ""),
                cache_len, tuple(ptrs), bool(sampling), wide,   # (the addresses: no hash to collide)
-               (int(beam), int(n_stops)), bool(ragged), bool(serve))
+               (int(beam), int(n_stops), bool(penalty)), bool(ragged), bool(serve))
         if st is not None and st["key"] == key:
             return st if st["ok"] else None
         if st is not None:
@@ -457,6 +512,8 @@ class Llama(nn.Module):
         if wide:
             # (the merge of the key-range partials happens in the output projection's load: at most 8 ranges)
             ok = int(os.environ.get("PDN_DECODE_SPLITS", "0") or 0) <= 8
+        if penalty and not all(_lib.provides(n) for n in _PEN_ENTRIES):
+            ok = False
         packs = []
         if ok:
             for layer in self.layers:
@@ -470,7 +527,8 @@ class Llama(nn.Module):
                 packs.append((qkv, gu))
             ok = ok and self.lm_head.weight.data.is_contiguous() and self.tok_embedding.weight.data.is_contiguous()
         st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged), "serve": bool(serve),
-              "wide": wide, "rows": bool(ragged or wide), "beam": int(beam), "full": bool(sampling or beam)}
+              "wide": wide, "rows": bool(ragged or wide), "beam": int(beam), "full": bool(sampling or beam or penalty),
+              "pen": bool(penalty)}
         if ok:
             nblk = _lib.lib().query("pdn_decode_wide_blocks" if wide else "pdn_decode_gemv_blocks", V)
             # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
@@ -528,6 +586,13 @@ class Llama(nn.Module):
                 st.update(req=hp.zeros((B,), np.int32), left=hp.zeros((B,), np.int32), ring=4, pending=0, issued=0)
             if beam:
                 st["bm"] = self._beam_buffers(B, int(beam), int(n_stops), cache_len + 2)
+            if penalty:
+                # (B = 256, V = 32000: 33 MB of counts -- penalty plans only)
+                st.update(counts=hp.zeros((B, V), np.int32), seen=hp.zeros((B, -(-V // 32)), np.int32),
+                          start=hp.zeros((B,), np.int32), pen_params=hp.zeros((2,), np.int64), pen_val=None, pen_run=None)
+                if not sampling:
+                    nc = _lib.lib().query("pdn_penalty_chunks", V)
+                    st.update(cand_v=hp.empty((B, nc), np.float32), cand_i=hp.empty((B, nc), np.int32))
             self._decode_ws = {"logits": st["logits"], "x": st["x"]}
         self._decode_st = st
         return st if ok else None
@@ -623,6 +688,7 @@ class Llama(nn.Module):
             cv, ci = (None, None) if st["full"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
             L.call("pdn_decode_gemv_sum_f32", xb, D, dparts, J, J * D, None, 0, self.norm.weight.data._ptr, self.norm.eps,
                    head.weight.data._ptr, V, V, 0, bias, logits, V, B, D, V, cv, ci, s)
+            self._pen_step(st, s)
             self._decode_tick(st, s)
             return
         for layer, (wqkv, wgu) in zip(self.layers, st["packs"]):
@@ -649,6 +715,7 @@ class Llama(nn.Module):
         cv, ci = (None, None) if st["full"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
         L.call("pdn_decode_gemv_f32", x, D, self.norm.weight.data._ptr, self.norm.eps, head.weight.data._ptr, V, V, 0,
                bias, None, 0, logits, V, B, D, V, 0, 0, 0, cv, ci, s)
+        self._pen_step(st, s)
         self._decode_tick(st, s)
 
     def _decode_launches_wide(self, st, s):
@@ -681,7 +748,36 @@ class Llama(nn.Module):
         cv, ci = (None, None) if st["full"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
         L.call("pdn_decode_wide_gemm_f32", x, D, 1, self.norm.weight.data._ptr, self.norm.eps, 0, 0, head.weight.data._ptr,
                V, V, 0, bias, logits, V, 0 if st["full"] else 2, cv, ci, pos, B, D, V, work, s)
+        self._pen_step(st, s)
         self._decode_tick(st, s)
+
+    def _pen_step(self, st, s):
+        """Penalty plans: between the vocabulary projection and the tick, each live row counts the token it is fed and its
+        logits are penalised in place (greedy plans: with the candidates the tick reduces, csrc/penalty.hip)."""
+        if not st["pen"]:
+            return
+        from .. import _lib
+        V, B = self.vocab_size, st["B"]
+        cv, ci = (None, None) if st["sampling"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
+        _lib.lib().call("pdn_penalty_step_f32", st["logits"]._ptr, V, B, V, st["pen_params"]._ptr, st["counts"]._ptr,
+                        st["seen"]._ptr, st["start"]._ptr, st["ids"]._ptr, st["pos"]._ptr, int(st["rows"]), cv, ci, s)
+
+    def _pen_reset(self, st, rows, prompts, penalty):
+        """Rows `rows` of a penalty plan take `prompts` (zero counts, prompt bits, prompt lengths; stream ordered after
+        every step queued before), and the plan's values become `penalty` (stream ordered too)."""
+        from .. import hipnp as hp, _lib
+        if st["pen_val"] != penalty:
+            st["pen_params"][...] = pen_np.params_bytes(*penalty)
+            st["pen_val"] = penalty
+        rows = np.asarray(rows, np.int32).reshape(-1)
+        if not rows.size:
+            return
+        ids, off = pen_np.packed(prompts)
+        # (device copies held until the call has been issued; the allocator orders their reuse on the stream)
+        d_rows, d_ids, d_off = hp.asarray(rows), hp.asarray(ids) if ids.size else None, hp.asarray(off)
+        _lib.lib().call("pdn_penalty_reset", st["counts"]._ptr, st["seen"]._ptr, st["start"]._ptr, st["B"],
+                        self.vocab_size, d_rows._ptr, int(rows.size), d_ids._ptr if ids.size else None, d_off._ptr,
+                        hp.stream())
 
     def _decode_tick(self, st, s):
         """The last launch of a step: the greedy pick over the projection's candidates, or (sampling plans) the sample
@@ -740,12 +836,14 @@ class Llama(nn.Module):
         _lib.lib().call("pdn_embedding_gather_f32", emb._ptr, self.vocab_size, self.embed_dim, emb._strides[0],
                         st["ids"]._ptr, st["B"], st["x"]._ptr, hp.err_flag_ptr(), hp.stream())
 
-    def _decode_step_hip(self, ids, pos: int, more: bool = False, sampling=None):
+    def _decode_step_hip(self, ids, pos: int, more: bool = False, sampling=None, pen=None):
         """One decode step (one new token per sequence) without building tape nodes.  ids: (B, 1) int64
         device array; returns the next ids, (B, 1) int64.  The step is ONE hipGraph replay: norm + projection,
         RoPE + cache append, decode attention, SwiGLU + down projection and the greedy pick all read the position
         from device memory (csrc/decode.hip), so nothing changes between replays but the data.  `sampling`: None =
-        greedy, else (temperature, top_k, top_p, seed) and the step ends in the sample tick (csrc/sample.hip)."""
+        greedy, else (temperature, top_k, top_p, seed) and the step ends in the sample tick (csrc/sample.hip).  `pen`
+        (llm/penalties.Rows of this generation, or None): a penalty plan; its rows are reset from the prompts when a new
+        generation begins."""
         from .. import hipnp as hp, _lib
         B = ids.shape[0]
         cache = self.layers[0].attention.cache_k
@@ -756,12 +854,13 @@ class Llama(nn.Module):
                              f"(max_seq_len {cache.shape[1]}, {self.freqs_cos.shape[0]} RoPE rows)")
         if B > cache.shape[0]:
             raise ValueError(f"batch {B} exceeds the KV cache's max_batch_size {cache.shape[0]}")
-        st = self._decode_plan(B, sampling is not None)
+        st = self._decode_plan(B, sampling is not None, penalty=pen is not None)
         if st is None:
-            return self._decode_step_generic(ids, pos, sampling)
+            return self._decode_step_generic(ids, pos, sampling, pen)
         ahead, st["ahead"] = st.get("ahead"), None
         if ahead is not None:
-            if ahead[0] == pos and ahead[1] is ids and st["params_val"] == sampling:   # exactly this step, queued ahead
+            if (ahead[0] == pos and ahead[1] is ids and st["params_val"] == sampling     # exactly this step, queued ahead
+                    and st.get("pen_run") is pen):
                 out = st["last_out"] = ahead[2]
                 if more and Llama.decode_ahead and pos + 1 < min(cache.shape[1], self.freqs_cos.shape[0]):
                     self._decode_ahead(st, pos + 1)
@@ -780,6 +879,9 @@ class Llama(nn.Module):
             if sampling is not None:
                 st["params"][...] = params_bytes(*sampling)      # (stream-ordered: earlier steps read the old values)
             st["params_val"] = sampling
+        if pen is not None and st["pen_run"] is not pen:         # a new generation: its rows' prompts, zero counts
+            self._pen_reset(st, np.arange(B), pen.prompts, pen.values)
+            st["pen_run"] = pen
         fresh = ids is not st["ids"] and ids is not st.get("last_out")
         if fresh:
             st["ids"][...] = ids                                 # (not the array the previous step returned: that
@@ -794,6 +896,7 @@ class Llama(nn.Module):
             # history meanwhile, so that slots pos / pos + 1 of the real one stay "not written" (-1) until the real
             # steps store there (a later step with other ids would otherwise read the capture's token as its own).
             keep = st["ids"].copy()
+            counts = st["counts"].copy() if st["pen"] else None  # (the capture's runs count their fed tokens too)
             scratch = hp.Mailbox(cache.shape[1], (B, 1))
             st["hist_ptr"][...] = np.int64(scratch._ptr)
             try:
@@ -810,6 +913,8 @@ class Llama(nn.Module):
             if st["rows"]:
                 st["step"][...] = np.int32(pos)
             st["ids"][...] = keep
+            if counts is not None:
+                st["counts"][...] = counts
             self._decode_gather(st)
         if g:
             g.replay()
@@ -840,7 +945,7 @@ class Llama(nn.Module):
         prev = st["last_out"]
         st["ahead"] = (pos, prev, st["hist"].slot(pos))
 
-    def _decode_step_generic(self, ids, pos: int, sampling=None):
+    def _decode_step_generic(self, ids, pos: int, sampling=None, pen=None):
         """The same step from the library's generic entry points (skinny `pdn_gemm_f32`, RMSNorm, RoPE, decode
         attention, SwiGLU), ~77 launches from preallocated buffers: for shapes / layouts the graph path does not take."""
         from .. import hipnp as hp, _lib
@@ -888,6 +993,9 @@ class Llama(nn.Module):
         L.call("pdn_rmsnorm_fwd_f32", x, self.norm.weight.data._ptr, h, None, B, D, self.norm.eps, st)
         gemv(h, D, self.lm_head.weight, logits, V,
              bias=self.lm_head.bias.data._ptr if getattr(self.lm_head, "bias", None) is not None else None)
+        if pen is not None:                           # (the statement of llm/penalties.py on the host counts)
+            pen.feed(ids.get(), np.full(B, pos))
+            ws["logits"][...] = pen.apply(ws["logits"].get())
         if sampling is None:
             return ws["logits"].argmax(-1, keepdims=True)
         out = hp.empty((B, 1), np.int64)              # (the sampled form of the pick: counter (pos, b))
@@ -907,9 +1015,9 @@ class Llama(nn.Module):
         cache = self.layers[0].attention.cache_k
         limit = min(cache.shape[1], self.freqs_cos.shape[0])
         pos = np.where(live, lens + i, -1).astype(np.int32)
-        st = self._decode_plan(B, sampling is not None, ragged=True)
+        st = self._decode_plan(B, sampling is not None, ragged=True, penalty=run.get("pen") is not None)
         if st is None:
-            out = self._decode_step_generic_rows(ids, pos, sampling)
+            out = self._decode_step_generic_rows(ids, pos, sampling, pen=run.get("pen"))
             if pos.min() >= 0:
                 return out
             tok = out.get().reshape(B, 1)
@@ -934,6 +1042,10 @@ class Llama(nn.Module):
             if sampling is not None:
                 st["params"][...] = params_bytes(*sampling)
             st["params_val"] = sampling
+        pen = run.get("pen")
+        if pen is not None and st["pen_run"] is not pen:         # a new run: its rows' prompts, zero counts
+            self._pen_reset(st, np.arange(B), pen.prompts, pen.values)
+            st["pen_run"] = pen
         if ids is not st["ids"] and ids is not st.get("last_out"):
             # (a stopped row's -1 is no token: any valid id stands in, its row computes nothing that is kept)
             st["ids"][...] = np.maximum(ids.get(), 0) if isinstance(ids, hp.readback_array) else ids
@@ -944,6 +1056,7 @@ class Llama(nn.Module):
             # capture once, as in `_decode_step_hip`: the capture's two real runs store into a scratch history; the
             # positions, the step counter and the ids are put back afterwards
             keep = st["ids"].copy()
+            counts = st["counts"].copy() if st["pen"] else None  # (the capture's runs count their fed tokens too)
             scratch = hp.Mailbox(run["hist"].n, (B, 1), unset=run["hist"].unset)
             st["hist_ptr"][...] = np.int64(scratch._ptr)
             try:
@@ -959,6 +1072,8 @@ class Llama(nn.Module):
             st["pos"][...] = pos
             st["step"][...] = np.int32(i)
             st["ids"][...] = keep
+            if counts is not None:
+                st["counts"][...] = counts
             self._decode_gather(st)
         if g:
             g.replay()
@@ -983,12 +1098,13 @@ class Llama(nn.Module):
         st["host_step"] = i + 1
         st["ahead"] = ((id(run), i), st["last_out"], run["hist"].slot(i))
 
-    def _decode_step_generic_rows(self, ids, pos, sampling=None, req=None):
+    def _decode_step_generic_rows(self, ids, pos, sampling=None, req=None, pen=None):
         """`_decode_step_generic` with a position per row (pos: host int32, -1 = a stopped row: computed at position 0,
         no cache slot written): k / v are projected into scratch rows and written to each row's own slot, RoPE takes
         each row's own cos / sin row, and the attention runs over each row's own key count (pdn_attention_decode_rows_f32).
-        `req` (Llama.serve): the counter id of each row, drawn by the slot tick (default: the row).  Returns the ids of
-        every row, (B, 1) int64."""
+        `req` (Llama.serve): the counter id of each row, drawn by the slot tick (default: the row).  `pen`
+        (llm/penalties.Rows): the statement of the penalties on the host counts.  Returns the ids of every row, (B, 1)
+        int64."""
         from .. import hipnp as hp, _lib
         L, st = _lib.lib(), hp.stream()
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
@@ -1043,6 +1159,9 @@ class Llama(nn.Module):
         L.call("pdn_rmsnorm_fwd_f32", x, self.norm.weight.data._ptr, h, None, B, D, self.norm.eps, st)
         gemv(h, D, self.lm_head.weight, logits, V,
              bias=self.lm_head.bias.data._ptr if getattr(self.lm_head, "bias", None) is not None else None)
+        if pen is not None:
+            pen.feed(idc.get(), pos)
+            ws["logits"][...] = pen.apply(ws["logits"].get())
         if sampling is None:
             return ws["logits"].argmax(-1, keepdims=True)
         out = hp.empty((B, 1), np.int64)              # (counter (pos[b], b): the per-row tick on scratch copies)
@@ -1058,7 +1177,7 @@ class Llama(nn.Module):
 
     # -- continuous batching (serve): a finished row takes the next waiting request -------------------------------
     def serve(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
-              prefill_chunk=None):
+              prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
         """Continuous batching: N requests (`prompts`, N may exceed max_batch_size) through `slots` decode rows
         (default min(N, max_batch_size)).  A row frees when its request yields a stop id or uses up its budget
         (`max_new_tokens`: one int, or one per request; 0 = the request yields nothing and never takes a row).  Before
@@ -1072,8 +1191,12 @@ class Llama(nn.Module):
         `prefill_chunk` = C (chunked prefill, the schedule of llm/chunked.py): no prompt pass stalls the other rows;
         every step feeds at most C prompt tokens in total to the rows still prefilling, in request order, and a row yields
         -1 until the step that feeds its last prompt token, which yields its first token.  The tokens of each request are
-        those of `serve`; only the step at which they appear changes.  slots + C <= 256."""
+        those of `serve`; only the step at which they appear changes.  slots + C <= 256.
+        `repetition_penalty` / `presence_penalty` / `frequency_penalty` (llm/penalties.py): one set of values for every
+        request; each request has its own prompt set and counts -- a row that takes a request starts from its prompt and
+        zero counts -- so the promise above holds with penalties too."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
+        penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty)
         V = self.vocab_size
         rows = [np.asarray(p.numpy() if isinstance(p, Tensor) else p).reshape(-1) for p in prompts]
         if not rows:
@@ -1109,13 +1232,15 @@ class Llama(nn.Module):
         sampling = (temperature, top_k, top_p, seed) if temperature > 0 else None
         C = chunked.check_chunk(prefill_chunk, slots)
         if C is not None:
-            return self._serve_chunked([p.astype(np.int64) for p in rows], budgets, int(slots), C, sampling, stops)
-        return self._serve([p.astype(np.int64) for p in rows], budgets, int(slots), sampling, stops)
+            return self._serve_chunked([p.astype(np.int64) for p in rows], budgets, int(slots), C, sampling, stops,
+                                       penalty)
+        return self._serve([p.astype(np.int64) for p in rows], budgets, int(slots), sampling, stops, penalty)
 
     def serve_all(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
-                  prefill_chunk=None):
+                  prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
         """`serve` run to the end: a list of N int64 arrays, request r's generated tokens in order."""
-        it = self.serve(prompts, max_new_tokens, slots, temperature, top_k, top_p, seed, stop_ids, prefill_chunk)
+        it = self.serve(prompts, max_new_tokens, slots, temperature, top_k, top_p, seed, stop_ids, prefill_chunk,
+                        repetition_penalty, presence_penalty, frequency_penalty)
         out = [[] for _ in range(len(prompts))]
         for reqs, toks in it:
             for r, t in zip(reqs, toks):
@@ -1123,7 +1248,7 @@ class Llama(nn.Module):
                     out[r].append(int(t))
         return [np.array(o, np.int64) for o in out]
 
-    def _serve(self, rows, budgets, S, sampling, stops):
+    def _serve(self, rows, budgets, S, sampling, stops, penalty=None):
         """The scheduler of `serve`.  Per step: the rows holding a request decode one token, then the rows freed by the
         previous step take the waiting requests in order through one prompt pass (`_serve_prefill`), then the step is
         yielded.  The host keeps, per row, the request, the position of its next decode step, the tokens it may still
@@ -1138,7 +1263,8 @@ class Llama(nn.Module):
         dev = self.tok_embedding.weight.device
         hip = (Llama.fast_decode and dev.is_hip and not self._train
                and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
-        st = self._serve_begin(S, sampling, stops) if hip else None      # None: the plan refuses -> generic HIP step
+        st = self._serve_begin(S, sampling, stops, penalty) if hip else None   # None: the plan refuses -> generic HIP step
+        pen = None if penalty is None or st is not None else pen_np.Rows(S, self.vocab_size, penalty)   # (host counts)
         q = 0
         try:
             while True:
@@ -1163,13 +1289,17 @@ class Llama(nn.Module):
                     ids, rq = last.reshape(S, 1), np.maximum(req, 0)
                     if hip:
                         from .. import hipnp as hp
-                        out = self._decode_step_generic_rows(hp.asarray(ids), p.astype(np.int32), sampling, rq).get()
+                        out = self._decode_step_generic_rows(hp.asarray(ids), p.astype(np.int32), sampling, rq,
+                                                             pen=pen).get()
                     else:
-                        out = self._step_module_rows(Tensor(ids, dtype=np.int64, device=dev), p, sampling, rq).numpy()
+                        out = self._step_module_rows(Tensor(ids, dtype=np.int64, device=dev), p, sampling, rq,
+                                                     pen=pen).numpy()
                     toks[run] = out.reshape(-1)[run]
                 shown = req.copy()
                 if adm.size:
-                    first = self._serve_prefill([rows[r] for r in new], adm, new, sampling)
+                    first = self._serve_prefill([rows[r] for r in new], adm, new, sampling, penalty)
+                    if pen is not None:
+                        pen.reset(adm, [rows[r] for r in new])
                     if st is not None and st["pending"]:
                         d = self._serve_read(st)                 # (stream order: that step ran before the prefill)
                         toks[run] = d[run]
@@ -1185,6 +1315,8 @@ class Llama(nn.Module):
                 req[done], pos[done], left[done] = -1, -1, 0
                 if st is not None and adm.size:
                     self._serve_write(st, req, pos, left, last)
+                    if st["pen"]:                                # (no step queued: after every step of the old request)
+                        self._pen_reset(st, adm, [rows[r] for r in new], penalty)
                     if (req >= 0).any():
                         self._serve_ahead(st, int(np.where(req >= 0, pos, -1).max()))
                 yield shown, toks
@@ -1194,14 +1326,17 @@ class Llama(nn.Module):
                 hp.synchronize()                                 # (queued steps store into this run's history)
                 st["pending"] = 0
 
-    def _serve_prefill(self, prompts, rows, reqs, sampling):
+    def _serve_prefill(self, prompts, rows, reqs, sampling, penalty=None):
         """Admit requests `reqs` (their prompts) into decode rows `rows`: the prompts right-padded to the longest run as one
         batched causal pass from position 0 into a staging cache (the layers' caches point at it meanwhile), then
         pdn_kv_store_slots_f32 puts prompt i's keys / values, positions [0, len_i), into cache row rows[i] and zeroes
         position len_i there -- the slot a decode step attends to but never writes (`generate`'s step at position p feeds
         the token of position p - 1), which in a fresh cache holds zeros.  No pad position and no other row is written.
-        Returns the first token of each request (counter (len_i, reqs[i]) when sampled), host int64."""
+        `penalty`: the logits penalised for each prompt first.  Returns the first token of each request (counter (len_i,
+        reqs[i]) when sampled), host int64."""
         logits = self._prefill_rows(prompts, rows)
+        if penalty is not None:
+            logits = self._penalize_prompt(logits, prompts, penalty)
         lens = np.array([p.size for p in prompts], np.int64)
         first = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, lens, *sampling, rows=reqs)
         return np.asarray(first.numpy()).reshape(-1).astype(np.int64)
@@ -1254,9 +1389,9 @@ class Llama(nn.Module):
 
     # (graph path of `serve`: the served plan holds the rows' state on the device; steps are issued, queued ahead and
     #  read in order, through a ring of `ring` history slots)
-    def _serve_begin(self, S, sampling, stops):
+    def _serve_begin(self, S, sampling, stops, penalty=None):
         from .. import hipnp as hp
-        st = self._decode_plan(S, sampling is not None, ragged=True, serve=True)
+        st = self._decode_plan(S, sampling is not None, ragged=True, serve=True, penalty=penalty is not None)
         if st is None:
             return None
         if st["pending"]:
@@ -1273,6 +1408,8 @@ class Llama(nn.Module):
         if sampling is not None and st["params_val"] != sampling:
             st["params"][...] = params_bytes(*sampling)
         st["params_val"] = sampling
+        if penalty is not None:                                  # (every row is reset when it takes a request)
+            self._pen_reset(st, [], [], penalty)
         st["pending"], st["read"] = 0, 0
         return st
 
@@ -1286,7 +1423,8 @@ class Llama(nn.Module):
         ns = self._decode_ns(st, top)
         g = False if st["nograph"] else st["graphs"].get((ns, st["sampling"]))
         if g is None and Llama.graph_decode:
-            keep = {n: st[n].copy() for n in ("ids", "pos", "step", "left")}
+            # (penalty plans: the capture's runs count their fed tokens too -- the counts are put back as well)
+            keep = {n: st[n].copy() for n in ("ids", "pos", "step", "left") + (("counts",) if st["pen"] else ())}
             scratch = hp.Mailbox(st["ring"], (st["B"], 1), unset=st["hist"].unset)
             st["hist_ptr"][...] = np.int64(scratch._ptr)
             try:
@@ -1343,7 +1481,7 @@ class Llama(nn.Module):
         self._decode_gather(st)
 
     # -- chunked prefill (serve(prefill_chunk=C)): prompts fed C tokens per step (statement: llm/chunked.py) -----------
-    def _serve_chunked(self, rows, budgets, S, C, sampling, stops):
+    def _serve_chunked(self, rows, budgets, S, C, sampling, stops, penalty=None):
         """The scheduler of `serve` with a chunk: llm/chunked.Schedule decides, per step, which rows decode and which
         prompt tokens are fed.  Graph path (`_mixed_begin`): a step with prompt tokens runs the mixed step (the decode
         rows and the chunks as query rows of the wide product, csrc/extend.hip), a step without runs the served step.
@@ -1354,11 +1492,17 @@ class Llama(nn.Module):
         dev = self.tok_embedding.weight.device
         hip = (Llama.fast_decode and dev.is_hip and not self._train
                and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
-        st = self._mixed_begin(S, C, sampling, stops) if hip else None
+        st = self._mixed_begin(S, C, sampling, stops, penalty) if hip else None
+        pen = None if penalty is None or st is not None else pen_np.Rows(S, self.vocab_size, penalty)   # (host counts)
         dirty = False                                           # (the device's row state differs from the host's)
         try:
             while True:
-                sch.admit()
+                adm, new = sch.admit()
+                if adm.size and penalty is not None:            # (stream order: after the steps of the rows' old requests)
+                    if st is not None:
+                        self._pen_reset(st, adm, [rows[r] for r in new], penalty)
+                    else:
+                        pen.reset(adm, [rows[r] for r in new])
                 if not sch.busy():
                     return
                 n, dec, comp = sch.plan()
@@ -1393,13 +1537,15 @@ class Llama(nn.Module):
                         ids = sch.last.reshape(S, 1)
                         if hip:
                             from .. import hipnp as hp
-                            out = self._decode_step_generic_rows(hp.asarray(ids), p.astype(np.int32), sampling, rq).get()
+                            out = self._decode_step_generic_rows(hp.asarray(ids), p.astype(np.int32), sampling, rq,
+                                                                 pen=pen).get()
                         else:
-                            out = self._step_module_rows(Tensor(ids, dtype=np.int64, device=dev), p, sampling, rq).numpy()
+                            out = self._step_module_rows(Tensor(ids, dtype=np.int64, device=dev), p, sampling, rq,
+                                                         pen=pen).numpy()
                         toks[dec] = out.reshape(-1)[dec]
                     if comp.any():
                         b = np.flatnonzero(comp)
-                        toks[b] = self._serve_prefill([rows[r] for r in sch.req[b]], b, sch.req[b], sampling)
+                        toks[b] = self._serve_prefill([rows[r] for r in sch.req[b]], b, sch.req[b], sampling, penalty)
                 shown = sch.finish(n, toks, stops)
                 yield shown, toks
         finally:
@@ -1416,12 +1562,12 @@ class Llama(nn.Module):
         return bool(Llama.wide_decode and S + C <= 256 and all(_lib.provides(n) for n in _MIXED_ENTRIES)
                     and L.query("pdn_decode_mixed_supported", D, H, D // H, F, V, cache_len))
 
-    def _mixed_begin(self, S, C, sampling, stops):
+    def _mixed_begin(self, S, C, sampling, stops, penalty=None):
         """The served plan (`_serve_begin`) plus the buffers of the mixed step (`mixed`), or None when either refuses."""
         from .. import hipnp as hp, _lib
         if not self._mixed_ok(S, C):
             return None
-        st = self._serve_begin(S, sampling, stops)
+        st = self._serve_begin(S, sampling, stops, penalty)
         if st is None or st["ns"] > 8:
             return None
         M = st.get("mixed")
@@ -1484,7 +1630,7 @@ class Llama(nn.Module):
         gk = (ns, st["sampling"], "mixed", st["mixed"]["C"])
         g = False if st["nograph"] else st["graphs"].get(gk)
         if g is None and Llama.graph_decode:
-            keep = {n: st[n].copy() for n in ("ids", "pos", "step", "left")}
+            keep = {n: st[n].copy() for n in ("ids", "pos", "step", "left") + (("counts",) if st["pen"] else ())}
             scratch = hp.Mailbox(st["ring"], (st["B"], 1), unset=st["hist"].unset)
             st["hist_ptr"][...] = np.int64(scratch._ptr)
             try:
@@ -1525,19 +1671,24 @@ class Llama(nn.Module):
         L.call("pdn_embedding_gather_f32", x, R, D, D, M["emit"]._ptr, S, xe, hp.err_flag_ptr(), s)
         head = self.lm_head
         bias = head.bias.data._ptr if getattr(head, "bias", None) is not None else None
-        full = st["sampling"]
+        full = st["sampling"] or st["pen"]
         cv, ci = (None, None) if full else (M["cand_v"]._ptr, M["cand_i"]._ptr)
         L.call("pdn_decode_wide_gemm_f32", xe, D, 1, self.norm.weight.data._ptr, self.norm.eps, 0, 0,
                head.weight.data._ptr, V, V, 0, bias, st["logits"]._ptr, V, 0 if full else 2, cv, ci, st["pos"]._ptr, S,
                D, V, work, s)
+        # (penalty plans: a row completing its prompt here is at position len = start and counts nothing; greedy: the
+        #  plan's candidates are those of the penalty kernel)
+        self._pen_step(st, s)
+        cands = st if st["pen"] else M
         cnt = (st["pos"]._ptr, st["step"]._ptr, M["arrive"]._ptr)
         out = (st["hist_ptr"]._ptr, emb._ptr, emb._strides[0], D, st["x"]._ptr, s)
-        if full:
+        if st["sampling"]:
             L.call("pdn_decode_wide_sample_tick_slots_f32", st["logits"]._ptr, V, S, V, st["params"]._ptr,
                    st["ids"]._ptr, *cnt, st["req"]._ptr, st["left"]._ptr, st["ring"], st["stop"]._ptr, *out)
         else:
-            L.call("pdn_decode_wide_pick_tick_slots_f32", M["cand_v"]._ptr, M["cand_i"]._ptr, S, M["cand_v"].shape[1],
-                   st["ids"]._ptr, *cnt, st["req"]._ptr, st["left"]._ptr, st["ring"], st["stop"]._ptr, *out)
+            L.call("pdn_decode_wide_pick_tick_slots_f32", cands["cand_v"]._ptr, cands["cand_i"]._ptr, S,
+                   cands["cand_v"].shape[1], st["ids"]._ptr, *cnt, st["req"]._ptr, st["left"]._ptr, st["ring"],
+                   st["stop"]._ptr, *out)
 
     def _mixed_layers(self, M, packs, n_runs, max_run, R, ns, s):
         """The layers of the mixed step on R query rows (M["x"] in, M["x"] out): q | k | v with RMSNorm in the load, the KV
