@@ -189,7 +189,8 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  32 beam search (csrc/beam.hip): pdn_beam_topk_rows_f32, pdn_beam_select_f32, pdn_kv_reorder_rows_f32
  *  33 chunked prefill (csrc/extend.hip): pdn_kv_append_rows_f32, pdn_decode_extend_attention_f32
  *  34 speculative decoding (csrc/speculative.hip): pdn_spec_draft_rows and the two pdn_spec_verify_*_tick_f32 entries
- *  35 decode penalties (csrc/penalty.hip): pdn_penalty_reset, pdn_penalty_step_f32, pdn_penalty_rows_f32 */
+ *  35 decode penalties (csrc/penalty.hip): pdn_penalty_reset, pdn_penalty_step_f32, pdn_penalty_rows_f32
+ *  36 token log-probabilities (csrc/logprobs.hip): pdn_logprobs_rows_f32, pdn_logprobs_tick_f32 */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -796,6 +797,28 @@ int pdn_penalty_step_f32(float* logits, int64_t row_stride, int B, int V, const 
 int pdn_penalty_rows_f32(float* logits, int64_t row_stride, int B, int V, const pdn_penalty_params* params,
                          const int* counts, const unsigned* seen, const int* pos, float* cand_v, int* cand_i,
                          void* stream);
+/* Token log-probabilities (csrc/logprobs.hip; Llama.generate / generate_ragged / serve with logprobs=n and Llama.score,
+ * the NumPy statement is pydynet_amd/llm/logprobs.py).  Row b's fp32 logits z: logp = float(z - lse), lse =
+ * log(sum exp z) in double and fixed order; the n (<= 20) best tokens by (logp desc, id asc); a row whose token is < 0
+ * yields token logp nan, ids -1, logps nan.  Per call: two launches of one workgroup per (2048-token chunk, row) -- the
+ * second one workgroup per row when n = 0 -- and for n > 0 a third, one wave per row, that merges the chunks' lists (no
+ * fences, no atomics: two runs give the same bits).  chunks(V) * n <= 4096.
+ *   pdn_logprobs_chunks      the vocabulary chunks of a row, ceil(V / 2048).
+ *   pdn_logprobs_work_bytes  the workspace of `rows` rows (scratch between the launches of one call).
+ *   pdn_logprobs_rows_f32    the standalone form: tokens (rows,) int64 -> token_lp (rows,) float, top_ids (rows, n)
+ *                            int64, top_lp (rows, n) float (both may be null when n == 0).
+ *   pdn_logprobs_tick_f32    the form appended after a decode tick: step = *counter - 1 (the counter the tick advanced),
+ *                            row b's token = (*history)[slot * B + b], slot = step (hist_ring 0) or step % hist_ring;
+ *                            row b's record, 1 + 2n int64 words (the token's logp, n ids, n logps; float bits
+ *                            zero-extended), goes to (*records)[((step % ring) * B + b) * (1 + 2n)] with system-scope
+ *                            stores (mapped host memory the host polls). */
+int pdn_logprobs_chunks(int V);
+int64_t pdn_logprobs_work_bytes(int rows, int V, int n);
+int pdn_logprobs_rows_f32(const float* logits, int64_t row_stride, int rows, int V, int n, const int64_t* tokens,
+                          float* token_lp, int64_t* top_ids, float* top_lp, void* work, void* stream);
+int pdn_logprobs_tick_f32(const float* logits, int64_t row_stride, int B, int V, int n, int64_t* const* history,
+                          int hist_ring, const int* counter, int64_t* const* records, int ring, void* work,
+                          void* stream);
 /* shapes the resident (K / V of a head chunk-wise in LDS) kernels above take: head_dim 48 or 64, L a multiple of 32 up
  * to 1024 -- sequences beyond 256 pass through LDS in 256-row chunks (forward: one online rescale per chunk) -- and
  * (round 6, csrc/attention_hd128.hip) head_dim 128 at ANY length 1 .. 1024, no RoPE inside: the shape of

@@ -58,7 +58,8 @@ enum {
   PDN_CNT_EXTEND = 33,            // chunked prefill (csrc/extend.hip): the KV append and the multi-query extend attention
   PDN_CNT_SPECULATE = 34,         // speculative decoding (csrc/speculative.hip): the draft kernel and the verify ticks
   PDN_CNT_PENALTY = 35,           // decode penalties (csrc/penalty.hip): the reset and the two apply entries
-  PDN_CNT_SLOTS = 36
+  PDN_CNT_LOGPROBS = 36,          // token log-probabilities (csrc/logprobs.hip): the rows entry and the tick form
+  PDN_CNT_SLOTS = 37
 };
 void pdn_count(int slot);
 

@@ -22,6 +22,7 @@ from ..core import Tensor, fused
 from ..special import zeros
 from . import beam as beam_np
 from . import chunked
+from . import logprobs as lp_np
 from . import penalties as pen_np
 from . import speculative as spec_np
 from .sampling import (check_args as check_sampling_args, params_bytes, params_buffer, sample_next,
@@ -38,6 +39,8 @@ _MIXED_ENTRIES = _WIDE_ENTRIES + ("pdn_decode_mixed_supported", "pdn_kv_append_r
 _SPEC_ENTRIES = _MIXED_ENTRIES + ("pdn_spec_draft_rows", "pdn_spec_verify_pick_tick_f32", "pdn_spec_verify_sample_tick_f32")
 # the entry points of the penalties (csrc/penalty.hip): without them every path applies the statement of llm/penalties.py
 _PEN_ENTRIES = ("pdn_penalty_chunks", "pdn_penalty_reset", "pdn_penalty_step_f32", "pdn_penalty_rows_f32")
+# ring slots of the log-probability records of a decode plan (csrc/logprobs.hip): more than the steps ever in flight
+_LP_RING = 8
 
 
 def compute_cos_sin_cache(head_dim: int, max_seq_len: int, base: int = 10000, dtype=None):
@@ -266,19 +269,22 @@ class Llama(nn.Module):
     fast_decode = True      # class switch: False keeps every decode step on the generic tape-node path
 
     def generate(self, input_ids, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0,
-                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=None):
         """Yield the next ids, (B, 1) int64, for positions L .. max_new_tokens - 1.  temperature 0 (the default): the
         greedy pick of the reference (model.py:258-269); temperature > 0: drawn with top-k / top-p and the seeded
         counter-based generator of llm/sampling.py (token at position t of row b: Philox counter (t, b)).
         `repetition_penalty` / `presence_penalty` / `frequency_penalty` (defaults: off): the penalties of llm/penalties.py
-        on each row's logits -- its prompt's tokens and the tokens it generated -- before the pick or the draw.  The
-        arguments are checked here, before anything runs."""
+        on each row's logits -- its prompt's tokens and the tokens it generated -- before the pick or the draw.
+        `logprobs` = n (an int in [0, 20]; None: off): every step yields (ids, lp) instead, lp an llm/logprobs.Logprobs
+        of the row the pick or the draw read -- token (B, 1), top_ids (B, n), top_logprobs (B, n).  The arguments are
+        checked here, before anything runs."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
         penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty)
+        n_lp = lp_np.check_n(logprobs)
         return self._generate(input_ids, max_new_tokens, (temperature, top_k, top_p, seed) if temperature > 0 else None,
-                              penalty)
+                              penalty, n_lp)
 
-    def _generate(self, input_ids, max_new_tokens, sampling, penalty=None):
+    def _generate(self, input_ids, max_new_tokens, sampling, penalty=None, n_lp=None):
         B, L = input_ids.shape
         next_id = None
         pen = None
@@ -291,18 +297,48 @@ class Llama(nn.Module):
                 if pen is not None:
                     logits = self._penalize_prompt(logits, pen.prompts, penalty)
                 next_id = logits.argmax(-1, True) if sampling is None else sample_next(logits, pos, *sampling)
+                lp = None if n_lp is None else self._logprobs_rows(logits, next_id.numpy(), n_lp)
             elif (Llama.fast_decode and next_id.device.is_hip and not self._train
                   and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0):
                 # (`more`: another token will be asked for -- the step after this one may be queued ahead)
-                next_id = Tensor(self._decode_step_hip(next_id.data, pos, more=pos + 1 < max_new_tokens,
-                                                       sampling=sampling, pen=pen),
-                                 dtype=np.int64, device=next_id.device, copy=False)
+                out = self._decode_step_hip(next_id.data, pos, more=pos + 1 < max_new_tokens, sampling=sampling,
+                                            pen=pen, n_lp=n_lp)
+                out, lp = out if n_lp is not None else (out, None)
+                next_id = Tensor(out, dtype=np.int64, device=next_id.device, copy=False)
             else:
                 logits = self(next_id, pos)[:, -1, :]
                 if pen is not None:
                     logits = self._penalize_step(logits, pen, next_id.numpy(), np.full(B, pos))
                 next_id = logits.argmax(-1, True) if sampling is None else sample_next(logits, pos, *sampling)
-            yield next_id
+                lp = None if n_lp is None else self._logprobs_rows(logits, next_id.numpy(), n_lp)
+            yield next_id if n_lp is None else (next_id, lp_np.as_step(lp))
+
+    def _logprobs_rows(self, logits, tokens, n):
+        """llm/logprobs.py on logit rows (R, V) (a Tensor or a device array) and the tokens (R,) they yielded (< 0: none).
+        On a HIP device: pdn_logprobs_rows_f32 (csrc/logprobs.hip); on `cpu` the statement.  Returns Logprobs of host
+        arrays: token (R,), top_ids / top_logprobs (R, n)."""
+        from .. import _lib
+        x = logits.data if isinstance(logits, Tensor) else logits
+        tokens = np.asarray(tokens.get() if hasattr(tokens, "get") else tokens, np.int64).reshape(-1)
+        if not getattr(getattr(logits, "device", None), "is_hip", False) and isinstance(x, np.ndarray):
+            return lp_np.rows(x.reshape(tokens.size, -1), tokens, n)
+        from .. import hipnp as hp
+        V = self.vocab_size
+        x = x.reshape(tokens.size, V) if len(x.shape) != 2 else x
+        if x.dtype != np.float32 or x._strides[1] != 1 or x._strides[0] < V:
+            x = x.astype(np.float32).copy() if x.dtype != np.float32 else x.copy()
+        R = tokens.size
+        tok, ids, top = (hp.empty((R,), np.float32), hp.empty((R, max(n, 1)), np.int64),
+                         hp.empty((R, max(n, 1)), np.float32))
+        step = 65535                                              # (rows per call: the grid's second dimension)
+        L = _lib.lib()
+        work = hp.zeros((L.query("pdn_logprobs_work_bytes", min(R, step), V, n) // 8 + 2,), np.int64)
+        for r0 in range(0, R, step):
+            r1 = min(R, r0 + step)
+            t = hp.asarray(tokens[r0:r1])
+            L.call("pdn_logprobs_rows_f32", x._ptr + r0 * x._strides[0] * 4, x._strides[0], r1 - r0, V, n, t._ptr,
+                   tok._ptr + r0 * 4, ids._ptr + r0 * max(n, 1) * 8, top._ptr + r0 * max(n, 1) * 4, work._ptr, hp.stream())
+        return lp_np.Logprobs(tok.get(), ids.get()[:, :n], top.get()[:, :n])
 
     def _penalize_prompt(self, logits, prompts, penalty):
         """The logits (A, V) of a prompt pass penalised for prompts[i] (no generated token yet: only the repetition penalty
@@ -329,8 +365,40 @@ class Llama(nn.Module):
         pen.feed(ids, pos)
         return Tensor(pen.apply(np.asarray(logits.numpy(), np.float32)), dtype=np.float32, device=logits.device)
 
+    def score(self, input_ids, logprobs=0):
+        """log p(x_t | x_<t) of given sequences: input_ids (B, L) int, L >= 2.  Returns llm/logprobs.Logprobs for
+        positions 1 .. L-1: token (B, L-1), top_ids / top_logprobs (B, L-1, n) for `logprobs` = n in [0, 20].  One forward
+        pass (`forward_logits`) in training mode under no_grad -- training mode writes no KV cache, so neither the cache
+        nor max_batch_size bounds it -- then the module's mode is restored.  Arguments are checked before anything runs.
+        Against the values generation reports: the first generated token (the prompt's causal pass) agrees; later ones
+        need not, since a decode step of `generate` at position p feeds the token of position p - 1 (as the reference
+        does) and attends to a never-written cache slot, so it is not a causal pass over prompt + generated tokens."""
+        from ..autograd import no_grad
+        n = lp_np.check_n(logprobs, allow_none=False)
+        ids = np.asarray(input_ids.numpy() if isinstance(input_ids, Tensor) else input_ids)
+        if ids.ndim != 2 or ids.shape[1] < 2:
+            raise ValueError(f"score takes (B, L) token ids with L >= 2, got shape {ids.shape}")
+        if ids.size and (ids.dtype.kind not in "iu" or ids.min() < 0 or ids.max() >= self.vocab_size):
+            raise ValueError(f"token ids must be integers in [0, {self.vocab_size})")
+        B, L = ids.shape
+        if L - 1 > self.freqs_cos.shape[0]:
+            raise ValueError(f"score: {L - 1} positions exceed the RoPE table's {self.freqs_cos.shape[0]} rows")
+        ids = ids.astype(np.int64)
+        mode = self._train
+        dev = self.tok_embedding.weight.device
+        try:
+            self.train(True)
+            with no_grad():
+                logits = self.forward_logits(Tensor(ids[:, :-1], dtype=np.int64, device=dev), 0)
+                lp = self._logprobs_rows(logits.reshape(B * (L - 1), self.vocab_size), ids[:, 1:].reshape(-1), n)
+        finally:
+            self.train(mode)
+        return lp_np.Logprobs(lp.token.reshape(B, L - 1), lp.top_ids.reshape(B, L - 1, n),
+                              lp.top_logprobs.reshape(B, L - 1, n))
+
     def generate_ragged(self, prompts, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
-                        speculate=0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+                        speculate=0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
+                        logprobs=None):
         """Generation for B prompts of different lengths, every row at its own position.  Yields a (B, 1) int64 Tensor
         per step: step i holds, for row b, the token at position len_b + i.  `max_new_tokens` is the number of NEW tokens
         per row -- `generate`'s second argument is an end position instead: for equal lengths L,
@@ -346,6 +414,8 @@ class Llama(nn.Module):
         run are in `last_speculation` (None after a call with speculate=0, which runs the plain decode).
         `repetition_penalty` / `presence_penalty` / `frequency_penalty`: as in `generate` (llm/penalties.py), row b's
         prompt and generated tokens; not with speculate > 0.
+        `logprobs` = n: as in `generate`, every step yields (ids, lp); a row that yields -1 has nan / -1 / nan.  Not with
+        speculate > 0.
         Every argument is checked here (ValueError), before anything runs."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
         V = self.vocab_size
@@ -358,6 +428,9 @@ class Llama(nn.Module):
             raise ValueError("generate_ragged needs at least one prompt")
         k = spec_np.check_speculate(speculate, len(rows))
         penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty, k)
+        n_lp = lp_np.check_n(logprobs)
+        if n_lp is not None and k:
+            raise ValueError("logprobs are not available with speculate > 0")
         if len(rows) > cache.shape[0]:
             raise ValueError(f"batch {len(rows)} exceeds the KV cache's max_batch_size {cache.shape[0]}")
         limit = min(cache.shape[1], self.freqs_cos.shape[0])     # positions the cache / RoPE table hold
@@ -377,19 +450,22 @@ class Llama(nn.Module):
         self.last_speculation = None if k == 0 else spec_np.counts()
         if k:
             return self._speculate([r.astype(np.int64) for r in rows], max_new_tokens, k, sampling, stops)
-        return self._generate_ragged([r.astype(np.int64) for r in rows], max_new_tokens, sampling, stops, penalty)
+        return self._generate_ragged([r.astype(np.int64) for r in rows], max_new_tokens, sampling, stops, penalty,
+                                     n_lp)
 
-    def _generate_ragged(self, rows, n, sampling, stops, penalty=None):
+    def _generate_ragged(self, rows, n, sampling, stops, penalty=None, n_lp=None):
         B = len(rows)
         lens = np.array([r.size for r in rows], np.int64)
         if n == 0:
             return
         pen = None if penalty is None else pen_np.Rows(B, self.vocab_size, penalty, rows)
-        nxt = self._prompt_rows(rows, lens, sampling, penalty)
+        nxt = self._prompt_rows(rows, lens, sampling, penalty, n_lp)
+        if n_lp is not None:
+            nxt, lp = nxt
         live = np.ones(B, bool)
         if stops.size:
             live = ~np.isin(nxt.numpy().reshape(-1), stops)
-        yield nxt
+        yield nxt if n_lp is None else (nxt, lp_np.as_step(lp))
         fast = (Llama.fast_decode and nxt.device.is_hip and not self._train
                 and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
         if fast:
@@ -399,7 +475,7 @@ class Llama(nn.Module):
             # tokens by STEP: slot i holds step i of every row (-1 for a stopped row), so "not written yet" is its own
             # value; two slots beyond the last step for the runs of a graph capture
             run = {"lens": lens, "live": live, "sampling": sampling, "stop_mask": mask.view(np.int32), "pen": pen,
-                   "hist": hp.Mailbox(n + 2, (B, 1), unset=np.iinfo(np.int64).min)}
+                   "hist": hp.Mailbox(n + 2, (B, 1), unset=np.iinfo(np.int64).min), "lp": n_lp}
         ids = nxt.data
         for i in range(1, n):
             if not live.any():
@@ -407,22 +483,24 @@ class Llama(nn.Module):
             if fast:
                 run["live"] = live
                 ids = self._decode_step_rows(ids, run, i, more=i + 1 < n)
+                ids, lp = ids if n_lp is not None else (ids, None)
                 nxt = Tensor(ids, dtype=np.int64, device=nxt.device, copy=False)
             else:
-                nxt = self._step_module_rows(nxt, np.where(live, lens + i, -1), sampling, pen=pen)
+                nxt = self._step_module_rows(nxt, np.where(live, lens + i, -1), sampling, pen=pen, n_lp=n_lp)
+                nxt, lp = nxt if n_lp is not None else (nxt, None)
             if stops.size:
-                yield nxt
+                yield nxt if n_lp is None else (nxt, lp_np.as_step(lp))
                 tok = nxt.numpy().reshape(-1)                    # (fast path: a poll of the mapped history slot)
                 live = live & (tok >= 0) & ~np.isin(tok, stops)
                 continue
-            yield nxt
+            yield nxt if n_lp is None else (nxt, lp_np.as_step(lp))
 
-    def _prompt_rows(self, rows, lens, sampling, penalty=None):
+    def _prompt_rows(self, rows, lens, sampling, penalty=None, n_lp=None):
         """The prompt pass of a ragged generation: the prompts right-padded to the longest and run as one batched
         causal pass from position 0 (no real token attends to a pad after it); each row's logits at its last real token,
         gathered before lm_head.  The cache slots the pads wrote, [len_b, L_max) of row b, are put back as they were: a
         row's cache is written at its own positions only.  `penalty`: the logits penalised for each row's prompt first.
-        Returns the first token of every row, (B, 1) int64."""
+        Returns the first token of every row, (B, 1) int64 (`n_lp`: and their Logprobs)."""
         B, Lm, lo = len(rows), int(lens.max()), int(lens.min())
         ids = np.zeros((B, Lm), np.int64)
         for b, r in enumerate(rows):
@@ -438,25 +516,29 @@ class Llama(nn.Module):
                 c.data[int(b), int(lens[b]):Lm] = keep[int(b), int(lens[b]) - lo:]
         if penalty is not None:
             logits = self._penalize_prompt(logits, rows, penalty)
-        if sampling is None:
-            return logits.argmax(-1, True)
-        return sample_next_rows(logits, lens, *sampling)
+        nxt = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, lens, *sampling)
+        if n_lp is None:
+            return nxt
+        return nxt, self._logprobs_rows(logits, nxt.numpy(), n_lp)
 
-    def _step_module_rows(self, ids, pos, sampling, req=None, pen=None):
+    def _step_module_rows(self, ids, pos, sampling, req=None, pen=None, n_lp=None):
         """One ragged decode step on the tape-node operators (the `cpu` device, fast_decode = False, training mode,
         other dtypes): row b's token at position pos[b] (-1: a stopped row, which yields -1).  The NumPy statement of what
         the per-row kernels compute.  `req`: the counter id of each row (Llama.serve; default: the row).  `pen`
-        (llm/penalties.Rows): the fed tokens counted and the logits penalised before the pick."""
+        (llm/penalties.Rows): the fed tokens counted and the logits penalised before the pick.  `n_lp`: returns (ids,
+        Logprobs of the rows, none for rows at -1)."""
         p = np.maximum(pos, 0)
         logits = self._step_logits_rows(ids, pos)
         if pen is not None:
             logits = self._penalize_step(logits, pen, ids.numpy(), pos)
         nxt = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, p, *sampling, rows=req)
-        if pos.min() >= 0:
+        if pos.min() < 0:
+            out = nxt.numpy().reshape(-1, 1)
+            out[pos < 0] = -1
+            nxt = Tensor(out, dtype=np.int64, device=ids.device)
+        if n_lp is None:
             return nxt
-        out = nxt.numpy().reshape(-1, 1)
-        out[pos < 0] = -1
-        return Tensor(out, dtype=np.int64, device=ids.device)
+        return nxt, self._logprobs_rows(logits, nxt.numpy(), n_lp)
 
     def _step_logits_rows(self, ids, pos):
         """The logits (B, V) of `_step_module_rows`' step: row b fed ids[b] at position pos[b] (-1: stopped)."""
@@ -473,7 +555,7 @@ class Llama(nn.Module):
     fused_decode = 2        # class switch: launches per layer = 2 (q|k|v inside the attention kernel), 1 -> 3, 0 / False -> 5
     wide_decode = True      # class switch: 9 .. 256 rows on the wide step (csrc/decode_wide.hip); False -> the generic step
 
-    def _decode_plan(self, B, sampling=False, ragged=False, serve=False, beam=0, n_stops=0, penalty=False):
+    def _decode_plan(self, B, sampling=False, ragged=False, serve=False, beam=0, n_stops=0, penalty=False, n_lp=None):
         """Buffers and weight views of the graph-replayable decode step (csrc/decode.hip), or None when the
         model's shapes / layout are outside what those kernels take (then the generic launches below run).
         `sampling`: the step ends in the sample tick (csrc/sample.hip) instead of the greedy pick; its parameters live in
@@ -490,7 +572,10 @@ class Llama(nn.Module):
         `penalty` (generation with penalties, csrc/penalty.hip): the projection writes full logit rows, and
         pdn_penalty_step_f32 counts each row's fed token and penalises them before the tick; the rows' counts / prompt
         bits / prompt lengths live in the plan (`counts`, `seen`, `start`), the values in `pen_params`.  A greedy plan's
-        `cand_v` / `cand_i` then hold the candidates of that kernel.  None when the library lacks the entries."""
+        `cand_v` / `cand_i` then hold the candidates of that kernel.  None when the library lacks the entries.
+        `n_lp` (generation with logprobs=n, csrc/logprobs.hip): pdn_logprobs_tick_f32 after the tick reads the logit rows
+        (which every plan writes) and the token the tick stored, and writes each row's record into a ring of `_LP_RING`
+        slots of mapped host memory (`lp_box`, reached through the device pointer `lp_ptr`)."""
         from .. import hipnp as hp, _lib
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
         st = getattr(self, "_decode_st", None)
@@ -501,7 +586,7 @@ class Llama(nn.Module):
         wide = B > 8 and Llama.wide_decode and self._decode_wide_ok(B, cache_len)
         key = (B, hp._state["device"], int(Llama.fused_decode or 0), os.environ.get("PDN_DECODE_SPLITS", ""),
                cache_len, tuple(ptrs), bool(sampling), wide,   # (the addresses: no hash to collide)
-               (int(beam), int(n_stops), bool(penalty)), bool(ragged), bool(serve))
+               (int(beam), int(n_stops), bool(penalty)), bool(ragged), bool(serve)) + (() if n_lp is None else (int(n_lp),))
         if st is not None and st["key"] == key:
             return st if st["ok"] else None
         if st is not None:
@@ -528,7 +613,7 @@ class Llama(nn.Module):
             ok = ok and self.lm_head.weight.data.is_contiguous() and self.tok_embedding.weight.data.is_contiguous()
         st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged), "serve": bool(serve),
               "wide": wide, "rows": bool(ragged or wide), "beam": int(beam), "full": bool(sampling or beam or penalty),
-              "pen": bool(penalty)}
+              "pen": bool(penalty), "lp_n": n_lp}
         if ok:
             nblk = _lib.lib().query("pdn_decode_wide_blocks" if wide else "pdn_decode_gemv_blocks", V)
             # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
@@ -593,6 +678,9 @@ class Llama(nn.Module):
                 if not sampling:
                     nc = _lib.lib().query("pdn_penalty_chunks", V)
                     st.update(cand_v=hp.empty((B, nc), np.float32), cand_i=hp.empty((B, nc), np.int32))
+            if n_lp is not None:
+                st.update(lp_ptr=hp.zeros((1,), np.int64), lp_box=None, lp_work=hp.zeros(
+                    (_lib.lib().query("pdn_logprobs_work_bytes", B, V, n_lp) // 8 + 2,), np.int64))
             self._decode_ws = {"logits": st["logits"], "x": st["x"]}
         self._decode_st = st
         return st if ok else None
@@ -690,6 +778,7 @@ class Llama(nn.Module):
                    head.weight.data._ptr, V, V, 0, bias, logits, V, B, D, V, cv, ci, s)
             self._pen_step(st, s)
             self._decode_tick(st, s)
+            self._lp_tick(st, s)
             return
         for layer, (wqkv, wgu) in zip(self.layers, st["packs"]):
             a, f = layer.attention, layer.ffn
@@ -717,6 +806,7 @@ class Llama(nn.Module):
                bias, None, 0, logits, V, B, D, V, 0, 0, 0, cv, ci, s)
         self._pen_step(st, s)
         self._decode_tick(st, s)
+        self._lp_tick(st, s)
 
     def _decode_launches_wide(self, st, s):
         """The wide step (9 .. 256 rows, csrc/decode_wide.hip): 5 launches per layer -- q | k | v with RMSNorm in the load,
@@ -750,6 +840,45 @@ class Llama(nn.Module):
                V, V, 0, bias, logits, V, 0 if st["full"] else 2, cv, ci, pos, B, D, V, work, s)
         self._pen_step(st, s)
         self._decode_tick(st, s)
+        self._lp_tick(st, s)
+
+    def _lp_tick(self, st, s):
+        """Plans with logprobs: after the tick, each row's record (csrc/logprobs.hip) of the step the tick just finished
+        -- the counter it advanced, the token it stored in the history -- into the plan's record ring."""
+        if st.get("lp_n") is None:
+            return
+        from .. import _lib
+        V, B = self.vocab_size, st["B"]
+        cnt = st["step"] if st["rows"] else st["pos"]
+        _lib.lib().call("pdn_logprobs_tick_f32", st["logits"]._ptr, V, B, V, st["lp_n"], st["hist_ptr"]._ptr,
+                        st["ring"] if st["serve"] else 0, cnt._ptr, st["lp_ptr"]._ptr, _LP_RING, st["lp_work"]._ptr, s)
+
+    def _lp_begin(self, st):
+        """A fresh record ring for a new generation (stream ordered, as the history pointer)."""
+        from .. import hipnp as hp
+        if st.get("lp_n") is None:
+            return
+        st["lp_box"] = hp.Mailbox(_LP_RING, (st["B"], lp_np.record_words(st["lp_n"])), unset=lp_np.UNSET)
+        st["lp_ptr"][...] = np.int64(st["lp_box"]._ptr)
+
+    def _lp_scratch(self, st):
+        """During a graph capture the record pointer goes to a scratch ring (as the history's); returns the restore."""
+        from .. import hipnp as hp
+        if st.get("lp_n") is None:
+            return lambda: None
+        scratch = hp.Mailbox(_LP_RING, (st["B"], lp_np.record_words(st["lp_n"])), unset=lp_np.UNSET)
+        st["lp_ptr"][...] = np.int64(scratch._ptr)
+
+        def restore(keep=scratch):                         # (the scratch lives until the capture's runs are done)
+            st["lp_ptr"][...] = np.int64(st["lp_box"]._ptr)
+        return restore
+
+    def _lp_read(self, st, i):
+        """The records of step i (a poll of its ring slot, then marked unwritten again) as Logprobs."""
+        box, k = st["lp_box"], i % _LP_RING
+        rec = np.array(box.slot(k).get()).reshape(st["B"], -1)
+        box.host[k] = box.unset
+        return lp_np.from_records(rec, st["lp_n"])
 
     def _pen_step(self, st, s):
         """Penalty plans: between the vocabulary projection and the tick, each live row counts the token it is fed and its
@@ -836,14 +965,14 @@ class Llama(nn.Module):
         _lib.lib().call("pdn_embedding_gather_f32", emb._ptr, self.vocab_size, self.embed_dim, emb._strides[0],
                         st["ids"]._ptr, st["B"], st["x"]._ptr, hp.err_flag_ptr(), hp.stream())
 
-    def _decode_step_hip(self, ids, pos: int, more: bool = False, sampling=None, pen=None):
+    def _decode_step_hip(self, ids, pos: int, more: bool = False, sampling=None, pen=None, n_lp=None):
         """One decode step (one new token per sequence) without building tape nodes.  ids: (B, 1) int64
         device array; returns the next ids, (B, 1) int64.  The step is ONE hipGraph replay: norm + projection,
         RoPE + cache append, decode attention, SwiGLU + down projection and the greedy pick all read the position
         from device memory (csrc/decode.hip), so nothing changes between replays but the data.  `sampling`: None =
         greedy, else (temperature, top_k, top_p, seed) and the step ends in the sample tick (csrc/sample.hip).  `pen`
         (llm/penalties.Rows of this generation, or None): a penalty plan; its rows are reset from the prompts when a new
-        generation begins."""
+        generation begins.  `n_lp`: returns (ids, Logprobs of the step)."""
         from .. import hipnp as hp, _lib
         B = ids.shape[0]
         cache = self.layers[0].attention.cache_k
@@ -854,9 +983,9 @@ class Llama(nn.Module):
                              f"(max_seq_len {cache.shape[1]}, {self.freqs_cos.shape[0]} RoPE rows)")
         if B > cache.shape[0]:
             raise ValueError(f"batch {B} exceeds the KV cache's max_batch_size {cache.shape[0]}")
-        st = self._decode_plan(B, sampling is not None, penalty=pen is not None)
+        st = self._decode_plan(B, sampling is not None, penalty=pen is not None, n_lp=n_lp)
         if st is None:
-            return self._decode_step_generic(ids, pos, sampling, pen)
+            return self._decode_step_generic(ids, pos, sampling, pen, n_lp)
         ahead, st["ahead"] = st.get("ahead"), None
         if ahead is not None:
             if (ahead[0] == pos and ahead[1] is ids and st["params_val"] == sampling     # exactly this step, queued ahead
@@ -864,7 +993,7 @@ class Llama(nn.Module):
                 out = st["last_out"] = ahead[2]
                 if more and Llama.decode_ahead and pos + 1 < min(cache.shape[1], self.freqs_cos.shape[0]):
                     self._decode_ahead(st, pos + 1)
-                return out
+                return out if n_lp is None else (out, self._lp_read(st, pos))
             hp.synchronize()                                     # a different request: the queued step is void
             st["host_pos"] = st["last_out"] = None               # (position and ids are uploaded again below)
         if st["host_pos"] != pos:
@@ -875,6 +1004,7 @@ class Llama(nn.Module):
             # a new generation: its own history -- slots in mapped host memory the pick kernel stores into directly
             st["hist"] = hp.Mailbox(cache.shape[1], (B, 1))
             st["hist_ptr"][...] = np.int64(st["hist"]._ptr)
+            self._lp_begin(st)
         if st["params_val"] != sampling:
             if sampling is not None:
                 st["params"][...] = params_bytes(*sampling)      # (stream-ordered: earlier steps read the old values)
@@ -899,6 +1029,7 @@ class Llama(nn.Module):
             counts = st["counts"].copy() if st["pen"] else None  # (the capture's runs count their fed tokens too)
             scratch = hp.Mailbox(cache.shape[1], (B, 1))
             st["hist_ptr"][...] = np.int64(scratch._ptr)
+            lp_restore = self._lp_scratch(st)
             try:
                 g = hp.Graph()
                 g.capture(lambda: self._decode_launches(st, ns))
@@ -909,6 +1040,7 @@ class Llama(nn.Module):
                 st["nograph"], g = True, False
             hp.synchronize()                                     # the capture's runs are done with the scratch history
             st["hist_ptr"][...] = np.int64(st["hist"]._ptr)
+            lp_restore()
             st["pos"][...] = np.int32(pos)
             if st["rows"]:
                 st["step"][...] = np.int32(pos)
@@ -927,7 +1059,7 @@ class Llama(nn.Module):
         if (more and Llama.decode_ahead and (st["graphs"] or st["nograph"])
                 and pos + 1 < min(cache.shape[1], self.freqs_cos.shape[0])):
             self._decode_ahead(st, pos + 1)
-        return out
+        return out if n_lp is None else (out, self._lp_read(st, pos))
 
     def _decode_ahead(self, st, pos):
         """Queue the step of position `pos` right behind the one just issued -- its input ids are already where the
@@ -945,7 +1077,7 @@ class Llama(nn.Module):
         prev = st["last_out"]
         st["ahead"] = (pos, prev, st["hist"].slot(pos))
 
-    def _decode_step_generic(self, ids, pos: int, sampling=None, pen=None):
+    def _decode_step_generic(self, ids, pos: int, sampling=None, pen=None, n_lp=None):
         """The same step from the library's generic entry points (skinny `pdn_gemm_f32`, RMSNorm, RoPE, decode
         attention, SwiGLU), ~77 launches from preallocated buffers: for shapes / layouts the graph path does not take."""
         from .. import hipnp as hp, _lib
@@ -997,10 +1129,13 @@ class Llama(nn.Module):
             pen.feed(ids.get(), np.full(B, pos))
             ws["logits"][...] = pen.apply(ws["logits"].get())
         if sampling is None:
-            return ws["logits"].argmax(-1, keepdims=True)
-        out = hp.empty((B, 1), np.int64)              # (the sampled form of the pick: counter (pos, b))
-        L.call("pdn_sample_rows_f32", logits, V, B, V, params_buffer(*sampling)._ptr, pos, out._ptr, st)
-        return out
+            out = ws["logits"].argmax(-1, keepdims=True)
+        else:
+            out = hp.empty((B, 1), np.int64)          # (the sampled form of the pick: counter (pos, b))
+            L.call("pdn_sample_rows_f32", logits, V, B, V, params_buffer(*sampling)._ptr, pos, out._ptr, st)
+        if n_lp is None:
+            return out
+        return out, self._logprobs_rows(ws["logits"], out.get(), n_lp)
 
     # -- ragged decode (generate_ragged): every row at its own position ------------------------------
     def _decode_step_rows(self, ids, run, i: int, more: bool = False):
@@ -1015,21 +1150,23 @@ class Llama(nn.Module):
         cache = self.layers[0].attention.cache_k
         limit = min(cache.shape[1], self.freqs_cos.shape[0])
         pos = np.where(live, lens + i, -1).astype(np.int32)
-        st = self._decode_plan(B, sampling is not None, ragged=True, penalty=run.get("pen") is not None)
+        n_lp = run.get("lp")
+        st = self._decode_plan(B, sampling is not None, ragged=True, penalty=run.get("pen") is not None, n_lp=n_lp)
         if st is None:
-            out = self._decode_step_generic_rows(ids, pos, sampling, pen=run.get("pen"))
-            if pos.min() >= 0:
-                return out
-            tok = out.get().reshape(B, 1)
-            tok[pos < 0] = -1
-            return hp.asarray(tok)
+            out = self._decode_step_generic_rows(ids, pos, sampling, pen=run.get("pen"), n_lp=n_lp)
+            out, lp = out if n_lp is not None else (out, None)
+            if pos.min() < 0:
+                tok = out.get().reshape(B, 1)
+                tok[pos < 0] = -1
+                out = hp.asarray(tok)
+            return out if n_lp is None else (out, lp)
         ahead, st["ahead"] = st.get("ahead"), None
         if ahead is not None:
             if ahead[0] == (id(run), i) and ahead[1] is ids and st["run"] is run:   # exactly this step, queued ahead
                 out = st["last_out"] = ahead[2]
                 if more and Llama.decode_ahead and top + 1 < limit:
                     self._decode_ahead_rows(st, run, i + 1)
-                return out
+                return out if n_lp is None else (out, self._lp_read(st, i))
             hp.synchronize()                                     # a different request: the queued step is void
             st["host_step"] = st["last_out"] = None
         if st["run"] is not run or st["host_step"] != i:
@@ -1038,6 +1175,7 @@ class Llama(nn.Module):
             st["step"][...] = np.int32(i)
             st["stop"][...] = run["stop_mask"]
             st["hist_ptr"][...] = np.int64(run["hist"]._ptr)
+            self._lp_begin(st)
         if st["params_val"] != sampling:
             if sampling is not None:
                 st["params"][...] = params_bytes(*sampling)
@@ -1059,6 +1197,7 @@ class Llama(nn.Module):
             counts = st["counts"].copy() if st["pen"] else None  # (the capture's runs count their fed tokens too)
             scratch = hp.Mailbox(run["hist"].n, (B, 1), unset=run["hist"].unset)
             st["hist_ptr"][...] = np.int64(scratch._ptr)
+            lp_restore = self._lp_scratch(st)
             try:
                 g = hp.Graph()
                 g.capture(lambda: self._decode_launches(st, ns))
@@ -1069,6 +1208,7 @@ class Llama(nn.Module):
                 st["nograph"], g = True, False
             hp.synchronize()
             st["hist_ptr"][...] = np.int64(run["hist"]._ptr)
+            lp_restore()
             st["pos"][...] = pos
             st["step"][...] = np.int32(i)
             st["ids"][...] = keep
@@ -1083,7 +1223,7 @@ class Llama(nn.Module):
         out = st["last_out"] = run["hist"].slot(i)
         if more and Llama.decode_ahead and (st["graphs"] or st["nograph"]) and top + 1 < limit:
             self._decode_ahead_rows(st, run, i + 1)
-        return out
+        return out if n_lp is None else (out, self._lp_read(st, i))
 
     def _decode_ahead_rows(self, st, run, i):
         """`_decode_ahead` for a ragged plan: queue step i right behind the one just issued."""
@@ -1098,13 +1238,13 @@ class Llama(nn.Module):
         st["host_step"] = i + 1
         st["ahead"] = ((id(run), i), st["last_out"], run["hist"].slot(i))
 
-    def _decode_step_generic_rows(self, ids, pos, sampling=None, req=None, pen=None):
+    def _decode_step_generic_rows(self, ids, pos, sampling=None, req=None, pen=None, n_lp=None):
         """`_decode_step_generic` with a position per row (pos: host int32, -1 = a stopped row: computed at position 0,
         no cache slot written): k / v are projected into scratch rows and written to each row's own slot, RoPE takes
         each row's own cos / sin row, and the attention runs over each row's own key count (pdn_attention_decode_rows_f32).
         `req` (Llama.serve): the counter id of each row, drawn by the slot tick (default: the row).  `pen`
         (llm/penalties.Rows): the statement of the penalties on the host counts.  Returns the ids of every row, (B, 1)
-        int64."""
+        int64 (`n_lp`: and the rows' Logprobs, none for rows at -1)."""
         from .. import hipnp as hp, _lib
         L, st = _lib.lib(), hp.stream()
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
@@ -1163,21 +1303,26 @@ class Llama(nn.Module):
             pen.feed(idc.get(), pos)
             ws["logits"][...] = pen.apply(ws["logits"].get())
         if sampling is None:
-            return ws["logits"].argmax(-1, keepdims=True)
-        out = hp.empty((B, 1), np.int64)              # (counter (pos[b], b): the per-row tick on scratch copies)
-        pd, step = hp.asarray(p.astype(np.int32)), hp.zeros((1,), np.int32)
-        if req is not None:                           # (counter (pos[b], req[b]): the slot tick, a budget of one token)
-            rq, left = hp.asarray(np.asarray(req, np.int32).reshape(B)), hp.asarray(np.ones(B, np.int32))
-            L.call("pdn_decode_sample_tick_slots_f32", logits, V, B, V, params_buffer(*sampling)._ptr, out._ptr,
-                   pd._ptr, step._ptr, rq._ptr, left._ptr, 1, None, None, None, 0, 0, None, st)
+            out = ws["logits"].argmax(-1, keepdims=True)
+        else:
+            out = hp.empty((B, 1), np.int64)          # (counter (pos[b], b): the per-row tick on scratch copies)
+            pd, step = hp.asarray(p.astype(np.int32)), hp.zeros((1,), np.int32)
+            if req is not None:                       # (counter (pos[b], req[b]): the slot tick, a budget of one token)
+                rq, left = hp.asarray(np.asarray(req, np.int32).reshape(B)), hp.asarray(np.ones(B, np.int32))
+                L.call("pdn_decode_sample_tick_slots_f32", logits, V, B, V, params_buffer(*sampling)._ptr, out._ptr,
+                       pd._ptr, step._ptr, rq._ptr, left._ptr, 1, None, None, None, 0, 0, None, st)
+            else:
+                L.call("pdn_decode_sample_tick_rows_f32", logits, V, B, V, params_buffer(*sampling)._ptr, out._ptr,
+                       pd._ptr, step._ptr, None, None, None, 0, 0, None, st)
+        if n_lp is None:
             return out
-        L.call("pdn_decode_sample_tick_rows_f32", logits, V, B, V, params_buffer(*sampling)._ptr, out._ptr, pd._ptr,
-               step._ptr, None, None, None, 0, 0, None, st)
-        return out
+        tok = np.array(out.get()).reshape(-1)
+        tok[pos < 0] = -1
+        return out, self._logprobs_rows(ws["logits"], tok, n_lp)
 
     # -- continuous batching (serve): a finished row takes the next waiting request -------------------------------
     def serve(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
-              prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+              prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=None):
         """Continuous batching: N requests (`prompts`, N may exceed max_batch_size) through `slots` decode rows
         (default min(N, max_batch_size)).  A row frees when its request yields a stop id or uses up its budget
         (`max_new_tokens`: one int, or one per request; 0 = the request yields nothing and never takes a row).  Before
@@ -1194,9 +1339,12 @@ class Llama(nn.Module):
         those of `serve`; only the step at which they appear changes.  slots + C <= 256.
         `repetition_penalty` / `presence_penalty` / `frequency_penalty` (llm/penalties.py): one set of values for every
         request; each request has its own prompt set and counts -- a row that takes a request starts from its prompt and
-        zero counts -- so the promise above holds with penalties too."""
+        zero counts -- so the promise above holds with penalties too.
+        `logprobs` = n (llm/logprobs.py): every step yields (reqs, toks, lp), lp of (slots,) / (slots, n) arrays; a slot
+        that yields no token has nan / -1 / nan."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
         penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty)
+        n_lp = lp_np.check_n(logprobs)
         V = self.vocab_size
         rows = [np.asarray(p.numpy() if isinstance(p, Tensor) else p).reshape(-1) for p in prompts]
         if not rows:
@@ -1233,22 +1381,35 @@ class Llama(nn.Module):
         C = chunked.check_chunk(prefill_chunk, slots)
         if C is not None:
             return self._serve_chunked([p.astype(np.int64) for p in rows], budgets, int(slots), C, sampling, stops,
-                                       penalty)
-        return self._serve([p.astype(np.int64) for p in rows], budgets, int(slots), sampling, stops, penalty)
+                                       penalty, n_lp)
+        return self._serve([p.astype(np.int64) for p in rows], budgets, int(slots), sampling, stops, penalty, n_lp)
 
     def serve_all(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
-                  prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
-        """`serve` run to the end: a list of N int64 arrays, request r's generated tokens in order."""
+                  prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
+                  logprobs=None):
+        """`serve` run to the end: a list of N int64 arrays, request r's generated tokens in order.  `logprobs` = n: a
+        list of (tokens, Logprobs) instead, the arrays of length k / (k, n) for a request's k tokens."""
         it = self.serve(prompts, max_new_tokens, slots, temperature, top_k, top_p, seed, stop_ids, prefill_chunk,
-                        repetition_penalty, presence_penalty, frequency_penalty)
+                        repetition_penalty, presence_penalty, frequency_penalty, logprobs)
         out = [[] for _ in range(len(prompts))]
-        for reqs, toks in it:
-            for r, t in zip(reqs, toks):
+        lps = [[] for _ in range(len(prompts))]
+        for step in it:
+            reqs, toks = step[0], step[1]
+            for b, (r, t) in enumerate(zip(reqs, toks)):
                 if r >= 0 and t >= 0:
                     out[r].append(int(t))
-        return [np.array(o, np.int64) for o in out]
+                    if logprobs is not None:
+                        lps[r].append((step[2].token[b], step[2].top_ids[b], step[2].top_logprobs[b]))
+        if logprobs is None:
+            return [np.array(o, np.int64) for o in out]
+        n = int(logprobs)
+        # (reshape to (k, n) by count: with n = 0 or k = 0 a -1 could not be inferred)
+        return [(np.array(o, np.int64), lp_np.Logprobs(np.array([e[0] for e in l], np.float32).reshape(len(l)),
+                                                       np.array([e[1] for e in l], np.int64).reshape(len(l), n),
+                                                       np.array([e[2] for e in l], np.float32).reshape(len(l), n)))
+                for o, l in zip(out, lps)]
 
-    def _serve(self, rows, budgets, S, sampling, stops, penalty=None):
+    def _serve(self, rows, budgets, S, sampling, stops, penalty=None, n_lp=None):
         """The scheduler of `serve`.  Per step: the rows holding a request decode one token, then the rows freed by the
         previous step take the waiting requests in order through one prompt pass (`_serve_prefill`), then the step is
         yielded.  The host keeps, per row, the request, the position of its next decode step, the tokens it may still
@@ -1263,7 +1424,7 @@ class Llama(nn.Module):
         dev = self.tok_embedding.weight.device
         hip = (Llama.fast_decode and dev.is_hip and not self._train
                and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
-        st = self._serve_begin(S, sampling, stops, penalty) if hip else None   # None: the plan refuses -> generic HIP step
+        st = self._serve_begin(S, sampling, stops, penalty, n_lp) if hip else None   # None: the plan refuses -> generic
         pen = None if penalty is None or st is not None else pen_np.Rows(S, self.vocab_size, penalty)   # (host counts)
         q = 0
         try:
@@ -1276,6 +1437,7 @@ class Llama(nn.Module):
                     return
                 p = np.where(run, pos, -1)
                 toks = np.full(S, -1, np.int64)
+                lpv = None if n_lp is None else lp_np.none(S, n_lp)
                 if st is not None:
                     # (invariant: at most one step is queued here, and it is this step's -- void if no row runs)
                     if run.any() and not st["pending"]:
@@ -1284,24 +1446,31 @@ class Llama(nn.Module):
                         nxt = np.where(run & (left > 1), p + 1, -1)
                         if nxt.max() >= 0:
                             self._serve_ahead(st, int(nxt.max()))    # the next step, queued before this one is read
-                        toks[run] = self._serve_read(st)[run]
+                        toks[run] = self._serve_read(st, lpv, run)[run]
                 elif run.any():
                     ids, rq = last.reshape(S, 1), np.maximum(req, 0)
                     if hip:
                         from .. import hipnp as hp
                         out = self._decode_step_generic_rows(hp.asarray(ids), p.astype(np.int32), sampling, rq,
-                                                             pen=pen).get()
+                                                             pen=pen, n_lp=n_lp)
                     else:
                         out = self._step_module_rows(Tensor(ids, dtype=np.int64, device=dev), p, sampling, rq,
-                                                     pen=pen).numpy()
+                                                     pen=pen, n_lp=n_lp)
+                    if n_lp is not None:
+                        out, lpr = out
+                        lp_np.merge(lpv, np.flatnonzero(run), lp_np.Logprobs(*(a[run] for a in lpr)))
+                    out = out.get() if hip else out.numpy()
                     toks[run] = out.reshape(-1)[run]
                 shown = req.copy()
                 if adm.size:
-                    first = self._serve_prefill([rows[r] for r in new], adm, new, sampling, penalty)
+                    first = self._serve_prefill([rows[r] for r in new], adm, new, sampling, penalty, n_lp)
+                    if n_lp is not None:
+                        first, lpf = first
+                        lp_np.merge(lpv, adm, lpf)
                     if pen is not None:
                         pen.reset(adm, [rows[r] for r in new])
                     if st is not None and st["pending"]:
-                        d = self._serve_read(st)                 # (stream order: that step ran before the prefill)
+                        d = self._serve_read(st, lpv, run)       # (stream order: that step ran before the prefill)
                         toks[run] = d[run]
                     toks[adm], shown[adm] = first, new
                     req[adm], pos[adm], left[adm] = new, lens[new], budgets[new]
@@ -1319,27 +1488,28 @@ class Llama(nn.Module):
                         self._pen_reset(st, adm, [rows[r] for r in new], penalty)
                     if (req >= 0).any():
                         self._serve_ahead(st, int(np.where(req >= 0, pos, -1).max()))
-                yield shown, toks
+                yield (shown, toks) if n_lp is None else (shown, toks, lpv)
         finally:
             if st is not None and st["pending"]:
                 from .. import hipnp as hp
                 hp.synchronize()                                 # (queued steps store into this run's history)
                 st["pending"] = 0
 
-    def _serve_prefill(self, prompts, rows, reqs, sampling, penalty=None):
+    def _serve_prefill(self, prompts, rows, reqs, sampling, penalty=None, n_lp=None):
         """Admit requests `reqs` (their prompts) into decode rows `rows`: the prompts right-padded to the longest run as one
         batched causal pass from position 0 into a staging cache (the layers' caches point at it meanwhile), then
         pdn_kv_store_slots_f32 puts prompt i's keys / values, positions [0, len_i), into cache row rows[i] and zeroes
         position len_i there -- the slot a decode step attends to but never writes (`generate`'s step at position p feeds
         the token of position p - 1), which in a fresh cache holds zeros.  No pad position and no other row is written.
         `penalty`: the logits penalised for each prompt first.  Returns the first token of each request (counter (len_i,
-        reqs[i]) when sampled), host int64."""
+        reqs[i]) when sampled), host int64 (`n_lp`: and their Logprobs)."""
         logits = self._prefill_rows(prompts, rows)
         if penalty is not None:
             logits = self._penalize_prompt(logits, prompts, penalty)
         lens = np.array([p.size for p in prompts], np.int64)
         first = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, lens, *sampling, rows=reqs)
-        return np.asarray(first.numpy()).reshape(-1).astype(np.int64)
+        first = np.asarray(first.numpy()).reshape(-1).astype(np.int64)
+        return first if n_lp is None else (first, self._logprobs_rows(logits, first, n_lp))
 
     def _prefill_rows(self, prompts, rows):
         """The prompt pass of `_serve_prefill` (and of `beam_search`): prompt i's keys / values into cache row rows[i],
@@ -1389,9 +1559,9 @@ class Llama(nn.Module):
 
     # (graph path of `serve`: the served plan holds the rows' state on the device; steps are issued, queued ahead and
     #  read in order, through a ring of `ring` history slots)
-    def _serve_begin(self, S, sampling, stops, penalty=None):
+    def _serve_begin(self, S, sampling, stops, penalty=None, n_lp=None):
         from .. import hipnp as hp
-        st = self._decode_plan(S, sampling is not None, ragged=True, serve=True, penalty=penalty is not None)
+        st = self._decode_plan(S, sampling is not None, ragged=True, serve=True, penalty=penalty is not None, n_lp=n_lp)
         if st is None:
             return None
         if st["pending"]:
@@ -1400,6 +1570,7 @@ class Llama(nn.Module):
         np.bitwise_or.at(mask, stops >> 5, np.uint32(1) << (stops & 31).astype(np.uint32))
         st["hist"] = hp.Mailbox(st["ring"], (S, 1), unset=np.iinfo(np.int64).min)
         st["hist_ptr"][...] = np.int64(st["hist"]._ptr)
+        self._lp_begin(st)
         st["stop"][...] = mask.view(np.int32)
         st["pos"][...] = np.full(S, -1, np.int32)
         st["step"][...] = np.int32(0)
@@ -1427,6 +1598,7 @@ class Llama(nn.Module):
             keep = {n: st[n].copy() for n in ("ids", "pos", "step", "left") + (("counts",) if st["pen"] else ())}
             scratch = hp.Mailbox(st["ring"], (st["B"], 1), unset=st["hist"].unset)
             st["hist_ptr"][...] = np.int64(scratch._ptr)
+            lp_restore = self._lp_scratch(st)
             try:
                 g = hp.Graph()
                 g.capture(lambda: self._decode_launches(st, ns))
@@ -1437,6 +1609,7 @@ class Llama(nn.Module):
                 st["nograph"], g = True, False
             hp.synchronize()
             st["hist_ptr"][...] = np.int64(st["hist"]._ptr)
+            lp_restore()
             for n, v in keep.items():
                 st[n][...] = v
             self._decode_gather(st)
@@ -1461,11 +1634,17 @@ class Llama(nn.Module):
             self._decode_launches(st, ns)
         st["pending"] += 1
 
-    def _serve_read(self, st):
+    def _serve_read(self, st, lpv=None, rows=None):
         """The tokens of the oldest unread step, (B,) host int64 (-1 for rows that computed nothing): a poll of its
-        mapped history slot, which is then marked unwritten for the step `ring` steps later."""
+        mapped history slot, which is then marked unwritten for the step `ring` steps later.  Plans with logprobs: the
+        step's records too, rows `rows` (bool) of them merged into `lpv`."""
         h, i = st["hist"], st["read"] % st["ring"]
         tok = np.array(h.slot(i).get()).reshape(-1)
+        if st.get("lp_n") is not None:
+            # (before the history slot is marked unwritten: the record kernel reads its tokens there)
+            lp = self._lp_read(st, st["read"])
+            if lpv is not None:
+                lp_np.merge(lpv, np.flatnonzero(rows), lp_np.Logprobs(*(a[rows] for a in lp)))
         h.host[i] = h.unset
         st["read"] += 1
         st["pending"] -= 1
@@ -1481,7 +1660,7 @@ class Llama(nn.Module):
         self._decode_gather(st)
 
     # -- chunked prefill (serve(prefill_chunk=C)): prompts fed C tokens per step (statement: llm/chunked.py) -----------
-    def _serve_chunked(self, rows, budgets, S, C, sampling, stops, penalty=None):
+    def _serve_chunked(self, rows, budgets, S, C, sampling, stops, penalty=None, n_lp=None):
         """The scheduler of `serve` with a chunk: llm/chunked.Schedule decides, per step, which rows decode and which
         prompt tokens are fed.  Graph path (`_mixed_begin`): a step with prompt tokens runs the mixed step (the decode
         rows and the chunks as query rows of the wide product, csrc/extend.hip), a step without runs the served step.
@@ -1492,7 +1671,7 @@ class Llama(nn.Module):
         dev = self.tok_embedding.weight.device
         hip = (Llama.fast_decode and dev.is_hip and not self._train
                and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
-        st = self._mixed_begin(S, C, sampling, stops, penalty) if hip else None
+        st = self._mixed_begin(S, C, sampling, stops, penalty, n_lp) if hip else None
         pen = None if penalty is None or st is not None else pen_np.Rows(S, self.vocab_size, penalty)   # (host counts)
         dirty = False                                           # (the device's row state differs from the host's)
         try:
@@ -1507,15 +1686,16 @@ class Llama(nn.Module):
                     return
                 n, dec, comp = sch.plan()
                 toks = np.full(S, -1, np.int64)
+                lpv = None if n_lp is None else lp_np.none(S, n_lp)
                 if st is not None:
                     got = np.zeros(S, bool)
                     if st["pending"]:                            # a served step queued ahead: this step's decode rows
-                        toks[dec] = self._serve_read(st)[dec]
+                        toks[dec] = self._serve_read(st, lpv, dec)[dec]
                         got |= dec
                     if n.any():
                         inc = dec & ~got
                         self._mixed_issue(st, sch, n, inc, comp, rows)
-                        t = self._serve_read(st)
+                        t = self._serve_read(st, lpv, inc | comp)
                         toks[inc | comp] = t[inc | comp]
                         dirty = True
                     elif not got.any() and dec.any():
@@ -1530,7 +1710,7 @@ class Llama(nn.Module):
                         if (nxt.max() >= 0 and not (sch.fed < sch.row_lens()).any()
                                 and (sch.q >= len(sch.queue) or not (dec & (sch.left <= 1)).any())):
                             self._serve_ahead(st, int(nxt.max()))
-                        toks[dec] = self._serve_read(st)[dec]
+                        toks[dec] = self._serve_read(st, lpv, dec)[dec]
                 else:
                     if dec.any():
                         p, rq = np.where(dec, sch.pos, -1), np.maximum(sch.req, 0)
@@ -1538,16 +1718,25 @@ class Llama(nn.Module):
                         if hip:
                             from .. import hipnp as hp
                             out = self._decode_step_generic_rows(hp.asarray(ids), p.astype(np.int32), sampling, rq,
-                                                                 pen=pen).get()
+                                                                 pen=pen, n_lp=n_lp)
                         else:
                             out = self._step_module_rows(Tensor(ids, dtype=np.int64, device=dev), p, sampling, rq,
-                                                         pen=pen).numpy()
+                                                         pen=pen, n_lp=n_lp)
+                        if n_lp is not None:
+                            out, lpr = out
+                            lp_np.merge(lpv, np.flatnonzero(dec), lp_np.Logprobs(*(a[dec] for a in lpr)))
+                        out = out.get() if hip else out.numpy()
                         toks[dec] = out.reshape(-1)[dec]
                     if comp.any():
                         b = np.flatnonzero(comp)
-                        toks[b] = self._serve_prefill([rows[r] for r in sch.req[b]], b, sch.req[b], sampling, penalty)
+                        first = self._serve_prefill([rows[r] for r in sch.req[b]], b, sch.req[b], sampling, penalty,
+                                                    n_lp)
+                        if n_lp is not None:
+                            first, lpf = first
+                            lp_np.merge(lpv, b, lpf)
+                        toks[b] = first
                 shown = sch.finish(n, toks, stops)
-                yield shown, toks
+                yield (shown, toks) if n_lp is None else (shown, toks, lpv)
         finally:
             if st is not None and st["pending"]:
                 from .. import hipnp as hp
@@ -1562,12 +1751,12 @@ class Llama(nn.Module):
         return bool(Llama.wide_decode and S + C <= 256 and all(_lib.provides(n) for n in _MIXED_ENTRIES)
                     and L.query("pdn_decode_mixed_supported", D, H, D // H, F, V, cache_len))
 
-    def _mixed_begin(self, S, C, sampling, stops, penalty=None):
+    def _mixed_begin(self, S, C, sampling, stops, penalty=None, n_lp=None):
         """The served plan (`_serve_begin`) plus the buffers of the mixed step (`mixed`), or None when either refuses."""
         from .. import hipnp as hp, _lib
         if not self._mixed_ok(S, C):
             return None
-        st = self._serve_begin(S, sampling, stops, penalty)
+        st = self._serve_begin(S, sampling, stops, penalty, n_lp)
         if st is None or st["ns"] > 8:
             return None
         M = st.get("mixed")
@@ -1633,6 +1822,7 @@ class Llama(nn.Module):
             keep = {n: st[n].copy() for n in ("ids", "pos", "step", "left") + (("counts",) if st["pen"] else ())}
             scratch = hp.Mailbox(st["ring"], (st["B"], 1), unset=st["hist"].unset)
             st["hist_ptr"][...] = np.int64(scratch._ptr)
+            lp_restore = self._lp_scratch(st)
             try:
                 g = hp.Graph()
                 g.capture(lambda: self._mixed_launches(st, ns))
@@ -1643,6 +1833,7 @@ class Llama(nn.Module):
                 st["nograph"], g = True, False
             hp.synchronize()
             st["hist_ptr"][...] = np.int64(st["hist"]._ptr)
+            lp_restore()
             for k, v in keep.items():
                 st[k][...] = v
             self._decode_gather(st)
@@ -1689,6 +1880,7 @@ class Llama(nn.Module):
             L.call("pdn_decode_wide_pick_tick_slots_f32", cands["cand_v"]._ptr, cands["cand_i"]._ptr, S,
                    cands["cand_v"].shape[1], st["ids"]._ptr, *cnt, st["req"]._ptr, st["left"]._ptr, st["ring"],
                    st["stop"]._ptr, *out)
+        self._lp_tick(st, s)
 
     def _mixed_layers(self, M, packs, n_runs, max_run, R, ns, s):
         """The layers of the mixed step on R query rows (M["x"] in, M["x"] out): q | k | v with RMSNorm in the load, the KV
