@@ -190,7 +190,9 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  33 chunked prefill (csrc/extend.hip): pdn_kv_append_rows_f32, pdn_decode_extend_attention_f32
  *  34 speculative decoding (csrc/speculative.hip): pdn_spec_draft_rows and the two pdn_spec_verify_*_tick_f32 entries
  *  35 decode penalties (csrc/penalty.hip): pdn_penalty_reset, pdn_penalty_step_f32, pdn_penalty_rows_f32
- *  36 token log-probabilities (csrc/logprobs.hip): pdn_logprobs_rows_f32, pdn_logprobs_tick_f32 */
+ *  36 token log-probabilities (csrc/logprobs.hip): pdn_logprobs_rows_f32, pdn_logprobs_tick_f32
+ *  37 lm_head forward on split-fp16 MFMA (csrc/lm_head_split.hip): pdn_linear_rowmax_split_fwd_f32, which also counts
+ *     in 5 (it IS the vocabulary projection + row maxima of a step) */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -237,6 +239,21 @@ int pdn_linear_rowmax_supported(int64_t M, int V, int K);
 int pdn_linear_rowmax_parts(int64_t M, int V, int K);      /* vectors of M maxima `rowmax` must hold (few rows: the chunk ranges) */
 int pdn_linear_rowmax_fwd_f32(const float* x, const float* w, const float* bias, float* logits, float* rowmax, int M,
                               int V, int K, int64_t ldx, int64_t ldw, int64_t ldl, void* stream);
+/* pdn_linear_rowmax_fwd_f32 on the f16 matrix pipe at fp32 accuracy (csrc/lm_head_split.hip; 16384 rows and more,
+ * K = 288, V a multiple of 32): every row of x and every column of W is scaled by its own power of two and split into
+ * two fp16 planes (a 2^s = h + l / 2048), the product is xh wh + (xh wl + xl wh) / 2048 in fp32 accumulators -- three f16
+ * MFMAs at 1/16 of the fp32 MFMA's cycles each -- and the scales leave exactly in the store.  Same logits layout, same
+ * `parts` vectors of row maxima (taken from the values as stored), deterministic.  `workspace`
+ * (pdn_linear_rowmax_split_workspace_bytes, 16-byte aligned) holds the planes for the duration of the call only; W is
+ * split on every call.  PDN_LMHEAD_SPLIT=0 makes `*_supported` answer 0 (A/B runs against the fp32 kernel).
+ * Within a row of x / a column of W, elements more than 2^11 below the row's / column's largest magnitude lose low bits
+ * relative to themselves; the error of a logit stays about 2^-22 max|x_row| max|w_col| per term. */
+int pdn_linear_rowmax_split_supported(int64_t M, int V, int K);
+int64_t pdn_linear_rowmax_split_workspace_bytes(int64_t M, int V, int K);
+int pdn_linear_rowmax_split_parts(int64_t M, int V, int K);
+int pdn_linear_rowmax_split_fwd_f32(const float* x, const float* w, const float* bias, float* logits, float* rowmax, int M,
+                                    int V, int K, int64_t ldx, int64_t ldw, int64_t ldl, void* workspace,
+                                    int64_t workspace_bytes, void* stream);
 int pdn_linear_ce_dx_deferred_supported(int64_t rows, int V, int in_features);
 int64_t pdn_linear_ce_dx_deferred_workspace_bytes(int64_t rows, int V, int in_features);   /* a W^T copy (V x 288: the rows W[:, target]
                                                                                              * are read from it) + the range slabs of few-row launches */

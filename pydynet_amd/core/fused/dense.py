@@ -7,6 +7,7 @@ import os
 
 import numpy as np
 
+from ... import _lib
 from ...autograd import is_grad_enable
 from ..tensor import Tensor, _Operator
 from ._common import _hip, _L, _contig, _require_f32, _foldable, _beside, _is_leaf_f32, _Deferred, hip_f32
@@ -326,6 +327,10 @@ class linear_cross_entropy(_Operator):
     # statistics split over the projection (row maxima) and the input-gradient product (sum of exponentials), the latter
     # run in the forward pass of a training step (A/B switch)
     deferred_norm = os.environ.get("PDN_NO_CE_DEFERRED", "0") != "1"
+    # the projection of the deferred form on split-fp16 MFMA where the library takes the shape (csrc/lm_head_split.hip).
+    # The library reads PDN_LMHEAD_SPLIT=0 itself (`pdn_linear_rowmax_split_supported` then answers 0); this attribute is
+    # the in-process form of the same A/B switch.
+    split_forward = True
 
     @staticmethod
     def applicable(x, w, b, targets, reduction="mean"):
@@ -376,10 +381,23 @@ class linear_cross_entropy(_Operator):
             # the loss follows from its log-sum-exp with one gather per row, and no pass over the logits exists
             # (few rows: both products cut the vocabulary into ranges over the grid -- `parts` vectors of maxima, a
             #  workspace of unnormalised rows and row sums)
-            parts = L.query("pdn_linear_rowmax_parts", n, V, fin)
-            rowmax = hp.empty((parts * n,), np.float32)
-            L.call("pdn_linear_rowmax_fwd_f32", x2._ptr, wd._ptr, bp, logits._ptr, rowmax._ptr, n, V, fin, x2._strides[0],
-                   V, V, hp.stream())
+            split = bool(linear_cross_entropy.split_forward and x2._strides[0] % 4 == 0
+                         and _lib.provides("pdn_linear_rowmax_split_fwd_f32")
+                         and L.query("pdn_linear_rowmax_split_supported", n, V, fin))
+            if split:
+                # both operands split into two fp16 planes, three f16 MFMAs per k-step: fp32 accuracy at 3/16 of the fp32
+                # pipe's cycles.  The planes live in the per-stream scratch for this launch only (the next call below
+                # takes the same scratch, in stream order).
+                parts = L.query("pdn_linear_rowmax_split_parts", n, V, fin)
+                rowmax = hp.empty((parts * n,), np.float32)
+                ws, wsb = hp.workspace(L.query("pdn_linear_rowmax_split_workspace_bytes", n, V, fin))
+                L.call("pdn_linear_rowmax_split_fwd_f32", x2._ptr, wd._ptr, bp, logits._ptr, rowmax._ptr, n, V, fin,
+                       x2._strides[0], V, V, ws, wsb, hp.stream())
+            else:
+                parts = L.query("pdn_linear_rowmax_parts", n, V, fin)
+                rowmax = hp.empty((parts * n,), np.float32)
+                L.call("pdn_linear_rowmax_fwd_f32", x2._ptr, wd._ptr, bp, logits._ptr, rowmax._ptr, n, V, fin,
+                       x2._strides[0], V, V, hp.stream())
             self._dxu = hp.empty((n, fin), np.float32)
             self._w_ptr = wd._ptr                          # (backward checks that the weight was not re-homed meanwhile)
             ws, wsb = hp.workspace(L.query("pdn_linear_ce_dx_deferred_workspace_bytes", n, V, fin))

@@ -26,7 +26,8 @@ enum {
   PDN_CNT_ROWTILE_SWIGLU_FWD = 2, // EPI 1: gate | up + SwiGLU
   PDN_CNT_ROWTILE_SWIGLU_BWD = 3, // EPI 2: dh + SwiGLU backward
   PDN_CNT_ROWTILE_ROPE = 4,       // EPI 3: q | k | v + RoPE
-  PDN_CNT_ROWTILE_ROWMAX = 5,     // EPI 5: vocabulary projection + row maxima
+  PDN_CNT_ROWTILE_ROWMAX = 5,     // vocabulary projection + row maxima: gemm_rowtile_kernel<EPI 5>, or the split-fp16
+                                  // kernel of csrc/lm_head_split.hip (which counts in 37 as well)
   PDN_CNT_ROWRES_CHUNK_EPI = 6,   // gemm_rowres_kernel with a fused epilogue (EPI 1 / 2 / 3 / 4 / 5)
   PDN_CNT_ATT_P_FWD = 7,          // attention_p_fwd_kernel (persistent, DMA-staged)
   PDN_CNT_ATT_P_BWD = 8,          // attention_p_bwd_dq / dkv kernels
@@ -59,7 +60,8 @@ enum {
   PDN_CNT_SPECULATE = 34,         // speculative decoding (csrc/speculative.hip): the draft kernel and the verify ticks
   PDN_CNT_PENALTY = 35,           // decode penalties (csrc/penalty.hip): the reset and the two apply entries
   PDN_CNT_LOGPROBS = 36,          // token log-probabilities (csrc/logprobs.hip): the rows entry and the tick form
-  PDN_CNT_SLOTS = 37
+  PDN_CNT_LMHEAD_SPLIT = 37,      // lm_head forward on split-fp16 MFMA (csrc/lm_head_split.hip): also counts in 5
+  PDN_CNT_SLOTS = 38
 };
 void pdn_count(int slot);
 

@@ -1,5 +1,8 @@
 """lm_head forward forms (csrc/gemm_rowres.hip): plain product, product + log-sum-exp (EPI 4), product + row maxima (EPI 5),
-the latter also with its maximum switched off (PDN_ROWRES_EPI_ABLATE=2) to see what the butterfly costs.
+the latter also with its maximum switched off (PDN_ROWRES_EPI_ABLATE=2) to see what the butterfly costs, and the
+split-fp16 form of the row-maxima product (csrc/lm_head_split.hip: the two split passes and the product in one figure).
+Its stores are switched off by PDN_LMHEAD_SPLIT_ABLATE=1, which the library reads once: run the probe a second time with
+it set to see the store phase's share.
 usage: python tools/lmhead_probe.py [tokens=65536] [vocab=32000]"""
 import os
 import sys
@@ -34,6 +37,13 @@ rows = [("plain", lambda: hp.gemm(x, w, logits), ""),
         ("+ lse (EPI 4)", lambda: L.call("pdn_linear_lse_fwd_f32", x._ptr, w._ptr, None, logits._ptr, st._ptr, T, V, K, K, V, V, hp.stream()), ""),
         ("+ max (EPI 5)", lambda: L.call("pdn_linear_rowmax_fwd_f32", x._ptr, w._ptr, None, logits._ptr, st._ptr, T, V, K, K, V, V, hp.stream()), "")]
 rows.append(("+ max, maximum left out", rows[2][1], "2"))
+if L.query("pdn_linear_rowmax_split_supported", T, V, K):
+    sparts = L.query("pdn_linear_rowmax_split_parts", T, V, K)
+    smx = hp.empty((sparts * T,))
+    ws, wsb = hp.workspace(L.query("pdn_linear_rowmax_split_workspace_bytes", T, V, K))
+    rows.append(("+ max, split fp16" + (" (NO stores)" if os.environ.get("PDN_LMHEAD_SPLIT_ABLATE", "0") != "0" else ""),
+                 lambda: L.call("pdn_linear_rowmax_split_fwd_f32", x._ptr, w._ptr, None, logits._ptr, smx._ptr, T, V, K, K, V, V,
+                                ws, wsb, hp.stream()), ""))
 for name, fn, ab in rows:
     os.environ["PDN_ROWRES_EPI_ABLATE"] = ab or "0"
     us = bench(fn)

@@ -12,7 +12,8 @@ P5="WRITE_SIZE"
 i=0
 for P in "$P1" "$P2" "$P3" "$P4" "$P5"; do
   i=$((i+1))
-  ( cd $R && timeout 600 rocprofv3 --kernel-trace --pmc $P --output-format csv -d $OUT/p$i -o g -- "$@" > $OUT/p$i.log 2>&1 )
+  # (a pass that fails or runs into its time limit ends the script: nothing more is started on a GPU that has just faulted)
+  ( cd $R && timeout -k 10 600 rocprofv3 --kernel-trace --pmc $P --output-format csv -d $OUT/p$i -o g -- "$@" > $OUT/p$i.log 2>&1 ) || { echo "pass $i failed"; tail -5 $OUT/p$i.log; exit 1; }
 done
 cd $R
 python - "$OUT" "$FILTER" <<'PY'
