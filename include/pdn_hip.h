@@ -192,7 +192,8 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  35 decode penalties (csrc/penalty.hip): pdn_penalty_reset, pdn_penalty_step_f32, pdn_penalty_rows_f32
  *  36 token log-probabilities (csrc/logprobs.hip): pdn_logprobs_rows_f32, pdn_logprobs_tick_f32
  *  37 lm_head forward on split-fp16 MFMA (csrc/lm_head_split.hip): pdn_linear_rowmax_split_fwd_f32, which also counts
- *     in 5 (it IS the vocabulary projection + row maxima of a step) */
+ *     in 5 (it IS the vocabulary projection + row maxima of a step)
+ *  38 prefix caching (csrc/prefix.hip): pdn_kv_copy_prefix_rows_f32 */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -836,6 +837,20 @@ int pdn_logprobs_rows_f32(const float* logits, int64_t row_stride, int rows, int
 int pdn_logprobs_tick_f32(const float* logits, int64_t row_stride, int B, int V, int n, int64_t* const* history,
                           int hist_ring, const int* counter, int64_t* const* records, int ring, void* work,
                           void* stream);
+/* Prefix caching (csrc/prefix.hip; Llama.serve(prefix_cache=...), the NumPy statement is pydynet_amd/llm/prefix.py): a
+ * decode row admitted with a prompt whose leading tokens another cache row holds takes that row's keys / values.
+ *   pdn_kv_copy_prefix_rows_f32   for each of the n_tensors caches (a device array of pointers, each (n_rows, max_len, D)
+ *                            floats with batch_stride floats between rows, 16-byte aligned) and every copy i < n_copies
+ *                            (<= 256): positions [0, min(len[i], max_len)) of row dst[i] take row src[i]'s contents AS
+ *                            THEY WERE BEFORE THE LAUNCH.  One launch covers all tensors and all copies.  A copy with
+ *                            dst[i] == src[i], len[i] <= 0 or either row outside [0, n_rows) is skipped.  dst values are
+ *                            distinct; a row may be the source of several copies and the destination of one (a swap, a
+ *                            chain 1 <- 2 <- 3): a workgroup owns (tensor, column slice, positions) for all rows, loads
+ *                            every copy's source there, synchronises, then stores.  D % 4 == 0 (and batch_stride % 4 ==
+ *                            0) moves 16-byte vectors, any other D floats.  Nothing outside the named positions of the
+ *                            named destination rows is written; two launches from the same start give the same bits. */
+int pdn_kv_copy_prefix_rows_f32(float* const* caches, int n_tensors, int64_t batch_stride, int n_rows, int max_len, int D,
+                                const int* dst, const int* src, const int* len, int n_copies, void* stream);
 /* shapes the resident (K / V of a head chunk-wise in LDS) kernels above take: head_dim 48 or 64, L a multiple of 32 up
  * to 1024 -- sequences beyond 256 pass through LDS in 256-row chunks (forward: one online rescale per chunk) -- and
  * (round 6, csrc/attention_hd128.hip) head_dim 128 at ANY length 1 .. 1024, no RoPE inside: the shape of

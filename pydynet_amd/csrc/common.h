@@ -61,7 +61,8 @@ enum {
   PDN_CNT_PENALTY = 35,           // decode penalties (csrc/penalty.hip): the reset and the two apply entries
   PDN_CNT_LOGPROBS = 36,          // token log-probabilities (csrc/logprobs.hip): the rows entry and the tick form
   PDN_CNT_LMHEAD_SPLIT = 37,      // lm_head forward on split-fp16 MFMA (csrc/lm_head_split.hip): also counts in 5
-  PDN_CNT_SLOTS = 38
+  PDN_CNT_PREFIX = 38,            // prefix caching (csrc/prefix.hip): the row-to-row copy of Llama.serve(prefix_cache=...)
+  PDN_CNT_SLOTS = 39
 };
 void pdn_count(int slot);
 

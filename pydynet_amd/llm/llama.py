@@ -24,6 +24,7 @@ from . import beam as beam_np
 from . import chunked
 from . import logprobs as lp_np
 from . import penalties as pen_np
+from . import prefix as prefix_np
 from . import speculative as spec_np
 from .sampling import (check_args as check_sampling_args, params_bytes, params_buffer, sample_next,
                        sample_next_rows)
@@ -1322,7 +1323,8 @@ class Llama(nn.Module):
 
     # -- continuous batching (serve): a finished row takes the next waiting request -------------------------------
     def serve(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
-              prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=None):
+              prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=None,
+              prefix_cache=False):
         """Continuous batching: N requests (`prompts`, N may exceed max_batch_size) through `slots` decode rows
         (default min(N, max_batch_size)).  A row frees when its request yields a stop id or uses up its budget
         (`max_new_tokens`: one int, or one per request; 0 = the request yields nothing and never takes a row).  Before
@@ -1341,10 +1343,21 @@ class Llama(nn.Module):
         request; each request has its own prompt set and counts -- a row that takes a request starts from its prompt and
         zero counts -- so the promise above holds with penalties too.
         `logprobs` = n (llm/logprobs.py): every step yields (reqs, toks, lp), lp of (slots,) / (slots, n) arrays; a slot
-        that yields no token has nan / -1 / nan."""
+        that yields no token has nan / -1 / nan.
+        `prefix_cache` = True or k >= 1 (True = 1; needs `prefill_chunk`; llm/prefix.py): a request whose prompt starts
+        with at least k tokens that a cache row still holds from an earlier prompt (its own row's previous request, or
+        another row's, live or not) is not fed those tokens: its row takes them -- one pdn_kv_copy_prefix_rows_f32 per
+        step for all rows that take from another row, none for a row's own contents -- and its prefill starts behind
+        them.  The last prompt token is always fed.  The tokens of each request are those of `serve` without the cache;
+        only the step at which they appear changes.  Only the graph path with the mixed step reuses anything: on every
+        other path (a library without the mixed step, more than 8 key ranges, wide_decode off, the generic rows, the
+        `cpu` device) a prompt completes with one whole pass from position 0, so every prompt is computed in full and
+        steps and tokens are exactly those without the cache.  `self.prefix_stats` holds the run's figures (requests,
+        hits, prompt_tokens, reused_tokens, copies, launches) as it goes; with the cache off it is left alone."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
         penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty)
         n_lp = lp_np.check_n(logprobs)
+        k_pre = prefix_np.check_arg(prefix_cache, prefill_chunk)
         V = self.vocab_size
         rows = [np.asarray(p.numpy() if isinstance(p, Tensor) else p).reshape(-1) for p in prompts]
         if not rows:
@@ -1381,16 +1394,16 @@ class Llama(nn.Module):
         C = chunked.check_chunk(prefill_chunk, slots)
         if C is not None:
             return self._serve_chunked([p.astype(np.int64) for p in rows], budgets, int(slots), C, sampling, stops,
-                                       penalty, n_lp)
+                                       penalty, n_lp, k_pre)
         return self._serve([p.astype(np.int64) for p in rows], budgets, int(slots), sampling, stops, penalty, n_lp)
 
     def serve_all(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
                   prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                  logprobs=None):
+                  logprobs=None, prefix_cache=False):
         """`serve` run to the end: a list of N int64 arrays, request r's generated tokens in order.  `logprobs` = n: a
         list of (tokens, Logprobs) instead, the arrays of length k / (k, n) for a request's k tokens."""
         it = self.serve(prompts, max_new_tokens, slots, temperature, top_k, top_p, seed, stop_ids, prefill_chunk,
-                        repetition_penalty, presence_penalty, frequency_penalty, logprobs)
+                        repetition_penalty, presence_penalty, frequency_penalty, logprobs, prefix_cache)
         out = [[] for _ in range(len(prompts))]
         lps = [[] for _ in range(len(prompts))]
         for step in it:
@@ -1660,23 +1673,37 @@ class Llama(nn.Module):
         self._decode_gather(st)
 
     # -- chunked prefill (serve(prefill_chunk=C)): prompts fed C tokens per step (statement: llm/chunked.py) -----------
-    def _serve_chunked(self, rows, budgets, S, C, sampling, stops, penalty=None, n_lp=None):
+    def _serve_chunked(self, rows, budgets, S, C, sampling, stops, penalty=None, n_lp=None, prefix=None):
         """The scheduler of `serve` with a chunk: llm/chunked.Schedule decides, per step, which rows decode and which
         prompt tokens are fed.  Graph path (`_mixed_begin`): a step with prompt tokens runs the mixed step (the decode
         rows and the chunks as query rows of the wide product, csrc/extend.hip), a step without runs the served step.
         Every other path decodes as `_serve` does, and a prompt pass runs when the schedule completes prompts: one
-        `_serve_prefill` for the requests whose prompts complete in that step."""
+        `_serve_prefill` for the requests whose prompts complete in that step.
+        `prefix` = k (the prefix cache, llm/prefix.Schedule): on the graph path the rows admitted in a step that reuse
+        another row's tokens take them through one copy launch, issued eagerly before the step (`_prefix_copy`), and
+        their prefill starts at fed = n; every other path starts every prompt at 0 (the schedule with reuse forced off)."""
         lens = np.array([r.size for r in rows], np.int64)
-        sch = chunked.Schedule(lens, budgets, S, C)
         dev = self.tok_embedding.weight.device
         hip = (Llama.fast_decode and dev.is_hip and not self._train
                and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
         st = self._mixed_begin(S, C, sampling, stops, penalty, n_lp) if hip else None
+        if prefix is None:
+            sch = chunked.Schedule(lens, budgets, S, C)
+        else:
+            sch = prefix_np.Schedule(rows, budgets, S, C, prefix if st is not None else None)
+            self.prefix_stats = sch.stats
+            if st is not None:
+                st.pop("prefix", None)                          # (the cache pointer table: built by the run's first copy)
         pen = None if penalty is None or st is not None else pen_np.Rows(S, self.vocab_size, penalty)   # (host counts)
         dirty = False                                           # (the device's row state differs from the host's)
         try:
             while True:
-                adm, new = sch.admit()
+                if prefix is None:
+                    adm, new = sch.admit()
+                else:
+                    adm, new, don, reuse = sch.admit()
+                    if st is not None and adm.size:              # (stream order: after every earlier step of any row)
+                        self._prefix_copy(st, sch, adm, don, reuse)
                 if adm.size and penalty is not None:            # (stream order: after the steps of the rows' old requests)
                     if st is not None:
                         self._pen_reset(st, adm, [rows[r] for r in new], penalty)
@@ -1742,6 +1769,30 @@ class Llama(nn.Module):
                 from .. import hipnp as hp
                 hp.synchronize()
                 st["pending"] = 0
+
+    def _prefix_copy(self, st, sch, adm, donors, reuse):
+        """The copies of one step's admissions (llm/prefix.py): rows `adm` take their first `reuse` positions from rows
+        `donors`, in every cache tensor, by ONE pdn_kv_copy_prefix_rows_f32 on the decode stream -- outside the captured
+        graphs, like `_pen_reset` -- that reads every source as it was before the launch (two admitted rows may take from
+        each other).  A row that is its own donor has the data already."""
+        from .. import hipnp as hp, _lib
+        take = (reuse > 0) & (donors != adm)
+        if not take.any():
+            return
+        P = st.get("prefix")
+        if P is None:
+            caches = [c.data for layer in self.layers for c in (layer.attention.cache_k, layer.attention.cache_v)]
+            if not all(c.dtype == np.float32 and c.is_contiguous() for c in caches):
+                raise RuntimeError("prefix_cache needs contiguous float32 KV caches")
+            P = st["prefix"] = dict(caches=hp.asarray(np.array([c._ptr for c in caches], np.int64)), n=len(caches),
+                                    bs=caches[0]._strides[0], rows=caches[0].shape[0], len=caches[0].shape[1])
+        # (device copies held until the call has been issued; the allocator orders their reuse on the stream)
+        dst, src, ln = (hp.asarray(a[take].astype(np.int32)) for a in (adm, donors, reuse))
+        # (the caches as far as the longest copy reaches: the launch is sized by the positions it is given)
+        _lib.lib().call("pdn_kv_copy_prefix_rows_f32", P["caches"]._ptr, P["n"], P["bs"], P["rows"],
+                        min(P["len"], int(reuse[take].max())), self.embed_dim, dst._ptr, src._ptr, ln._ptr,
+                        int(take.sum()), hp.stream())
+        sch.stats["launches"] += 1
 
     def _mixed_ok(self, S, C):
         """Whether the library provides the mixed step and takes this model (any row count up to 256 query rows)."""
