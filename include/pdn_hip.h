@@ -193,7 +193,9 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  36 token log-probabilities (csrc/logprobs.hip): pdn_logprobs_rows_f32, pdn_logprobs_tick_f32
  *  37 lm_head forward on split-fp16 MFMA (csrc/lm_head_split.hip): pdn_linear_rowmax_split_fwd_f32, which also counts
  *     in 5 (it IS the vocabulary projection + row maxima of a step)
- *  38 prefix caching (csrc/prefix.hip): pdn_kv_copy_prefix_rows_f32 */
+ *  38 prefix caching (csrc/prefix.hip): pdn_kv_copy_prefix_rows_f32
+ *  39 lm_head input gradient on split-fp16 MFMA (csrc/lm_head_dx_split.hip): pdn_linear_ce_dx_deferred_split_f32, which
+ *     also counts in 12 (it IS the input gradient + sum of exponentials of a step) */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -261,6 +263,19 @@ int64_t pdn_linear_ce_dx_deferred_workspace_bytes(int64_t rows, int V, int in_fe
 int pdn_linear_ce_dx_deferred_f32(const float* logits, const float* rowmax, int max_parts, const int64_t* targets,
                                   float gscale, const float* W, float* dx, float* lse, int64_t rows, int V,
                                   int in_features, void* workspace, int64_t workspace_bytes, void* stream);
+/* pdn_linear_ce_dx_deferred_f32 on the f16 matrix pipe at fp32 accuracy (csrc/lm_head_dx_split.hip; 32768 rows and more,
+ * in = 288, V a multiple of 32): same arguments, same results.  e = exp(logit - max) is formed from the fp32 logits as
+ * today (Z and lse from the unsplit fp32 e), scaled by 2^15 and split into two fp16 planes on the fly; W is split once per
+ * call with one power of two per output column (a row of W as stored); u = eh wh + (eh wl + el wh) / 2048 in fp32
+ * accumulators, the exponents, 1 / Z, - W[:, target] and gscale applied in the store.  Deterministic.  `workspace`
+ * (pdn_linear_ce_dx_deferred_split_workspace_bytes, 16-byte aligned): the W^T copy, W's plane images and exponents, for the
+ * duration of the call.  PDN_LMHEAD_DX_SPLIT=0 makes `*_supported` answer 0 (A/B runs against the fp32 kernel);
+ * PDN_LMHEAD_DX_SPLIT_ABLATE=1 / 2 are timing ablations with WRONG results (announced on stderr). */
+int pdn_linear_ce_dx_deferred_split_supported(int64_t rows, int V, int in_features);
+int64_t pdn_linear_ce_dx_deferred_split_workspace_bytes(int64_t rows, int V, int in_features);
+int pdn_linear_ce_dx_deferred_split_f32(const float* logits, const float* rowmax, int max_parts, const int64_t* targets,
+                                        float gscale, const float* W, float* dx, float* lse, int64_t rows, int V,
+                                        int in_features, void* workspace, int64_t workspace_bytes, void* stream);
 int pdn_gateup_swiglu_supported(int M, int F, int K);
 int pdn_gateup_swiglu_fwd_f32(const float* x, const float* w_gate, int64_t w_stride, float* gu, float* h, int M,
                               int F, int K, int64_t ldx, void* stream);

@@ -331,6 +331,9 @@ class linear_cross_entropy(_Operator):
     # The library reads PDN_LMHEAD_SPLIT=0 itself (`pdn_linear_rowmax_split_supported` then answers 0); this attribute is
     # the in-process form of the same A/B switch.
     split_forward = True
+    # the same for the input-gradient product of the deferred form (csrc/lm_head_dx_split.hip; library switch
+    # PDN_LMHEAD_DX_SPLIT=0, after which `pdn_linear_ce_dx_deferred_split_supported` answers 0)
+    split_dx = True
 
     @staticmethod
     def applicable(x, w, b, targets, reduction="mean"):
@@ -400,8 +403,13 @@ class linear_cross_entropy(_Operator):
                        x2._strides[0], V, V, hp.stream())
             self._dxu = hp.empty((n, fin), np.float32)
             self._w_ptr = wd._ptr                          # (backward checks that the weight was not re-homed meanwhile)
-            ws, wsb = hp.workspace(L.query("pdn_linear_ce_dx_deferred_workspace_bytes", n, V, fin))
-            L.call("pdn_linear_ce_dx_deferred_f32", logits._ptr, rowmax._ptr, parts, self._t._ptr,
+            # the logits split on the fly, W once per call: the same three-product form as the projection above
+            dx_entry = "pdn_linear_ce_dx_deferred_f32"
+            if (linear_cross_entropy.split_dx and _lib.provides("pdn_linear_ce_dx_deferred_split_f32")
+                    and L.query("pdn_linear_ce_dx_deferred_split_supported", n, V, fin)):
+                dx_entry = "pdn_linear_ce_dx_deferred_split_f32"
+            ws, wsb = hp.workspace(L.query(dx_entry.replace("_f32", "_workspace_bytes"), n, V, fin))
+            L.call(dx_entry, logits._ptr, rowmax._ptr, parts, self._t._ptr,
                    1.0 / n if mean else 1.0, wd._ptr, self._dxu._ptr, lse._ptr, n, V, fin, ws, wsb, hp.stream())
             L.call("pdn_cross_entropy_from_lse_f32", logits._ptr, V, lse._ptr, self._t._ptr, n, V, mean, loss_row._ptr,
                    out._ptr, hp.err_flag_ptr(), hp.stream())

@@ -34,7 +34,8 @@ enum {
   PDN_CNT_ATT_RES_FWD = 9,        // attention_fwd_kernel (resident, chunked)
   PDN_CNT_ATT_RES_BWD = 10,
   PDN_CNT_ATT_STREAM = 11,        // attn_*_stream_kernel, forward or backward
-  PDN_CNT_CE_DX_DEFERRED = 12,    // gemm_outres_kernel<.., CE 2>: lm_head input gradient + sum of exponentials
+  PDN_CNT_CE_DX_DEFERRED = 12,    // lm_head input gradient + sum of exponentials: gemm_outres_kernel<.., CE 2>, or the
+                                  // split-fp16 kernel of csrc/lm_head_dx_split.hip (which counts in 39 as well)
   PDN_CNT_CE_DW = 13,             // gemm_outres_tn_kernel with the cross-entropy gradient formed inside
   PDN_CNT_OUTRES = 14,            // gemm_outres_kernel, plain
   PDN_CNT_OUTRES_TN = 15,         // gemm_outres_tn_kernel, plain
@@ -62,7 +63,8 @@ enum {
   PDN_CNT_LOGPROBS = 36,          // token log-probabilities (csrc/logprobs.hip): the rows entry and the tick form
   PDN_CNT_LMHEAD_SPLIT = 37,      // lm_head forward on split-fp16 MFMA (csrc/lm_head_split.hip): also counts in 5
   PDN_CNT_PREFIX = 38,            // prefix caching (csrc/prefix.hip): the row-to-row copy of Llama.serve(prefix_cache=...)
-  PDN_CNT_SLOTS = 39
+  PDN_CNT_CE_DX_SPLIT = 39,       // lm_head input gradient on split-fp16 MFMA (csrc/lm_head_dx_split.hip): also counts in 12
+  PDN_CNT_SLOTS = 40
 };
 void pdn_count(int slot);
 

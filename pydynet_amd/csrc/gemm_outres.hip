@@ -630,6 +630,13 @@ __global__ __launch_bounds__(256) void outres_wt_transpose_kernel(const float* _
     if (v0 + r < V) Wt[(int64_t)(v0 + r) * OR_N + k0 + tx] = tile[tx][r];
 }
 
+// (for csrc/lm_head_dx_split.hip, whose store reads the rows W[:, target] from the same copy)
+int pdn_outres_wt_transpose_launch(const float* W, int64_t ldw, int V, float* Wt, void* stream) {
+  hipLaunchKernelGGL(outres_wt_transpose_kernel, dim3((V + 31) / 32, OR_N / 32), dim3(256), 0, (hipStream_t)stream, W, ldw, V, Wt);
+  PDN_LAUNCH_CHECK();
+  return PDN_OK;
+}
+
 extern "C" int pdn_linear_ce_dx_deferred_supported(int64_t M, int V, int K) {
   return (K == OR_N && V % OR_KP == 0 && V >= OR_KP && M >= 1 && M < (1ll << 31) && (int64_t)OR_N * V < (1ll << 30)) ? 1 : 0;
 }

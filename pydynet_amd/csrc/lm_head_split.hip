@@ -33,6 +33,7 @@
 // one whole 128-byte line -- which brought the launch to 6.8 ms (stores off: 5.7 ms = 1.26 PFLOP/s of f16 MFMA).
 // Deterministic: fixed order, no atomics.
 #include "common.h"
+#include "lm_head_split.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -48,30 +49,8 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 #define LS_STG (32 * 144)                 // a wave's leaving tile on its way out: 32 rows of 32 floats, 16 bytes of padding each
 #define LS_MIN_ROWS 16384
 
-// Timing-ablation switch (tools/lmhead_probe.py), read ONCE per process and announced: a non-zero value makes the kernel
-// skip its stores, i.e. the logits are WRONG.
-static int ls_env_switch(const char* name, int dflt, const char* what) {
-  const char* e = getenv(name);
-  const int v = e ? atoi(e) : dflt;
-  if (v != dflt) fprintf(stderr, "[pdnhip] WARNING: %s=%d -- %s\n", name, v, what);
-  return v;
-}
-
-// the exponent that puts `amax` into [2^8, 2^9); 0 for an all-zero and for a non-finite row / column (whose Inf / NaN
-// then reach the product as they are: its logits come out non-finite like those of the fp32 kernel).
-// frexp: amax = f 2^E, f in [0.5, 1), subnormals included, so the result lies in [-119, 157]: clamped by construction,
-// and applied by ldexp -- 2^157 is never formed as a float.
-__device__ __forceinline__ int ls_shift(float amax) {
-  if (!(amax < INFINITY) || amax == 0.f) return 0;
-  int E;
-  (void)frexpf(amax, &E);
-  return 9 - E;
-}
-__device__ __forceinline__ void ls_split(float a, int sh, _Float16& h, _Float16& l) {
-  const float t = ldexpf(a, sh);
-  h = (_Float16)t;
-  l = (_Float16)((t - (float)h) * 2048.f);
-}
+// (switches, ls_shift, ls_split: lm_head_split.h.  PDN_LMHEAD_SPLIT_ABLATE, tools/lmhead_probe.py: a non-zero value makes
+// the kernel skip its stores, i.e. the logits are WRONG.)
 
 // ---- x: one wave per row ------------------------------------------------------------------------------------------
 // rows M .. Mpad - 1 (Mpad: a multiple of 256) are written as zeros, so that every wave of the product kernel loads
