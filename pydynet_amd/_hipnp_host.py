@@ -1,6 +1,6 @@
 """Host-visible values of device arrays (one part of ``pydynet_amd.hipnp``, re-exported there): arrays whose host
 value arrives by itself (`readback_array`), mapped pinned host blocks, `read_later` (a copy + event of its own instead of
-a blocking copy on the compute stream) and the `Mailbox` a kernel stores into directly (greedy decode, llm/llama.py).
+a blocking copy on the compute stream) and the `Mailbox` a kernel stores into directly (greedy decode, llm/decode_steps.py).
 Split out of hipnp.py in round 5; nothing here computes."""
 from __future__ import annotations
 
@@ -18,7 +18,7 @@ class readback_array(ndarray):
     """A device array whose HOST value arrives by itself: its producer leaves it in host-visible memory
     (`Mailbox.slot`: a kernel stores straight into mapped host memory); `get()` / `item()` wait for THAT value only
     instead of synchronising the compute stream -- which may already be running later work (the next decode step,
-    llm/llama.py).  Basic-index views (`a[0]`) keep the property.  Writing into the array drops the host value: it is
+    llm/decode_steps.py).  Basic-index views (`a[0]`) keep the property.  Writing into the array drops the host value: it is
     an ordinary device array from then on."""
 
     __slots__ = ("_rb", "_host")
