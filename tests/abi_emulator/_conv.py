@@ -19,6 +19,8 @@ class ConvMixin:
         return oh, ow, (N, C, k, k, oh, ow), (s0, s1, s2, s3, s2 * s, s3 * s)
 
     def pdn_im2col2d_f32(self, x, N, C, H, W, k, s, p, col, rows, ones_row, stream):
+        if N and (rows < C * k * k + (1 if ones_row else 0) or rows > 65535 or N > 65535):
+            return -1                                   # no room for the ones row, or past the launch's grid limits
         xp = np.pad(flat(x, N * C * H * W).reshape(N, C, H, W), [(0, 0), (0, 0), (p, p), (p, p)])
         oh, ow, shape, strides = self._windows(xp, k, s)
         ckk, M = C * k * k, oh * ow
