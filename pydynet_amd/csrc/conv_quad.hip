@@ -514,9 +514,16 @@ __global__ __launch_bounds__(512, 1) void conv_quad_wgrad_kernel(const float* __
     for (int i = 0; i < NW; ++i) dm[i] = oc < O ? hb[i] : 0u;
   };
   // B operand bases of this lane's columns (floats, buffer 0)
+  // (the plane of ones lies behind BOTH image buffers and does not move with them: bit t of ones_lane marks a bias /
+  //  padding column, whose base stays where it is when the buffers flip)
   int bb[CT];
+  unsigned ones_lane = 0;
 #pragma unroll
-  for (int t = 0; t < CT; ++t) bb[t] = 4 * perm.slot[t * 32 + l31] + row0 * W + 4 * half;
+  for (int t = 0; t < CT; ++t) {
+    const int slot = perm.slot[t * 32 + l31];
+    bb[t] = 4 * slot + row0 * W + 4 * half;
+    if (slot >= G::ONES / 4) ones_lane |= 1u << t;
+  }
 
   f32x16 acc[CT];
 #pragma unroll
@@ -544,13 +551,15 @@ __global__ __launch_bounds__(512, 1) void conv_quad_wgrad_kernel(const float* __
     issue_x(nn);
     issue_dy(nn);
     __builtin_amdgcn_sched_barrier(0);
-    const float* fb = lds + buf * BUF;
+    int cb[CT];
+#pragma unroll
+    for (int t = 0; t < CT; ++t) cb[t] = bb[t] + (((ones_lane >> t) & 1u) ? 0 : buf * BUF);
     // step i = (row yy, position group g, column tile t); the B fragment of step i + 1 is in flight while step i multiplies
     constexpr int NS = RW * GPR * CT;
     f32x4 b[2];
     auto load_b = [&](int i, f32x4& bf) {
       const int t = i % CT, kg = i / CT, g = kg % GPR, yy = kg / GPR;
-      bf = *reinterpret_cast<const f32x4*>(fb + bb[t] + yy * W + 8 * g);
+      bf = *reinterpret_cast<const f32x4*>(lds + cb[t] + yy * W + 8 * g);
     };
     load_b(0, b[0]);
     float a[4];

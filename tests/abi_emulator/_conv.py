@@ -58,6 +58,8 @@ class ConvMixin:
         return np.lib.stride_tricks.as_strided(xp, shape, strides).reshape(N, C * k * k, oh * ow), oh, ow
 
     def pdn_conv2d_fwd_f32(self, x, w, bias, y, N, C, H, W, O, k, s, p, stream):
+        if N and not self.pdn_conv2d_direct_supported(C, H, W, O, k, s, p) & 1:
+            return -2                                   # PDN_EUNSUPPORTED, as the library: nothing is written
         col, oh, ow = self._conv_cols(x, N, C, H, W, k, s, p)
         out = np.matmul(flat(w, O * C * k * k).reshape(O, -1), col)
         if bias:
@@ -66,6 +68,8 @@ class ConvMixin:
         return 0
 
     def pdn_conv2d_bwd_data_f32(self, dy, w, dx, N, C, H, W, O, k, s, p, stream):
+        if N and not self.pdn_conv2d_direct_supported(C, H, W, O, k, s, p) & 2:
+            return -2
         oh, ow = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
         g = flat(dy, N * O * oh * ow).reshape(N, O, oh * ow)
         dcol = np.matmul(flat(w, O * C * k * k).reshape(O, -1).T, g)
@@ -78,6 +82,8 @@ class ConvMixin:
     def pdn_conv2d_bwd_weight_workspace_bytes(self, N, C, H, W, O, k, s, p): return 4096
 
     def pdn_conv2d_bwd_weight_f32(self, x, dy, dw, db, acc, N, C, H, W, O, k, s, p, ws, wsb, stream):
+        if N and not self.pdn_conv2d_direct_supported(C, H, W, O, k, s, p) & 4:
+            return -2
         col, oh, ow = self._conv_cols(x, N, C, H, W, k, s, p)
         g = flat(dy, N * O * oh * ow).reshape(N, O, oh * ow)
         if dw:

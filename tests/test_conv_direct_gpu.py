@@ -7,6 +7,8 @@ im2col + GEMM path of the same library.  fp32 MFMA accumulates in another order 
 import numpy as np
 import pytest
 
+from tests.conv_ref import conv_ref as _ref         # the float64 statement, shared with tests/test_conv_variants.py
+
 pytestmark = pytest.mark.gpu
 
 CASES = [   # N, C, H, W, O, k, stride, pad
@@ -19,26 +21,6 @@ CASES = [   # N, C, H, W, O, k, stride, pad
     (3, 8, 12, 12, 16, 1, 1, 0),      # 1x1 taps
     (2, 6, 10, 10, 12, 5, 1, 2),      # 5x5 same-size
 ]
-
-
-def _ref(x, w, b, g, s, p):
-    x, w, g = x.astype(np.float64), w.astype(np.float64), g.astype(np.float64)
-    N, C, H, W = x.shape
-    O, _, k, _ = w.shape
-    xp = np.pad(x, [(0, 0), (0, 0), (p, p), (p, p)])
-    oh, ow = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-    s0, s1, s2, s3 = xp.strides
-    col = np.lib.stride_tricks.as_strided(xp, (N, C, k, k, oh, ow), (s0, s1, s2, s3, s2 * s, s3 * s))
-    a = col.transpose(0, 4, 5, 1, 2, 3).reshape(N * oh * ow, -1)
-    y = (a @ w.reshape(O, -1).T + (b.astype(np.float64) if b is not None else 0)).reshape(N, oh, ow, O).transpose(0, 3, 1, 2)
-    g2 = g.transpose(0, 2, 3, 1).reshape(N * oh * ow, O)
-    dw = (g2.T @ a).reshape(w.shape)
-    db = g2.sum(0)
-    dcol = (g2 @ w.reshape(O, -1)).reshape(N, oh, ow, C, k, k).transpose(0, 3, 4, 5, 1, 2)
-    dxp = np.zeros_like(xp)
-    t0, t1, t2, t3 = dxp.strides
-    np.add.at(np.lib.stride_tricks.as_strided(dxp, (N, C, k, k, oh, ow), (t0, t1, t2, t3, t2 * s, t3 * s)), (...,), dcol)
-    return y, dxp[:, :, p:p + H, p:p + W], dw, db
 
 
 def _close(a, b, what):

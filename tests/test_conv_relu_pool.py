@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from tests.conftest import device_variants
+from tests.conv_ref import conv_relu_pool_ref as _ref   # float64, reference tie semantics (shared with tests/test_conv_variants.py)
 
 CASES = [   # N, C, H, W, O     (k = 3, stride 1, pad 1)
     (5, 3, 32, 32, 20),       # LeNet conv1 (OW = 32: the window's rows are two chunks of one wave)
@@ -23,31 +24,6 @@ CASES = [   # N, C, H, W, O     (k = 3, stride 1, pad 1)
     (3, 6, 8, 8, 12),         # OW = 8: four rows per chunk
     (2, 4, 16, 32, 7),        # rectangular, odd channel count
 ]
-
-
-def _ref(x, w, b, gp):
-    """float64: pooled output and the gradients of sum(pooled * gp) w.r.t. x, w, b (reference tie semantics)."""
-    x, w, b, gp = (a.astype(np.float64) for a in (x, w, b, gp))
-    N, C, H, W = x.shape
-    O = w.shape[0]
-    xp = np.pad(x, [(0, 0), (0, 0), (1, 1), (1, 1)])
-    s0, s1, s2, s3 = xp.strides
-    col = np.lib.stride_tricks.as_strided(xp, (N, C, 3, 3, H, W), (s0, s1, s2, s3, s2, s3))
-    a = col.transpose(0, 4, 5, 1, 2, 3).reshape(N * H * W, -1)
-    y = (a @ w.reshape(O, -1).T + b).reshape(N, H, W, O).transpose(0, 3, 1, 2)
-    r = np.maximum(0.0, y)
-    win = r.reshape(N, O, H // 2, 2, W // 2, 2)
-    pooled = win.max((3, 5))
-    dr = ((win == pooled[:, :, :, None, :, None]) * gp[:, :, :, None, :, None]).reshape(N, O, H, W)
-    dy = (r == y) * dr                                     # maximum(0., y): the gradient passes where out == y
-    g2 = dy.transpose(0, 2, 3, 1).reshape(N * H * W, O)
-    dw = (g2.T @ a).reshape(w.shape)
-    db = g2.sum(0)
-    dcol = (g2 @ w.reshape(O, -1)).reshape(N, H, W, C, 3, 3).transpose(0, 3, 4, 5, 1, 2)
-    dxp = np.zeros_like(xp)
-    t0, t1, t2, t3 = dxp.strides
-    np.add.at(np.lib.stride_tricks.as_strided(dxp, (N, C, 3, 3, H, W), (t0, t1, t2, t3, t2, t3)), (...,), dcol)
-    return pooled, dxp[:, :, 1:-1, 1:-1], dw, db
 
 
 def _run(dev, x, w, b, gp, defer, x_grad=True):
