@@ -10,16 +10,40 @@ CPU tests compare against the oracle at fp32 round-off.
 from pydynet_amd import _lib
 from ._base import _NP, _ints, view, flat  # noqa: F401
 from ._runtime import RuntimeMixin
-from ._gemm import GemmMixin
+from ._gemm import GemmMixin, counters  # noqa: F401
 from ._pointwise import PointwiseMixin
 from ._attention import AttentionMixin
 from ._decode import DecodeMixin
 from ._recurrent_norm import RecurrentNormMixin
 from ._conv import ConvMixin
+from ._clip import ClipMixin
+from ._sampling import SamplingMixin, margin, read_sample_params  # noqa: F401
+from ._decode_rows import DecodeRowsMixin, candidates, gemm_np  # noqa: F401
+from ._extend import ExtendMixin, append_np, copy_prefix_np, draft_np, extend_np, rotate, settle_np  # noqa: F401
+from ._beam import BeamMixin
+from ._penalty import PenaltyMixin, apply_np, bits_to_rows, penalty_chunks, read_penalty_params, reset_np  # noqa: F401
+from ._logprobs import LogprobsMixin, logprobs_chunks, work_bytes  # noqa: F401
+
+# entries of include/pdn_hip.h that the emulator leaves out: `_lib.provides` answers False and the callers take their
+# other path (the split-fp16 lm_head, hipGraph capture and its pool) or never ask on this library (the rest)
+NOT_EMULATED = (
+    "pdn_linear_rowmax_split_supported", "pdn_linear_rowmax_split_workspace_bytes", "pdn_linear_rowmax_split_parts",
+    "pdn_linear_rowmax_split_fwd_f32", "pdn_linear_ce_dx_deferred_split_supported",
+    "pdn_linear_ce_dx_deferred_split_workspace_bytes", "pdn_linear_ce_dx_deferred_split_f32",
+    "pdn_graph_destroy", "pdn_graph_end_capture", "pdn_graph_launch", "pdn_pool_destroy", "pdn_pool_stats",
+    "pdn_adam_multi_tick_f32", "pdn_device_info", "pdn_gemm_prof_collect", "pdn_get_device", "pdn_last_error")
 
 
-class EmulatedLib(RuntimeMixin, GemmMixin, PointwiseMixin, AttentionMixin, DecodeMixin, RecurrentNormMixin, ConvMixin):
-    """Every `pdn_*` entry point of include/pdn_hip.h, one mixin per kernel family (round 6: split out of one 1670-line file)."""
+class EmulatedLib(RuntimeMixin, GemmMixin, PointwiseMixin, AttentionMixin, DecodeMixin, RecurrentNormMixin, ConvMixin,
+                  ClipMixin, SamplingMixin, DecodeRowsMixin, ExtendMixin, BeamMixin, PenaltyMixin, LogprobsMixin):
+    """Every `pdn_*` entry point of include/pdn_hip.h but NOT_EMULATED, one mixin per kernel family."""
+
+
+def remove(monkeypatch, emu, *names):
+    """A library without the entries `names` for the rest of the test: each is deleted from the mixin that defines it, so
+    `_lib.provides(name)` answers False."""
+    for name in names:
+        monkeypatch.delattr(next(c for c in type(emu).__mro__ if name in vars(c)), name)
 
 
 def install(monkeypatch):

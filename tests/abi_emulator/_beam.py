@@ -1,33 +1,14 @@
-"""TEST-ONLY NumPy statements of the beam-search entry points of include/pdn_hip.h (csrc/beam.hip: the top-k, select and
-KV-cache reorder launches), attached to the emulated library of tests/abi_emulator by the `beam_emulated` fixture below,
-with launch counter 32 next to the wide-decode slot 31 (tests/wide_abi_emulation.py).  They run the statement of
-pydynet_amd/llm/beam.py, so the emulated fast path and the `cpu` device compute the same bits."""
-import ctypes
-
+"""The beam-search entry points (csrc/beam.hip): the top-k, select and KV-cache reorder launches, launch counter 32.  They
+run the statement of pydynet_amd/llm/beam.py, so the emulated fast path and the `cpu` device compute the same bits.
+(One part of the TEST-ONLY host emulation of the pdnhip C ABI: see tests/abi_emulator/__init__.py.)"""
 import numpy as np
-import pytest
 
 from pydynet_amd.llm import beam
-from tests import wide_abi_emulation
-from tests.abi_emulator import flat, view
-from tests.wide_abi_emulation import wide_emulated  # noqa: F401  (fixture)
-
-SLOTS = 33
+from ._base import view, flat
 
 
-def attach(monkeypatch, emu):
-    count = [0]
-    base_counters = emu.pdn_kernel_counters
-
-    def pdn_kernel_counters(out, n, reset):
-        base_counters(out, n, reset)
-        if out and int(n) > 32:
-            ctypes.cast(out, ctypes.POINTER(ctypes.c_int64))[32] = count[0]
-        if reset:
-            count[0] = 0
-        return 0
-
-    def pdn_beam_topk_rows_f32(logits, rs, B, V, W, first, pos, stops, S, cand_lp, cand_id, stop_lp, stream):
+class BeamMixin:
+    def pdn_beam_topk_rows_f32(self, logits, rs, B, V, W, first, pos, stops, S, cand_lp, cand_id, stop_lp, stream):
         if B == 0:
             return 0
         if not (logits and cand_lp and cand_id and 1 <= W <= 16 and 0 <= S <= 16 and V - S >= W and rs >= V
@@ -44,11 +25,11 @@ def attach(monkeypatch, emu):
             flat(cand_id, B * W, np.int32).reshape(B, W)[rows] = ids
             if S:
                 flat(stop_lp, B * S).reshape(B, S)[rows] = slp
-        count[0] += 1
+        self._count(32)
         return 0
 
-    def pdn_beam_select_f32(cand_lp, cand_id, stop_lp, stops, S, G, W, first, scores, next_ids, parent, pos, step, arrive,
-                            live_acc, hist, n_hist, fin_n, fin, live_out, n_live, emb, emb_rs, D, x_next, stream):
+    def pdn_beam_select_f32(self, cand_lp, cand_id, stop_lp, stops, S, G, W, first, scores, next_ids, parent, pos, step,
+                            arrive, live_acc, hist, n_hist, fin_n, fin, live_out, n_live, emb, emb_rs, D, x_next, stream):
         if G == 0:
             return 0
         if not (cand_lp and cand_id and scores and next_ids and parent and pos and step and arrive and live_acc and fin_n
@@ -92,10 +73,10 @@ def attach(monkeypatch, emu):
         if live_out and s < n_live:
             flat(live_out + 8 * s, 1, np.int64)[0] = live
         flat(step, 1, np.int32)[0] = s + 1
-        count[0] += 1
+        self._count(32)
         return 0
 
-    def pdn_kv_reorder_rows_f32(caches, n_tensors, bs, B, max_len, D, parent, pos, stream):
+    def pdn_kv_reorder_rows_f32(self, caches, n_tensors, bs, B, max_len, D, parent, pos, stream):
         if n_tensors == 0 or B == 0:
             return 0
         if not (caches and parent and pos and 0 < B <= 256 and D % 4 == 0 and bs >= max_len * D):
@@ -108,23 +89,5 @@ def attach(monkeypatch, emu):
                 n = min(int(P[r]), max_len)
                 if par[r] != r and 0 <= par[r] < B and n > 0:
                     rows[r, :n * D] = old[par[r], :n * D]
-        count[0] += 1
+        self._count(32)
         return 0
-
-    for name, f in list(locals().items()):
-        if name.startswith("pdn_"):
-            monkeypatch.setattr(emu, name, f, raising=False)
-    return emu
-
-
-@pytest.fixture()
-def beam_emulated(wide_emulated, monkeypatch):  # noqa: F811
-    """The emulated C ABI with every decode entry point up to the wide step and the beam-search entry points attached."""
-    from pydynet_amd import _lib
-    attach(monkeypatch, _lib._LIB)
-    yield wide_emulated
-
-
-def counters(n=SLOTS):
-    """Launch counters 0 .. n-1 since the last call (reset after reading)."""
-    return wide_abi_emulation.counters(n)

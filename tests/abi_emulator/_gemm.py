@@ -8,6 +8,15 @@ import numpy as np  # noqa: F401
 from pydynet_amd import _lib  # noqa: F401
 from ._base import _NP, _ints, view, flat  # noqa: F401
 
+SLOTS = 40                                       # PDN_CNT_SLOTS of csrc/common.h
+
+
+def counters(n=SLOTS):
+    """Launch counters 0 .. n-1 since the last call (reset after reading), from whichever library is installed."""
+    buf = (ctypes.c_int64 * n)()
+    _lib.lib().call("pdn_kernel_counters", buf, n, 1)
+    return [int(v) for v in buf]
+
 
 class GemmMixin:
     # -- gemm -------------------------------------------------------------------------------
@@ -76,17 +85,16 @@ class GemmMixin:
     #    the library would have launched for the same arguments (its dispatch rules restated), so the gates of bench.py
     #    and the path assertions of the tests run without a GPU
     def _count(self, slot):
-        self._counters = getattr(self, "_counters", [0] * 24)
-        self._counters[slot] += 1
+        self.__dict__.setdefault("_counters", [0] * SLOTS)[slot] += 1
 
     def pdn_kernel_counters(self, out, n, reset):
-        c = getattr(self, "_counters", [0] * 24)
+        c = self.__dict__.setdefault("_counters", [0] * SLOTS)
         if out:
             arr = ctypes.cast(out, ctypes.POINTER(ctypes.c_int64))
-            for i in range(min(int(n), 24)):
+            for i in range(min(int(n), SLOTS)):
                 arr[i] = c[i]
         if reset:
-            self._counters = [0] * 24
+            c[:] = [0] * SLOTS
         return 0
 
     @staticmethod

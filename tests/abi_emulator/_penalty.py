@@ -1,23 +1,16 @@
-"""TEST-ONLY NumPy statements of the penalty entry points of include/pdn_hip.h (csrc/penalty.hip: the reset and the two
-apply entries), attached to the emulated library of tests/abi_emulator by the `penalty_emulated` fixture below, with launch
-counter 35 next to the speculative slot 34 (tests/speculative_abi_emulation.py).  `apply_np` / `reset_np` are also the
-references of the GPU tests; both follow pydynet_amd/llm/penalties.py."""
-import ctypes
-
+"""The penalty entry points (csrc/penalty.hip): the reset and the two apply entries, launch counter 35.  `apply_np` /
+`reset_np` are also the references of the GPU tests; both follow pydynet_amd/llm/penalties.py.
+(One part of the TEST-ONLY host emulation of the pdnhip C ABI: see tests/abi_emulator/__init__.py.)"""
 import numpy as np
-import pytest
 
 from pydynet_amd.llm import penalties
-from tests import speculative_abi_emulation
-from tests.abi_emulator import flat, view
-from tests.speculative_abi_emulation import speculative_emulated  # noqa: F401  (fixture)
+from ._base import view, flat
 
-SLOTS = 36
-CHUNK = 1024                                     # vocabulary tokens per workgroup of csrc/penalty.hip
+PENALTY_CHUNK = 1024                                     # vocabulary tokens per workgroup of csrc/penalty.hip
 
 
-def chunks(V):
-    return -(-V // CHUNK) if V > 0 else 0
+def penalty_chunks(V):
+    return -(-V // PENALTY_CHUNK) if V > 0 else 0
 
 
 def bits_to_rows(words, V):
@@ -45,7 +38,7 @@ def apply_np(z, params, counts=None, seen=None, pos=None, start=None, ids=None, 
     1024-token chunk: its first maximum (rows skipped: unset, NaN / -1)."""
     B, V = z.shape
     r, p, f = params
-    n = chunks(V)
+    n = penalty_chunks(V)
     cv, ci = np.full((B, n), np.nan, np.float32), np.full((B, n), -1, np.int32)
     for b in range(B):
         pb = 0 if pos is None else int(pos[b])
@@ -57,32 +50,21 @@ def apply_np(z, params, counts=None, seen=None, pos=None, start=None, ids=None, 
         s = np.zeros(V, bool) if seen is None else bits_to_rows(seen[b:b + 1], V)[0]
         z[b] = penalties.penalize(z[b:b + 1], c[None], s[None], r, p, f)[0]
         for j in range(n):
-            seg = z[b, j * CHUNK:(j + 1) * CHUNK]
+            seg = z[b, j * PENALTY_CHUNK:(j + 1) * PENALTY_CHUNK]
             k = int(np.argmax(seg))
-            cv[b, j], ci[b, j] = seg[k], j * CHUNK + k
+            cv[b, j], ci[b, j] = seg[k], j * PENALTY_CHUNK + k
     return cv, ci
 
 
-def read_params(ptr):
+def read_penalty_params(ptr):
     return tuple(float(v) for v in np.array(flat(ptr, 4, np.float32))[:3])
 
 
-def attach(monkeypatch, emu):
-    count = [0]
-    base_counters = emu.pdn_kernel_counters
+class PenaltyMixin:
+    def pdn_penalty_chunks(self, V):
+        return penalty_chunks(V)
 
-    def pdn_kernel_counters(out, n, reset):
-        base_counters(out, n, reset)
-        if out and int(n) > 35:
-            ctypes.cast(out, ctypes.POINTER(ctypes.c_int64))[35] = count[0]
-        if reset:
-            count[0] = 0
-        return 0
-
-    def pdn_penalty_chunks(V):
-        return chunks(V)
-
-    def pdn_penalty_reset(counts, seen, start, B, V, rows, n_rows, ids, offsets, stream):
+    def pdn_penalty_reset(self, counts, seen, start, B, V, rows, n_rows, ids, offsets, stream):
         if n_rows == 0:
             return 0
         if not (counts and seen and start and rows and offsets and B > 0 and V > 0 and n_rows > 0):
@@ -91,10 +73,10 @@ def attach(monkeypatch, emu):
         reset_np(flat(counts, B * V, np.int32).reshape(B, V), flat(seen, B * -(-V // 32), np.int32).reshape(B, -1),
                  flat(start, B, np.int32), np.array(flat(rows, n_rows, np.int32)),
                  np.array(flat(ids, int(off[-1]), np.int64)) if ids else np.zeros(0, np.int64), off)
-        count[0] += 1
+        self._count(35)
         return 0
 
-    def apply(logits, rs, B, V, params, counts, seen, pos, pos_rows, cand_v, cand_i, start=None, ids=None, cnt=False):
+    def _apply(self, logits, rs, B, V, params, counts, seen, pos, pos_rows, cand_v, cand_i, start=None, ids=None, cnt=False):
         Z = view(logits, (B, V), (rs, 1), np.float32)
         C = flat(counts, B * V, np.int32).reshape(B, V) if counts else None
         S = np.array(flat(seen, B * -(-V // 32), np.int32)).reshape(B, -1) if seen else None
@@ -106,47 +88,29 @@ def attach(monkeypatch, emu):
         fed = np.array(flat(ids, B, np.int64)) if ids else None
         z = np.array(Z)
         c64 = None if C is None else C.astype(np.int64)
-        cv, ci = apply_np(z, read_params(params), c64, S, P, st, fed, cnt)
+        cv, ci = apply_np(z, read_penalty_params(params), c64, S, P, st, fed, cnt)
         Z[...] = z
         if C is not None and cnt:
             C[...] = c64
         if cand_v:
-            n = chunks(V)
+            n = penalty_chunks(V)
             V_, I_ = flat(cand_v, B * n, np.float32).reshape(B, n), flat(cand_i, B * n, np.int32).reshape(B, n)
             live = ~np.isnan(cv[:, 0]) if n else np.zeros(B, bool)
             V_[live], I_[live] = cv[live], ci[live]
-        count[0] += 1
+        self._count(35)
         return 0
 
-    def pdn_penalty_step_f32(logits, rs, B, V, params, counts, seen, start, ids, pos, pos_per_row, cand_v, cand_i,
+    def pdn_penalty_step_f32(self, logits, rs, B, V, params, counts, seen, start, ids, pos, pos_per_row, cand_v, cand_i,
                              stream):
         if B == 0:
             return 0
         if not (logits and params and counts and seen and start and ids and pos and V > 0 and rs >= V):
             return -1
-        return apply(logits, rs, B, V, params, counts, seen, pos, pos_per_row, cand_v, cand_i, start, ids, True)
+        return self._apply(logits, rs, B, V, params, counts, seen, pos, pos_per_row, cand_v, cand_i, start, ids, True)
 
-    def pdn_penalty_rows_f32(logits, rs, B, V, params, counts, seen, pos, cand_v, cand_i, stream):
+    def pdn_penalty_rows_f32(self, logits, rs, B, V, params, counts, seen, pos, cand_v, cand_i, stream):
         if B == 0:
             return 0
         if not (logits and params and V > 0 and rs >= V):
             return -1
-        return apply(logits, rs, B, V, params, counts, seen, pos, 1, cand_v, cand_i)
-
-    for name, f in list(locals().items()):
-        if name.startswith("pdn_"):
-            monkeypatch.setattr(emu, name, f, raising=False)
-    return emu
-
-
-@pytest.fixture()
-def penalty_emulated(speculative_emulated, monkeypatch):  # noqa: F811
-    """The emulated C ABI with every decode entry point up to speculative decoding and the penalty entry points."""
-    from pydynet_amd import _lib
-    attach(monkeypatch, _lib._LIB)
-    yield speculative_emulated
-
-
-def counters(n=SLOTS):
-    """Launch counters 0 .. n-1 since the last call (reset after reading)."""
-    return speculative_abi_emulation.counters(n)
+        return self._apply(logits, rs, B, V, params, counts, seen, pos, 1, cand_v, cand_i)

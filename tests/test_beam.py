@@ -1,6 +1,6 @@
 """Beam search (`Llama.beam_search`) on the CPU: the statement of pydynet_amd/llm/beam.py, its identities (one beam is
 `generate_ragged`; enough beams give the exact top-W of all sequences), and the emulated C ABI with the entry points of
-tests/beam_abi_emulation.py (the beam plan at every fused level, rows form and wide step, graph and no graph, the
+tests/abi_emulator/_beam.py (the beam plan at every fused level, rows form and wide step, graph and no graph, the
 generic HIP step) against the `cpu` device, bit for bit."""
 import itertools
 
@@ -11,12 +11,7 @@ import pydynet_amd as pdn
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm import beam
 from pydynet_amd.llm.llama import Llama
-from tests.beam_abi_emulation import beam_emulated, counters  # noqa: F401  (fixture)
-from tests.clip_abi_emulation import clip_emulated  # noqa: F401  (fixture)
-from tests.ragged_abi_emulation import ragged_emulated  # noqa: F401  (fixture)
-from tests.sampling_abi_emulation import sampling_emulated  # noqa: F401  (fixture)
-from tests.serve_abi_emulation import serve_emulated  # noqa: F401  (fixture)
-from tests.wide_abi_emulation import wide_emulated  # noqa: F401  (fixture)
+from tests.abi_emulator import counters
 
 V = 64
 
@@ -180,7 +175,7 @@ CASES = [([3, 1, 6], 2, (), 7), ([2, 5], 4, (7, 11, 30), 8), ([4], 8, (5,), 6), 
 @pytest.mark.parametrize("fused", [2, 1, 0])
 @pytest.mark.parametrize("graph", [True, False])
 @pytest.mark.parametrize("case", range(len(CASES)))
-def test_emulated_fast_path_matches_cpu(beam_emulated, monkeypatch, fused, graph, case):
+def test_emulated_fast_path_matches_cpu(emulated_hip, monkeypatch, fused, graph, case):
     Graph.clear()
     lens, W, stops, n = CASES[case]
     prompts = _prompts(lens, seed=case)
@@ -197,7 +192,7 @@ def test_emulated_fast_path_matches_cpu(beam_emulated, monkeypatch, fused, graph
     assert m._decode_st["wide"] == (len(lens) * W > 8)
 
 
-def test_emulated_generic_step_matches_cpu(beam_emulated, monkeypatch):
+def test_emulated_generic_step_matches_cpu(emulated_hip, monkeypatch):
     """wide_decode = False past 8 rows: the generic per-row step, the beam launches one by one."""
     Graph.clear()
     lens, W, stops, n = CASES[3]
@@ -212,7 +207,7 @@ def test_emulated_generic_step_matches_cpu(beam_emulated, monkeypatch):
     assert c[32] >= 3 * n - 2 and m._decode_st is None or not m._decode_st["ok"]
 
 
-def test_groups_finish_at_different_steps(beam_emulated):
+def test_groups_finish_at_different_steps(emulated_hip):
     """Many stop ids: groups end early and at different steps; the emulated path still equals the cpu device."""
     Graph.clear()
     prompts = _prompts([2, 3, 5, 1], seed=9)
@@ -224,7 +219,7 @@ def test_groups_finish_at_different_steps(beam_emulated):
     assert len(set(ends)) > 1, ends
 
 
-def test_greedy_generate_unchanged_around_beam_search(beam_emulated):
+def test_greedy_generate_unchanged_around_beam_search(emulated_hip):
     Graph.clear()
     m = _model("hip:0")
     ids = np.random.default_rng(3).integers(0, V, (2, 4))

@@ -7,7 +7,7 @@ import pydynet_amd as pdn
 from pydynet_amd import _lib
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm.llama import Llama
-from tests.beam_abi_emulation import counters
+from tests.abi_emulator import counters
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32

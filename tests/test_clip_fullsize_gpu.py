@@ -9,7 +9,7 @@ import pydynet_amd as pdn
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm.clip import CLIP
 from pydynet_amd.optim import SGD
-from tests.clip_abi_emulation import counters
+from tests.abi_emulator import counters
 
 RT = 1e-4
 

@@ -27,3 +27,15 @@ def test_kernel_test_body_on_emulator(emulated_hip, name, kw):
     if "hip" not in inspect.signature(fn).parameters:
         pytest.skip("drives the real library in a subprocess; nothing to emulate")
     fn(emulated_hip, **kw)
+
+
+def test_emulator_covers_the_header():
+    """Every entry declared in include/pdn_hip.h is a method of the emulator or listed in NOT_EMULATED, and the emulator
+    defines no entry the header lacks."""
+    from pydynet_amd import _lib
+    from tests.abi_emulator import NOT_EMULATED, EmulatedLib
+    declared = set(_lib.parse_header())
+    emulated = {n for n in dir(EmulatedLib) if n.startswith("pdn_")}
+    assert len(set(NOT_EMULATED)) == len(NOT_EMULATED) and not emulated & set(NOT_EMULATED)
+    assert declared - emulated == set(NOT_EMULATED)
+    assert not emulated - declared

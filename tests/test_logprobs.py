@@ -1,7 +1,7 @@
 """Token log-probabilities (`logprobs=` of `generate`, `generate_ragged`, `serve`, `serve_all`; `Llama.score`) on the
 CPU: the statement of llm/logprobs.py by hand cases, the `cpu` device against a hand loop of `forward_logits` plus the
 statement, `score` against generation, argument errors, and the emulated C ABI with the entry points of
-tests/logprobs_abi_emulation.py (the graph-replayed steps, with and without graphs) against `cpu`."""
+tests/abi_emulator/_logprobs.py (the graph-replayed steps, with and without graphs) against `cpu`."""
 import numpy as np
 import pytest
 
@@ -10,17 +10,8 @@ from pydynet_amd.core import Tensor
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm import beam, logprobs as lp_np, penalties
 from pydynet_amd.llm.llama import Llama
-from tests.beam_abi_emulation import beam_emulated  # noqa: F401  (fixture)
-from tests.chunked_abi_emulation import chunked_emulated  # noqa: F401  (fixture)
-from tests.clip_abi_emulation import clip_emulated  # noqa: F401  (fixture)
-from tests.logprobs_abi_emulation import counters, logprobs_emulated  # noqa: F401  (fixture)
-from tests.penalty_abi_emulation import penalty_emulated  # noqa: F401  (fixture)
-from tests.ragged_abi_emulation import ragged_emulated  # noqa: F401  (fixture)
-from tests.sampling_abi_emulation import sampling_emulated  # noqa: F401  (fixture)
-from tests.serve_abi_emulation import serve_emulated  # noqa: F401  (fixture)
-from tests.speculative_abi_emulation import speculative_emulated  # noqa: F401  (fixture)
+from tests.abi_emulator import counters
 from tests.test_ragged import SAMPLED, V, _gen, _model, _prompts, _ragged
-from tests.wide_abi_emulation import wide_emulated  # noqa: F401  (fixture)
 
 PEN = dict(repetition_penalty=1.8, presence_penalty=0.7, frequency_penalty=0.4)
 
@@ -258,7 +249,7 @@ BAD = [-1, 21, True, 2.0, "1"]
 
 
 @pytest.mark.parametrize("bad", BAD)
-def test_bad_n_raises_before_any_launch(logprobs_emulated, bad):
+def test_bad_n_raises_before_any_launch(emulated_hip, bad):
     from pydynet_amd import _lib
     m = _model("hip:0")
     prompts = _prompts([2, 3])
@@ -274,7 +265,7 @@ def test_bad_n_raises_before_any_launch(logprobs_emulated, bad):
     assert len(_lib._LIB.calls) == n0
 
 
-def test_score_arguments(logprobs_emulated):
+def test_score_arguments(emulated_hip):
     from pydynet_amd import _lib
     m = _model("hip:0")
     n0 = len(_lib._LIB.calls)
@@ -297,7 +288,7 @@ RUNTIME = ("pdn_malloc", "pdn_free", "pdn_set_device", "pdn_compute_stream", "pd
            "pdn_memcpy")
 
 
-def test_default_launches_unchanged(logprobs_emulated):
+def test_default_launches_unchanged(emulated_hip):
     from pydynet_amd import _lib
     Graph.clear()
     ids = np.stack(_prompts([4, 4], seed=10))
@@ -319,7 +310,7 @@ def test_default_launches_unchanged(logprobs_emulated):
 
 @pytest.mark.parametrize("graphs", [True, False])
 @pytest.mark.parametrize("B,kw", [(3, {}), (5, SAMPLED[1]), (12, {}), (10, PEN)])
-def test_emulated_generate_ragged_equals_cpu(logprobs_emulated, graphs, B, kw, monkeypatch):
+def test_emulated_generate_ragged_equals_cpu(emulated_hip, graphs, B, kw, monkeypatch):
     monkeypatch.setattr(Llama, "graph_decode", graphs)
     Graph.clear()
     prompts = _prompts([1 + (3 * i) % 7 for i in range(B)], seed=12)
@@ -336,7 +327,7 @@ def test_emulated_generate_ragged_equals_cpu(logprobs_emulated, graphs, B, kw, m
 
 @pytest.mark.parametrize("graphs", [True, False])
 @pytest.mark.parametrize("B,kw,n", [(3, {}, 0), (2, SAMPLED[2], 20), (12, {}, 3)])
-def test_emulated_generate_equals_cpu(logprobs_emulated, graphs, B, kw, n, monkeypatch):
+def test_emulated_generate_equals_cpu(emulated_hip, graphs, B, kw, n, monkeypatch):
     monkeypatch.setattr(Llama, "graph_decode", graphs)
     Graph.clear()
     ids = np.stack(_prompts([5] * B, seed=13))
@@ -349,7 +340,7 @@ def test_emulated_generate_equals_cpu(logprobs_emulated, graphs, B, kw, n, monke
 @pytest.mark.parametrize("graphs", [True, False])
 @pytest.mark.parametrize("S,chunk,kw", [(3, None, {}), (3, 4, {}), (2, None, SAMPLED[1]), (10, None, PEN),
                                          (10, 3, SAMPLED[0])])
-def test_emulated_serve_equals_cpu(logprobs_emulated, graphs, S, chunk, kw, monkeypatch):
+def test_emulated_serve_equals_cpu(emulated_hip, graphs, S, chunk, kw, monkeypatch):
     monkeypatch.setattr(Llama, "graph_decode", graphs)
     Graph.clear()
     N = S + 4
@@ -363,7 +354,7 @@ def test_emulated_serve_equals_cpu(logprobs_emulated, graphs, S, chunk, kw, monk
         assert np.array_equal(t0, t1) and _agree((t0,) + tuple(l0), (t1,) + tuple(l1))
 
 
-def test_emulated_score_equals_cpu(logprobs_emulated):
+def test_emulated_score_equals_cpu(emulated_hip):
     seq = np.random.default_rng(15).integers(0, V, (3, 10))
     want = _model("cpu").score(seq, 6)
     m = _model("hip:0")
@@ -374,7 +365,7 @@ def test_emulated_score_equals_cpu(logprobs_emulated):
     np.testing.assert_allclose(got.top_logprobs, want.top_logprobs, atol=1e-5)
 
 
-def test_emulated_speculate_with_logprobs_raises_before_any_launch(logprobs_emulated):
+def test_emulated_speculate_with_logprobs_raises_before_any_launch(emulated_hip):
     from pydynet_amd import _lib
     m = _model("hip:0")
     n0 = len(_lib._LIB.calls)

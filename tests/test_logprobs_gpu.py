@@ -15,7 +15,7 @@ from pydynet_amd import _lib
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm import logprobs as lp_np
 from pydynet_amd.llm.llama import Llama
-from tests.logprobs_abi_emulation import chunks, counters
+from tests.abi_emulator import counters, logprobs_chunks as chunks
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32

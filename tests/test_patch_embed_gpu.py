@@ -12,7 +12,7 @@ import pytest
 import pydynet_amd as pdn
 from pydynet_amd.core import fused
 from pydynet_amd.core.tensor import Graph
-from tests.clip_abi_emulation import clip_emulated, counters  # noqa: F401  (fixture)
+from tests.abi_emulator import counters
 
 PE_FWD, PE_BWD, L2_FWD, L2_BWD = 24, 25, 26, 27
 SHAPES = [  # N, C, H, W, p, D, taken by the kernels
@@ -32,7 +32,7 @@ def variants(namespace, fn):
         Graph.clear()
         fn("hip:0")
 
-    def on_emulator(clip_emulated):  # noqa: F811
+    def on_emulator(emulated_hip):
         fn("hip:0")
 
     namespace[f"test_{name}_gpu"] = on_gpu

@@ -1,7 +1,7 @@
 """Repetition, presence and frequency penalties (`generate`, `generate_ragged`, `serve`, `serve_all`) on the CPU: the
 statement of llm/penalties.py by hand cases, the `cpu` device against a hand loop of `forward_logits` plus the statement,
 `serve_all` against `generate_ragged`, argument errors, and the emulated C ABI with the entry points of
-tests/penalty_abi_emulation.py (the graph-replayed steps, with and without graphs) against `cpu`."""
+tests/abi_emulator/_penalty.py (the graph-replayed steps, with and without graphs) against `cpu`."""
 import numpy as np
 import pytest
 
@@ -10,16 +10,8 @@ from pydynet_amd.core import Tensor
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm import penalties, sampling
 from pydynet_amd.llm.llama import Llama
-from tests.beam_abi_emulation import beam_emulated  # noqa: F401  (fixture)
-from tests.chunked_abi_emulation import chunked_emulated  # noqa: F401  (fixture)
-from tests.clip_abi_emulation import clip_emulated  # noqa: F401  (fixture)
-from tests.penalty_abi_emulation import apply_np, counters, penalty_emulated, reset_np  # noqa: F401  (fixture)
-from tests.ragged_abi_emulation import ragged_emulated  # noqa: F401  (fixture)
-from tests.sampling_abi_emulation import sampling_emulated  # noqa: F401  (fixture)
-from tests.serve_abi_emulation import serve_emulated  # noqa: F401  (fixture)
-from tests.speculative_abi_emulation import speculative_emulated  # noqa: F401  (fixture)
+from tests.abi_emulator import apply_np, counters, remove, reset_np
 from tests.test_ragged import SAMPLED, V, _gen, _model, _prompts, _ragged
-from tests.wide_abi_emulation import wide_emulated  # noqa: F401  (fixture)
 
 PEN = dict(repetition_penalty=1.8, presence_penalty=0.7, frequency_penalty=0.4)
 PENS = [PEN, dict(repetition_penalty=1.3), dict(presence_penalty=1.5, frequency_penalty=0.25)]
@@ -205,7 +197,7 @@ BAD = [dict(repetition_penalty=0.0), dict(repetition_penalty=-1.0), dict(repetit
 
 
 @pytest.mark.parametrize("bad", BAD)
-def test_bad_arguments_raise_before_any_launch(penalty_emulated, bad):
+def test_bad_arguments_raise_before_any_launch(emulated_hip, bad):
     from pydynet_amd import _lib
     m = _model("hip:0")
     prompts = _prompts([2, 3])
@@ -228,7 +220,7 @@ def test_penalties_refused_with_speculation():
 
 
 # -- the emulated HIP path --------------------------------------------------------------------------------------------
-def test_default_launches_unchanged(penalty_emulated):
+def test_default_launches_unchanged(emulated_hip):
     from pydynet_amd import _lib
     Graph.clear()
     ids = np.stack(_prompts([4, 4], seed=10))
@@ -259,7 +251,7 @@ def _fed_counts(got, prompts, n_rows, V):
 
 @pytest.mark.parametrize("graphs", [True, False])
 @pytest.mark.parametrize("B,kw", [(3, {}), (5, SAMPLED[1]), (12, {}), (10, SAMPLED[0])])
-def test_emulated_generate_ragged_equals_cpu(penalty_emulated, graphs, B, kw, monkeypatch):
+def test_emulated_generate_ragged_equals_cpu(emulated_hip, graphs, B, kw, monkeypatch):
     monkeypatch.setattr(Llama, "graph_decode", graphs)
     Graph.clear()
     prompts = _prompts([1 + (3 * i) % 7 for i in range(B)], seed=12)
@@ -276,7 +268,7 @@ def test_emulated_generate_ragged_equals_cpu(penalty_emulated, graphs, B, kw, mo
 
 @pytest.mark.parametrize("graphs", [True, False])
 @pytest.mark.parametrize("B,kw", [(3, {}), (2, SAMPLED[2]), (12, {})])
-def test_emulated_generate_equals_cpu(penalty_emulated, graphs, B, kw, monkeypatch):
+def test_emulated_generate_equals_cpu(emulated_hip, graphs, B, kw, monkeypatch):
     monkeypatch.setattr(Llama, "graph_decode", graphs)
     Graph.clear()
     ids = np.stack(_prompts([5] * B, seed=13))
@@ -289,7 +281,7 @@ def test_emulated_generate_equals_cpu(penalty_emulated, graphs, B, kw, monkeypat
 @pytest.mark.parametrize("graphs", [True, False])
 @pytest.mark.parametrize("S,chunk,kw", [(3, None, {}), (3, 4, {}), (2, None, SAMPLED[1]), (10, None, {}),
                                          (10, 3, SAMPLED[0])])
-def test_emulated_serve_equals_cpu(penalty_emulated, graphs, S, chunk, kw, monkeypatch):
+def test_emulated_serve_equals_cpu(emulated_hip, graphs, S, chunk, kw, monkeypatch):
     monkeypatch.setattr(Llama, "graph_decode", graphs)
     Graph.clear()
     N = S + 4
@@ -301,11 +293,11 @@ def test_emulated_serve_equals_cpu(penalty_emulated, graphs, S, chunk, kw, monke
     assert got == want and counters()[35] > 0
 
 
-def test_emulated_refusing_library_follows_the_statement(penalty_emulated, monkeypatch):
+def test_emulated_refusing_library_follows_the_statement(emulated_hip, monkeypatch):
     """Without the penalty entries every path applies the statement on the host; tokens as on `cpu`."""
     from pydynet_amd import _lib
     Graph.clear()
-    monkeypatch.delattr(_lib._LIB, "pdn_penalty_step_f32")
+    remove(monkeypatch, _lib._LIB, "pdn_penalty_step_f32")
     prompts = _prompts([3, 6, 2], seed=15)
     want = _ragged(_model("cpu"), prompts, 9, **PEN)
     counters()
@@ -317,7 +309,7 @@ def test_emulated_refusing_library_follows_the_statement(penalty_emulated, monke
     assert served == _expected_serve(prompts, budgets, **PEN)
 
 
-def test_emulated_entries_follow_the_statement(penalty_emulated):
+def test_emulated_entries_follow_the_statement(emulated_hip):
     """The emulated reset / apply entries through the library's call path: the statement on random rows."""
     from pydynet_amd import _lib, hipnp as hp
     rng = np.random.default_rng(16)

@@ -1,5 +1,5 @@
 """Penalties on a real MI355X: the entries of csrc/penalty.hip bit for bit against the float32 statement
-(tests/penalty_abi_emulation.py), the plan's counts after a graph-replayed run, and `generate`, `generate_ragged` and
+(tests/abi_emulator/_penalty.py), the plan's counts after a graph-replayed run, and `generate`, `generate_ragged` and
 `serve` (plain and chunked) end to end against the `cpu` device under the first-difference margin rule of
 tests/test_serve_gpu.py, on the narrow (<= 8 rows) and the wide step."""
 import numpy as np
@@ -10,8 +10,7 @@ from pydynet_amd import _lib
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm import penalties
 from pydynet_amd.llm.llama import Llama
-from tests.penalty_abi_emulation import apply_np, chunks, reset_np
-from tests.sampling_abi_emulation import margin
+from tests.abi_emulator import apply_np, margin, penalty_chunks as chunks, reset_np
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32

@@ -1,6 +1,6 @@
 """Prefix caching (`Llama.serve(..., prefill_chunk=C, prefix_cache=k)`) on the CPU: the statement of llm/prefix.py against a
 brute-force restatement, the argument checks, and end to end on the `cpu` device (where every prompt is computed in full) and
-on the emulated C ABI with the copy entry of tests/prefix_abi_emulation.py (the graph path: the mixed step starts a row's
+on the emulated C ABI with the copy entry of tests/abi_emulator/_extend.py (the graph path: the mixed step starts a row's
 prefill behind the tokens it took), against the `cpu` reference of tests/test_serve.py under its first-difference margin
 rule -- with at most one request of a case differing at all."""
 import numpy as np
@@ -9,18 +9,8 @@ import pytest
 import pydynet_amd as pdn
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm import chunked, penalties, prefix
-from tests.beam_abi_emulation import beam_emulated  # noqa: F401  (fixture)
-from tests.chunked_abi_emulation import chunked_emulated  # noqa: F401  (fixture)
-from tests.clip_abi_emulation import clip_emulated  # noqa: F401  (fixture)
-from tests.logprobs_abi_emulation import logprobs_emulated  # noqa: F401  (fixture)
-from tests.penalty_abi_emulation import penalty_emulated  # noqa: F401  (fixture)
-from tests.prefix_abi_emulation import copy_prefix_np, counters, prefix_emulated  # noqa: F401  (fixture)
-from tests.ragged_abi_emulation import ragged_emulated  # noqa: F401  (fixture)
-from tests.sampling_abi_emulation import margin, sampling_emulated  # noqa: F401  (fixture)
-from tests.serve_abi_emulation import serve_emulated  # noqa: F401  (fixture)
-from tests.speculative_abi_emulation import speculative_emulated  # noqa: F401  (fixture)
+from tests.abi_emulator import copy_prefix_np, counters, margin
 from tests.test_serve import SAMPLED, V, _eval, _model, _reference, _want
-from tests.wide_abi_emulation import wide_emulated  # noqa: F401  (fixture)
 
 PEN = dict(repetition_penalty=1.3, presence_penalty=0.4, frequency_penalty=0.2)
 KINDS = {"own", "copy", "swap", "live", "short", "cap"}
@@ -294,7 +284,7 @@ def compare(got, want, ref_logits, prompts, kw):
 
 # -- arguments ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("bad", [0, -1, 1.5, "1", [1], np.float32(2.0), 2.0])
-def test_bad_prefix_cache_raises_before_anything_runs(prefix_emulated, bad):
+def test_bad_prefix_cache_raises_before_anything_runs(emulated_hip, bad):
     from pydynet_amd import _lib
     m = _model("hip:0")
     counters()
@@ -338,7 +328,7 @@ def test_cpu_device_computes_every_prompt(S, C, cache, kw):
 
 @pytest.mark.parametrize("graphs", [True, False])
 @pytest.mark.parametrize("S,C,cache,kw", E2E)
-def test_emulated_matches_cpu_without_the_cache(prefix_emulated, S, C, cache, kw, graphs, monkeypatch):
+def test_emulated_matches_cpu_without_the_cache(emulated_hip, S, C, cache, kw, graphs, monkeypatch):
     from pydynet_amd.llm.llama import Llama
     monkeypatch.setattr(Llama, "graph_decode", graphs)
     Graph.clear()
@@ -359,7 +349,7 @@ def test_emulated_matches_cpu_without_the_cache(prefix_emulated, S, C, cache, kw
 
 
 @pytest.mark.parametrize("S,C,cache", CASES[:2])
-def test_emulated_logprobs(prefix_emulated, S, C, cache):
+def test_emulated_logprobs(emulated_hip, S, C, cache):
     Graph.clear()
     prompts, budgets = requests(V, SEED)
     _, logits = _reference(prompts, budgets)
@@ -375,7 +365,7 @@ def test_emulated_logprobs(prefix_emulated, S, C, cache):
     assert m.prefix_stats == simulate(prompts, budgets, S, C, _k(cache))[0] and m.prefix_stats["copies"] > 0
 
 
-def test_emulated_refusing_library_computes_every_prompt(prefix_emulated, monkeypatch):
+def test_emulated_refusing_library_computes_every_prompt(emulated_hip, monkeypatch):
     """Without the mixed step a prompt completes with one whole pass from position 0: nothing is reused."""
     from pydynet_amd.llm.llama import Llama
     Graph.clear()
@@ -390,7 +380,7 @@ def test_emulated_refusing_library_computes_every_prompt(prefix_emulated, monkey
     assert m.prefix_stats == simulate(prompts, budgets, 3, 4, None)[0] and m.prefix_stats["reused_tokens"] == 0
 
 
-def test_stats_during_a_run_and_left_alone_when_off(prefix_emulated):
+def test_stats_during_a_run_and_left_alone_when_off(emulated_hip):
     Graph.clear()
     prompts, budgets = requests(V, SEED)
     m = _model("hip:0")
@@ -413,7 +403,7 @@ def test_stats_during_a_run_and_left_alone_when_off(prefix_emulated):
 
 # -- off means off -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kw", [{}, SAMPLED[1]])
-def test_off_means_off(prefix_emulated, kw):
+def test_off_means_off(emulated_hip, kw):
     from pydynet_amd import _lib
     prompts, budgets = requests(V, SEED)
 

@@ -1,5 +1,5 @@
 """Prefix caching on a real MI355X: pdn_kv_copy_prefix_rows_f32 (csrc/prefix.hip) bit-exact against the NumPy statement of
-tests/prefix_abi_emulation.py, and `Llama.serve(prefill_chunk=C, prefix_cache=k)` end to end against the `cpu`
+tests/abi_emulator/_extend.py, and `Llama.serve(prefill_chunk=C, prefix_cache=k)` end to end against the `cpu`
 generate_ragged reference under the first-difference margin rule of tests/test_serve_gpu.py, with at most one request of a
 case differing at all (tests/test_prefix.py: `compare`; its `test_gpu_reference_alone_shows_no_difference` checks on the
 CPU that the reference run of these requests has no near-tie of its own)."""
@@ -9,7 +9,7 @@ import pytest
 import pydynet_amd as pdn
 from pydynet_amd import _lib
 from pydynet_amd.core.tensor import Graph
-from tests.prefix_abi_emulation import copy_prefix_np, counters
+from tests.abi_emulator import copy_prefix_np, counters
 from tests.test_prefix import CASES, GPU_SEED, PEN, _k, compare, requests, simulate
 from tests.test_serve_gpu import SAMPLED, _model, _ragged_reference, _serve_all
 

@@ -1,15 +1,13 @@
 """Ragged-batch generation (`Llama.generate_ragged`: prompts of different lengths, a position per row, stop ids) on the
 CPU: the `cpu` device (the NumPy statement, `Attention.step_rows`) and the emulated C ABI with the per-row entry points
-of tests/ragged_abi_emulation.py (the graph-path plan, the three- and two-launch layers, the generic HIP step)."""
+of tests/abi_emulator/_decode_rows.py (the graph-path plan, the three- and two-launch layers, the generic HIP step)."""
 import numpy as np
 import pytest
 
 import pydynet_amd as pdn
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm.llama import Llama
-from tests.clip_abi_emulation import clip_emulated  # noqa: F401  (fixture)
-from tests.ragged_abi_emulation import counters, ragged_emulated  # noqa: F401  (fixture)
-from tests.sampling_abi_emulation import sampling_emulated  # noqa: F401  (fixture)
+from tests.abi_emulator import counters
 
 V = 64
 
@@ -66,7 +64,7 @@ def test_equal_lengths_match_generate_on_cpu(kw):
 
 @pytest.mark.parametrize("H", [2, 4])
 @pytest.mark.parametrize("kw", [{}] + SAMPLED)
-def test_equal_lengths_match_generate_emulated(ragged_emulated, H, kw):
+def test_equal_lengths_match_generate_emulated(emulated_hip, H, kw):
     Graph.clear()
     ids = np.stack(_prompts([5, 5], seed=2))
     ref = _gen(_model("hip:0", H=H), ids, 5 + 8, **kw)
@@ -110,7 +108,7 @@ def test_ragged_rows_match_single_prompt_generate(B):
 
 @pytest.mark.parametrize("H", [2, 4])
 @pytest.mark.parametrize("kw", [{}] + SAMPLED[1:])
-def test_ragged_emulated_equals_cpu(ragged_emulated, H, kw):
+def test_ragged_emulated_equals_cpu(emulated_hip, H, kw):
     Graph.clear()
     prompts = _prompts([1, 6, 3, 8, 2], seed=7)
     cpu = _ragged(_model("cpu", H=H), prompts, 10, **kw)
@@ -121,19 +119,23 @@ def test_ragged_emulated_equals_cpu(ragged_emulated, H, kw):
 
 
 @pytest.mark.parametrize("kw", [{}, SAMPLED[0]])
-def test_ragged_generic_step_beyond_the_plan(ragged_emulated, kw):
-    """B = 12 > 8: the generic HIP step with pdn_attention_decode_rows_f32."""
+def test_ragged_generic_step_beyond_the_plan(emulated_hip, kw):
+    """B = 12 > 8 and the wide step off: the generic HIP step with pdn_attention_decode_rows_f32."""
     Graph.clear()
     prompts = _prompts([1 + i % 6 for i in range(12)], seed=12)
     cpu = _ragged(_model("cpu", B=12), prompts, 7, **kw)
-    counters()
-    emu = _ragged(_model("hip:0", B=12), prompts, 7, **kw)
-    assert counters()[29] > 0
+    Llama.wide_decode = False
+    try:
+        counters()
+        emu = _ragged(_model("hip:0", B=12), prompts, 7, **kw)
+        assert counters()[29] > 0
+    finally:
+        Llama.wide_decode = True
     assert np.array_equal(emu, cpu)
 
 
 @pytest.mark.parametrize("fast", [True, False])
-def test_unfused_and_module_paths_on_emulated(ragged_emulated, fast):
+def test_unfused_and_module_paths_on_emulated(emulated_hip, fast):
     Graph.clear()
     prompts = _prompts([2, 5, 1], seed=4)
     cpu = _ragged(_model("cpu"), prompts, 8)
@@ -150,7 +152,7 @@ def _first_hit(row, stop):
 
 
 @pytest.mark.parametrize("dev", ["cpu", "hip:0"])
-def test_stop_ids(ragged_emulated, dev):
+def test_stop_ids(emulated_hip, dev):
     Graph.clear()
     prompts = _prompts([3, 6, 2], seed=9)
     free = _ragged(_model("cpu"), prompts, 12)
@@ -170,7 +172,7 @@ def test_stop_ids(ragged_emulated, dev):
             assert np.array_equal(l.attention.cache_k.numpy()[b, last + 1:], k0[b, last + 1:])
 
 
-def test_all_rows_stopped_by_the_prompt_pass_yields_one_step(ragged_emulated):
+def test_all_rows_stopped_by_the_prompt_pass_yields_one_step(emulated_hip):
     prompts = _prompts([3, 4], seed=3)
     first = _ragged(_model("hip:0", B=2), prompts, 1)[:, 0]
     got = _ragged(_model("hip:0", B=2), prompts, 10, stop_ids=set(first.tolist()))
@@ -189,7 +191,7 @@ def test_all_rows_stopped_by_the_prompt_pass_yields_one_step(ragged_emulated):
     dict(prompts=[[1, 2]], n=-1),
     dict(prompts=[]),
 ])
-def test_invalid_arguments_raise_before_anything_runs(ragged_emulated, bad):
+def test_invalid_arguments_raise_before_anything_runs(emulated_hip, bad):
     m = _model("hip:0")
     counters()
     kw = dict(bad)
@@ -200,12 +202,12 @@ def test_invalid_arguments_raise_before_anything_runs(ragged_emulated, bad):
     assert getattr(m, "_decode_st", None) is None
 
 
-def test_last_position_bound_is_per_row(ragged_emulated):
+def test_last_position_bound_is_per_row(emulated_hip):
     m = _model("hip:0", B=2)
     assert _ragged(m, [[1] * 20, [2]], 12).shape == (2, 12)       # row 0's last step at position 31: accepted
 
 
-def test_ragged_then_rectangular_then_ragged(ragged_emulated):
+def test_ragged_then_rectangular_then_ragged(emulated_hip):
     """One model, three generations: the tokens are those of the same sequence on the `cpu` device (`generate` reads
     cache slot L, which no step writes -- as the reference's -- so each run depends on the ones before it), and the
     rectangular run re-plans exactly as `generate` alone does: same key, graphs, launches, slot 29 at zero."""

@@ -1,6 +1,6 @@
 """Sampled generation (pydynet_amd/llm/sampling.py, csrc/sample.hip) on the CPU: the Philox generator against NumPy's own,
 properties of the NumPy statement of the contract, and `Llama.generate(..., temperature=...)` on the `cpu` device and on
-the emulated C ABI (tests/sampling_abi_emulation.py), greedy mode unchanged."""
+the emulated C ABI (tests/abi_emulator/_sampling.py), greedy mode unchanged."""
 import numpy as np
 import pytest
 
@@ -8,8 +8,7 @@ import pydynet_amd as pdn
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm import sampling
 from pydynet_amd.llm.llama import Llama
-from tests.clip_abi_emulation import clip_emulated  # noqa: F401  (fixture)
-from tests.sampling_abi_emulation import counters, sampling_emulated  # noqa: F401  (fixture)
+from tests.abi_emulator import counters
 
 
 def word0(counter, key):
@@ -110,7 +109,7 @@ def test_invalid_arguments_raise_before_anything_runs(bad):
         m.generate(PROMPT, 10, **bad)                     # (not iterated: the call itself refuses)
 
 
-def test_default_generate_is_greedy_with_unchanged_launches(sampling_emulated):
+def test_default_generate_is_greedy_with_unchanged_launches(emulated_hip):
     Graph.clear()
     m = _tiny("hip:0")
     counters()
@@ -129,7 +128,7 @@ def test_default_generate_is_greedy_with_unchanged_launches(sampling_emulated):
 
 @pytest.mark.parametrize("kw", [dict(temperature=1.0, seed=3), dict(temperature=0.8, top_p=0.9, seed=11),
                                 dict(temperature=1.3, top_k=5, top_p=0.95, seed=2 ** 64 - 1)])
-def test_sampled_generate_emulated_equals_cpu(sampling_emulated, kw):
+def test_sampled_generate_emulated_equals_cpu(emulated_hip, kw):
     Graph.clear()
     cpu = _gen(_tiny("cpu"), PROMPT, 16, **kw)
     counters()
@@ -141,14 +140,14 @@ def test_sampled_generate_emulated_equals_cpu(sampling_emulated, kw):
 
 
 @pytest.mark.parametrize("dev", ["cpu", "hip:0"])
-def test_top_k_one_gives_the_greedy_tokens(sampling_emulated, dev):
+def test_top_k_one_gives_the_greedy_tokens(emulated_hip, dev):
     greedy = _gen(_tiny(dev), PROMPT, 14)
     for T in (0.3, 1.0, 4.0):
         assert np.array_equal(_gen(_tiny(dev), PROMPT, 14, temperature=T, top_k=1, seed=int(T * 10)), greedy)
 
 
 @pytest.mark.parametrize("fast", [True, False])
-def test_sampled_then_greedy_on_one_model(sampling_emulated, fast):
+def test_sampled_then_greedy_on_one_model(emulated_hip, fast):
     Llama.fast_decode = fast
     try:
         greedy = _gen(_tiny("hip:0"), PROMPT, 14)
@@ -161,9 +160,14 @@ def test_sampled_then_greedy_on_one_model(sampling_emulated, fast):
         Llama.fast_decode = True
 
 
-def test_generic_step_samples_beyond_the_plan(sampling_emulated):
-    """B > 8: the decode step of the library's generic entry points ends in pdn_sample_rows_f32."""
+def test_generic_step_samples_beyond_the_plan(emulated_hip):
+    """B > 8 and the wide step off: the decode step of the library's generic entry points ends in pdn_sample_rows_f32."""
     Graph.clear()
     prompt = np.random.default_rng(3).integers(0, 64, (9, 3))
     kw = dict(temperature=0.9, top_p=0.9, seed=21)
-    assert np.array_equal(_gen(_tiny("hip:0", B=9), prompt, 10, **kw), _gen(_tiny("cpu", B=9), prompt, 10, **kw))
+    Llama.wide_decode = False
+    try:
+        got = _gen(_tiny("hip:0", B=9), prompt, 10, **kw)
+    finally:
+        Llama.wide_decode = True
+    assert np.array_equal(got, _gen(_tiny("cpu", B=9), prompt, 10, **kw))

@@ -1,7 +1,8 @@
 """Continuous batching (`Llama.serve` / `serve_all`: more requests than rows, a freed row refilled before the next step) on
-the CPU: the `cpu` device (the module path) and the emulated C ABI with the entry points of tests/serve_abi_emulation.py
-(the served graph-path plan at every fused level, without graphs, the generic HIP step).  The contract: request r's
-tokens are the first budget_r tokens of row r of `generate_ragged` over all requests, cut after its first stop id."""
+the CPU: the `cpu` device (the module path) and the emulated C ABI with the slot entry points of
+tests/abi_emulator/_decode_rows.py (the served graph-path plan at every fused level, without graphs, the generic HIP
+step).  The contract: request r's tokens are the first budget_r tokens of row r of `generate_ragged` over all requests,
+cut after its first stop id."""
 import numpy as np
 import pytest
 
@@ -9,10 +10,7 @@ import pydynet_amd as pdn
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm import sampling
 from pydynet_amd.llm.llama import Llama
-from tests.clip_abi_emulation import clip_emulated  # noqa: F401  (fixture)
-from tests.ragged_abi_emulation import ragged_emulated  # noqa: F401  (fixture)
-from tests.sampling_abi_emulation import margin, sampling_emulated  # noqa: F401  (fixture)
-from tests.serve_abi_emulation import counters, serve_emulated  # noqa: F401  (fixture)
+from tests.abi_emulator import counters, margin
 
 V = 64
 
@@ -113,7 +111,7 @@ def test_serve_matches_generate_ragged_on_cpu(slots, kw):
 @pytest.mark.parametrize("H", [2, 4])
 @pytest.mark.parametrize("slots", [1, 2, 3, 5])
 @pytest.mark.parametrize("kw", [{}] + SAMPLED[1:])
-def test_serve_matches_generate_ragged_emulated(serve_emulated, H, slots, kw):
+def test_serve_matches_generate_ragged_emulated(emulated_hip, H, slots, kw):
     Graph.clear()
     prompts = _prompts(LENS, seed=2)
     ref, logits = _reference(prompts, BUDGETS, H=H, **kw)
@@ -128,7 +126,7 @@ def test_serve_matches_generate_ragged_emulated(serve_emulated, H, slots, kw):
 
 @pytest.mark.parametrize("dev", ["cpu", "hip:0"])
 @pytest.mark.parametrize("kw", [{}, SAMPLED[1]])
-def test_more_requests_than_rows(serve_emulated, dev, kw):
+def test_more_requests_than_rows(emulated_hip, dev, kw):
     """N = 11 > max_batch_size = 4; the reference is one generate_ragged run on a model with 11 cache rows."""
     Graph.clear()
     lens = [1 + (5 * i) % 9 for i in range(11)]
@@ -142,7 +140,7 @@ def test_more_requests_than_rows(serve_emulated, dev, kw):
 
 @pytest.mark.parametrize("dev", ["cpu", "hip:0"])
 @pytest.mark.parametrize("kw", [{}, SAMPLED[0]])
-def test_stop_ids(serve_emulated, dev, kw):
+def test_stop_ids(emulated_hip, dev, kw):
     Graph.clear()
     prompts = _prompts([3, 6, 2, 4, 5, 1], seed=9)
     budgets = [12] * 6
@@ -176,7 +174,7 @@ def _schedule(budgets, lengths, S):
 
 
 @pytest.mark.parametrize("dev", ["cpu", "hip:0"])
-def test_admission_order_and_stream(serve_emulated, dev):
+def test_admission_order_and_stream(emulated_hip, dev):
     Graph.clear()
     prompts = _prompts([2, 4, 1, 3, 6, 2, 5], seed=4)
     budgets = [5, 1, 3, 0, 7, 2, 4]
@@ -201,7 +199,7 @@ def test_admission_order_and_stream(serve_emulated, dev):
 
 
 @pytest.mark.parametrize("dev", ["cpu", "hip:0"])
-def test_admission_prefill_leaves_other_rows_alone(serve_emulated, dev):
+def test_admission_prefill_leaves_other_rows_alone(emulated_hip, dev):
     m = _model(dev, B=4)
     rng = np.random.default_rng(0)
     for layer in m.layers:
@@ -233,7 +231,7 @@ def test_admission_prefill_leaves_other_rows_alone(serve_emulated, dev):
 
 @pytest.mark.parametrize("mode", ["fused1", "unfused", "nograph", "module", "generic"])
 @pytest.mark.parametrize("kw", [{}, SAMPLED[1]])
-def test_every_path_emulated(serve_emulated, mode, kw):
+def test_every_path_emulated(emulated_hip, mode, kw):
     Graph.clear()
     n_req, rows = (12, 10) if mode == "generic" else (7, 3)       # generic: 10 slots > 8, the plan refuses
     prompts = _prompts([1 + (3 * i) % 7 for i in range(n_req)], seed=8)
@@ -242,13 +240,14 @@ def test_every_path_emulated(serve_emulated, mode, kw):
     Llama.fused_decode = {"fused1": 1, "unfused": 0}.get(mode, 2)
     Llama.graph_decode = mode != "nograph"
     Llama.fast_decode = mode != "module"
+    Llama.wide_decode = mode != "generic"                         # (generic: not the wide step either)
     try:
         m = _model("hip:0", B=rows)
         counters()
         got = _serve_all(m, prompts, budgets, **kw)
         c = counters()
     finally:
-        Llama.fused_decode, Llama.graph_decode, Llama.fast_decode = 2, True, True
+        Llama.fused_decode, Llama.graph_decode, Llama.fast_decode, Llama.wide_decode = 2, True, True, True
     assert all(np.array_equal(g, w) for g, w in zip(got, cpu))
     if mode == "generic":
         assert c[29] > 0 and m._decode_st["B"] == rows and not m._decode_st["ok"]
@@ -277,7 +276,7 @@ def test_every_path_emulated(serve_emulated, mode, kw):
     dict(prompts=[[1, 2]], top_p=0.0),
     dict(prompts=[[1, 2]], seed=-1),
 ])
-def test_invalid_arguments_raise_before_anything_runs(serve_emulated, bad):
+def test_invalid_arguments_raise_before_anything_runs(emulated_hip, bad):
     m = _model("hip:0")
     counters()
     kw = dict(bad)
@@ -290,13 +289,13 @@ def test_invalid_arguments_raise_before_anything_runs(serve_emulated, bad):
     assert getattr(m, "_decode_st", None) is None
 
 
-def test_bounds_are_per_request(serve_emulated):
+def test_bounds_are_per_request(emulated_hip):
     m = _model("hip:0", B=2)
     got = _serve_all(m, [[1] * 20, [2], [3] * 31], [12, 30, 0])   # last positions 31 and 30; a budget of 0 is not bound
     assert [len(g) for g in got] == [12, 30, 0]
 
 
-def test_generate_and_generate_ragged_never_use_the_slot_entries(serve_emulated):
+def test_generate_and_generate_ragged_never_use_the_slot_entries(emulated_hip):
     Graph.clear()
     m = _model("hip:0")
     ids = np.stack(_prompts([4, 4, 4], seed=6))
@@ -309,7 +308,7 @@ def test_generate_and_generate_ragged_never_use_the_slot_entries(serve_emulated)
     assert not m._decode_st["serve"]
 
 
-def test_serve_then_ragged_then_serve(serve_emulated):
+def test_serve_then_ragged_then_serve(emulated_hip):
     """One model, three runs: serve re-plans with its own key (a serve plan never shares a plan or a graph)."""
     Graph.clear()
     prompts = _prompts([2, 6, 4, 3], seed=5)
@@ -324,7 +323,7 @@ def test_serve_then_ragged_then_serve(serve_emulated):
     assert all(np.array_equal(x, y) for x, y in zip(a, b))
 
 
-def test_abandoned_serve_then_a_new_one(serve_emulated):
+def test_abandoned_serve_then_a_new_one(emulated_hip):
     Graph.clear()
     prompts = _prompts([2, 6, 4, 3, 5], seed=7)
     m = _model("hip:0")

@@ -1,5 +1,5 @@
 """Chunked prefill (`Llama.serve(..., prefill_chunk=C)`) on the CPU: the schedule statement of llm/chunked.py by hand
-cases, the `cpu` device against `serve`, and the emulated C ABI with the entry points of tests/chunked_abi_emulation.py
+cases, the `cpu` device against `serve`, and the emulated C ABI with the entry points of tests/abi_emulator/_extend.py
 (the mixed step of the served plan, with and without graphs) against the `cpu` reference of tests/test_serve.py."""
 import numpy as np
 import pytest
@@ -7,13 +7,7 @@ import pytest
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm import chunked
 from pydynet_amd.llm.llama import Llama
-from tests.beam_abi_emulation import beam_emulated  # noqa: F401  (fixture)
-from tests.chunked_abi_emulation import chunked_emulated, counters  # noqa: F401  (fixture)
-from tests.clip_abi_emulation import clip_emulated  # noqa: F401  (fixture)
-from tests.ragged_abi_emulation import ragged_emulated  # noqa: F401  (fixture)
-from tests.sampling_abi_emulation import sampling_emulated  # noqa: F401  (fixture)
-from tests.serve_abi_emulation import serve_emulated  # noqa: F401  (fixture)
-from tests.wide_abi_emulation import wide_emulated  # noqa: F401  (fixture)
+from tests.abi_emulator import counters
 from tests.test_serve import (BUDGETS, LENS, SAMPLED, _check, _eval, _model, _prompts, _reference, _serve_all, _stream,
                               _want)
 
@@ -132,7 +126,7 @@ def test_small_chunk_delays_first_tokens():
 @pytest.mark.parametrize("graphs", [True, False])
 @pytest.mark.parametrize("slots,C", [(2, 1), (3, 4), (5, 64), (12, 16)])
 @pytest.mark.parametrize("kw", [{}, SAMPLED[1]])
-def test_emulated_matches_cpu(chunked_emulated, graphs, slots, C, kw, monkeypatch):
+def test_emulated_matches_cpu(emulated_hip, graphs, slots, C, kw, monkeypatch):
     monkeypatch.setattr(Llama, "graph_decode", graphs)
     Graph.clear()
     lens = [1 + (5 * i) % 9 for i in range(13)]
@@ -149,7 +143,7 @@ def test_emulated_matches_cpu(chunked_emulated, graphs, slots, C, kw, monkeypatc
     assert st["serve"] and st["B"] == slots and st["mixed"]["C"] == C
 
 
-def test_emulated_without_chunk_is_unchanged(chunked_emulated):
+def test_emulated_without_chunk_is_unchanged(emulated_hip):
     Graph.clear()
     prompts = _prompts(LENS, seed=2)
     m = _model("hip:0")
@@ -161,7 +155,7 @@ def test_emulated_without_chunk_is_unchanged(chunked_emulated):
     assert all(len(k) == 2 for k in m._decode_st["graphs"])
 
 
-def test_emulated_refusing_library_follows_the_schedule(chunked_emulated, monkeypatch):
+def test_emulated_refusing_library_follows_the_schedule(emulated_hip, monkeypatch):
     """Without the mixed entries the prompt passes run when the schedule completes prompts; tokens as on `cpu`."""
     Graph.clear()
     monkeypatch.setattr(Llama, "wide_decode", False)

@@ -7,7 +7,7 @@ import pytest
 import pydynet_amd as pdn
 from pydynet_amd import _lib
 from pydynet_amd.core.tensor import Graph
-from tests.chunked_abi_emulation import counters, rotate
+from tests.abi_emulator import counters, rotate
 from tests.test_serve_gpu import SAMPLED, _check, _model, _ragged_reference, _serve_all
 
 pytestmark = pytest.mark.gpu

@@ -9,8 +9,7 @@ from pydynet_amd import _lib
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm import sampling
 from pydynet_amd.llm.llama import Llama
-from tests.sampling_abi_emulation import margin
-from tests.serve_abi_emulation import counters
+from tests.abi_emulator import counters, margin
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32

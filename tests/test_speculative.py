@@ -1,6 +1,6 @@
 """Prompt-lookup speculative decoding (`Llama.generate_ragged(..., speculate=k)`) on the CPU: the draft and accept rules of
 llm/speculative.py by hand cases, the `cpu` device against `speculate=0`, argument errors, and the emulated C ABI with
-the entry points of tests/speculative_abi_emulation.py (the graph-replayed pass, with and without graphs) against the
+the entry points of tests/abi_emulator/_extend.py (the graph-replayed pass, with and without graphs) against the
 statement."""
 import numpy as np
 import pytest
@@ -8,15 +8,8 @@ import pytest
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm import speculative
 from pydynet_amd.llm.llama import Llama
-from tests.beam_abi_emulation import beam_emulated  # noqa: F401  (fixture)
-from tests.chunked_abi_emulation import chunked_emulated  # noqa: F401  (fixture)
-from tests.clip_abi_emulation import clip_emulated  # noqa: F401  (fixture)
-from tests.ragged_abi_emulation import ragged_emulated  # noqa: F401  (fixture)
-from tests.sampling_abi_emulation import sampling_emulated  # noqa: F401  (fixture)
-from tests.serve_abi_emulation import serve_emulated  # noqa: F401  (fixture)
-from tests.speculative_abi_emulation import counters, draft_np, speculative_emulated  # noqa: F401  (fixture)
+from tests.abi_emulator import counters, draft_np, remove
 from tests.test_ragged import SAMPLED, V, _model, _prompts, _ragged
-from tests.wide_abi_emulation import wide_emulated  # noqa: F401  (fixture)
 
 
 def _draft(h, k=4, left=100):
@@ -162,7 +155,7 @@ def test_speculate_zero_runs_the_plain_decode():
 
 
 # -- the emulated HIP path --------------------------------------------------------------------------------------------
-def test_draft_entry_edge_cases(speculative_emulated):
+def test_draft_entry_edge_cases(emulated_hip):
     hist = np.zeros((4, 10), np.int32)
     hist[0, :5] = [1, 2, 3, 1, 2]
     hist[1, :3] = [5, 6, 7]
@@ -176,7 +169,7 @@ def test_draft_entry_edge_cases(speculative_emulated):
 
 @pytest.mark.parametrize("graphs", [True, False])
 @pytest.mark.parametrize("B,k,kw", [(1, 4, {}), (5, 2, {}), (3, 3, SAMPLED[1]), (12, 1, {})])
-def test_emulated_matches_statement(speculative_emulated, graphs, B, k, kw, monkeypatch):
+def test_emulated_matches_statement(emulated_hip, graphs, B, k, kw, monkeypatch):
     monkeypatch.setattr(Llama, "graph_decode", graphs)
     monkeypatch.setattr(Llama, "decode_ahead", False)
     Graph.clear()
@@ -193,7 +186,7 @@ def test_emulated_matches_statement(speculative_emulated, graphs, B, k, kw, monk
     assert m._spec_st["B"] == B and m._spec_st["k"] == k
 
 
-def test_emulated_plan_is_reused(speculative_emulated):
+def test_emulated_plan_is_reused(emulated_hip):
     Graph.clear()
     prompts = _repetitive([3, 5], seed=7)
     m = _model("hip:0")
@@ -203,11 +196,11 @@ def test_emulated_plan_is_reused(speculative_emulated):
     assert m._spec_st is st and np.array_equal(a, b)
 
 
-def test_emulated_refusing_library_follows_the_statement(speculative_emulated, monkeypatch):
+def test_emulated_refusing_library_follows_the_statement(emulated_hip, monkeypatch):
     """Without the speculative entries the passes run on the generic rows step; tokens and counts as on `cpu`."""
     Graph.clear()
     from pydynet_amd import _lib
-    monkeypatch.delattr(_lib._LIB, "pdn_spec_draft_rows")
+    remove(monkeypatch, _lib._LIB, "pdn_spec_draft_rows")
     prompts = _repetitive([3, 6, 2], seed=8)
     want, wc = _spec(_model("cpu"), prompts, 9, 3, stop_ids=[9])
     m = _model("hip:0")

@@ -9,7 +9,7 @@ from pydynet_amd import _lib
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm.llama import Llama
 from pydynet_amd.llm.sampling import params_bytes
-from tests.speculative_abi_emulation import counters, draft_np, settle_np
+from tests.abi_emulator import counters, draft_np, settle_np
 from tests.test_serve_gpu import SAMPLED, _check, _model, _ragged_reference
 
 pytestmark = pytest.mark.gpu

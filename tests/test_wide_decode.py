@@ -1,6 +1,6 @@
 """The wide decode step (9 .. 256 rows, csrc/decode_wide.hip) on the CPU: the emulated C ABI with the entry points of
-tests/wide_abi_emulation.py against the `cpu` device (the module path).  `generate`, `generate_ragged` and `serve` past
-8 rows take the wide plan and give the module path's tokens, greedy and sampled; `Llama.wide_decode = False`, more than
+tests/abi_emulator/_decode_rows.py against the `cpu` device (the module path).  `generate`, `generate_ragged` and `serve`
+past 8 rows take the wide plan and give the module path's tokens, greedy and sampled; `Llama.wide_decode = False`, more than
 256 rows and shapes the wide step does not take keep the generic step."""
 import numpy as np
 import pytest
@@ -8,11 +8,7 @@ import pytest
 import pydynet_amd as pdn
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm.llama import Llama
-from tests.clip_abi_emulation import clip_emulated  # noqa: F401  (fixture)
-from tests.ragged_abi_emulation import ragged_emulated  # noqa: F401  (fixture)
-from tests.sampling_abi_emulation import sampling_emulated  # noqa: F401  (fixture)
-from tests.serve_abi_emulation import serve_emulated  # noqa: F401  (fixture)
-from tests.wide_abi_emulation import counters, wide_emulated  # noqa: F401  (fixture)
+from tests.abi_emulator import counters
 
 V = 64
 SAMPLED = dict(temperature=0.9, top_k=20, top_p=0.95, seed=7)
@@ -64,7 +60,7 @@ def _wide(m, B):
 
 @pytest.mark.parametrize("B", [9, 16, 33])
 @pytest.mark.parametrize("kw", [{}, SAMPLED])
-def test_generate_on_the_wide_step(wide_emulated, B, kw):
+def test_generate_on_the_wide_step(emulated_hip, B, kw):
     Graph.clear()
     ids = _ids(B)
     cpu = _generate(_model("cpu", B), ids, 12, **kw)
@@ -78,7 +74,7 @@ def test_generate_on_the_wide_step(wide_emulated, B, kw):
 
 @pytest.mark.parametrize("B", [9, 16, 33])
 @pytest.mark.parametrize("kw", [{}, SAMPLED])
-def test_generate_ragged_with_stops_on_the_wide_step(wide_emulated, B, kw):
+def test_generate_ragged_with_stops_on_the_wide_step(emulated_hip, B, kw):
     Graph.clear()
     prompts = _prompts([1 + (5 * i) % 9 for i in range(B)], seed=B)
     stops = [3, 17, 40]
@@ -92,7 +88,7 @@ def test_generate_ragged_with_stops_on_the_wide_step(wide_emulated, B, kw):
 
 
 @pytest.mark.parametrize("kw", [{}, SAMPLED])
-def test_serve_on_the_wide_step(wide_emulated, kw):
+def test_serve_on_the_wide_step(emulated_hip, kw):
     """20 requests through 12 slots, budgets from 0 to 9."""
     Graph.clear()
     prompts = _prompts([1 + (3 * i) % 8 for i in range(20)], seed=3)
@@ -107,7 +103,7 @@ def test_serve_on_the_wide_step(wide_emulated, kw):
 
 
 @pytest.mark.parametrize("kw", [{}, SAMPLED])
-def test_wide_decode_off_keeps_the_generic_step(wide_emulated, kw):
+def test_wide_decode_off_keeps_the_generic_step(emulated_hip, kw):
     Graph.clear()
     B = 16
     ids, prompts = _ids(B), _prompts([2 + i % 5 for i in range(B)], seed=9)
@@ -124,7 +120,7 @@ def test_wide_decode_off_keeps_the_generic_step(wide_emulated, kw):
     assert c[31] == 0 and not m._decode_st["ok"] and not m2._decode_st["ok"]
 
 
-def test_beyond_256_rows_takes_the_generic_step(wide_emulated):
+def test_beyond_256_rows_takes_the_generic_step(emulated_hip):
     Graph.clear()
     B = 257
     ids = _ids(B, L=2)
@@ -136,7 +132,7 @@ def test_beyond_256_rows_takes_the_generic_step(wide_emulated):
     assert counters()[31] == 0 and not m._decode_st["ok"]
 
 
-def test_unsupported_shape_takes_the_generic_step(wide_emulated):
+def test_unsupported_shape_takes_the_generic_step(emulated_hip):
     """F = 90 (not a multiple of 4): pdn_decode_wide_supported refuses."""
     Graph.clear()
     B = 12
@@ -149,7 +145,7 @@ def test_unsupported_shape_takes_the_generic_step(wide_emulated):
     assert counters()[31] == 0 and not m._decode_st["ok"]
 
 
-def test_at_most_8_rows_keep_their_plan(wide_emulated):
+def test_at_most_8_rows_keep_their_plan(emulated_hip):
     Graph.clear()
     ids = _ids(8)
     cpu = _generate(_model("cpu", 8), ids, 10)

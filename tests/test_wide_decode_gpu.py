@@ -12,9 +12,8 @@ from pydynet_amd import _lib
 from pydynet_amd.core.tensor import Graph
 from pydynet_amd.llm import sampling
 from pydynet_amd.llm.llama import Llama
-from tests.sampling_abi_emulation import margin
+from tests.abi_emulator import counters, margin
 from tests.test_serve_gpu import _check, _model, _ragged_reference, _serve_all
-from tests.wide_abi_emulation import counters
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
