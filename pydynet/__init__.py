@@ -14,7 +14,7 @@ from pydynet_amd import __all__  # noqa: F401
 for _name in ("core", "core.tensor", "core.function", "core.fused", "nn", "nn.functional", "nn.init",
               "nn.parameter", "nn.modules", "nn.modules.module", "nn.modules.linear", "nn.modules.conv",
               "nn.modules.norm", "nn.modules.rnn", "nn.modules.activation", "nn.modules.dropout",
-              "nn.modules.loss", "nn.modules.pool", "optim", "optim.optimizer", "optim.lr_scheduler",
+              "nn.modules.loss", "nn.modules.pool", "nn.utils", "optim", "optim.optimizer", "optim.lr_scheduler",
               "cuda", "autograd", "special", "distributed", "hipnp"):
     sys.modules[f"pydynet.{_name}"] = importlib.import_module(f"pydynet_amd.{_name}")
 

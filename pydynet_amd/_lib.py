@@ -14,6 +14,9 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PDN_LIB") or os.path.join(_HERE, "libpdnhip.so")     # PDN_LIB: another build, for same-box A/B runs
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pdn_hip.h")
+# extension entries (prefix pdnx_): exported by the same library and declared in headers of their own (the reason is in
+# include/pdn_optim.h); tests/test_optim_abi_cpu.py holds them to the same header = exports = emulation rule as the core ABI
+EXT_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "pdn_optim.h"),)
 
 _CTYPE = {
     "int": ctypes.c_int,
@@ -29,7 +32,7 @@ def parse_header(path: str = HEADER_PATH):
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     text = re.sub(r"//[^\n]*", "", text)
     protos = {}
-    for m in re.finditer(r"(const\s+char\s*\*|int64_t|int)\s+(pdn_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
+    for m in re.finditer(r"(const\s+char\s*\*|int64_t|int)\s+(pdnx?_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
         ret, name, args = m.group(1), m.group(2), m.group(3)
         restype = ctypes.c_char_p if "char" in ret else _CTYPE[ret]
         argtypes = []
@@ -65,6 +68,8 @@ class _Lib:
         # later by another package in the same process resolves to the same libamdhip64.
         self.cdll = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         self.protos = parse_header()
+        for path in EXT_HEADER_PATHS:
+            self.protos.update(parse_header(path))
         self.fn = {}
         for name, (restype, argtypes) in self.protos.items():
             f = getattr(self.cdll, name)  # AttributeError if the .so lacks a declared symbol

@@ -1,2 +1,2 @@
-from .optimizer import Optimizer, SGD, Adagrad, Adadelta, Adam
+from .optimizer import Optimizer, SGD, Adagrad, Adadelta, Adam, AdamW
 from .lr_scheduler import ExponentialLR, StepLR, MultiStepLR, CosineAnnealingLR
