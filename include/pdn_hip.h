@@ -195,7 +195,10 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *     in 5 (it IS the vocabulary projection + row maxima of a step)
  *  38 prefix caching (csrc/prefix.hip): pdn_kv_copy_prefix_rows_f32
  *  39 lm_head input gradient on split-fp16 MFMA (csrc/lm_head_dx_split.hip): pdn_linear_ce_dx_deferred_split_f32, which
- *     also counts in 12 (it IS the input gradient + sum of exponentials of a step) */
+ *     also counts in 12 (it IS the input gradient + sum of exponentials of a step)
+ *  40 lm_head weight gradient on split-fp16 MFMA (csrc/lm_head_dw_split.hip): no entry of its own, the form
+ *     pdn_linear_ce_backward_f32 takes for dW / dbias (see there); also counts in 13 (it IS the weight gradient with the
+ *     cross-entropy gradient formed inside) */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -954,7 +957,18 @@ int pdn_cross_entropy_bwd_f32(const float* logits, const int64_t* targets, const
  * from the saved logits and the row statistics of pdn_cross_entropy_fwd_f32 as they consume it:
  *   dx (rows x in) = dlogits W^T (+ dx_residual);  dW (in x V) = dw_beta dW + x^T dlogits;
  *   dbias (V) = db_beta dbias + column sums of dlogits.   W (in x V) row-major; any of dx / dW / dbias may be null.
- * in = 288 only (pdn_linear_ce_supported); other shapes use pdn_cross_entropy_bwd_f32 + pdn_gemm_f32. */
+ * in = 288 only (pdn_linear_ce_supported); other shapes use pdn_cross_entropy_bwd_f32 + pdn_gemm_f32.
+ * dW / dbias on split-fp16 MFMA at fp32 accuracy (csrc/lm_head_dw_split.hip: x and the gradient formed from the logits as
+ * two fp16 planes each, three f16 products, the K ranges and slabs of the fp32 kernel; counter slot 40): taken when
+ *   (a) PDN_LMHEAD_DW_SPLIT is not 0 (environment, read once, announced on stderr when 0;
+ *       PDN_LMHEAD_DW_SPLIT_ABLATE = 1 / 2 are timing experiments with WRONG results, announced too),
+ *   (b) rows >= 32768 and V >= 128 (and, as for every shape, in = 288, rows and V multiples of 32),
+ *   (c) the workspace holds the split form's extra region.  pdn_linear_ce_workspace_bytes is, for the shapes of (b) and
+ *       whatever (a) says, the fp32 kernels' need rounded up to 256 bytes PLUS that region, which comes LAST:
+ *           (rows / 32) * 37888 + 1152 bytes
+ *       (x's plane images, 37 KiB per 32 rows, and 288 exponents).  A caller that passes the size less those bytes
+ *       selects the fp32 kernel, silently and correctly: the in-process A/B switch.
+ * Everything else stays on the fp32 MFMA kernel. */
 int pdn_linear_ce_supported(int64_t rows, int V, int in_features);
 int64_t pdn_linear_ce_workspace_bytes(int64_t rows, int V, int in_features);
 int pdn_linear_ce_backward_f32(const float* x, int64_t ldx, const float* logits, const float* lse,

@@ -334,6 +334,15 @@ class linear_cross_entropy(_Operator):
     # the same for the input-gradient product of the deferred form (csrc/lm_head_dx_split.hip; library switch
     # PDN_LMHEAD_DX_SPLIT=0, after which `pdn_linear_ce_dx_deferred_split_supported` answers 0)
     split_dx = True
+    # the same for the weight gradient (csrc/lm_head_dw_split.hip; library switch PDN_LMHEAD_DW_SPLIT=0).  This product has
+    # no entry of its own: `pdn_linear_ce_backward_f32` takes the split form when the workspace holds its extra region --
+    # the LAST (rows / 32) * 37888 + 1152 bytes of `pdn_linear_ce_workspace_bytes` for rows >= 32768 and V >= 128
+    # (include/pdn_hip.h) -- so the in-process form of the switch is to hand it the workspace without that region.
+    split_dw = True
+
+    @staticmethod
+    def _dw_split_extra(rows, V):
+        return (rows // 32) * 37888 + 1152 if (rows >= 32768 and V >= 128) else 0
 
     @staticmethod
     def applicable(x, w, b, targets, reduction="mean"):
@@ -462,7 +471,10 @@ class linear_cross_entropy(_Operator):
             else:
                 db = hp.empty((V,), np.float32)
                 grads[2] = db.reshape(b.shape)
-        ws, wsb = hp.workspace(L.query("pdn_linear_ce_workspace_bytes", n, V, fin)) if (dw is not None or db is not None) else (None, 0)
+        need = L.query("pdn_linear_ce_workspace_bytes", n, V, fin) if (dw is not None or db is not None) else 0
+        ws, wsb = hp.workspace(need) if need else (None, 0)
+        if not linear_cross_entropy.split_dw and need > linear_cross_entropy._dw_split_extra(n, V):
+            wsb = need - linear_cross_entropy._dw_split_extra(n, V)     # (the scratch buffer itself may be larger than asked for)
         L.call("pdn_linear_ce_backward_f32", x2._ptr, x2._strides[0], logits._ptr, lse._ptr, self._t._ptr,
                1.0 / n if self.reduction == "mean" else 1.0, g._ptr, w.data._ptr,
                dx._ptr if dx is not None else None, ex._ptr if ex is not None else None,

@@ -36,7 +36,8 @@ enum {
   PDN_CNT_ATT_STREAM = 11,        // attn_*_stream_kernel, forward or backward
   PDN_CNT_CE_DX_DEFERRED = 12,    // lm_head input gradient + sum of exponentials: gemm_outres_kernel<.., CE 2>, or the
                                   // split-fp16 kernel of csrc/lm_head_dx_split.hip (which counts in 39 as well)
-  PDN_CNT_CE_DW = 13,             // gemm_outres_tn_kernel with the cross-entropy gradient formed inside
+  PDN_CNT_CE_DW = 13,             // gemm_outres_tn_kernel with the cross-entropy gradient formed inside, or the split-fp16
+                                  // kernel of csrc/lm_head_dw_split.hip (which counts in 40 as well)
   PDN_CNT_OUTRES = 14,            // gemm_outres_kernel, plain
   PDN_CNT_OUTRES_TN = 15,         // gemm_outres_tn_kernel, plain
   PDN_CNT_LINEAR_RELU_FWD = 16,   // tiled kernel with the relu + bit-mask store (pdn_linear_relu_fwd_f32)
@@ -64,7 +65,8 @@ enum {
   PDN_CNT_LMHEAD_SPLIT = 37,      // lm_head forward on split-fp16 MFMA (csrc/lm_head_split.hip): also counts in 5
   PDN_CNT_PREFIX = 38,            // prefix caching (csrc/prefix.hip): the row-to-row copy of Llama.serve(prefix_cache=...)
   PDN_CNT_CE_DX_SPLIT = 39,       // lm_head input gradient on split-fp16 MFMA (csrc/lm_head_dx_split.hip): also counts in 12
-  PDN_CNT_SLOTS = 40
+  PDN_CNT_CE_DW_SPLIT = 40,       // lm_head weight gradient on split-fp16 MFMA (csrc/lm_head_dw_split.hip): also counts in 13
+  PDN_CNT_SLOTS = 41
 };
 void pdn_count(int slot);
 

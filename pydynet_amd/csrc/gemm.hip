@@ -913,6 +913,13 @@ int pdn_outres_ce_dx_launch(const float* logits, int64_t ldl, const float* lse, 
 int pdn_outres_ce_dw_launch(const float* X, const float* logits, float* C, int N, int K, int64_t ldx, int64_t ldg,
                             int64_t ldc, int64_t slab, int nw, int k_per_split, const float* lse,
                             const int64_t* targets, float gscale, const float* gdev, float* colsum, void* stream);
+// the same product on split-fp16 MFMA (csrc/lm_head_dw_split.hip): same slabs, same column-sum slabs
+int pdn_outres_ce_dw_split_enabled();
+int pdn_outres_ce_dw_split_supported(int64_t rows, int V, int in_features);
+int64_t pdn_outres_ce_dw_split_extra_bytes(int64_t rows);
+int pdn_outres_ce_dw_split_launch(const float* x, int64_t ldx, const float* logits, float* C, int V, int64_t rows,
+                                  int64_t slab, int k_per_split, const float* lse, const int64_t* targets, float gscale,
+                                  const float* gdev, float* colsum, void* extra, void* stream);
 
 int pdn_outres_ce_dx_deferred_launch(const float* logits, int64_t ldl, const float* rowmax, int max_parts,
                                      const int64_t* targets, float gscale, const float* W, int64_t ldw, float* dx,
@@ -954,8 +961,12 @@ extern "C" int64_t pdn_linear_ce_workspace_bytes(int64_t rows, int V, int in_fea
   if (!pdn_linear_ce_supported(rows, V, in_features)) return 0;
   int nw, kps;
   const int splits = pdn_gemm_outres_tn_plan(V, (int)rows, &nw, &kps);
-  // [weight-gradient slabs | column-sum slabs | input-gradient slabs (K split over the grid when rows are few)]
-  return (int64_t)splits * (in_features + 1) * V * 4 + pdn_gemm_outres_workspace_bytes((int)rows, V);
+  // [weight-gradient slabs | column-sum slabs | input-gradient slabs (K split over the grid when rows are few) |
+  //  rows >= 32768, V >= 128: x's fp16 plane images and 288 exponents for the split-fp16 weight gradient, LAST, at the next
+  //  multiple of 256 bytes: (rows / 32) * 37888 + 1152 bytes, whatever PDN_LMHEAD_DW_SPLIT says]
+  const int64_t base = (int64_t)splits * (in_features + 1) * V * 4 + pdn_gemm_outres_workspace_bytes((int)rows, V);
+  if (!pdn_outres_ce_dw_split_supported(rows, V, in_features)) return base;
+  return ((base + 255) & ~(int64_t)255) + pdn_outres_ce_dw_split_extra_bytes(rows);
 }
 
 extern "C" int pdn_linear_ce_backward_f32(const float* x, int64_t ldx, const float* logits, const float* lse,
@@ -1015,8 +1026,15 @@ extern "C" int pdn_linear_ce_backward_f32(const float* x, int64_t ldx, const flo
                   (long long)workspace_bytes, (long long)need);
     float* slabs = (float*)workspace;
     float* cs = slabs + (int64_t)splits * in_features * V;
-    int rc = pdn_outres_ce_dw_launch(x, logits, slabs, V, (int)rows, ldx, V, V, (int64_t)in_features * V, nw, kps, lse,
-                                     targets, gscale, upstream, dbias ? cs : nullptr, stream);
+    // split-fp16 form: switched on, a shape it takes, and a workspace that holds its extra region behind everything else
+    // (a caller that passes only the fp32 kernel's need selects the fp32 kernel: the in-process A/B switch)
+    const int64_t xoff = ((need + pdn_gemm_outres_workspace_bytes((int)rows, V) + 255) & ~(int64_t)255);
+    const bool split = pdn_outres_ce_dw_split_enabled() && pdn_outres_ce_dw_split_supported(rows, V, in_features) &&
+                       workspace_bytes >= xoff + pdn_outres_ce_dw_split_extra_bytes(rows) && (((uintptr_t)workspace & 15) == 0);
+    int rc = split ? pdn_outres_ce_dw_split_launch(x, ldx, logits, slabs, V, rows, (int64_t)in_features * V, kps, lse, targets,
+                                                   gscale, upstream, dbias ? cs : nullptr, (char*)workspace + xoff, stream)
+                   : pdn_outres_ce_dw_launch(x, logits, slabs, V, (int)rows, ldx, V, V, (int64_t)in_features * V, nw, kps, lse,
+                                             targets, gscale, upstream, dbias ? cs : nullptr, stream);
     if (rc) return rc;
     GemmParams p{};
     p.N = V; p.nb2 = 1; p.splits = splits;
