@@ -198,13 +198,19 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *     also counts in 12 (it IS the input gradient + sum of exponentials of a step)
  *  40 lm_head weight gradient on split-fp16 MFMA (csrc/lm_head_dw_split.hip): no entry of its own, the form
  *     pdn_linear_ce_backward_f32 takes for dW / dbias (see there); also counts in 13 (it IS the weight gradient with the
- *     cross-entropy gradient formed inside) */
+ *     cross-entropy gradient formed inside)
+ *  41 q | k | v + RoPE and gate | up + SwiGLU on split-fp16 MFMA (csrc/rowtile_split.hip): no entry of its own, the form
+ *     the four pdn_{qkv_rope,gateup_swiglu}[_norm]_fwd_f32 entries take at 16384 rows and more (see there); also counts in
+ *     4 / 2 (it IS the q | k | v + RoPE / gate | up + SwiGLU launch of a layer) */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
  * and epilogue reads drained under the next tile's MFMAs) takes a shape when every CU gets an 8-wave workgroup; the chunk
  * kernel of csrc/gemm_rowres.hip the rest.  mode 0 = chunk kernel only, 1 = as described (default), 2 = tile-piece kernel
- * for every valid shape (tests), anything else = query.  Returns the previous mode.  Results are bit-identical. */
+ * for every valid shape (tests), 3 = as 1, but never the split-fp16 form of the q | k | v and gate | up projections (the
+ * in-process A/B switch of csrc/rowtile_split.hip; modes 0 and 2 do not reach it below 16384 rows either), anything else =
+ * query.  Returns the previous mode.  Results of modes 0, 1 below 16384 rows, 2 below 16384 rows and 3 are bit-identical;
+ * the split form agrees with them to fp32 round-off. */
 int pdn_gemm_rowtile_mode(int mode);
 /* Projections with the bandwidth pass next to them folded into the store of the accumulators (round 4;
  * csrc/gemm_rowres.hip, contraction 288 only -- `*_supported` says whether a shape is taken; PDN_EUNSUPPORTED otherwise):
@@ -214,7 +220,15 @@ int pdn_gemm_rowtile_mode(int mode);
  *    saved gu -- dh itself is never written;
  *  - q | k | v projection + RoPE on the q and k blocks (model.py:23-44, 93-104): qkv (M x 3D) = x [Wq | Wk | Wv], row m is
  *    position m % L; `rope` is the (L x hd x 2) table pdn_rope_table_f32 expands from the reference's (L x hd/2)
- *    cos / sin tables: (cos, sin with the sign of the column's place in its pair). */
+ *    cos / sin tables: (cos, sin with the sign of the column's place in its pair).
+ * The 16384-row split form (csrc/rowtile_split.hip, counter slot 41): pdn_gateup_swiglu_fwd_f32, pdn_qkv_rope_fwd_f32 and
+ * their *_norm_* forms run on split-fp16 MFMA at fp32 accuracy -- x (after the RMSNorm, where one is folded in) and W as two
+ * fp16 planes each with one power of two per row of x and per column of W, three f16 products, the scale removed by one
+ * ldexp before RoPE / SwiGLU -- when M >= 16384, hd is a multiple of 4, the operands are 16-byte aligned, the stream is
+ * not being captured (the tile images of W, (3D / 32 or 2F / 32) x 37120 bytes, come from pdn_malloc and are rebuilt on
+ * every call), PDN_ROWTILE_SPLIT is not 0 (environment, read once, announced on stderr when 0; PDN_ROWTILE_SPLIT_ABLATE =
+ * 1 / 2 are timing experiments with WRONG results, announced too) and pdn_gemm_rowtile_mode is not 3.  Everything else
+ * stays on the fp32 MFMA kernels.  xn and rms are left exactly as the fp32 form leaves them (to fp32 round-off). */
 /* dX (M x 288) = [d_1 | ... | d_nb] (M x nb * kb) [W_1 | ... | W_nb]^T (+ residual): the input gradient of projections
  * that share their input, the weights W_i (288 x kb, row-major, `b_block_stride` floats apart) read where they live
  * (csrc/gemm_outres.hip; `grad @ W^T` of tensor.py:670, one contraction over all projections) */

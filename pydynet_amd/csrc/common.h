@@ -23,9 +23,9 @@ void pdn_set_error(const char* fmt, ...);
 enum {
   PDN_CNT_ROWRES_CHUNK = 0,       // gemm_rowres_kernel (chunk kernel), any epilogue
   PDN_CNT_ROWTILE_PLAIN = 1,      // gemm_rowtile_kernel<EPI 0>
-  PDN_CNT_ROWTILE_SWIGLU_FWD = 2, // EPI 1: gate | up + SwiGLU
+  PDN_CNT_ROWTILE_SWIGLU_FWD = 2, // EPI 1: gate | up + SwiGLU (gemm_rowtile_kernel, or the split-fp16 kernel of csrc/rowtile_split.hip: 41 as well)
   PDN_CNT_ROWTILE_SWIGLU_BWD = 3, // EPI 2: dh + SwiGLU backward
-  PDN_CNT_ROWTILE_ROPE = 4,       // EPI 3: q | k | v + RoPE
+  PDN_CNT_ROWTILE_ROPE = 4,       // EPI 3: q | k | v + RoPE (likewise)
   PDN_CNT_ROWTILE_ROWMAX = 5,     // vocabulary projection + row maxima: gemm_rowtile_kernel<EPI 5>, or the split-fp16
                                   // kernel of csrc/lm_head_split.hip (which counts in 37 as well)
   PDN_CNT_ROWRES_CHUNK_EPI = 6,   // gemm_rowres_kernel with a fused epilogue (EPI 1 / 2 / 3 / 4 / 5)
@@ -66,7 +66,8 @@ enum {
   PDN_CNT_PREFIX = 38,            // prefix caching (csrc/prefix.hip): the row-to-row copy of Llama.serve(prefix_cache=...)
   PDN_CNT_CE_DX_SPLIT = 39,       // lm_head input gradient on split-fp16 MFMA (csrc/lm_head_dx_split.hip): also counts in 12
   PDN_CNT_CE_DW_SPLIT = 40,       // lm_head weight gradient on split-fp16 MFMA (csrc/lm_head_dw_split.hip): also counts in 13
-  PDN_CNT_SLOTS = 41
+  PDN_CNT_ROWTILE_SPLIT = 41,     // q | k | v + RoPE / gate | up + SwiGLU on split-fp16 MFMA (csrc/rowtile_split.hip): also counts in 4 / 2
+  PDN_CNT_SLOTS = 42
 };
 void pdn_count(int slot);
 

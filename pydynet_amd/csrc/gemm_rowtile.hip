@@ -525,11 +525,12 @@ static void rowtile_plan(const RowTileArgs& a, int* pieces, int* ppw, int* nspli
 }
 
 // 0 = never (the chunk kernel of gemm_rowres.hip runs), 1 = when every CU gets an 8-wave workgroup (default), 2 = whenever
-// the shape is valid (tests: small and ragged shapes on this kernel).  PDN_ROWTILE sets the initial value.
+// the shape is valid (tests: small and ragged shapes on this kernel), 3 = as 1, but never the split-fp16 form of the
+// q | k | v and gate | up projections (csrc/rowtile_split.hip): the in-process A/B switch.  PDN_ROWTILE sets the initial value.
 static int g_rowtile_mode = getenv("PDN_ROWTILE") ? atoi(getenv("PDN_ROWTILE")) : 1;
 extern "C" int pdn_gemm_rowtile_mode(int mode) {
   const int prev = g_rowtile_mode;
-  if (mode >= 0 && mode <= 2) g_rowtile_mode = mode;
+  if (mode >= 0 && mode <= 3) g_rowtile_mode = mode;
   return prev;
 }
 
@@ -554,6 +555,7 @@ int pdn_rowtile_launch(const RowTileArgs& a, void* stream) {
   int pieces, ppw, nsplit;
   rowtile_plan(a, &pieces, &ppw, &nsplit);
   if (a.epi == 5 && !a.lse) { if (a.parts) *a.parts = nsplit; return PDN_OK; }
+  if (g_rowtile_mode != 3 && pdn_rowtile_split_takes(a, stream)) return pdn_rowtile_split_launch(a, stream);
   RowTileParams p;
   memset(&p, 0, sizeof(p));
   p.A = a.A; p.B = a.B; p.C = a.C;
