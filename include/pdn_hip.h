@@ -116,7 +116,19 @@ int pdn_comm_allgather(void* comm, const void* send, void* recv, int64_t bytes_p
  * Optional epilogue fusions: `residual` (indexed like C) is added to the result -- the
  * `x + sublayer(x)` of llm/llama/model.py:146,150; `b_colsum[N]` receives the column sums of B
  * for the A^T-form product x^T @ g -- the bias gradient the engine obtains by summing the
- * broadcast axes (tensor.py:360-370) -- in the same pass that forms dW. */
+ * broadcast axes (tensor.py:360-370) -- in the same pass that forms dW.
+ * The packed layer weight gradients -- A = x^T (288 x K, a_rs 1), B = dq | dk | dv or dgate | dup as `nbatch` column
+ * blocks of one K x (N nbatch) matrix (768 .. 8192 columns in all, b_rs possibly padded), K >= 16384 -- run on the
+ * output-resident TN kernel with K split into slabs.  From K = 32768 on, with N a multiple of 16 and 16-byte aligned
+ * operands and workspace, they take the split-fp16 MFMA form of csrc/outres_tn_split.hip (x as per-column-scaled plane
+ * images made by three passes per call, g split in registers under a running exponent per wave; fp32 accuracy) when
+ *   (a) PDN_OUTRES_TN_SPLIT is not 0 (environment, read once, announced on stderr when 0; PDN_OUTRES_TN_SPLIT_ABLATE = 1 / 2
+ *       are timing experiments with WRONG results, announced too), and
+ *   (b) `workspace_bytes` holds the extra region pdn_gemm_f32_workspace_bytes places LAST for these shapes, whatever the
+ *       switch says: behind the 64 slabs (64 * 288 * N * nbatch * 4 bytes), at the next multiple of 256 bytes,
+ *       (K / 32) * 36864 + 1152 bytes.  A caller that passes the size less those bytes gets the fp32 kernel, silently and
+ *       correctly: the in-process A/B switch.
+ * Nothing is allocated inside the call (it may run on a capturing stream).  Counter slot 42, and 15 as before. */
 int pdn_gemm_f32(int M, int N, int K, float alpha, const float* A, int64_t a_rs, int64_t a_cs,
                  const float* B, int64_t b_rs, int64_t b_cs, float beta, float* C, int64_t ldc,
                  const float* bias, int nb1, int nb2, int64_t a_bs1, int64_t a_bs2,
@@ -201,7 +213,10 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *     cross-entropy gradient formed inside)
  *  41 q | k | v + RoPE and gate | up + SwiGLU on split-fp16 MFMA (csrc/rowtile_split.hip): no entry of its own, the form
  *     the four pdn_{qkv_rope,gateup_swiglu}[_norm]_fwd_f32 entries take at 16384 rows and more (see there); also counts in
- *     4 / 2 (it IS the q | k | v + RoPE / gate | up + SwiGLU launch of a layer) */
+ *     4 / 2 (it IS the q | k | v + RoPE / gate | up + SwiGLU launch of a layer)
+ *  42 packed layer weight gradients on split-fp16 MFMA (csrc/outres_tn_split.hip): no entry of its own, the form
+ *     pdn_gemm_f32 takes for x^T against dq | dk | dv / dgate | dup at 32768 tokens and more (see there); also counts in
+ *     15 (it IS the output-resident TN launch of the product) */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores

@@ -39,7 +39,8 @@ enum {
   PDN_CNT_CE_DW = 13,             // gemm_outres_tn_kernel with the cross-entropy gradient formed inside, or the split-fp16
                                   // kernel of csrc/lm_head_dw_split.hip (which counts in 40 as well)
   PDN_CNT_OUTRES = 14,            // gemm_outres_kernel, plain
-  PDN_CNT_OUTRES_TN = 15,         // gemm_outres_tn_kernel, plain
+  PDN_CNT_OUTRES_TN = 15,         // gemm_outres_tn_kernel, plain, or the split-fp16 kernel of csrc/outres_tn_split.hip
+                                  // for the packed layer weight gradients (which counts in 42 as well)
   PDN_CNT_LINEAR_RELU_FWD = 16,   // tiled kernel with the relu + bit-mask store (pdn_linear_relu_fwd_f32)
   PDN_CNT_LINEAR_DX_MASKED = 17,  // tiled kernel with the bit mask applied in the store (pdn_linear_dx_masked_f32)
   PDN_CNT_CE_SMALL = 18,          // ce_small_kernel: cross entropy over <= 32 classes, one thread per row
@@ -67,7 +68,9 @@ enum {
   PDN_CNT_CE_DX_SPLIT = 39,       // lm_head input gradient on split-fp16 MFMA (csrc/lm_head_dx_split.hip): also counts in 12
   PDN_CNT_CE_DW_SPLIT = 40,       // lm_head weight gradient on split-fp16 MFMA (csrc/lm_head_dw_split.hip): also counts in 13
   PDN_CNT_ROWTILE_SPLIT = 41,     // q | k | v + RoPE / gate | up + SwiGLU on split-fp16 MFMA (csrc/rowtile_split.hip): also counts in 4 / 2
-  PDN_CNT_SLOTS = 42
+  PDN_CNT_OUTRES_TN_SPLIT = 42,   // packed layer weight gradients (x^T against dq | dk | dv, dgate | dup) on split-fp16 MFMA
+                                  // (csrc/outres_tn_split.hip): also counts in 15
+  PDN_CNT_SLOTS = 43
 };
 void pdn_count(int slot);
 

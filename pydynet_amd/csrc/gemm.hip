@@ -202,10 +202,22 @@ extern "C" int pdn_gemm_rowres_f32(const float* A, const float* B, float* C, con
 int pdn_gemm_rowres_blocks(const float* A, const float* B, float* C, int M, int N, int K, int64_t lda, int64_t ldb,
                            int64_t ldc, int b_trans, int nblocks, int64_t b_block_stride, void* stream);
 
+// csrc/outres_tn_split.hip: the packed layer weight gradients on split-fp16 MFMA
+int pdn_outres_tn_split_enabled();
+int pdn_outres_tn_split_supported(int M, int nb_cols, int nbatch, int K);
+int64_t pdn_outres_tn_split_extra_bytes(int K);
+int pdn_outres_tn_split_ranges(int n_all, int K, int plan);
+int pdn_outres_tn_split_launch(const float* X, const float* G, float* C, int n_all, int K, int64_t ldx, int64_t ldg,
+                               int nb_cols, int k_per_split, void* extra, void* stream);
+
 extern "C" int64_t pdn_gemm_f32_workspace_bytes(int M, int N, int K, int nbatch) {
   // Enough for up to 64 splits of one output; pdn_gemm_f32 never uses more than it is given.
-  (void)K;
-  return (int64_t)64 * M * N * (int64_t)nbatch * 4;
+  // [64 slabs | the shapes of the split-fp16 packed weight gradients (288 rows, two or more blocks, K >= 32768): x's fp16
+  //  plane images and 288 exponents, LAST, at the next multiple of 256 bytes: (K / 32) * 36864 + 1152 bytes, whatever
+  //  PDN_OUTRES_TN_SPLIT says]
+  const int64_t base = (int64_t)64 * M * N * (int64_t)nbatch * 4;
+  if (!pdn_outres_tn_split_supported(M, N, nbatch, K)) return base;
+  return ((base + 255) & ~(int64_t)255) + pdn_outres_tn_split_extra_bytes(K);
 }
 
 // csrc/gemm_narrow.hip: products with at most 16 output columns (bandwidth kernels)
@@ -455,7 +467,17 @@ static int gemm_f32_impl(int M, int N, int K, float alpha, const float* A, int64
         b_rs >= n_all && alpha == 1.f && !b_colsum && !bias && !residual && N % 32 == 0 && n_all >= 768 && n_all <= 8192 &&
         K % 32 == 0 && K >= 16384 && m4(a_cs) && m4(b_rs) && al16(A) && al16(B) && !getenv("PDN_GEMM_NO_OUTRES")) {
       int nw = 8, kps = K;
-      const int splits = pdn_gemm_outres_tn_plan((int)n_all, K, &nw, &kps);
+      int splits = pdn_gemm_outres_tn_plan((int)n_all, K, &nw, &kps);
+      // split-fp16 form (csrc/outres_tn_split.hip): switched on, a shape it takes, 16-byte aligned operands, and a workspace
+      // that holds its extra region behind the 64 slabs (a caller that passes only the slabs selects the fp32 kernel: the
+      // in-process A/B switch).  It cuts K into its own number of ranges, at most 64.
+      const int64_t xoff = (((int64_t)64 * M * n_all * 4 + 255) & ~(int64_t)255);
+      const bool split16 = pdn_outres_tn_split_supported(M, N, nbatch, K) && pdn_outres_tn_split_enabled() && workspace &&
+                           workspace_bytes >= xoff + pdn_outres_tn_split_extra_bytes(K) && al16(workspace);
+      if (split16) {
+        kps = ((K / 32 + pdn_outres_tn_split_ranges((int)n_all, K, splits) - 1) / pdn_outres_tn_split_ranges((int)n_all, K, splits)) * 32;
+        splits = (K + kps - 1) / kps;
+      }
       if (splits > 1 && (int64_t)splits * M * n_all <= ws_cap && nbatch * splits <= 65535) {
         bool prof;
         ProfRec rec;
@@ -471,9 +493,11 @@ static int gemm_f32_impl(int M, int N, int K, float alpha, const float* A, int64
           PDN_HIP(hipEventRecord(rec.e0, st));
         }
         if (getenv("PDN_GEMM_DEBUG"))
-          fprintf(stderr, "pdn_gemm_f32 M=%d N=%lld K=%d -> output-resident TN (%d blocks, splits %d)\n", M,
-                  (long long)n_all, K, nbatch, splits);
-        int rc = pdn_gemm_outres_tn_blocks_launch(A, B, (float*)workspace, (int)n_all, K, a_cs, b_rs, N, nw, kps, stream);
+          fprintf(stderr, "pdn_gemm_f32 M=%d N=%lld K=%d -> output-resident TN%s (%d blocks, splits %d)\n", M,
+                  (long long)n_all, K, split16 ? ", split-fp16" : "", nbatch, splits);
+        int rc = split16 ? pdn_outres_tn_split_launch(A, B, (float*)workspace, (int)n_all, K, a_cs, b_rs, N, kps,
+                                                      (char*)workspace + xoff, stream)
+                         : pdn_gemm_outres_tn_blocks_launch(A, B, (float*)workspace, (int)n_all, K, a_cs, b_rs, N, nw, kps, stream);
         if (rc) return rc;
         p.splits = splits;
         const int64_t total = (int64_t)M * n_all;

@@ -68,19 +68,17 @@ __global__ __launch_bounds__(288) void ldw_x_colmax_kernel(const float* __restri
   partial[(int64_t)blockIdx.x * LDW_N + d] = fmaxf(fmaxf(sm[0][d], sm[1][d]), fmaxf(sm[2][d], sm[3][d]));
 }
 
-// 9 blocks x (32 columns x 8 partial groups)
+// one workgroup per column: thread i takes parts i, i + 256, .. (eight trips at 2048 parts over 288 workgroups; nine
+// workgroups of 32 columns x 8 part groups made 256 dependent trips, 51 us of latency)
 __global__ __launch_bounds__(256) void ldw_x_shift_kernel(const float* __restrict__ partial, int nparts, int* __restrict__ xsh) {
-  __shared__ float sm[8][32];
-  const int c = threadIdx.x & 31, g = threadIdx.x >> 5, d = blockIdx.x * 32 + c;
+  __shared__ float sm[4];
+  const int d = blockIdx.x;
   float m = 0.f;
-  for (int b = g; b < nparts; b += 8) m = fmaxf(m, partial[(int64_t)b * LDW_N + d]);
-  sm[g][c] = m;
+  for (int b = threadIdx.x; b < nparts; b += 256) m = fmaxf(m, partial[(int64_t)b * LDW_N + d]);
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
   __syncthreads();
-  if (g == 0) {
-#pragma unroll
-    for (int i = 1; i < 8; ++i) m = fmaxf(m, sm[i][c]);
-    xsh[d] = ls_shift(m);
-  }
+  if (threadIdx.x == 0) xsh[d] = ls_shift(fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])));
 }
 
 // ---- X: the plane images, one workgroup per piece of 32 tokens; the tail holds the row statistics of the NEXT piece ------
@@ -352,7 +350,7 @@ int pdn_outres_ce_dw_split_launch(const float* x, int64_t ldx, const float* logi
   const int nparts = ldw_partials(rows);
   const int rpb = (M + nparts - 1) / nparts;
   hipLaunchKernelGGL(ldw_x_colmax_kernel, dim3((M + rpb - 1) / rpb), dim3(288), 0, st, x, ldx, M, rpb, partial);
-  hipLaunchKernelGGL(ldw_x_shift_kernel, dim3(LDW_N / 32), dim3(256), 0, st, partial, (M + rpb - 1) / rpb, xsh);
+  hipLaunchKernelGGL(ldw_x_shift_kernel, dim3(LDW_N), dim3(256), 0, st, partial, (M + rpb - 1) / rpb, xsh);
   hipLaunchKernelGGL(ldw_split_x_kernel, dim3(npieces), dim3(256), 0, st, x, ldx, xsh, lse, targets, M, ximg);
   LdwParams p;
   memset(&p, 0, sizeof(p));
