@@ -191,16 +191,18 @@ def on_reshape(t, new_shape):
     return _linear(x.reshape(*shape[:-1], x.shape[-1]), w, b)
 
 
-def on_cross_entropy(y_pred, y_true, reduction):
+def on_cross_entropy(y_pred, y_true, reduction, ignore_index=None):
     """Hook of F.cross_entropy_loss (class-index targets, 2-D float32 predictions)."""
     if not (loss_chain.enabled and _pending_linear(y_pred) and y_pred.ndim == 2):
         return None
     x, w = y_pred._pending[0], y_pred._pending[1]
     b = y_pred._pending[2] if y_pred.has_bias else None
-    if not _linear_ce.applicable(x, w, b, y_true, reduction):
+    if not _linear_ce.applicable(x, w, b, y_true, reduction, ignore_index):
         return None
     loss_chain.fused_built += 1
-    return _linear_ce(x, w, b, y_true, reduction)
+    if ignore_index is None:
+        return _linear_ce(x, w, b, y_true, reduction)
+    return _linear_ce(x, w, b, y_true, reduction, ignore_index)
 
 
 # ---- the backward pass of the reference's rotary embedding (llm/llama/model.py:23-44) ----------------------------------

@@ -11,6 +11,7 @@ from ... import _lib
 from ...autograd import is_grad_enable
 from ..tensor import Tensor, _Operator
 from ._common import _hip, _L, _contig, _require_f32, _foldable, _beside, _is_leaf_f32, _Deferred, hip_f32
+from . import masked_loss
 
 
 class linear(_Deferred, _Operator):
@@ -236,12 +237,20 @@ class embedding(_Operator):
 
 
 class cross_entropy(_Operator):
-    """mean / sum over rows of  logsumexp(x_n) - x_n[t_n]   (integer targets)."""
+    """mean / sum over rows of  logsumexp(x_n) - x_n[t_n]   (integer targets).
 
-    def __init__(self, logits, targets, reduction="mean"):
+    `ignore_index` (None: off, exactly the node above): rows whose target equals it add nothing to the loss and get a
+    gradient row of exactly 0; 'mean' divides by the number of remaining rows.  The statement is core/fused/masked_loss.py.  With no
+    row left the loss is 0 and every gradient is 0 -- torch returns NaN there; a replayed training step cannot look at its
+    loss before the optimizer runs, and a NaN gradient would poison Adam's moments for good.  On a HIP device the count and
+    its reciprocal stay on the device (`pdnl_*` entries of include/pdn_loss.h): nothing is read back, so the node can be
+    captured in a `hipnp.Graph` and follows a targets buffer whose mask changes between replays."""
+
+    def __init__(self, logits, targets, reduction="mean", ignore_index=None):
         if reduction not in ("mean", "sum"):
             raise ValueError("reduction must be mean or sum.")
         self.reduction = reduction
+        self.ignore_index = None if ignore_index is None else int(ignore_index)
         self._t = targets.data if isinstance(targets, Tensor) else targets
         super().__init__(logits)
 
@@ -251,6 +260,13 @@ class cross_entropy(_Operator):
             t = np.asarray(self._t)
             m = x.data.max(-1, keepdims=True)
             self._lse = np.log(np.exp(x.data - m).sum(-1, keepdims=True)) + m
+            if self.ignore_index is not None:
+                masked_loss.check_targets(t, self.ignore_index, V)
+                self._valid = masked_loss.valid_rows(t, self.ignore_index)
+                self._ts = np.where(self._valid, t, 0)
+                self._factor = masked_loss.scale(t, self.ignore_index, self.reduction)[1]
+                rows = np.where(self._valid, self._lse[:, 0] - x.data[np.arange(n), self._ts], 0)
+                return (rows.sum() * np.asarray(self._factor, x.dtype)).astype(x.dtype)
             rows = self._lse[:, 0] - x.data[np.arange(n), t]
             return rows.mean() if self.reduction == "mean" else rows.sum()
         _require_f32(self, x)
@@ -265,6 +281,22 @@ class cross_entropy(_Operator):
         mean = 1 if self.reduction == "mean" else 0
         self._dx = None
         from ...autograd import is_grad_enable
+        if self.ignore_index is not None:
+            # the masked entries: the count and 1 / count are device scalars (`_stats`), read by the kernels themselves
+            self._stats = hp.empty((4,), np.float32)
+            if x.requires_grad and is_grad_enable():
+                self._dx = hp.empty((n, V), np.float32)
+                wsb = L.query("pdnl_cross_entropy_colsum_workspace_bytes", n, V)
+                cs = hp.empty((V,), np.float32) if wsb else None
+                ws, wsb = hp.workspace(wsb) if wsb else (None, 0)
+                L.call("pdnl_cross_entropy_fwd_bwd_f32", self._x._ptr, self._t._ptr, self.ignore_index, n, V, mean,
+                       loss_row._ptr, self._lse._ptr, out._ptr, self._stats._ptr, self._dx._ptr,
+                       cs._ptr if cs is not None else None, ws, wsb, hp.err_flag_ptr(), hp.stream())
+                self._dx._aux = ("colsum", cs) if cs is not None else None
+            else:
+                L.call("pdnl_cross_entropy_fwd_f32", self._x._ptr, self._t._ptr, self.ignore_index, n, V, mean, loss_row._ptr,
+                       self._lse._ptr, out._ptr, self._stats._ptr, hp.err_flag_ptr(), hp.stream())
+            return out.reshape(())
         if x.requires_grad and is_grad_enable():
             # the gradient w.r.t. the logits needs nothing computed later: write it now, while each
             # row is still in L2 (one pass over HBM for forward + backward)
@@ -289,6 +321,10 @@ class cross_entropy(_Operator):
         scale = 1.0 / n if self.reduction == "mean" else 1.0
         if self.xp is np:
             sm = np.exp(x.data - self._lse)
+            if self.ignore_index is not None:
+                sm[np.arange(n), self._ts] -= 1
+                sm[~self._valid] = 0
+                return [sm * (g * np.asarray(self._factor, x.dtype))]
             sm[np.arange(n), np.asarray(self._t)] -= 1
             return [sm * (g * np.asarray(scale, x.dtype))]
         hp, L = _hip(), _L()
@@ -301,6 +337,10 @@ class cross_entropy(_Operator):
                 L.call("pdn_scale_by_device_scalar_f32", aux[1]._ptr, aux[1].size, g._ptr, hp.stream())
             return [dx]
         dx = hp.empty((n, V), np.float32)
+        if self.ignore_index is not None:
+            L.call("pdnl_cross_entropy_bwd_f32", self._x._ptr, self._t._ptr, self.ignore_index, self._lse._ptr, g._ptr,
+                   self._stats._ptr, dx._ptr, n, V, hp.stream())
+            return [dx]
         L.call("pdn_cross_entropy_bwd_f32", self._x._ptr, self._t._ptr, self._lse._ptr, g._ptr,
                scale, dx._ptr, n, V, hp.stream())
         return [dx]
@@ -318,7 +358,14 @@ class linear_cross_entropy(_Operator):
     validation losses in `no_grad()` -- and (ii) dx is formed from the weights as they are at forward time: updating the
     weight IN PLACE between forward and backward leaves dx consistent with the forward pass (as the reference's tape is)
     but not with a dW computed from the new weights; `backward_all` asserts that the weight buffer is still the one
-    forward read."""
+    forward read.
+    `ignore_index` (None: off, exactly the node above; the contract is `cross_entropy`'s, core/fused/masked_loss.py): the products
+    stay the kernels they are.  `pdnl_linear_ce_finish_f32` takes the place of the loss-from-lse launch: it leaves the count
+    and 1 / count on the device, a copy of the targets with V on every ignored row and an lse of +inf there, with which both
+    terms of dlogits the weight-gradient product forms are exactly 0 on those rows; under 'mean' the products run with
+    gscale 1 and the upstream device scalar carries 1 / count.  `pdnl_linear_ce_backward_f32` then sets the rows of ignored
+    tokens in dx to 0 (the input-gradient kernels subtract a gathered weight column whatever the row).  Nothing is folded
+    into dx on this path.  On the `cpu` device the node is the NumPy statement of the same contract."""
 
     folds_existing = True
     enabled = True
@@ -345,7 +392,7 @@ class linear_cross_entropy(_Operator):
         return (rows // 32) * 37888 + 1152 if (rows >= 32768 and V >= 128) else 0
 
     @staticmethod
-    def applicable(x, w, b, targets, reduction="mean"):
+    def applicable(x, w, b, targets, reduction="mean", ignore_index=None):
         if not (linear_cross_entropy.enabled and x.device.is_hip and x.dtype == np.float32 and w.dtype == np.float32
                 and (b is None or b.dtype == np.float32) and reduction in ("mean", "sum") and w.ndim == 2):
             return False
@@ -360,18 +407,61 @@ class linear_cross_entropy(_Operator):
                 and rows >= linear_cross_entropy.min_rows
                 and bool(_L().query("pdn_linear_ce_supported", rows, w.shape[1], w.shape[0])))
 
-    def __init__(self, x, weight, bias, targets, reduction="mean"):
+    def __init__(self, x, weight, bias, targets, reduction="mean", ignore_index=None):
+        if reduction not in ("mean", "sum"):
+            raise ValueError("reduction must be mean or sum.")
         self.reduction = reduction
+        self.ignore_index = None if ignore_index is None else int(ignore_index)
         self.has_bias = bias is not None
         self._t = targets.data if isinstance(targets, Tensor) else targets
         super().__init__(*([x, weight] + ([bias] if self.has_bias else [])))
 
+    def _forward_np(self, x, w, b):
+        x2 = x.data.reshape(-1, w.shape[0])
+        z = x2 @ w.data
+        if b is not None:
+            z = z + b.data.reshape(-1)
+        n, V = z.shape
+        t = np.asarray(self._t).reshape(-1)
+        if self.ignore_index is None:
+            valid, ts, factor = np.ones(n, bool), t, (1.0 / n if self.reduction == "mean" else 1.0)
+        else:
+            masked_loss.check_targets(t, self.ignore_index, V)
+            valid = masked_loss.valid_rows(t, self.ignore_index)
+            ts, factor = np.where(valid, t, 0), masked_loss.scale(t, self.ignore_index, self.reduction)[1]
+        m = z.max(-1, keepdims=True)
+        lse = np.log(np.exp(z - m).sum(-1, keepdims=True)) + m
+        rows = np.where(valid, lse[:, 0] - z[np.arange(n), ts], 0)
+        self._saved = (x2, z, lse, valid, ts, factor)
+        return (rows.sum() * np.asarray(factor, z.dtype)).astype(z.dtype)
+
+    def _backward_np(self, g):
+        x, w = self.last[0], self.last[1]
+        b = self.last[2] if self.has_bias else None
+        x2, z, lse, valid, ts, factor = self._saved
+        self._saved = None
+        d = np.exp(z - lse)
+        d[np.arange(len(ts)), ts] -= 1
+        d[~valid] = 0
+        d *= g * np.asarray(factor, z.dtype)
+        grads = [None] * len(self.last)
+        if x.requires_grad:
+            grads[0] = (d @ w.data.T).reshape(x.shape)
+        if w.requires_grad:
+            grads[1] = x2.T @ d
+        if b is not None and b.requires_grad:
+            grads[2] = d.sum(0).reshape(b.shape)
+        return grads
+
     def forward_(self, x, w, b=None):
+        if self.xp is np:
+            return self._forward_np(x, w, b)
         _require_f32(self, x, w, b)
         hp, L = _hip(), _L()
         fin, V = w.shape
         x2 = _contig(x.data).reshape(-1, fin)
         n = x2.shape[0]
+        masked = self.ignore_index is not None
         if not hasattr(self._t, "_ptr"):
             self._t = hp.from_numpy(np.asarray(self._t).astype(np.int64))
         self._t = _contig(self._t)
@@ -387,6 +477,17 @@ class linear_cross_entropy(_Operator):
         self._dxu = None
         bp = b.data._ptr if b is not None else None
         mean = 1 if self.reduction == "mean" else 0
+        if masked:
+            # what the finish leaves for the backward: {count, 1 / count, upstream / count} and the sanitised targets
+            self._stats, self._t_safe = hp.empty((4,), np.float32), hp.empty((n,), np.int64)
+
+        def finish():
+            if masked:
+                L.call("pdnl_linear_ce_finish_f32", logits._ptr, V, lse._ptr, self._t._ptr, self.ignore_index, n, V, mean,
+                       loss_row._ptr, out._ptr, self._stats._ptr, self._t_safe._ptr, hp.err_flag_ptr(), hp.stream())
+            else:
+                L.call("pdn_cross_entropy_from_lse_f32", logits._ptr, V, lse._ptr, self._t._ptr, n, V, mean, loss_row._ptr,
+                       out._ptr, hp.err_flag_ptr(), hp.stream())
         if self.deferred:
             # the projection leaves the row maxima; the input-gradient product -- it needs exp(logit - max) anyway, and not
             # the upstream gradient, a scalar applied in backward -- sums the exponentials as it multiplies: it runs HERE,
@@ -418,17 +519,24 @@ class linear_cross_entropy(_Operator):
                     and L.query("pdn_linear_ce_dx_deferred_split_supported", n, V, fin)):
                 dx_entry = "pdn_linear_ce_dx_deferred_split_f32"
             ws, wsb = hp.workspace(L.query(dx_entry.replace("_f32", "_workspace_bytes"), n, V, fin))
+            # (masked: unscaled -- 1 / count is not known yet and is applied with the upstream scalar; the kernel clamps the
+            #  target whose column it subtracts, and the rows of ignored tokens are set to 0 in backward)
             L.call(dx_entry, logits._ptr, rowmax._ptr, parts, self._t._ptr,
-                   1.0 / n if mean else 1.0, wd._ptr, self._dxu._ptr, lse._ptr, n, V, fin, ws, wsb, hp.stream())
-            L.call("pdn_cross_entropy_from_lse_f32", logits._ptr, V, lse._ptr, self._t._ptr, n, V, mean, loss_row._ptr,
-                   out._ptr, hp.err_flag_ptr(), hp.stream())
+                   1.0 / n if (mean and not masked) else 1.0, wd._ptr, self._dxu._ptr, lse._ptr, n, V, fin, ws, wsb,
+                   hp.stream())
+            finish()
         elif self.stats_in_gemm:
             # the projection leaves the rows' log-sum-exp itself (transposed accumulators: a lane owns a token): no
             # pass over the logits for the statistics, the loss is one gather per row
             L.call("pdn_linear_lse_fwd_f32", x2._ptr, wd._ptr, bp, logits._ptr, lse._ptr, n, V, fin, x2._strides[0], V, V,
                    hp.stream())
-            L.call("pdn_cross_entropy_from_lse_f32", logits._ptr, V, lse._ptr, self._t._ptr, n, V, mean, loss_row._ptr,
-                   out._ptr, hp.err_flag_ptr(), hp.stream())
+            finish()
+        elif masked:
+            # statistics by a pass over the logits (which skips the ignored rows); the finish then masks their lse
+            hp.gemm(x2, wd, logits, bias=b.data.reshape(-1) if b is not None else None)
+            L.call("pdnl_cross_entropy_fwd_f32", logits._ptr, self._t._ptr, self.ignore_index, n, V, mean, loss_row._ptr, lse._ptr,
+                   out._ptr, self._stats._ptr, hp.err_flag_ptr(), hp.stream())
+            finish()
         else:
             hp.gemm(x2, wd, logits, bias=b.data.reshape(-1) if b is not None else None)
             L.call("pdn_cross_entropy_fwd_f32", logits._ptr, self._t._ptr, n, V, mean, loss_row._ptr, lse._ptr, out._ptr,
@@ -437,10 +545,13 @@ class linear_cross_entropy(_Operator):
         return out.reshape(())
 
     def backward_all(self, g):
+        if self.xp is np:
+            return self._backward_np(g)
         hp, L = _hip(), _L()
         x, w = self.last[0], self.last[1]
         b = self.last[2] if self.has_bias else None
         fin, V = w.shape
+        masked = self.ignore_index is not None
         x2, logits, lse = self._saved
         self._saved = None
         n = x2.shape[0]
@@ -452,11 +563,12 @@ class linear_cross_entropy(_Operator):
             raise RuntimeError("linear_cross_entropy: the weight's buffer was replaced between forward and backward; the "
                                "input gradient of the deferred form was formed from the forward pass's weights")
         if x.requires_grad and dxu is not None:
-            dxu *= g.reshape(())                           # formed in the forward pass, up to the upstream scalar
+            if not masked:
+                dxu *= g.reshape(())                       # formed in the forward pass, up to the upstream scalar
             grads[0] = dxu.reshape(x.shape)
         elif x.requires_grad:
             dx = hp.empty(x.shape, np.float32)
-            ex = _foldable(self, 0, x)
+            ex = _foldable(self, 0, x) if not masked else None
             grads[0] = dx
         dw, dw_beta = None, 0.0
         if w.requires_grad:
@@ -475,6 +587,13 @@ class linear_cross_entropy(_Operator):
         ws, wsb = hp.workspace(need) if need else (None, 0)
         if not linear_cross_entropy.split_dw and need > linear_cross_entropy._dw_split_extra(n, V):
             wsb = need - linear_cross_entropy._dw_split_extra(n, V)     # (the scratch buffer itself may be larger than asked for)
+        if masked:
+            dxd = dxu if (x.requires_grad and dxu is not None) else None
+            L.call("pdnl_linear_ce_backward_f32", x2._ptr, x2._strides[0], logits._ptr, lse._ptr, self._t_safe._ptr,
+                   self._stats._ptr, g._ptr, w.data._ptr, dx._ptr if dx is not None else None,
+                   dxd._ptr if dxd is not None else None, dw._ptr if dw is not None else None, dw_beta,
+                   db._ptr if db is not None else None, db_beta, n, V, fin, ws, wsb, hp.stream())
+            return grads
         L.call("pdn_linear_ce_backward_f32", x2._ptr, x2._strides[0], logits._ptr, lse._ptr, self._t._ptr,
                1.0 / n if self.reduction == "mean" else 1.0, g._ptr, w.data._ptr,
                dx._ptr if dx is not None else None, ex._ptr if ex is not None else None,

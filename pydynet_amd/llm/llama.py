@@ -230,7 +230,15 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
             trainable, frozen = trainable + p.requires_grad, frozen + (not p.requires_grad)
         return trainable, frozen
 
-    def loss(self, input_ids, target_ids, criterion=None, start_pos: int = 0):
+    def loss(self, input_ids, target_ids, criterion=None, start_pos: int = 0, ignore_index=None):
+        """Cross entropy of the next-token logits.  `criterion.ignore_index` (nn.CrossEntropyLoss), or the `ignore_index`
+        keyword when no criterion is given: targets equal to it -- a prompt region, right padding -- add nothing to the loss
+        or the gradients and the mean runs over the remaining tokens (core/fused/masked_loss.py; 0, not NaN, when none
+        remains).  Under data parallel each rank divides by its own count."""
+        if criterion is not None and ignore_index is not None:
+            raise ValueError("pass ignore_index through the criterion (nn.CrossEntropyLoss(ignore_index=...)), not beside it")
+        if criterion is not None:
+            ignore_index = getattr(criterion, "ignore_index", None)
         h = self._forward_hidden(input_ids, start_pos)
         if isinstance(target_ids, Tensor):
             targets = target_ids.reshape(-1)
@@ -240,18 +248,23 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         bias = getattr(head, "bias", None)
         reduction = getattr(criterion, "reduction", "mean") if criterion is not None else "mean"
         if ((criterion is None or type(criterion) is nn.CrossEntropyLoss) and type(head) is nn.Linear
-                and fused.linear_cross_entropy.applicable(h, head.weight, bias, targets, reduction)):
+                and fused.linear_cross_entropy.applicable(h, head.weight, bias, targets, reduction, ignore_index)):
             # lm_head + cross entropy as one node: the (tokens, vocab) gradient of the logits is never written
-            return fused.linear_cross_entropy(h, head.weight, bias, targets, reduction)
+            if ignore_index is None:
+                return fused.linear_cross_entropy(h, head.weight, bias, targets, reduction)
+            return fused.linear_cross_entropy(h, head.weight, bias, targets, reduction, ignore_index)
         logits = head(h)
         B, L, V = logits.shape
-        return (criterion or nn.CrossEntropyLoss())(logits.reshape(B * L, V), targets)
+        if criterion is None:
+            criterion = nn.CrossEntropyLoss() if ignore_index is None else nn.CrossEntropyLoss(ignore_index=ignore_index)
+        return criterion(logits.reshape(B * L, V), targets)
 
-    def finetune_step(self, input_ids, target_ids, optimizer, criterion=None, start_pos: int = 0):
-        """zero_grad -> forward -> cross entropy -> backward -> optimizer step; returns the loss."""
+    def finetune_step(self, input_ids, target_ids, optimizer, criterion=None, start_pos: int = 0, ignore_index=None):
+        """zero_grad -> forward -> cross entropy -> backward -> optimizer step; returns the loss.  `ignore_index`: see
+        `loss`."""
         self.train(True)
         optimizer.zero_grad()
-        loss = self.loss(input_ids, target_ids, criterion, start_pos)
+        loss = self.loss(input_ids, target_ids, criterion, start_pos, ignore_index)
         loss.backward()
         optimizer.step()
         return loss.item()

@@ -155,9 +155,18 @@ def nll_loss(y_pred, y_true, reduction='mean'):
     return _reduce(-y_pred * y_true, reduction)
 
 
-def cross_entropy_loss(y_pred, y_true, reduction='mean'):
+def cross_entropy_loss(y_pred, y_true, reduction='mean', ignore_index=None):
+    """`ignore_index` (an extension; None: off): rows whose class-index target equals it add nothing to the loss or to any
+    gradient, and 'mean' divides by the number of remaining rows -- 0, not torch's NaN, when none remains (the contract and
+    the reason are in core/fused/masked_loss.py).  Under data parallel each rank divides by its own count."""
     if reduction not in ('mean', 'sum'):
         raise ValueError("reduction must be mean or sum.")
+    if ignore_index is not None:
+        if y_true.ndim != 1 or y_pred.ndim != 2:
+            raise ValueError("ignore_index needs class-index targets (rows,) and (rows, classes) predictions, "
+                             "not one-hot or soft targets")
+        r = fused.chain.on_cross_entropy(y_pred, y_true, reduction, ignore_index) if y_pred.dtype == np.float32 else None
+        return r if r is not None else fused.cross_entropy(y_pred, y_true, reduction, ignore_index)
     if y_true.ndim == 1 and y_pred.ndim == 2 and y_pred.dtype == np.float32:
         # a projection that has not run yet + this loss = one node (model.py:239-249 written with plain operators)
         r = fused.chain.on_cross_entropy(y_pred, y_true, reduction)
