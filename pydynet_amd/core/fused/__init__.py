@@ -14,7 +14,8 @@ expression.  Reference chains replaced:
     softmax         nn/functional.py:43-49          (last axis)
     rope            llm/llama/model.py:23-44        (26 nodes)
     attention       llm/llama/model.py:112-121      (transpose, matmul, /sqrt(hd), +mask, softmax, matmul); the same chain
-                                                    BUILT from plain operators is recognised link by link (chain.py)
+                                                    BUILT from plain operators is recognised link by link (chain.py);
+                                                    `segment_ids=`: the document mask of packed rows (segments.py, no counterpart)
     embedding       nn/functional.py:14-20 + tensor.py:937-940 (scatter-ASSIGN gradient)
     cross_entropy   nn/functional.py:364-381        (7 nodes, integer targets)
     linear_cross_entropy  llm/llama/model.py:179 + :239-249 (lm_head -> reshape -> cross entropy as one node); the same
@@ -27,7 +28,7 @@ from ._common import (_hip, _L, _contig, hip_f32, _require_f32, _foldable, two_s
 from .dense import linear, linear_relu, embedding, cross_entropy, linear_cross_entropy
 from .pointwise import gated_sigmoid, swiglu, silu, softmax, rope
 from .norm import rms_norm, layer_norm, col_norm
-from .attn import _attn_layout, _attn_mask_args, _attn_kernel, attention, qkv_attention
+from .attn import _attn_layout, _attn_mask_args, _attn_kernel, attention, qkv_attention, SegmentBounds, segment_bounds
 from .ffn import gate_up_swiglu, ffn_swiglu
 from .conv import relu, conv2d, conv2d_relu_pool, pool2d
 from .recurrent import _cell_grads, rnn_cell, lstm_cell, gru_cell, gru_sequence

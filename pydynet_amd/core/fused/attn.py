@@ -8,6 +8,7 @@ import os
 
 import numpy as np
 
+from . import segments as _seg
 from .norm import rms_norm
 from ..tensor import Tensor, _Operator
 from ._common import _hip, _L, _contig, _require_f32, _beside, _is_leaf_f32, _dx_of_shared_input
@@ -66,6 +67,53 @@ def _attn_kernel(B, H, hd, Lq, Lk, start_pos, mask, layouts):
     return None, None
 
 
+class SegmentBounds:
+    """`start` / `end` of every position's document ((B, L) each; core/fused/segments.py), made once per step from the
+    `segment_ids` and handed to every attention node of the step.  On a HIP device both are int32 device arrays written
+    by pdns_segment_bounds_i32 and never read by the host: a captured step follows an id buffer that is rewritten between
+    replays."""
+    __slots__ = ("start", "end", "shape", "on_hip")
+
+    def __init__(self, start, end, shape, on_hip):
+        self.start, self.end, self.shape, self.on_hip = start, end, tuple(shape), on_hip
+
+
+def segment_bounds(segment_ids, on_hip):
+    """`SegmentBounds` from (B, L) ids: a NumPy integer array (or nested lists) -- checked on the host, ValueError for a row
+    that decreases, uploaded as int32 -- or an int32 device array / Tensor, checked on the device (a row that decreases
+    raises the library's error flag and is attended causally).  A `SegmentBounds` passes through."""
+    if isinstance(segment_ids, SegmentBounds):
+        if segment_ids.on_hip != bool(on_hip):
+            raise ValueError("segment bounds were made for another device")
+        return segment_ids
+    ids = segment_ids.data if isinstance(segment_ids, Tensor) else segment_ids
+    if not on_hip:
+        if not isinstance(ids, (np.ndarray, list, tuple)):
+            ids = ids.get()
+        ids = _seg.check(ids)
+        start, end = _seg.bounds(ids)
+        return SegmentBounds(start, end, ids.shape, False)
+    hp, L = _hip(), _L()
+    if isinstance(ids, (np.ndarray, list, tuple)):
+        ids = hp.asarray(_seg.check(ids).astype(np.int32))
+    elif ids.ndim != 2 or ids.dtype != np.int32:
+        raise ValueError(f"segment_ids on the device must be a (B, L) int32 array, got shape {ids.shape} and dtype {ids.dtype}")
+    ids = _contig(ids)
+    B, Ls = ids.shape
+    start, end = hp.empty((B, Ls), np.int32), hp.empty((B, Ls), np.int32)
+    L.call("pdns_segment_bounds_i32", ids._ptr, B, Ls, start._ptr, end._ptr, hp.err_flag_ptr(), hp.stream())
+    return SegmentBounds(start, end, (B, Ls), True)
+
+
+def _segment_mask(seg, Lq):
+    """The additive (B, 1, L, L) float32 block mask on the device for the shapes the segmented kernels do not take:
+    log(key >= start[query]) is 0 for the keys of the query's document and behind, -inf in front of it."""
+    hp = _hip()
+    keys = hp.asarray(np.arange(Lq, dtype=np.float32)).reshape(1, 1, 1, Lq)
+    B = seg.shape[0]
+    return hp.log((keys >= seg.start.astype(np.float32).reshape(B, 1, Lq, 1)).astype(np.float32))
+
+
 class attention(_Operator):
     """softmax(q k^T / sqrt(hd) + causal_mask + mask) v  per (batch, head).
 
@@ -73,18 +121,25 @@ class attention(_Operator):
     through strides (no transposes, no copies; views into a packed QKV projection or a KV cache are
     fine).  Output (B, L, H, hd).  `causal` applies the additive -inf upper-triangular mask of
     llm/llama/model.py:199-203 with `start_pos`; `mask` is an optional constant additive mask
-    broadcastable to (B, H, L, Lk) (padding masks, llm/clip's causal mask tensor)."""
+    broadcastable to (B, H, L, Lk) (padding masks, llm/clip's causal mask tensor).  `segment_ids` ((B, L) integers,
+    non-decreasing along a row, or a `SegmentBounds`): the documents of a packed row -- a query sees the keys of its own
+    document only (core/fused/segments.py); needs `causal`, `start_pos` 0 and L == Lk.  Resident shapes (hd 48 / 64, L a
+    multiple of 32 up to 1024) run the segmented kernels of include/pdn_segattn.h, any other shape the masked path with
+    the block mask formed on the device."""
 
     use_flash = True      # class switch: False forces the GEMM + softmax path (A/B and tests)
     use_resident = True   # class switch: False sends the benchmark shape through the streaming kernels too
 
-    def __init__(self, q, k, v, causal=True, start_pos=0, mask=None):
+    def __init__(self, q, k, v, causal=True, start_pos=0, mask=None, segment_ids=None):
         self.causal, self.start_pos = bool(causal), int(start_pos)
         self._mask = mask.data if isinstance(mask, Tensor) else mask
         self._kind = None
+        self._segments = segment_ids
+        if segment_ids is not None and (not self.causal or self.start_pos != 0 or q.shape[1] != k.shape[1]):
+            raise ValueError("attention: segment_ids need causal=True, start_pos=0 and as many keys as queries")
         super().__init__(q, k, v)
 
-    def _np_mask(self, Lq, Lk, dtype):
+    def _np_mask(self, Lq, Lk, dtype, B=None):
         add = None
         if self.causal and Lq > 1:
             m = np.triu(np.full((Lq, Lq), float("-inf")), k=1)
@@ -92,14 +147,23 @@ class attention(_Operator):
         if self._mask is not None:
             mk = np.asarray(self._mask, dtype=dtype)
             add = mk if add is None else add + mk
+        if self._segments is not None:
+            mk = _seg.block_mask(self._bounds(B, Lq, False).start, dtype)
+            add = mk if add is None else add + mk
         return add
+
+    def _bounds(self, B, Lq, on_hip):
+        seg = segment_bounds(self._segments, on_hip)
+        if seg.shape != (B, Lq):
+            raise ValueError(f"attention: segment_ids of shape {seg.shape} for {B} rows of {Lq} positions")
+        return seg
 
     def forward_(self, q, k, v):
         B, Lq, H, hd = q.shape
         Lk = k.shape[1]
         if self.xp is np:
             s = np.matmul(q.data.transpose(0, 2, 1, 3), k.data.transpose(0, 2, 3, 1)) / np.asarray(math.sqrt(hd), q.dtype)
-            add = self._np_mask(Lq, Lk, q.dtype)
+            add = self._np_mask(Lq, Lk, q.dtype, B)
             if add is not None:
                 s = s + add
             e = np.exp(s - s.max(-1, keepdims=True))
@@ -110,6 +174,22 @@ class attention(_Operator):
         causal = 1 if (self.causal and Lq > 1) else 0
         layouts = (_attn_layout(q.data), _attn_layout(k.data), _attn_layout(v.data))
         mask_dev = hp.asarray(self._mask) if self._mask is not None else None
+        if self._segments is not None:
+            seg = self._bounds(B, Lq, True)
+            if (mask_dev is None and attention.use_flash and attention.use_resident and None not in layouts
+                    and layouts[0] == layouts[1] == layouts[2] and L.query("pdns_attention_supported", Lq, hd)):
+                self._kind = "segmented"
+                rs, bs = layouts[0]
+                out = hp.empty((B, Lq, H, hd), np.float32)
+                self._lse = hp.empty((B, H, Lq), np.float32)
+                self._res = (q.data, k.data, v.data, seg, rs, bs)
+                L.call("pdns_attention_fwd_f32", q.data._ptr, k.data._ptr, v.data._ptr, out._ptr, self._lse._ptr,
+                       B, H, Lq, hd, rs, bs, H * hd, Lq * H * hd, None, None, seg.start._ptr, hp.stream())
+                return out
+            # any other shape: the block mask as an additive mask of the existing paths
+            block = _segment_mask(seg, Lq)
+            mask_dev = block if mask_dev is None else block + mask_dev.astype(np.float32)
+        self._mask_eff = mask_dev
         self._kind, kb = _attn_kernel(B, H, hd, Lq, Lk, self.start_pos, mask_dev, layouts)
         if self._kind == "resident":
             # scores stay in registers: one kernel, nothing of size L x L in HBM; lse kept for backward
@@ -145,8 +225,8 @@ class attention(_Operator):
         p = hp.empty((B, H, Lq, Lk), np.float32)
         hp.gemm(q.data.transpose(0, 2, 1, 3), k.data.transpose(0, 2, 3, 1), p)
         div = math.sqrt(hd)
-        if self._mask is not None:
-            p = p / np.float32(div) + hp.asarray(self._mask).astype(np.float32)
+        if mask_dev is not None:
+            p = p / np.float32(div) + mask_dev.astype(np.float32)
             div = 1.0
         L.call("pdn_softmax_fwd_f32", p._ptr, p._ptr, B * H * Lq, Lk, div,
                Lq if causal else 0, self.start_pos, hp.stream())
@@ -160,6 +240,21 @@ class attention(_Operator):
         B, Lq, H, hd = q.shape
         Lk = k.shape[1]
         causal = 1 if (self.causal and Lq > 1) else 0
+        if self.xp is not np and self._kind == "segmented":
+            hp, L = _hip(), _L()
+            qd, kd, vd, seg, rs, bs = self._res
+            self._res = None
+            do = _contig(do)
+            dq, dk, dv = (hp.empty((B, Lq, H, hd), np.float32) for _ in range(3))
+            if rs != H * hd or (B > 1 and bs != Lq * H * hd):
+                # (gradients are written with the operand strides: see the resident branch below)
+                qd, kd, vd = qd.copy(), kd.copy(), vd.copy()
+                rs, bs = H * hd, Lq * H * hd
+            ws, wsb = hp.workspace(L.query("pdn_attention_bwd_workspace_bytes", B, H, Lq))
+            L.call("pdns_attention_bwd_f32", qd._ptr, kd._ptr, vd._ptr, self.data._ptr, do._ptr, self._lse._ptr,
+                   dq._ptr, dk._ptr, dv._ptr, B, H, Lq, hd, rs, bs, H * hd, Lq * H * hd, None, None, 0,
+                   seg.start._ptr, seg.end._ptr, ws, wsb, hp.stream())
+            return [dq, dk, dv]
         if self.xp is not np and self._kind == "resident":
             hp, L = _hip(), _L()
             qd, kd, vd, kb, rs, bs = self._res
@@ -190,7 +285,7 @@ class attention(_Operator):
             dk, dv = hp.empty(k.shape, np.float32), hp.empty(v.shape, np.float32)
             klay = (H * hd, Lk * H * hd if B > 1 else 0)
             mp, sb, sh, sq, sk, keep = _attn_mask_args(self._mask_dev, B, H, Lq, Lk) \
-                if self._mask is not None else (None, 0, 0, 0, 0, None)
+                if self._mask_eff is not None else (None, 0, 0, 0, 0, None)
             ws, wsb = hp.workspace(L.query("pdn_attention_stream_bwd_workspace_bytes", B, H, Lq))
             qlay = (H * hd, Lq * H * hd if B > 1 else 0)
             qsrc = self._q_used
@@ -251,8 +346,9 @@ class qkv_attention(_Operator):
             ent = qkv_attention._rope_tables[key] = (tab, cos, sin)
         return ent[0]
 
-    def __init__(self, x, wq, wk, wv, cos, sin, n_heads):
+    def __init__(self, x, wq, wk, wv, cos, sin, n_heads, segment_ids=None):
         self._cos, self._sin, self.H = cos, sin, int(n_heads)
+        self._segments = segment_ids      # documents of packed rows (see `attention`): the segmented resident kernels
         super().__init__(x, wq, wk, wv)
 
     @staticmethod
@@ -260,10 +356,12 @@ class qkv_attention(_Operator):
         return bool(attention.use_resident and _L().query("pdn_attention_supported", L, hd))
 
     @staticmethod
-    def applicable(x, L, hd):
+    def applicable(x, L, hd, segment_ids=None):
         if not (qkv_attention.enabled and attention.use_flash and x.device.is_hip and x.dtype == np.float32
                 and x.ndim == 3):
             return False
+        if segment_ids is not None:       # the segmented kernels take the resident shapes only
+            return qkv_attention._resident(L, hd) and bool(_L().query("pdns_attention_supported", L, hd))
         return qkv_attention._resident(L, hd) or bool(_L().query("pdn_attention_stream_supported", hd))
 
     @staticmethod
@@ -324,7 +422,15 @@ class qkv_attention(_Operator):
         out = hp.empty((B, Lq, H, hd), np.float32)
         lse = hp.empty((B, H, Lq), np.float32)
         q, k, v = qkv._ptr, qkv._ptr + 4 * D, qkv._ptr + 8 * D
-        if resident:
+        self._seg = None
+        if self._segments is not None:
+            self._seg = seg = segment_bounds(self._segments, True)
+            if seg.shape != (B, Lq) or not (resident and L.query("pdns_attention_supported", Lq, hd)):
+                raise ValueError(f"qkv_attention: segment_ids of shape {seg.shape} for x of shape {tuple(x.shape)} "
+                                 "(segments need a resident shape: see qkv_attention.applicable)")
+            L.call("pdns_attention_fwd_f32", q, k, v, out._ptr, lse._ptr, B, H, Lq, hd, 3 * D, Lq * 3 * D, D, Lq * D,
+                   None if self.rotated else cos._ptr, None if self.rotated else sin._ptr, seg.start._ptr, hp.stream())
+        elif resident:
             L.call("pdn_attention_fwd_f32", q, k, v, out._ptr, lse._ptr, B, H, Lq, hd, 3 * D, Lq * 3 * D,
                    D, Lq * D, 1, None if self.rotated else cos._ptr, None if self.rotated else sin._ptr, hp.stream())
         else:                   # any length / head dim: key tiles stream through LDS, RoPE still in the loads
@@ -349,7 +455,12 @@ class qkv_attention(_Operator):
         dblocks = self._blocks(dqkv, T, D)
         q, k, v = qkv._ptr, qkv._ptr + 4 * D, qkv._ptr + 8 * D
         dq, dk, dv = dqkv._ptr, dqkv._ptr + 4 * D, dqkv._ptr + 8 * D
-        if qkv_attention._resident(Lq, hd):
+        if self._seg is not None:
+            ws_, wsb = hp.workspace(L.query("pdn_attention_bwd_workspace_bytes", B, H, Lq))
+            L.call("pdns_attention_bwd_f32", q, k, v, self.data._ptr, do._ptr, lse._ptr, dq, dk, dv, B, H, Lq, hd,
+                   3 * D, Lq * 3 * D, D, Lq * D, cos._ptr, sin._ptr, 1 if self.rotated else 0,
+                   self._seg.start._ptr, self._seg.end._ptr, ws_, wsb, hp.stream())
+        elif qkv_attention._resident(Lq, hd):
             ws_, wsb = hp.workspace(L.query("pdn_attention_bwd_workspace_bytes", B, H, Lq))
             L.call("pdn_attention_bwd_rotated_f32" if self.rotated else "pdn_attention_bwd_f32", q, k, v, self.data._ptr,
                    do._ptr, lse._ptr, dq, dk, dv, B, H, Lq, hd,

@@ -281,12 +281,17 @@ __device__ __attribute__((noinline)) void att_stage_pad_call(float* s0, float* s
 }
 
 // MULTI = false: L <= 256, one chunk (the chunk loop and the rescale fold away).
-template <int HD, int ABLATE = 0, bool MULTI = false>
+// SEG = true (include/pdn_segattn.h, always causal, no key bias): SS[b][q] is the first position of query q's document
+// (non-decreasing along a row); keys in front of it are masked like the causal ones and key tiles wholly in front of a
+// wave's first query are not multiplied.  Everything SEG adds sits under `if constexpr (SEG)` / `SEG &&`: the plain
+// instantiations compile from the code they always had.
+template <int HD, int ABLATE = 0, bool MULTI = false, bool SEG = false>
 __global__ __launch_bounds__(512, 1) void attention_fwd_kernel(
     const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
     float* __restrict__ O, float* __restrict__ LSE, int H, int L, int64_t row_stride,
     int64_t batch_stride, int64_t o_row_stride, int64_t o_batch_stride, float sqrt_hd, int causal,
-    const float* __restrict__ RC, const float* __restrict__ RS, const float* __restrict__ KB, int64_t kb_bs) {
+    const float* __restrict__ RC, const float* __restrict__ RS, const float* __restrict__ KB, int64_t kb_bs,
+    const int* __restrict__ SS) {
   static_assert(HD % 8 == 0 && HD > 32 && HD <= 64, "head dim: two 32-row MFMA tiles");
   constexpr int LD = ATT_LD(HD);
   constexpr int NT8 = HD / 8;                    // k-groups of 8 along the head dim
@@ -326,6 +331,16 @@ __global__ __launch_bounds__(512, 1) void attention_fwd_kernel(
   const int qpos_l = (active ? qt : 0) * 32 + li;
   // (without RoPE the same loads read the first floats of Q: unconditional, never used)
   if constexpr (!MULTI) rr.load(RC ? RC : Q, RC ? RS : Q, RC ? qpos_l : 0, lh, HD / 2);
+  // SEG: the lane's own bound, and -- `start` is monotone along a row -- the wave's smallest (lane 0 = its first query)
+  // and largest (lane 31 = its last) as wave-uniform values; the workgroup's first chunk from ITS first query
+  int qstart = 0, kt_first = 0, start_hi = 0, c_first = 0;
+  if constexpr (SEG) {
+    qstart = SS[(int64_t)b * L + qpos_l];
+    kt_first = __builtin_amdgcn_readfirstlane(qstart) >> 5;
+    start_hi = __builtin_amdgcn_readlane(qstart, 31);
+    // (clamped: whatever the array holds, no chunk outside the row is staged)
+    if constexpr (MULTI) c_first = min(max(__builtin_amdgcn_readfirstlane(SS[(int64_t)b * L + qg * ATT_CHUNK]), 0) / ATT_CHUNK, qg);
+  }
   float4 qraw[MULTI ? 1 : NT8];                  // single chunk: the Q rows go out before the staging (see dQ kernel)
   if (!MULTI) {
     const float* qrow = Qb + (int64_t)qpos_l * row_stride + 4 * lh;
@@ -339,10 +354,10 @@ __global__ __launch_bounds__(512, 1) void attention_fwd_kernel(
     ATT_T(2);
     if (!active) return;                         // no workgroup barrier below this point
   }
-  for (int c = 0; c <= c_last; ++c) {
+  for (int c = SEG ? c_first : 0; c <= c_last; ++c) {
     const int row0 = c * ATT_CHUNK, nrows = min(ATT_CHUNK, L - row0);
     if (MULTI) {
-      if (c) __syncthreads();                    // every wave is done with the previous chunk's images
+      if (SEG ? c != c_first : c != 0) __syncthreads();   // every wave is done with the previous chunk's images
       if (!(ABLATE & 1))
         att_stage_kv_call<HD>(Ks, Vs, K + base + (int64_t)row0 * row_stride, V + base + (int64_t)row0 * row_stride, nrows,
                               row0, row_stride, tid, RC, RS);
@@ -351,6 +366,7 @@ __global__ __launch_bounds__(512, 1) void attention_fwd_kernel(
     }
     const bool diag = causal && c == qg;         // the chunk that holds this group's own positions
     const int nk = diag ? qtl + 1 : nrows / 32;  // key tiles of this chunk that can be unmasked
+    const int k0 = SEG ? max(kt_first - c * ATT_MAX_TILES, 0) : 0;   // SEG: ... and the first one (may be >= nk: none)
     // Q fragments: lane (li, lh) holds Q[q = qt*32+li][8t + 4lh .. +3]  (re-read per chunk -- six cache-resident
     // loads -- rather than kept live across the staging of the next chunk)
     float4 qf[NT8];
@@ -367,7 +383,7 @@ __global__ __launch_bounds__(512, 1) void attention_fwd_kernel(
     f32x16 s[ATT_MAX_TILES];
 #pragma unroll
     for (int kt = 0; kt < ATT_MAX_TILES; ++kt) {
-      if (kt < nk && !(ABLATE & 2)) {
+      if ((!SEG || kt >= k0) && kt < nk && !(ABLATE & 2)) {
         const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         const float* krow = Ks + (kt * 32 + li) * LD + 4 * lh;
 #pragma unroll
@@ -396,11 +412,18 @@ __global__ __launch_bounds__(512, 1) void attention_fwd_kernel(
     float mc = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < ATT_MAX_TILES; ++kt) {
-      if (kt < nk && !(ABLATE & 4)) {
+      if ((!SEG || kt >= k0) && kt < nk && !(ABLATE & 4)) {
         if (diag && kt == qtl) {
 #pragma unroll
           for (int r = 0; r < 16; ++r)
             if (att_krow(r, lh) > li) s[kt][r] = -INFINITY;
+        }
+        if constexpr (SEG) {
+          if (row0 + kt * 32 < start_hi) {         // (uniform) a document of this wave starts inside or behind the tile
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              if (row0 + kt * 32 + att_krow(r, lh) < qstart) s[kt][r] = -INFINITY;
+          }
         }
 #pragma unroll
         for (int r = 0; r < 16; r += 2) mc = fmaxf(mc, fmaxf(s[kt][r], s[kt][r + 1]));      // v_max3_f32
@@ -424,7 +447,7 @@ __global__ __launch_bounds__(512, 1) void attention_fwd_kernel(
     float lc = 0.f;
 #pragma unroll
     for (int kt = 0; kt < ATT_MAX_TILES; ++kt) {
-      if (kt < nk && !(ABLATE & 4)) {
+      if ((!SEG || kt >= k0) && kt < nk && !(ABLATE & 4)) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           s[kt][r] = __builtin_amdgcn_exp2f(fmaf(s[kt][r], c1, c2));
@@ -441,7 +464,7 @@ __global__ __launch_bounds__(512, 1) void attention_fwd_kernel(
     }
 #pragma unroll
     for (int kt = 0; kt < ATT_MAX_TILES; ++kt) {
-      if (kt < nk && !(ABLATE & 8)) {
+      if ((!SEG || kt >= k0) && kt < nk && !(ABLATE & 8)) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float* vrow = Vs + (kt * 32 + att_krow(r, lh)) * ATT_LDV;
@@ -576,7 +599,8 @@ static int att_fwd_impl(const float* q, const float* k, const float* v, float* o
   const bool multi = L > ATT_CHUNK;
 #define ATT_FWD(HD_, M_)                                                                                              \
   hipLaunchKernelGGL((attention_fwd_kernel<HD_, 0, M_>), grid, dim3(512), shm, (hipStream_t)stream, q, k, v, o, lse, H, L, \
-                     row_stride, batch_stride, o_row_stride, o_batch_stride, sq, causal, rope_cos, rope_sin, key_bias, kb_bs)
+                     row_stride, batch_stride, o_row_stride, o_batch_stride, sq, causal, rope_cos, rope_sin, key_bias, kb_bs, \
+                     (const int*)nullptr)
   if (head_dim == 48) { if (multi) ATT_FWD(48, true); else ATT_FWD(48, false); }
   else { if (multi) ATT_FWD(64, true); else ATT_FWD(64, false); }
 #undef ATT_FWD
@@ -623,13 +647,15 @@ extern "C" int pdn_attention_fwd_bias_f32(const float* q, const float* k, const 
 // L x L touches HBM; the only intermediate is delta (B*H*L floats of workspace).  The accumulators simply carry
 // from chunk to chunk (P is recomputed from the saved log-sum-exp: no rescale).
 // ======================================================================================
-template <int HD, bool MULTI>
+// SEG: as in the forward kernel (SS = the documents' first positions)
+template <int HD, bool MULTI, bool SEG = false>
 __global__ __launch_bounds__(512, 1) void attention_bwd_dq_kernel(
     const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
     const float* __restrict__ O, const float* __restrict__ dO, const float* __restrict__ LSE,
     float* __restrict__ dQ, float* __restrict__ Delta, int H, int L, int64_t row_stride,
     int64_t batch_stride, int64_t o_row_stride, int64_t o_batch_stride, float sqrt_hd, int causal,
-    const float* __restrict__ RC, const float* __restrict__ RS, int prerot, const float* __restrict__ KB, int64_t kb_bs) {
+    const float* __restrict__ RC, const float* __restrict__ RS, int prerot, const float* __restrict__ KB, int64_t kb_bs,
+    const int* __restrict__ SS) {
   constexpr int LD = ATT_LD(HD);
   constexpr int NT8 = HD / 8;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -676,6 +702,14 @@ __global__ __launch_bounds__(512, 1) void attention_bwd_dq_kernel(
     }
     lse_q = LSE[(int64_t)bh * L + qpos_l];
   }
+  int qstart = 0, kt_first = 0, start_hi = 0, c_first = 0;    // (see the forward kernel)
+  if constexpr (SEG) {
+    qstart = SS[(int64_t)b * L + qpos_l];
+    kt_first = __builtin_amdgcn_readfirstlane(qstart) >> 5;
+    start_hi = __builtin_amdgcn_readlane(qstart, 31);
+    // (clamped: whatever the array holds, no chunk outside the row is staged)
+    if constexpr (MULTI) c_first = min(max(__builtin_amdgcn_readfirstlane(SS[(int64_t)b * L + qg * ATT_CHUNK]), 0) / ATT_CHUNK, qg);
+  }
   if (!MULTI) {
     att_stage_two_pad<HD, 512, true, false>(Ks, Vs, K + base, V + base, L, 0, row_stride, row_stride, tid, RC, RS, !prerot, false);
     __syncthreads();
@@ -697,10 +731,10 @@ __global__ __launch_bounds__(512, 1) void attention_bwd_dq_kernel(
 #pragma unroll
   for (int r = 0; r < 16; ++r) { dq0[r] = 0.f; dq1[r] = 0.f; }
   const int c_last = MULTI ? (causal ? qg : G - 1) : 0;
-  for (int c = 0; c <= c_last; ++c) {
+  for (int c = SEG ? c_first : 0; c <= c_last; ++c) {
     const int row0 = c * ATT_CHUNK, nrows = min(ATT_CHUNK, L - row0);
     if (MULTI) {
-      if (c) __syncthreads();
+      if (SEG ? c != c_first : c != 0) __syncthreads();
       att_stage_pad_call<HD, false>(Ks, Vs, K + base + (int64_t)row0 * row_stride, V + base + (int64_t)row0 * row_stride,
                                     nrows, row0, row_stride, row_stride, tid, RC, RS, !prerot);
       __syncthreads();
@@ -708,7 +742,7 @@ __global__ __launch_bounds__(512, 1) void attention_bwd_dq_kernel(
     }
     const bool diag = causal && c == qg;
     const int nk = diag ? qtl + 1 : nrows / 32;
-    for (int kt = 0; kt < nk; ++kt) {
+    for (int kt = SEG ? max(kt_first - c * ATT_MAX_TILES, 0) : 0; kt < nk; ++kt) {
       f32x16 s, dp;
       const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       const float* krow = Ks + (kt * 32 + li) * LDK + 4 * lh;
@@ -738,6 +772,13 @@ __global__ __launch_bounds__(512, 1) void attention_bwd_dq_kernel(
         for (int r = 0; r < 16; ++r)
           if (att_krow(r, lh) > li) s[r] = -INFINITY;
       }
+      if constexpr (SEG) {
+        if (row0 + kt * 32 < start_hi) {            // (uniform) the tile straddles a document boundary of this wave
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (row0 + kt * 32 + att_krow(r, lh) < qstart) s[r] = -INFINITY;
+        }
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float p = __builtin_amdgcn_exp2f(fmaf(s[r], c1, c2q));
@@ -760,13 +801,16 @@ __global__ __launch_bounds__(512, 1) void attention_bwd_dq_kernel(
   }
 }
 
-template <int HD, bool MULTI>
+// SEG: SE[b][k] is one past the last position of key k's document (non-decreasing along a row); queries at or behind it
+// are masked and query tiles wholly behind the wave's last key's document are not multiplied.
+template <int HD, bool MULTI, bool SEG = false>
 __global__ __launch_bounds__(512, 1) void attention_bwd_dkv_kernel(
     const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
     const float* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ Delta,
     float* __restrict__ dK, float* __restrict__ dV, int H, int L, int64_t row_stride,
     int64_t batch_stride, int64_t o_row_stride, int64_t o_batch_stride, float sqrt_hd, int causal,
-    const float* __restrict__ RC, const float* __restrict__ RS, int prerot, const float* __restrict__ KB, int64_t kb_bs) {
+    const float* __restrict__ RC, const float* __restrict__ RS, int prerot, const float* __restrict__ KB, int64_t kb_bs,
+    const int* __restrict__ SE) {
   constexpr int NT8 = HD / 8;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int LDP = ATT_LDP;
@@ -801,6 +845,16 @@ __global__ __launch_bounds__(512, 1) void attention_bwd_dkv_kernel(
   const int kpos = kt * 32 + li;
   // additive key bias of this wave's key tile (lane = key): the B operand of one extra rank-1 step per score tile
   const float kbias = (KB && lh == 0) ? KB[(int64_t)b * kb_bs + kpos_l] * sqrt_hd : 0.f;
+  // SEG: the lane's own bound, the wave's smallest (lane 0) and largest (lane 31) as wave-uniform values, and the last
+  // chunk the workgroup stages: that of the last query its last key's document holds
+  int kend = 0, end_lo = 0, qt_end = 0, c_end = 0;
+  if constexpr (SEG) {
+    kend = SE[(int64_t)b * L + kpos_l];
+    end_lo = __builtin_amdgcn_readfirstlane(kend);
+    qt_end = (__builtin_amdgcn_readlane(kend, 31) + 31) >> 5;
+    // (clamped: whatever the array holds, no chunk outside the row is staged)
+    c_end = min((__builtin_amdgcn_readfirstlane(SE[(int64_t)b * L + min(L, (kg + 1) * ATT_CHUNK) - 1]) - 1) / ATT_CHUNK, G - 1);
+  }
   float4 kf[NT8], vf[NT8];                          // (issued before the staging, consumed after the barrier: see dQ)
   {
     const float* krow = Kb + (int64_t)kpos_l * row_stride + 4 * lh;
@@ -833,7 +887,7 @@ __global__ __launch_bounds__(512, 1) void attention_bwd_dkv_kernel(
 #pragma unroll
   for (int r = 0; r < 16; ++r) { dk0[r] = 0.f; dk1[r] = 0.f; dv0[r] = 0.f; dv1[r] = 0.f; }
   const int c_first = (MULTI && causal) ? kg : 0;
-  for (int c = c_first; c < G; ++c) {
+  for (int c = c_first; SEG ? c <= c_end : c < G; ++c) {
     const int row0 = c * ATT_CHUNK, nrows = min(ATT_CHUNK, L - row0);
     if (MULTI) {
       if (c != c_first) __syncthreads();
@@ -848,7 +902,8 @@ __global__ __launch_bounds__(512, 1) void attention_bwd_dkv_kernel(
     }
     const bool diag = causal && c == kg;
     const int q_first = diag ? ktl : 0;            // query tiles (inside the chunk) that can see this key tile
-    for (int qt = q_first; qt < nrows / 32; ++qt) {
+    const int q_last = SEG ? min(nrows / 32, qt_end - c * ATT_MAX_TILES) : nrows / 32;   // (SEG: may be <= q_first: none)
+    for (int qt = q_first; qt < q_last; ++qt) {
       f32x16 s, dp;
       const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       const float* qrow = Qs + (qt * 32 + li) * LDP + 4 * lh;
@@ -874,6 +929,13 @@ __global__ __launch_bounds__(512, 1) void attention_bwd_dkv_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           if (li > att_krow(r, lh)) s[r] = -INFINITY;
+      }
+      if constexpr (SEG) {
+        if (row0 + qt * 32 + 32 > end_lo) {         // (uniform) a document of this wave's keys ends inside or before the tile
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (row0 + qt * 32 + att_krow(r, lh) >= kend) s[r] = -INFINITY;
+        }
       }
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {                      // registers 4 g4 .. 4 g4 + 3 are four consecutive queries
@@ -977,11 +1039,11 @@ static int att_bwd_impl(const float* q, const float* k, const float* v, const fl
 #define ATT_BWD(HD_, M_)                                                                                               \
   hipLaunchKernelGGL((attention_bwd_dq_kernel<HD_, M_>), grid, dim3(512), (size_t)att_dq_lds_bytes(L, head_dim), st, q, k, v, \
                      o, d_o, lse, dq, delta, H, L, row_stride, batch_stride, o_row_stride, o_batch_stride, sq, causal,    \
-                     rope_cos, rope_sin, prerot, key_bias, kb_bs);                                                        \
+                     rope_cos, rope_sin, prerot, key_bias, kb_bs, (const int*)nullptr);                                   \
   PDN_LAUNCH_CHECK();                                                                                                     \
   hipLaunchKernelGGL((attention_bwd_dkv_kernel<HD_, M_>), grid, dim3(512), (size_t)pdn_attention_bwd_lds_bytes(L, head_dim),  \
                      st, q, k, v, d_o, lse, delta, dk, dv, H, L, row_stride, batch_stride, o_row_stride, o_batch_stride,  \
-                     sq, causal, rope_cos, rope_sin, prerot, key_bias, kb_bs);                                            \
+                     sq, causal, rope_cos, rope_sin, prerot, key_bias, kb_bs, (const int*)nullptr);                       \
   PDN_LAUNCH_CHECK();
   const bool multi = L > ATT_CHUNK;
   pdn_count(PDN_CNT_ATT_RES_BWD);
@@ -1023,6 +1085,115 @@ extern "C" int pdn_attention_bwd_rotated_f32(const float* q, const float* k, con
   PDN_CHECK_ARG(rope_cos && rope_sin, "pdn_attention_bwd_rotated_f32: the rope tables are required");
   return att_bwd_impl(q, k, v, o, d_o, lse, dq, dk, dv, B, H, L, head_dim, row_stride, batch_stride, o_row_stride,
                       o_batch_stride, causal, rope_cos, rope_sin, workspace, workspace_bytes, stream, 1);
+}
+
+// ======================================================================================
+// Document-masked (segmented) causal attention: include/pdn_segattn.h, statement pydynet_amd/core/fused/segments.py.
+// The SEG instantiations of the three resident kernels above, for every resident shape -- rotation-free operands too,
+// which the persistent kernels would take without segments.  seg_start / seg_end: (B, L) int32 from
+// pdns_segment_bounds_i32 (csrc/segments.hip); the host never reads them.
+// ======================================================================================
+static bool seg_shape_ok(int L, int head_dim) {
+  return (head_dim == 48 || head_dim == 64) && L % 32 == 0 && L >= 32 && L <= ATT_MAX_L;
+}
+extern "C" int pdns_attention_supported(int L, int head_dim) { return seg_shape_ok(L, head_dim) ? 1 : 0; }
+
+extern "C" int pdns_attention_fwd_f32(const float* q, const float* k, const float* v, float* o, float* lse, int B, int H, int L,
+                                      int head_dim, int64_t row_stride, int64_t batch_stride, int64_t o_row_stride,
+                                      int64_t o_batch_stride, const float* rope_cos, const float* rope_sin,
+                                      const int* seg_start, void* stream) {
+  if (B == 0 || H == 0 || L == 0) return PDN_OK;
+  PDN_CHECK_ARG(q && k && v && o && lse && seg_start, "pdns_attention_fwd_f32: null operand");
+  PDN_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr) && ((((uintptr_t)rope_cos | (uintptr_t)rope_sin) & 7) == 0),
+                "pdns_attention_fwd_f32: rope tables must come as an 8-byte aligned pair");
+  if (!seg_shape_ok(L, head_dim)) {
+    pdn_set_error("pdns_attention_fwd_f32: head_dim 48 / 64, L a multiple of 32 and <= %d", ATT_MAX_L);
+    return PDN_EUNSUPPORTED;
+  }
+  PDN_CHECK_ARG((row_stride % 4) == 0 && (batch_stride % 4) == 0 && (o_row_stride % 4) == 0 && (o_batch_stride % 4) == 0 &&
+                    ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) == 0) &&
+                    (((uintptr_t)seg_start & 3) == 0),
+                "pdns_attention_fwd_f32: 16-byte alignment required");
+  static bool attr_set = false;
+  if (!attr_set) {
+#define ATT_ATTR(K_) PDN_HIP(hipFuncSetAttribute((const void*)K_, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
+    ATT_ATTR((attention_fwd_kernel<48, 0, false, true>)); ATT_ATTR((attention_fwd_kernel<64, 0, false, true>));
+    ATT_ATTR((attention_fwd_kernel<48, 0, true, true>)); ATT_ATTR((attention_fwd_kernel<64, 0, true, true>));
+#undef ATT_ATTR
+    attr_set = true;
+  }
+  const size_t shm = (size_t)pdn_attention_lds_bytes(L, head_dim);
+  const dim3 grid((unsigned)(B * H * att_groups(L)));
+  const float sq = sqrtf((float)head_dim);
+  const bool multi = L > ATT_CHUNK;
+#define ATT_FWD(HD_, M_)                                                                                                  \
+  hipLaunchKernelGGL((attention_fwd_kernel<HD_, 0, M_, true>), grid, dim3(512), shm, (hipStream_t)stream, q, k, v, o, lse, H, L, \
+                     row_stride, batch_stride, o_row_stride, o_batch_stride, sq, 1, rope_cos, rope_sin,                   \
+                     (const float*)nullptr, (int64_t)0, seg_start)
+  if (head_dim == 48) { if (multi) ATT_FWD(48, true); else ATT_FWD(48, false); }
+  else { if (multi) ATT_FWD(64, true); else ATT_FWD(64, false); }
+#undef ATT_FWD
+  pdn_count(PDN_CNT_ATT_RES_FWD);
+  pdn_count(PDN_CNT_ATT_SEG);
+  PDN_LAUNCH_CHECK();
+  return PDN_OK;
+}
+
+extern "C" int pdns_attention_bwd_f32(const float* q, const float* k, const float* v, const float* o, const float* d_o,
+                                      const float* lse, float* dq, float* dk, float* dv, int B, int H, int L, int head_dim,
+                                      int64_t row_stride, int64_t batch_stride, int64_t o_row_stride, int64_t o_batch_stride,
+                                      const float* rope_cos, const float* rope_sin, int prerotated, const int* seg_start,
+                                      const int* seg_end, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (B == 0 || H == 0 || L == 0) return PDN_OK;
+  PDN_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr) && ((((uintptr_t)rope_cos | (uintptr_t)rope_sin) & 7) == 0),
+                "pdns_attention_bwd_f32: rope tables must come as an 8-byte aligned pair");
+  PDN_CHECK_ARG(!prerotated || rope_cos, "pdns_attention_bwd_f32: prerotated operands need the rope tables");
+  PDN_CHECK_ARG(q && k && v && o && d_o && lse && dq && dk && dv && seg_start && seg_end, "pdns_attention_bwd_f32: null operand");
+  if (!seg_shape_ok(L, head_dim)) {
+    pdn_set_error("pdns_attention_bwd_f32: head_dim 48 / 64, L a multiple of 32 and <= %d", ATT_MAX_L);
+    return PDN_EUNSUPPORTED;
+  }
+  PDN_CHECK_ARG((row_stride % 4) == 0 && (batch_stride % 4) == 0 && (o_row_stride % 4) == 0 && (o_batch_stride % 4) == 0 &&
+                    ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o | (uintptr_t)dq |
+                       (uintptr_t)dk | (uintptr_t)dv) & 15) == 0) &&
+                    ((((uintptr_t)seg_start | (uintptr_t)seg_end) & 3) == 0),
+                "pdns_attention_bwd_f32: 16-byte alignment required");
+  if (!workspace || workspace_bytes < pdn_attention_bwd_workspace_bytes(B, H, L)) {
+    pdn_set_error("pdns_attention_bwd_f32: workspace too small");
+    return PDN_EWORKSPACE;
+  }
+  float* delta = (float*)workspace;
+  static bool attr_set = false;
+  if (!attr_set) {
+#define ATT_ATTR(K_) PDN_HIP(hipFuncSetAttribute((const void*)K_, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
+    ATT_ATTR((attention_bwd_dq_kernel<48, false, true>)); ATT_ATTR((attention_bwd_dkv_kernel<48, false, true>));
+    ATT_ATTR((attention_bwd_dq_kernel<64, false, true>)); ATT_ATTR((attention_bwd_dkv_kernel<64, false, true>));
+    ATT_ATTR((attention_bwd_dq_kernel<48, true, true>)); ATT_ATTR((attention_bwd_dkv_kernel<48, true, true>));
+    ATT_ATTR((attention_bwd_dq_kernel<64, true, true>)); ATT_ATTR((attention_bwd_dkv_kernel<64, true, true>));
+#undef ATT_ATTR
+    attr_set = true;
+  }
+  const float sq = sqrtf((float)head_dim);
+  const dim3 grid((unsigned)(B * H * att_groups(L)));
+  hipStream_t st = (hipStream_t)stream;
+  const int prerot = prerotated ? 1 : 0;
+#define ATT_BWD(HD_, M_)                                                                                                  \
+  hipLaunchKernelGGL((attention_bwd_dq_kernel<HD_, M_, true>), grid, dim3(512), (size_t)att_dq_lds_bytes(L, head_dim), st, q, \
+                     k, v, o, d_o, lse, dq, delta, H, L, row_stride, batch_stride, o_row_stride, o_batch_stride, sq, 1,   \
+                     rope_cos, rope_sin, prerot, (const float*)nullptr, (int64_t)0, seg_start);                           \
+  PDN_LAUNCH_CHECK();                                                                                                     \
+  hipLaunchKernelGGL((attention_bwd_dkv_kernel<HD_, M_, true>), grid, dim3(512),                                          \
+                     (size_t)pdn_attention_bwd_lds_bytes(L, head_dim), st, q, k, v, d_o, lse, delta, dk, dv, H, L,        \
+                     row_stride, batch_stride, o_row_stride, o_batch_stride, sq, 1, rope_cos, rope_sin, prerot,           \
+                     (const float*)nullptr, (int64_t)0, seg_end);                                                         \
+  PDN_LAUNCH_CHECK();
+  const bool multi = L > ATT_CHUNK;
+  pdn_count(PDN_CNT_ATT_RES_BWD);
+  pdn_count(PDN_CNT_ATT_SEG);
+  if (head_dim == 48) { if (multi) { ATT_BWD(48, true) } else { ATT_BWD(48, false) } }
+  else { if (multi) { ATT_BWD(64, true) } else { ATT_BWD(64, false) } }
+#undef ATT_BWD
+  return PDN_OK;
 }
 
 // ======================================================================================

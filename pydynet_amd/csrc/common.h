@@ -70,7 +70,9 @@ enum {
   PDN_CNT_ROWTILE_SPLIT = 41,     // q | k | v + RoPE / gate | up + SwiGLU on split-fp16 MFMA (csrc/rowtile_split.hip): also counts in 4 / 2
   PDN_CNT_OUTRES_TN_SPLIT = 42,   // packed layer weight gradients (x^T against dq | dk | dv, dgate | dup) on split-fp16 MFMA
                                   // (csrc/outres_tn_split.hip): also counts in 15
-  PDN_CNT_SLOTS = 43
+  PDN_CNT_ATT_SEG = 43,           // document-masked resident attention (the SEG kernels of csrc/attention.hip, include/pdn_segattn.h),
+                                  // either direction: also counts in 9 / 10
+  PDN_CNT_SLOTS = 44
 };
 void pdn_count(int slot);
 

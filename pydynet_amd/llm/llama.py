@@ -122,9 +122,11 @@ class Attention(nn.Module):
             buf[i] = w.data
             w.data = buf[i]
 
-    def __call__(self, x, start_pos, mask, freqs_cos, freqs_sin, residual=None):
+    def __call__(self, x, start_pos, mask, freqs_cos, freqs_sin, residual=None, segment_ids=None):
         B, L, _ = x.shape
         H, hd = self.n_heads, self.head_dim
+        if segment_ids is not None:
+            return self._segmented(x, start_pos, mask, freqs_cos, freqs_sin, residual, segment_ids)
         if (self._train and start_pos == 0 and mask is not None and is_grad_enable()
                 and fused.qkv_attention.applicable(x, L, hd)):
             out = fused.qkv_attention(x, self.Q.weight, self.K.weight, self.V.weight, freqs_cos, freqs_sin, H)
@@ -147,6 +149,27 @@ class Attention(nn.Module):
             return self.O(out)
         return fused.linear(out, self.O.weight, None, residual)
 
+    def _segmented(self, x, start_pos, mask, freqs_cos, freqs_sin, residual, segment_ids):
+        """Packed rows (`segment_ids`: core/fused/segments.py): a query sees the keys of its own document only.  Training
+        at start_pos 0 only; the one-node form where its kernels take the shape, else the separate nodes with the same
+        mask."""
+        B, L, _ = x.shape
+        H, hd = self.n_heads, self.head_dim
+        if not self._train or start_pos != 0 or mask is None:
+            raise ValueError("segment_ids are for training passes over whole rows (train mode, start_pos 0, more than one position)")
+        if is_grad_enable() and fused.qkv_attention.applicable(x, L, hd, segment_ids):
+            out = fused.qkv_attention(x, self.Q.weight, self.K.weight, self.V.weight, freqs_cos, freqs_sin, H,
+                                      segment_ids=segment_ids)
+        else:
+            xq = self.Q(x).reshape(B, L, H, hd)
+            xk = self.K(x).reshape(B, L, H, hd)
+            xv = self.V(x).reshape(B, L, H, hd)
+            xq, xk = apply_rotary_emb(xq, xk, freqs_cos, freqs_sin)
+            out = fused.attention(xq, xk, xv, causal=True, start_pos=0, segment_ids=segment_ids)
+        out = out.reshape(B, L, -1)
+        if residual is None:
+            return self.O(out)
+        return fused.linear(out, self.O.weight, None, residual)
 
     def step_rows(self, x, pos, freqs_cos, freqs_sin, residual=None):
         """One new token per row, row b at its own position pos[b] (Llama.generate_ragged; pos[b] < 0: a stopped row,
@@ -182,9 +205,12 @@ class TransformerBlock(nn.Module):
         self.input_norm = nn.RMSNorm(dim, dtype=dtype)
         self.post_attn_norm = nn.RMSNorm(dim, dtype=dtype)
 
-    def forward(self, x, start_pos, mask, freqs_cos, freqs_sin):
+    def forward(self, x, start_pos, mask, freqs_cos, freqs_sin, segment_ids=None):
         # z = x + attn(norm(x)); out = z + ffn(norm(z)) -- both adds ride in the GEMM epilogues
-        z = self.attention(self.input_norm(x), start_pos, mask, freqs_cos, freqs_sin, residual=x)
+        if segment_ids is None:
+            z = self.attention(self.input_norm(x), start_pos, mask, freqs_cos, freqs_sin, residual=x)
+        else:
+            z = self.attention(self.input_norm(x), start_pos, mask, freqs_cos, freqs_sin, residual=x, segment_ids=segment_ids)
         return self.ffn(self.post_attn_norm(z), residual=z)
 
     def step_rows(self, x, pos, freqs_cos, freqs_sin):
@@ -208,16 +234,26 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         self.norm = nn.RMSNorm(embed_dim, dtype=dtype)
         self.lm_head = nn.Linear(embed_dim, vocab_size, dtype=dtype)      # bias=True, as the reference
 
-    def _forward_hidden(self, input_ids, start_pos: int):
+    def _forward_hidden(self, input_ids, start_pos: int, segment_ids=None):
         L = input_ids.shape[-1]
         h = self.tok_embedding(input_ids)
+        if segment_ids is not None:
+            # packed rows: the documents' bounds once per step, shared by every layer (core/fused/segments.py)
+            if not self._train or start_pos != 0:
+                raise ValueError("segment_ids are for training passes over whole rows (train mode, start_pos 0)")
+            segment_ids = fused.segment_bounds(segment_ids, h.device.is_hip)
+            if segment_ids.shape != tuple(h.shape[:2]):
+                raise ValueError(f"segment_ids of shape {segment_ids.shape} for input_ids of shape {tuple(h.shape[:2])}")
+            if L == 1:
+                segment_ids = None            # (a single position sees itself)
         cos = self.freqs_cos[start_pos:start_pos + L]
         sin = self.freqs_sin[start_pos:start_pos + L]
         # the reference rebuilds an additive -inf mask on the host every call (model.py:199-203);
         # here causality is a flag of the fused attention node and nothing is uploaded.
         mask = True if L > 1 else None
         for layer in self.layers:
-            h = layer(h, start_pos, mask, cos, sin)
+            h = layer(h, start_pos, mask, cos, sin) if segment_ids is None else \
+                layer(h, start_pos, mask, cos, sin, segment_ids=segment_ids)
         return self.norm(h)
 
     def forward_logits(self, input_ids, start_pos: int = 0):
@@ -230,8 +266,11 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
             trainable, frozen = trainable + p.requires_grad, frozen + (not p.requires_grad)
         return trainable, frozen
 
-    def loss(self, input_ids, target_ids, criterion=None, start_pos: int = 0, ignore_index=None):
-        """Cross entropy of the next-token logits.  `criterion.ignore_index` (nn.CrossEntropyLoss), or the `ignore_index`
+    def loss(self, input_ids, target_ids, criterion=None, start_pos: int = 0, ignore_index=None, segment_ids=None):
+        """Cross entropy of the next-token logits.  `segment_ids` ((B, L) integers, non-decreasing along a row; a NumPy
+        array, or an int32 device array a captured step re-reads at every replay): the documents of packed rows -- every
+        attention looks inside the query's document only (core/fused/segments.py; llm/packing.py builds such rows and
+        their targets).  Training mode and start_pos 0 only.  `criterion.ignore_index` (nn.CrossEntropyLoss), or the `ignore_index`
         keyword when no criterion is given: targets equal to it -- a prompt region, right padding -- add nothing to the loss
         or the gradients and the mean runs over the remaining tokens (core/fused/masked_loss.py; 0, not NaN, when none
         remains).  Under data parallel each rank divides by its own count."""
@@ -239,7 +278,8 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
             raise ValueError("pass ignore_index through the criterion (nn.CrossEntropyLoss(ignore_index=...)), not beside it")
         if criterion is not None:
             ignore_index = getattr(criterion, "ignore_index", None)
-        h = self._forward_hidden(input_ids, start_pos)
+        h = self._forward_hidden(input_ids, start_pos) if segment_ids is None else \
+            self._forward_hidden(input_ids, start_pos, segment_ids=segment_ids)
         if isinstance(target_ids, Tensor):
             targets = target_ids.reshape(-1)
         else:
@@ -259,12 +299,16 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
             criterion = nn.CrossEntropyLoss() if ignore_index is None else nn.CrossEntropyLoss(ignore_index=ignore_index)
         return criterion(logits.reshape(B * L, V), targets)
 
-    def finetune_step(self, input_ids, target_ids, optimizer, criterion=None, start_pos: int = 0, ignore_index=None):
-        """zero_grad -> forward -> cross entropy -> backward -> optimizer step; returns the loss.  `ignore_index`: see
-        `loss`."""
+    def finetune_step(self, input_ids, target_ids, optimizer, criterion=None, start_pos: int = 0, ignore_index=None,
+                      segment_ids=None):
+        """zero_grad -> forward -> cross entropy -> backward -> optimizer step; returns the loss.  `ignore_index`,
+        `segment_ids`: see `loss`."""
         self.train(True)
         optimizer.zero_grad()
-        loss = self.loss(input_ids, target_ids, criterion, start_pos, ignore_index)
+        if segment_ids is None:
+            loss = self.loss(input_ids, target_ids, criterion, start_pos, ignore_index)
+        else:
+            loss = self.loss(input_ids, target_ids, criterion, start_pos, ignore_index, segment_ids=segment_ids)
         loss.backward()
         optimizer.step()
         return loss.item()
