@@ -256,7 +256,10 @@ int pdn_gemm_outres_blocks_nt_f32(const float* A, const float* W, int64_t b_bloc
  * logits (M x V) = x (M x 288) W (288 x V) + bias and lse[m] = log sum_v exp(logits[m][v]) in one launch (transposed
  * accumulators: a lane owns a token); pdn_cross_entropy_from_lse_f32 then forms the loss with one gather per row --
  * loss_row[r] = lse[r] - logits[r][target[r]], loss_out = their sum (mean != 0: mean) -- instead of the pass over the
- * logits pdn_cross_entropy_fwd_f32 makes.  err_flag is set to 1 on an out-of-range target. */
+ * logits pdn_cross_entropy_fwd_f32 makes.  err_flag is set to 1 on an out-of-range target -- and, unlike
+ * pdn_cross_entropy_fwd_f32 / _fwd_bwd_f32 / _bwd_f32, which wrap a target in [-V, 0) as NumPy does, on ANY negative
+ * target: the GEMMs that form the gradient of this loss (pdn_linear_ce_dx_deferred_f32, pdn_linear_ce_backward_f32) clamp
+ * their targets into [0, V) and rely on this entry to report them, so it must not accept what they would not follow. */
 int pdn_linear_lse_supported(int64_t M, int V, int K);
 int pdn_linear_lse_fwd_f32(const float* x, const float* w, const float* bias, float* logits, float* lse, int M, int V,
                            int K, int64_t ldx, int64_t ldw, int64_t ldl, void* stream);
@@ -389,7 +392,8 @@ int pdn_masked_fill(int dtype, double value, int ndim, const int64_t* shape, con
 
 /* ---- reductions: getattr(xp,'sum'|'mean'|'max'|'min'|'argmax'|'argmin')(x, axis, keepdims)
  * (tensor.py:701,705) and the engine's un-broadcast sums (tensor.py:360-370).
- * reduce_axis[k] != 0 marks a reduced dim; out is contiguous over the kept dims. */
+ * reduce_axis[k] != 0 marks a reduced dim; out is contiguous over the kept dims.  NaN follows NumPy: max / min return
+ * it, argmax / argmin return the index of the first one; among equal values the lowest index wins. */
 int pdn_reduce(int dtype, int op, int ndim, const int64_t* shape, const int64_t* strides,
                const uint8_t* reduce_axis, const void* x, void* out, void* workspace,
                int64_t workspace_bytes, void* stream);
@@ -403,7 +407,8 @@ int pdn_softmax_bwd_f32(const float* y, const float* dy, float* dx, int64_t rows
                         float divisor, void* stream);
 
 /* ---- RMSNorm (nn/modules/norm.py:245-248): y = x / sqrt(mean(x^2)+eps) * w; `rms` (rows,)
- * is saved for backward.  bwd: dw (+)= sum_rows dy*x/rms when dw != NULL. */
+ * is saved for backward.  bwd: dw (+)= sum_rows dy*x/rms when dw != NULL.  cols % 4 == 0, cols <= 2048, and x, w, y
+ * (bwd: x, w, dy, dx_residual, dx) on 16-byte boundaries, or the call is refused (PDN_EINVAL) before any launch. */
 int pdn_rmsnorm_fwd_f32(const float* x, const float* w, float* y, float* rms, int64_t rows,
                         int cols, float eps, void* stream);
 int pdn_rmsnorm_bwd_f32(const float* x, const float* w, const float* rms, const float* dy,

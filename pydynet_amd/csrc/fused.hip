@@ -362,6 +362,8 @@ extern "C" int pdn_rmsnorm_bwd_f32(const float* x, const float* w, const float* 
   PDN_CHECK_ARG(x && w && rms && dy && dx, "pdn_rmsnorm_bwd_f32: null operand");
   PDN_CHECK_ARG(cols > 0 && cols % 4 == 0 && cols <= 2048,
                 "pdn_rmsnorm_bwd_f32: cols=%d must be a multiple of 4 and <= 2048", cols);
+  PDN_CHECK_ARG((((uintptr_t)x | (uintptr_t)w | (uintptr_t)dy | (uintptr_t)dx_residual | (uintptr_t)dx) & 15) == 0,
+                "pdn_rmsnorm_bwd_f32: 16B alignment");
   hipStream_t st = (hipStream_t)stream;
   int64_t nb = (rows + 15) / 16; if (nb > 1024) nb = 1024; if (nb < 1) nb = 1;
   float* part = nullptr;
@@ -851,6 +853,9 @@ extern "C" int pdn_cross_entropy_fwd_f32(const float* logits, const int64_t* tar
 // loss from row statistics that already exist (the vocabulary projection left lse[row], csrc/gemm_rowres.hip EPI 4):
 // loss_row[r] = lse[r] - logits[r][target[r]], loss_out = (mean ? 1 / rows : 1) * sum -- one 4-byte gather per row
 // instead of a pass over the logits.
+// A NEGATIVE target is an error here (flag raised, the row reads column 0), where pdn_cross_entropy_fwd_f32 wraps it as
+// NumPy does: the products that form this loss's gradient from the same targets (csrc/gemm_outres.hip, lm_head_d*_split.hip)
+// clamp a target into [0, V) and leave the report to this kernel, so a wrapped loss would go with a clamped gradient.
 __global__ void ce_rows_from_lse_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ lse,
                                         const int64_t* __restrict__ tgt, int64_t rows, int V, float* __restrict__ loss_row,
                                         int* __restrict__ err) {

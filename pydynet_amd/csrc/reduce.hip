@@ -46,8 +46,13 @@ template <typename T, int OP> struct Acc {
     if (OP == ROP_SUM || OP == ROP_MEAN) v += x;
     else if (OP == ROP_MAX) v = (x > v || x != x) ? x : v;
     else if (OP == ROP_MIN) v = (x < v || x != x) ? x : v;
-    else if (OP == ROP_ARGMAX) { if (idx < 0 || x > v || (x == v && i < idx)) { v = x; idx = i; } }
-    else { if (idx < 0 || x < v || (x == v && i < idx)) { v = x; idx = i; } }
+    else {
+      // NumPy's order: a NaN beats every number, and among equals (two NaNs included) the lowest index wins -- whatever
+      // the order in which elements and partial results arrive (`idx < 0`: nothing held yet)
+      const bool xn = x != x, vn = v != v;
+      const bool better = OP == ROP_ARGMAX ? x > v : x < v;
+      if (idx < 0 || (xn ? (!vn || i < idx) : (!vn && (better || (x == v && i < idx))))) { v = x; idx = i; }
+    }
   }
   __device__ __forceinline__ void merge(T ov, int64_t oi) {
     if (OP >= ROP_ARGMAX) { if (oi >= 0) push(ov, oi); }

@@ -246,6 +246,9 @@ class DecodeMixin:
                                       loss_out, dlogits, colsum, ws, wsb, err, stream):
         self.pdn_cross_entropy_fwd_f32(logits, targets, rows, V, mean, loss_row, lse_row, loss_out, err, stream)
         rc = self.pdn_cross_entropy_bwd_f32(logits, targets, lse_row, None, gscale, dlogits, rows, V, stream)
+        t = flat(targets, rows, np.int64)
+        bad = np.flatnonzero((t < -V) | (t >= V))                 # the fused kernels subtract the one at column 0 there
+        flat(dlogits, rows * V).reshape(rows, V)[bad, 0] -= np.float32(gscale)
         if V <= 32 and rows >= 1024 and not colsum:
             self._count(18)                     # ce_small_kernel: one thread per row
         if colsum:

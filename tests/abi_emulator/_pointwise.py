@@ -9,6 +9,21 @@ from pydynet_amd import _lib  # noqa: F401
 from ._base import _NP, _ints, view, flat  # noqa: F401
 
 
+def _wrapped(idx, n, err=None):
+    """Indices as the kernels read them: negative ones count from the end; `ok` marks those inside [0, n), and the error
+    flag (when the entry has one) is raised for the others."""
+    idx = np.array(idx, np.int64)
+    idx = np.where(idx < 0, idx + n, idx)
+    ok = (idx >= 0) & (idx < n)
+    if err and not ok.all():
+        flat(err, 1, np.int32)[0] = 1
+    return idx, ok
+
+
+def _misaligned(*ptrs):
+    return any(int(p or 0) & 15 for p in ptrs)
+
+
 class PointwiseMixin:
     # -- elementwise --------------------------------------------------------------------------
     def pdn_ew_binary(self, dt, op, mode, ndim, shape, a, sa, b, sb, scalar, out, so, stream):
@@ -104,6 +119,8 @@ class PointwiseMixin:
         return 0
 
     def pdn_rmsnorm_fwd_f32(self, x, w, y, rms, rows, cols, eps, stream):
+        if rows and (cols <= 0 or cols % 4 or cols > 2048 or _misaligned(x, w, y)):
+            return -1
         a = flat(x, rows * cols).reshape(rows, cols)
         r = np.sqrt((a * a).mean(-1, keepdims=True) + np.float32(eps))
         flat(y, rows * cols).reshape(rows, cols)[...] = a / r * flat(w, cols)
@@ -112,6 +129,10 @@ class PointwiseMixin:
         return 0
 
     def pdn_rmsnorm_bwd_f32(self, x, w, rms, dy, res, dx, dw, acc, rows, cols, ws, wsb, stream):
+        if rows and (cols <= 0 or cols % 4 or cols > 2048 or _misaligned(x, w, dy, res, dx)):
+            return -1
+        if rows and dw and (not ws or wsb < min(max((rows + 15) // 16, 1), 1024) * cols * 4):
+            return -3
         a = flat(x, rows * cols).reshape(rows, cols)
         g = np.array(flat(dy, rows * cols).reshape(rows, cols))
         r = flat(rms, rows)[:, None]
@@ -144,12 +165,16 @@ class PointwiseMixin:
         return 0
 
     def pdn_swiglu_rows_fwd_f32(self, gu, y, rows, F, stream):
+        if rows and F and (F % 4 or _misaligned(gu, y)):
+            return -1
         a = flat(gu, rows * 2 * F).reshape(rows, 2 * F)
         g, u = a[:, :F], a[:, F:]
         flat(y, rows * F).reshape(rows, F)[...] = g / (1 + np.exp(-g)) * u
         return 0
 
     def pdn_swiglu_rows_bwd_f32(self, gu, dy, dgu, rows, F, stream):
+        if rows and F and (F % 4 or _misaligned(gu, dy, dgu)):
+            return -1
         a = np.array(flat(gu, rows * 2 * F).reshape(rows, 2 * F))
         g, u, d = a[:, :F], a[:, F:], flat(dy, rows * F).reshape(rows, F)
         sg = 1 / (1 + np.exp(-g))
@@ -177,13 +202,18 @@ class PointwiseMixin:
 
     def pdn_embedding_gather_f32(self, W, V, D, rs, ids, n, out, err, stream):
         w = view(W, (V, D), (rs, 1), np.float32)
-        flat(out, n * D).reshape(n, D)[...] = w[flat(ids, n, np.int64)]
+        idx, ok = _wrapped(flat(ids, n, np.int64), V, err)
+        flat(out, n * D).reshape(n, D)[ok] = w[idx[ok]]          # (a row with a bad id is left as it was)
         return 0
 
     def pdn_embedding_scatter_f32(self, g, ids, n, dW, V, D, mode, owner, tag, ws, wsb, stream):
         w = flat(dW, V * D).reshape(V, D)
         gg = np.array(flat(g, n * D).reshape(n, D))
-        idx = np.array(flat(ids, n, np.int64))
+        idx, ok = _wrapped(flat(ids, n, np.int64), V)
+        idx, gg = idx[ok], gg[ok]                                 # (a bad id is skipped; this entry has no flag)
+        if owner and mode == 2:
+            mine = flat(owner, V)[idx] == np.float32(tag)
+            idx, gg = idx[mine], gg[mine]
         if owner and mode != 2:
             # last occurrence first (over ALL local rows), then the data-parallel owner filter
             last = {int(i): r for r, i in enumerate(idx)}
@@ -200,16 +230,19 @@ class PointwiseMixin:
 
     def pdn_take_cols_f32(self, x, n, C, rs, idx, out, err, stream):
         a = view(x, (n, C), (rs, 1), np.float32)
-        flat(out, n)[...] = a[np.arange(n), flat(idx, n, np.int64)]
+        c, ok = _wrapped(flat(idx, n, np.int64), C, err)
+        flat(out, n)[ok] = a[np.arange(n)[ok], c[ok]]
         return 0
 
     def pdn_put_cols_f32(self, g, idx, dx, n, C, stream):
-        flat(dx, n * C).reshape(n, C)[np.arange(n), flat(idx, n, np.int64)] = flat(g, n)
+        c, ok = _wrapped(flat(idx, n, np.int64), C)
+        flat(dx, n * C).reshape(n, C)[np.arange(n)[ok], c[ok]] = flat(g, n)[ok]
         return 0
 
     def pdn_cross_entropy_fwd_f32(self, logits, targets, rows, V, mean, loss_row, lse_row, loss_out, err, stream):
         a = flat(logits, rows * V).reshape(rows, V)
-        t = flat(targets, rows, np.int64)
+        t, ok = _wrapped(flat(targets, rows, np.int64), V, err)
+        t[~ok] = 0                                                # (flag raised; the row reads column 0)
         m = a.max(-1, keepdims=True)
         lse = (np.log(np.exp(a - m).sum(-1, keepdims=True)) + m)[:, 0]
         lr = lse - a[np.arange(rows), t]
@@ -220,9 +253,9 @@ class PointwiseMixin:
 
     def pdn_cross_entropy_bwd_f32(self, logits, targets, lse_row, upstream, gscale, dlogits, rows, V, stream):
         a = np.array(flat(logits, rows * V).reshape(rows, V))
-        t = flat(targets, rows, np.int64)
+        t, ok = _wrapped(flat(targets, rows, np.int64), V)
         sm = np.exp(a - flat(lse_row, rows)[:, None])
-        sm[np.arange(rows), t] -= 1
+        sm[np.arange(rows)[ok], t[ok]] -= 1                       # (a bad target matches no column: ce_bwd_kernel)
         gs = np.float32(gscale) * (flat(upstream, 1)[0] if upstream else np.float32(1))
         flat(dlogits, rows * V).reshape(rows, V)[...] = sm * gs
         return 0

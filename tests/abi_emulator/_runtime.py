@@ -151,7 +151,7 @@ class RuntimeMixin:
         dist.all_gather(parts, torch.from_numpy(np.array(flat(send, nbytes, np.uint8))))
         return 0
     def pdn_gemm_f32_workspace_bytes(self, M, N, K, nb): return 64 * M * N * nb * 4
-    def pdn_rmsnorm_bwd_workspace_bytes(self, rows, cols): return 1024 * cols * 4
+    def pdn_rmsnorm_bwd_workspace_bytes(self, rows, cols): return min(max((rows + 15) // 16, 1), 1024) * cols * 4
     def pdn_embedding_scatter_workspace_bytes(self, V): return V * 4
     def pdn_gemm_prof_enable(self, on): return 0
     def pdn_gemm_prof_collect_families(self, ms, fl, n): return 0
