@@ -192,7 +192,7 @@ def on_reshape(t, new_shape):
 
 
 def on_cross_entropy(y_pred, y_true, reduction, ignore_index=None):
-    """Hook of F.cross_entropy_loss (class-index targets, 2-D float32 predictions)."""
+    """Hook of F.cross_entropy_loss (class-index targets, 2-D float32 predictions); `reduction` 'none' is passed through."""
     if not (loss_chain.enabled and _pending_linear(y_pred) and y_pred.ndim == 2):
         return None
     x, w = y_pred._pending[0], y_pred._pending[1]

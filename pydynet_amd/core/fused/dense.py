@@ -11,7 +11,7 @@ from ... import _lib
 from ...autograd import is_grad_enable
 from ..tensor import Tensor, _Operator
 from ._common import _hip, _L, _contig, _require_f32, _foldable, _beside, _is_leaf_f32, _Deferred, hip_f32
-from . import masked_loss
+from . import masked_loss, row_loss
 
 
 class linear(_Deferred, _Operator):
@@ -244,18 +244,73 @@ class cross_entropy(_Operator):
     row left the loss is 0 and every gradient is 0 -- torch returns NaN there; a replayed training step cannot look at its
     loss before the optimizer runs, and a NaN gradient would poison Adam's moments for good.  On a HIP device the count and
     its reciprocal stay on the device (`pdnl_*` entries of include/pdn_loss.h): nothing is read back, so the node can be
-    captured in a `hipnp.Graph` and follows a targets buffer whose mask changes between replays."""
+    captured in a `hipnp.Graph` and follows a targets buffer whose mask changes between replays.
+
+    reduction 'none' (an extension; the statement is core/fused/row_loss.py): the node's value is the (rows,) vector of row
+    losses, 0 at ignored rows, and its backward takes a (rows,) float32 gradient -- dlogits_n = (softmax - onehot) * g_n,
+    exactly 0 at ignored rows whatever g_n holds (`pdnr_cross_entropy_bwd_rows_f32` of include/pdn_rowloss.h).  No count and
+    no factor: normalisation is the caller's."""
 
     def __init__(self, logits, targets, reduction="mean", ignore_index=None):
-        if reduction not in ("mean", "sum"):
-            raise ValueError("reduction must be mean or sum.")
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("reduction must be mean, sum or none.")
         self.reduction = reduction
         self.ignore_index = None if ignore_index is None else int(ignore_index)
         self._t = targets.data if isinstance(targets, Tensor) else targets
         super().__init__(logits)
 
+    def _forward_rows(self, x):
+        """reduction 'none': the rows the forward entries leave anyway (every variant of them writes loss_row and lse_row)"""
+        n, V = x.shape
+        if self.xp is np:
+            t = np.asarray(self._t).reshape(-1)
+            row_loss.check_targets(t, self.ignore_index, V)
+            self._valid = row_loss.valid_rows(t, self.ignore_index)
+            self._ts = np.where(self._valid, t, 0)
+            m = x.data.max(-1, keepdims=True)
+            self._lse = np.log(np.exp(x.data - m).sum(-1, keepdims=True)) + m
+            return np.where(self._valid, self._lse[:, 0] - x.data[np.arange(n), self._ts], 0).astype(x.dtype)
+        _require_f32(self, x)
+        hp, L = _hip(), _L()
+        if not hasattr(self._t, "_ptr"):
+            self._t = hp.from_numpy(np.asarray(self._t).astype(np.int64))
+        self._x = _contig(x.data)
+        self._t = _contig(self._t)
+        loss_row = hp.empty((n,), np.float32)
+        self._lse = hp.empty((n,), np.float32)
+        out = hp.empty((1,), np.float32)
+        if self.ignore_index is not None:
+            stats = hp.empty((4,), np.float32)
+            L.call("pdnl_cross_entropy_fwd_f32", self._x._ptr, self._t._ptr, self.ignore_index, n, V, 0, loss_row._ptr,
+                   self._lse._ptr, out._ptr, stats._ptr, hp.err_flag_ptr(), hp.stream())
+        else:
+            L.call("pdn_cross_entropy_fwd_f32", self._x._ptr, self._t._ptr, n, V, 0, loss_row._ptr, self._lse._ptr, out._ptr,
+                   hp.err_flag_ptr(), hp.stream())
+        return loss_row
+
+    def _backward_rows(self, g):
+        x = self.last[0]
+        n, V = x.shape
+        if self.xp is np:
+            sm = np.exp(x.data - self._lse)
+            sm[np.arange(n), self._ts] -= 1
+            sm *= np.where(self._valid, np.asarray(g, x.dtype).reshape(-1), 0)[:, None]
+            sm[~self._valid] = 0
+            return [sm]
+        hp, L = _hip(), _L()
+        g = _contig(g).reshape(-1)
+        if g.dtype != np.float32 or g.shape[0] != n:
+            raise TypeError(f"cross_entropy(reduction='none'): the upstream gradient must be ({n},) float32, got {g.shape} {g.dtype}")
+        dx = hp.empty((n, V), np.float32)
+        masked = self.ignore_index is not None
+        L.call("pdnr_cross_entropy_bwd_rows_f32", self._x._ptr, self._t._ptr, 1 if masked else 0,
+               self.ignore_index if masked else 0, self._lse._ptr, g._ptr, dx._ptr, n, V, hp.stream())
+        return [dx]
+
     def forward_(self, x):
         n, V = x.shape
+        if self.reduction == "none":
+            return self._forward_rows(x)
         if self.xp is np:
             t = np.asarray(self._t)
             m = x.data.max(-1, keepdims=True)
@@ -316,6 +371,8 @@ class cross_entropy(_Operator):
         return out.reshape(())
 
     def backward_all(self, g):
+        if self.reduction == "none":
+            return self._backward_rows(g)
         x = self.last[0]
         n, V = x.shape
         scale = 1.0 / n if self.reduction == "mean" else 1.0
@@ -365,7 +422,14 @@ class linear_cross_entropy(_Operator):
     terms of dlogits the weight-gradient product forms are exactly 0 on those rows; under 'mean' the products run with
     gscale 1 and the upstream device scalar carries 1 / count.  `pdnl_linear_ce_backward_f32` then sets the rows of ignored
     tokens in dx to 0 (the input-gradient kernels subtract a gathered weight column whatever the row).  Nothing is folded
-    into dx on this path.  On the `cpu` device the node is the NumPy statement of the same contract."""
+    into dx on this path.  On the `cpu` device the node is the NumPy statement of the same contract.
+    reduction 'none' (the statement is core/fused/row_loss.py): the value is the (rows,) vector of row losses and backward
+    takes a (rows,) float32 gradient u.  The products again stay the kernels they are, and take one upstream scalar; the
+    per-row factor goes around them (`pdnr_linear_ce_backward_rows_f32` of include/pdn_rowloss.h): dx is the product with
+    gscale 1, its rows scaled by u afterwards (ignored rows set to 0); dW = (diag(u / s) x)^T (s dz) from a scaled copy of x
+    with s = max |u| as the product's device scalar; dbias, which the product can only sum unweighted, is one more pass over
+    the saved logits, run only when the bias needs a gradient.  Nothing is read back, so the node replays from a
+    `hipnp.Graph` over changing targets and weights."""
 
     folds_existing = True
     enabled = True
@@ -394,7 +458,7 @@ class linear_cross_entropy(_Operator):
     @staticmethod
     def applicable(x, w, b, targets, reduction="mean", ignore_index=None):
         if not (linear_cross_entropy.enabled and x.device.is_hip and x.dtype == np.float32 and w.dtype == np.float32
-                and (b is None or b.dtype == np.float32) and reduction in ("mean", "sum") and w.ndim == 2):
+                and (b is None or b.dtype == np.float32) and reduction in ("mean", "sum", "none") and w.ndim == 2):
             return False
         rows = 1
         for d in x.shape[:-1]:
@@ -408,8 +472,8 @@ class linear_cross_entropy(_Operator):
                 and bool(_L().query("pdn_linear_ce_supported", rows, w.shape[1], w.shape[0])))
 
     def __init__(self, x, weight, bias, targets, reduction="mean", ignore_index=None):
-        if reduction not in ("mean", "sum"):
-            raise ValueError("reduction must be mean or sum.")
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("reduction must be mean, sum or none.")
         self.reduction = reduction
         self.ignore_index = None if ignore_index is None else int(ignore_index)
         self.has_bias = bias is not None
@@ -423,7 +487,11 @@ class linear_cross_entropy(_Operator):
             z = z + b.data.reshape(-1)
         n, V = z.shape
         t = np.asarray(self._t).reshape(-1)
-        if self.ignore_index is None:
+        if self.reduction == "none":
+            row_loss.check_targets(t, self.ignore_index, V)
+            valid = row_loss.valid_rows(t, self.ignore_index)
+            ts, factor = np.where(valid, t, 0), 1.0
+        elif self.ignore_index is None:
             valid, ts, factor = np.ones(n, bool), t, (1.0 / n if self.reduction == "mean" else 1.0)
         else:
             masked_loss.check_targets(t, self.ignore_index, V)
@@ -433,6 +501,8 @@ class linear_cross_entropy(_Operator):
         lse = np.log(np.exp(z - m).sum(-1, keepdims=True)) + m
         rows = np.where(valid, lse[:, 0] - z[np.arange(n), ts], 0)
         self._saved = (x2, z, lse, valid, ts, factor)
+        if self.reduction == "none":
+            return rows.astype(z.dtype)
         return (rows.sum() * np.asarray(factor, z.dtype)).astype(z.dtype)
 
     def _backward_np(self, g):
@@ -442,8 +512,11 @@ class linear_cross_entropy(_Operator):
         self._saved = None
         d = np.exp(z - lse)
         d[np.arange(len(ts)), ts] -= 1
+        if self.reduction == "none":
+            d *= np.where(valid, np.asarray(g, z.dtype).reshape(-1), 0)[:, None]      # (an ignored row's g may hold anything)
+        else:
+            d *= g * np.asarray(factor, z.dtype)
         d[~valid] = 0
-        d *= g * np.asarray(factor, z.dtype)
         grads = [None] * len(self.last)
         if x.requires_grad:
             grads[0] = (d @ w.data.T).reshape(x.shape)
@@ -462,6 +535,7 @@ class linear_cross_entropy(_Operator):
         x2 = _contig(x.data).reshape(-1, fin)
         n = x2.shape[0]
         masked = self.ignore_index is not None
+        by_rows = self.reduction == "none"
         if not hasattr(self._t, "_ptr"):
             self._t = hp.from_numpy(np.asarray(self._t).astype(np.int64))
         self._t = _contig(self._t)
@@ -480,9 +554,16 @@ class linear_cross_entropy(_Operator):
         if masked:
             # what the finish leaves for the backward: {count, 1 / count, upstream / count} and the sanitised targets
             self._stats, self._t_safe = hp.empty((4,), np.float32), hp.empty((n,), np.int64)
+        elif by_rows:
+            self._t_safe = hp.empty((n,), np.int64)
 
         def finish():
-            if masked:
+            if by_rows:
+                # the masked finish without its reduction: loss_row is the node's value
+                L.call("pdnr_linear_ce_finish_rows_f32", logits._ptr, V, lse._ptr, self._t._ptr, 1 if masked else 0,
+                       self.ignore_index if masked else 0, n, V, loss_row._ptr, self._t_safe._ptr, hp.err_flag_ptr(),
+                       hp.stream())
+            elif masked:
                 L.call("pdnl_linear_ce_finish_f32", logits._ptr, V, lse._ptr, self._t._ptr, self.ignore_index, n, V, mean,
                        loss_row._ptr, out._ptr, self._stats._ptr, self._t_safe._ptr, hp.err_flag_ptr(), hp.stream())
             else:
@@ -541,8 +622,10 @@ class linear_cross_entropy(_Operator):
             hp.gemm(x2, wd, logits, bias=b.data.reshape(-1) if b is not None else None)
             L.call("pdn_cross_entropy_fwd_f32", logits._ptr, self._t._ptr, n, V, mean, loss_row._ptr, lse._ptr, out._ptr,
                    hp.err_flag_ptr(), hp.stream())
+            if by_rows:
+                finish()
         self._saved = (x2, logits, lse)
-        return out.reshape(())
+        return loss_row if by_rows else out.reshape(())
 
     def backward_all(self, g):
         if self.xp is np:
@@ -556,6 +639,12 @@ class linear_cross_entropy(_Operator):
         self._saved = None
         n = x2.shape[0]
         g = _contig(g)
+        by_rows = self.reduction == "none"
+        if by_rows:
+            g = g.reshape(-1)
+            if g.dtype != np.float32 or g.shape[0] != n:
+                raise TypeError(f"linear_cross_entropy(reduction='none'): the upstream gradient must be ({n},) float32, "
+                                f"got {g.shape} {g.dtype}")
         grads = [None] * len(self.last)
         dx = ex = None
         dxu, self._dxu = self._dxu, None
@@ -563,12 +652,12 @@ class linear_cross_entropy(_Operator):
             raise RuntimeError("linear_cross_entropy: the weight's buffer was replaced between forward and backward; the "
                                "input gradient of the deferred form was formed from the forward pass's weights")
         if x.requires_grad and dxu is not None:
-            if not masked:
+            if not masked and not by_rows:
                 dxu *= g.reshape(())                       # formed in the forward pass, up to the upstream scalar
             grads[0] = dxu.reshape(x.shape)
         elif x.requires_grad:
             dx = hp.empty(x.shape, np.float32)
-            ex = _foldable(self, 0, x) if not masked else None
+            ex = _foldable(self, 0, x) if not (masked or by_rows) else None
             grads[0] = dx
         dw, dw_beta = None, 0.0
         if w.requires_grad:
@@ -583,6 +672,24 @@ class linear_cross_entropy(_Operator):
             else:
                 db = hp.empty((V,), np.float32)
                 grads[2] = db.reshape(b.shape)
+        if by_rows:
+            # the bias gradient is a pass of its own over the logits (the product sums its columns unweighted): it is not
+            # asked of the product, and it runs first, so it shares the products' scratch
+            cneed = L.query("pdnr_weighted_colsum_workspace_bytes", n, V) if db is not None else 0
+            need = L.query("pdn_linear_ce_workspace_bytes", n, V, fin) if dw is not None else 0
+            ws, got = hp.workspace(max(need, cneed)) if max(need, cneed) else (None, 0)
+            wsb = got if dw is not None else 0
+            if dw is not None and not linear_cross_entropy.split_dw and need > linear_cross_entropy._dw_split_extra(n, V):
+                wsb = need - linear_cross_entropy._dw_split_extra(n, V)
+            xs = hp.empty((n, fin), np.float32) if dw is not None else None       # diag(u / s) x
+            s_dev = hp.empty((2,), np.float32) if dw is not None else None        # {s, 1 / s}
+            dxd = dxu if (x.requires_grad and dxu is not None) else None
+            L.call("pdnr_linear_ce_backward_rows_f32", x2._ptr, x2._strides[0], logits._ptr, lse._ptr, self._t_safe._ptr,
+                   g._ptr, w.data._ptr, dx._ptr if dx is not None else None, dxd._ptr if dxd is not None else None,
+                   dw._ptr if dw is not None else None, dw_beta, db._ptr if db is not None else None, db_beta,
+                   xs._ptr if xs is not None else None, s_dev._ptr if s_dev is not None else None, n, V, fin,
+                   ws if wsb else None, wsb, ws if cneed else None, cneed, hp.stream())
+            return grads
         need = L.query("pdn_linear_ce_workspace_bytes", n, V, fin) if (dw is not None or db is not None) else 0
         ws, wsb = hp.workspace(need) if need else (None, 0)
         if not linear_cross_entropy.split_dw and need > linear_cross_entropy._dw_split_extra(n, V):

@@ -72,7 +72,8 @@ enum {
                                   // (csrc/outres_tn_split.hip): also counts in 15
   PDN_CNT_ATT_SEG = 43,           // document-masked resident attention (the SEG kernels of csrc/attention.hip, include/pdn_segattn.h),
                                   // either direction: also counts in 9 / 10
-  PDN_CNT_SLOTS = 44
+  PDN_CNT_ROW_LOSS = 44,          // cross entropy with reduction='none' (csrc/row_loss.hip, include/pdn_rowloss.h): once per pdnr_* entry
+  PDN_CNT_SLOTS = 45
 };
 void pdn_count(int slot);
 

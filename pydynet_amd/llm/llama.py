@@ -299,6 +299,51 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
             criterion = nn.CrossEntropyLoss() if ignore_index is None else nn.CrossEntropyLoss(ignore_index=ignore_index)
         return criterion(logits.reshape(B * L, V), targets)
 
+    def token_losses(self, input_ids, target_ids, start_pos: int = 0, ignore_index=None, segment_ids=None):
+        """The cross entropy of every next-token prediction, a (B, L) tensor on the tape, 0 at tokens whose target equals
+        `ignore_index`; nothing is counted or divided (core/fused/row_loss.py).  What follows plain SFT is built from it
+        with plain operators -- `(token_losses * w).sum() / w.sum()` for per-token or per-document weights, a sum per row
+        for sequence log-probabilities -- and still ends in the one lm_head + loss node, whose backward then takes a
+        different upstream gradient per token.  `segment_ids`: as in `loss`."""
+        h = self._forward_hidden(input_ids, start_pos) if segment_ids is None else \
+            self._forward_hidden(input_ids, start_pos, segment_ids=segment_ids)
+        B, L = h.shape[0], h.shape[1]
+        if isinstance(target_ids, Tensor):
+            targets = target_ids.reshape(-1)
+        else:
+            targets = Tensor(np.asarray(target_ids).reshape(-1), dtype=np.int64, device=h.device)
+        head = self.lm_head
+        bias = getattr(head, "bias", None)
+        if type(head) is nn.Linear and fused.linear_cross_entropy.applicable(h, head.weight, bias, targets, "none", ignore_index):
+            rows = fused.linear_cross_entropy(h, head.weight, bias, targets, "none", ignore_index)
+        else:
+            logits = head(h)
+            rows = nn.CrossEntropyLoss("none", ignore_index)(logits.reshape(B * L, logits.shape[-1]), targets)
+        return rows.reshape(B, L)
+
+    def sequence_logprobs(self, input_ids, target_ids, start_pos: int = 0, ignore_index=None, segment_ids=None):
+        """log p(targets | inputs) of every row, (B,) on the tape: minus the sum of the row's `token_losses`."""
+        return self.token_losses(input_ids, target_ids, start_pos, ignore_index, segment_ids).sum(-1) * -1.0
+
+    def preference_step(self, chosen_ids, chosen_targets, rejected_ids, rejected_targets, ref_chosen_logps, ref_rejected_logps,
+                        optimizer, beta=0.1, ignore_index=-100):
+        """One DPO step (llm/preference.py): zero_grad -> ONE forward over the chosen and the rejected batch stacked to
+        (2B, L), so one lm_head + loss node -> mean -logsigmoid(beta * ((pc - pr) - (rc - rr))) from plain operators on
+        the (B,) sequence log-probabilities -> backward -> optimizer step; returns the loss.  `ref_*_logps`: the reference
+        model's sequence log-probabilities, (B,) arrays or tensors without gradient."""
+        from . import preference
+        self.train(True)
+        optimizer.zero_grad()
+        host = lambda v: v.numpy() if isinstance(v, Tensor) else np.asarray(v)      # noqa: E731
+        ids = np.concatenate([host(chosen_ids), host(rejected_ids)], 0)
+        targets = np.concatenate([host(chosen_targets), host(rejected_targets)], 0)
+        B = ids.shape[0] // 2
+        logps = self.sequence_logprobs(ids, targets, ignore_index=ignore_index)
+        loss = preference.dpo_loss_tensor(logps[:B], logps[B:], ref_chosen_logps, ref_rejected_logps, beta)
+        loss.backward()
+        optimizer.step()
+        return loss.item()
+
     def finetune_step(self, input_ids, target_ids, optimizer, criterion=None, start_pos: int = 0, ignore_index=None,
                       segment_ids=None):
         """zero_grad -> forward -> cross entropy -> backward -> optimizer step; returns the loss.  `ignore_index`,

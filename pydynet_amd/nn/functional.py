@@ -158,9 +158,26 @@ def nll_loss(y_pred, y_true, reduction='mean'):
 def cross_entropy_loss(y_pred, y_true, reduction='mean', ignore_index=None):
     """`ignore_index` (an extension; None: off): rows whose class-index target equals it add nothing to the loss or to any
     gradient, and 'mean' divides by the number of remaining rows -- 0, not torch's NaN, when none remains (the contract and
-    the reason are in core/fused/masked_loss.py).  Under data parallel each rank divides by its own count."""
-    if reduction not in ('mean', 'sum'):
-        raise ValueError("reduction must be mean or sum.")
+    the reason are in core/fused/masked_loss.py).  Under data parallel each rank divides by its own count.
+    reduction 'none' (an extension; class-index targets only): the (rows,) vector of row losses, 0 at ignored rows, on
+    the tape -- its backward takes one upstream number per row (core/fused/row_loss.py).  No count and no factor."""
+    if reduction not in ('mean', 'sum', 'none'):
+        raise ValueError("reduction must be mean, sum or none.")
+    if reduction == 'none':
+        if y_true.ndim != 1 or y_pred.ndim != 2:
+            raise ValueError("reduction 'none' needs class-index targets (rows,) and (rows, classes) predictions, "
+                             "not one-hot or soft targets")
+        if y_pred.dtype != np.float32:
+            # float64: the plain-operator chain (no kernel of this node computes in float64)
+            shifted = y_pred - y_pred.max().item()
+            neg_log_sm = tensor.log(tensor.sum(tensor.exp(shifted), 1, keepdims=True)) - shifted
+            t = np.asarray(y_true.numpy() if isinstance(y_true, tensor.Tensor) else y_true).reshape(-1)
+            keep = np.ones(t.shape, bool) if ignore_index is None else t != int(ignore_index)
+            nll = neg_log_sm[range(len(t)), np.where(keep, t, 0)]
+            return nll if keep.all() else nll * tensor.Tensor(keep.astype(y_pred.dtype), dtype=y_pred.dtype,
+                                                              device=y_pred.device)
+        r = fused.chain.on_cross_entropy(y_pred, y_true, reduction, ignore_index)
+        return r if r is not None else fused.cross_entropy(y_pred, y_true, reduction, ignore_index)
     if ignore_index is not None:
         if y_true.ndim != 1 or y_pred.ndim != 2:
             raise ValueError("ignore_index needs class-index targets (rows,) and (rows, classes) predictions, "
