@@ -41,6 +41,7 @@
 
 #include "gemm_tiled.h"    // GemmParams, tile loaders, gemm_f32_mfma_kernel, split-K reduce
 #include "gemm_stream.h"   // gemm_tn_stream_{,lds_,dma_}kernel, gemm_skinny_kernel
+#include "split_tn.h"      // host entry points of the split-fp16 weight gradients (pdn_outres_tn_split_*, pdn_outres_ce_dw_split_*)
 
 // ---- host side ----------------------------------------------------------------------
 struct TileCfg {
@@ -201,14 +202,6 @@ extern "C" int pdn_gemm_rowres_f32(const float* A, const float* B, float* C, con
                                    int64_t ldc, int b_trans, void* stream);
 int pdn_gemm_rowres_blocks(const float* A, const float* B, float* C, int M, int N, int K, int64_t lda, int64_t ldb,
                            int64_t ldc, int b_trans, int nblocks, int64_t b_block_stride, void* stream);
-
-// csrc/outres_tn_split.hip: the packed layer weight gradients on split-fp16 MFMA
-int pdn_outres_tn_split_enabled();
-int pdn_outres_tn_split_supported(int M, int nb_cols, int nbatch, int K);
-int64_t pdn_outres_tn_split_extra_bytes(int K);
-int pdn_outres_tn_split_ranges(int n_all, int K, int plan);
-int pdn_outres_tn_split_launch(const float* X, const float* G, float* C, int n_all, int K, int64_t ldx, int64_t ldg,
-                               int nb_cols, int k_per_split, void* extra, void* stream);
 
 extern "C" int64_t pdn_gemm_f32_workspace_bytes(int M, int N, int K, int nbatch) {
   // Enough for up to 64 splits of one output; pdn_gemm_f32 never uses more than it is given.
@@ -937,13 +930,7 @@ int pdn_outres_ce_dx_launch(const float* logits, int64_t ldl, const float* lse, 
 int pdn_outres_ce_dw_launch(const float* X, const float* logits, float* C, int N, int K, int64_t ldx, int64_t ldg,
                             int64_t ldc, int64_t slab, int nw, int k_per_split, const float* lse,
                             const int64_t* targets, float gscale, const float* gdev, float* colsum, void* stream);
-// the same product on split-fp16 MFMA (csrc/lm_head_dw_split.hip): same slabs, same column-sum slabs
-int pdn_outres_ce_dw_split_enabled();
-int pdn_outres_ce_dw_split_supported(int64_t rows, int V, int in_features);
-int64_t pdn_outres_ce_dw_split_extra_bytes(int64_t rows);
-int pdn_outres_ce_dw_split_launch(const float* x, int64_t ldx, const float* logits, float* C, int V, int64_t rows,
-                                  int64_t slab, int k_per_split, const float* lse, const int64_t* targets, float gscale,
-                                  const float* gdev, float* colsum, void* extra, void* stream);
+// (the same product on split-fp16 MFMA, csrc/lm_head_dw_split.hip: pdn_outres_ce_dw_split_* of split_tn.h)
 
 int pdn_outres_ce_dx_deferred_launch(const float* logits, int64_t ldl, const float* rowmax, int max_parts,
                                      const int64_t* targets, float gscale, const float* W, int64_t ldw, float* dx,

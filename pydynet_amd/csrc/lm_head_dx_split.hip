@@ -33,13 +33,7 @@
 // "W's piece s has landed" and, with it, everything older: the logits of piece s + 2 and before.  Three pieces of logits
 // stay in flight and are never waited for earlier than two pieces after their issue.
 // Deterministic: fixed order, no atomics.
-#include "common.h"
-#include "lm_head_split.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "split_tn.h"
 
 #define LD_N 288                          // output columns: 18 tiles of 16
 #define LD_NT 18
@@ -110,13 +104,6 @@ struct LdxParams {
   float gscale;
 };
 
-// 16 bytes per lane from `g` to LDS address `lds` + 16 lane (`lds` wave-uniform).  Opaque to the compiler on purpose (see
-// the head of the file): nothing in the loop is a load in its eyes, the waits are written out below.  (m0 is reserved:
-// the compiler keeps nothing in it, and this kernel has no other instruction that reads it.)
-__device__ __forceinline__ void ldx_dma16(const void* g, unsigned lds) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds) : "memory");
-}
-
 // two logits of the row: e = exp(logit - max), their sum for Z, their planes at 2^15 as two packed halves each.
 // The empty asm pins the pair where it is written: the compiler otherwise collects the splits of a whole piece behind its
 // last MFMA, a VALU phase of its own in which both waves of a SIMD leave the matrix pipe idle.
@@ -155,7 +142,7 @@ __global__ __launch_bounds__(512, 1) void ldx_main_kernel(LdxParams p) {
 #pragma unroll
     for (int e = 0; e < 5; ++e) {
       const int I = min(e * 8 + wave, 35);
-      ldx_dma16(src + I * 1024, __builtin_amdgcn_readfirstlane(lds0 + slot + I * 1024));
+      split_dma16(src + I * 1024, __builtin_amdgcn_readfirstlane(lds0 + slot + I * 1024));
     }
   };
   // logits: instruction i (0, 1) fetches rows 8 i .. 8 i + 7 of the wave's sixteen, lane l the 16-byte chunk at POSITION
@@ -171,8 +158,8 @@ __global__ __launch_bounds__(512, 1) void ldx_main_kernel(LdxParams p) {
   }
   auto dma_raw = [&](int piece, int ring) __attribute__((always_inline)) {
     const int64_t o = (int64_t)min(piece, np - 1) * LD_KP;     // (behind the last piece: a repeated fetch, never split)
-    ldx_dma16(lsrc[0] + o, __builtin_amdgcn_readfirstlane(lds0 + rw_base + ring * LD_RAW));
-    ldx_dma16(lsrc[1] + o, __builtin_amdgcn_readfirstlane(lds0 + rw_base + ring * LD_RAW + 1024));
+    split_dma16(lsrc[0] + o, __builtin_amdgcn_readfirstlane(lds0 + rw_base + ring * LD_RAW));
+    split_dma16(lsrc[1] + o, __builtin_amdgcn_readfirstlane(lds0 + rw_base + ring * LD_RAW + 1024));
   };
   // lane (t, q) reads logits 8 q .. 8 q + 7 of row t: chunks 2 q and 2 q + 1, at positions (2 q) ^ f and that ^ 1
   const int raw_lane = rw_base + r * 128 + (((2 * q) ^ ((r >> 1) & 7)) << 4);

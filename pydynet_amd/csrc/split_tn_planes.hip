@@ -1,0 +1,106 @@
+// The passes over x of the split-fp16 TN pipeline (csrc/lm_head_dw_split.hip, csrc/outres_tn_split.hip; gfx950 only):
+//
+//   x[:, d] 2^s(d) = xh + xl / 2048      one power of two per COLUMN d of x = per row of dW
+//
+// in three launches: partial column maxima over ranges of rows, the exponent of every column, then the plane images, one per
+// piece of 32 tokens, transposed, in LDS order (csrc/split_tn_index.h).  With lse and targets the images are 37 KiB and
+// their tails carry the row statistics of the NEXT piece (the lm_head weight gradient), without 36 KiB.
+#include "split_tn.h"
+
+#define STN_L2E 1.4426950408889634f
+
+// ---- column maxima over a range of rows (partial), then the exponent of every column ---------------------------------
+// 288 threads: thread (c4 = tid % 72, g = tid / 72) takes the float4 c4 of rows g, g + 4, .. of the block's range
+__global__ __launch_bounds__(288) void stn_x_colmax_kernel(const float* __restrict__ x, int64_t ldx, int rows, int rows_per_block,
+                                                            float* __restrict__ partial) {
+  __shared__ float sm[4][STN_N];
+  const int c4 = threadIdx.x % 72, g = threadIdx.x / 72;
+  const int r0 = blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
+  float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 z = m;                 // fmaxf drops a NaN: 0 * v stays 0 for every finite v and turns NaN for Inf and NaN
+#pragma unroll 4
+  for (int r = r0 + g; r < r1; r += 4) {
+    const float4 v = *reinterpret_cast<const float4*>(x + (int64_t)r * ldx + 4 * c4);
+    m.x = fmaxf(m.x, fabsf(v.x)); m.y = fmaxf(m.y, fabsf(v.y)); m.z = fmaxf(m.z, fabsf(v.z)); m.w = fmaxf(m.w, fabsf(v.w));
+    z.x = fmaf(v.x, 0.f, z.x); z.y = fmaf(v.y, 0.f, z.y); z.z = fmaf(v.z, 0.f, z.z); z.w = fmaf(v.w, 0.f, z.w);
+  }
+  if (z.x != z.x) m.x = INFINITY;
+  if (z.y != z.y) m.y = INFINITY;
+  if (z.z != z.z) m.z = INFINITY;
+  if (z.w != z.w) m.w = INFINITY;
+  sm[g][4 * c4 + 0] = m.x; sm[g][4 * c4 + 1] = m.y; sm[g][4 * c4 + 2] = m.z; sm[g][4 * c4 + 3] = m.w;
+  __syncthreads();
+  const int d = threadIdx.x;
+  partial[(int64_t)blockIdx.x * STN_N + d] = fmaxf(fmaxf(sm[0][d], sm[1][d]), fmaxf(sm[2][d], sm[3][d]));
+}
+
+// one workgroup per column: thread i takes parts i, i + 256, .. (eight trips at 2048 parts over 288 workgroups; nine
+// workgroups of 32 columns x 8 part groups made 256 dependent trips, 51 us of latency)
+__global__ __launch_bounds__(256) void stn_x_shift_kernel(const float* __restrict__ partial, int nparts, int* __restrict__ xsh) {
+  __shared__ float sm[4];
+  const int d = blockIdx.x;
+  float m = 0.f;
+  for (int b = threadIdx.x; b < nparts; b += 256) m = fmaxf(m, partial[(int64_t)b * STN_N + d]);
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) xsh[d] = ls_shift(fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])));
+}
+
+// ---- the plane images, one workgroup per piece of 32 tokens; TAIL: the row statistics of the NEXT piece behind the planes --
+template <int XKIB, bool TAIL>
+__device__ __forceinline__ void stn_split_x(const float* __restrict__ x, int64_t ldx, const int* __restrict__ xsh,
+                                            const float* __restrict__ lse, const int64_t* __restrict__ targets, int rows,
+                                            char* __restrict__ ximg) {
+  char* img = ximg + (int64_t)blockIdx.x * stn_xpiece(XKIB);
+  const float* xp = x + (int64_t)blockIdx.x * STN_KP * ldx;
+  for (int i = threadIdx.x; i < STN_N * 4; i += 256) {
+    const int d = i % STN_N, q = i / STN_N;
+    const int sh = xsh[d];
+    f16x8 hv, lv;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      _Float16 h, l;
+      ls_split(xp[(int64_t)(8 * q + k) * ldx + d], sh, h, l);
+      hv[k] = h; lv[k] = l;
+    }
+    char* dst = img + stn_x_unit(d, q);
+    *reinterpret_cast<f16x8*>(dst) = hv;
+    *reinterpret_cast<f16x8*>(dst + STN_PLANE) = lv;
+  }
+  // tail: 1 KiB = 256 dwords; dwords 0..31 -lse log2 e, 32..63 the targets, the rest zero
+  if (TAIL) {
+    const int i = threadIdx.x;
+    const int64_t t = ((int64_t)blockIdx.x + 1) * STN_KP + (i & 31);
+    unsigned v = 0u;
+    if (i < 64 && t < rows) v = i < 32 ? __float_as_uint(-STN_L2E * lse[t]) : (unsigned)(int)targets[t];
+    reinterpret_cast<unsigned*>(img + LDW_TAIL)[i] = v;
+  }
+}
+// (two kernels of their own arguments around the one body: neither carries what it does not read)
+__global__ __launch_bounds__(256) void stn_split_x_kernel(const float* __restrict__ x, int64_t ldx, const int* __restrict__ xsh,
+                                                           char* __restrict__ ximg) {
+  stn_split_x<OTS_XKIB, false>(x, ldx, xsh, nullptr, nullptr, 0, ximg);
+}
+__global__ __launch_bounds__(256) void stn_split_x_tail_kernel(const float* __restrict__ x, int64_t ldx, const int* __restrict__ xsh,
+                                                                const float* __restrict__ lse, const int64_t* __restrict__ targets,
+                                                                int rows, char* __restrict__ ximg) {
+  stn_split_x<LDW_XKIB, true>(x, ldx, xsh, lse, targets, rows, ximg);
+}
+
+int* stn_x_planes_launch(const float* x, int64_t ldx, int rows, void* extra, const float* lse, const int64_t* targets, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const bool tail = lse != nullptr;
+  const int npieces = rows / STN_KP;
+  char* ximg = static_cast<char*>(extra);
+  int* xsh = reinterpret_cast<int*>(ximg + (int64_t)npieces * stn_xpiece(tail ? LDW_XKIB : OTS_XKIB));
+  float* partial = reinterpret_cast<float*>(ximg);               // parked in the image region until the plane pass
+  const int nparts = stn_partials(rows);
+  const int rpb = (rows + nparts - 1) / nparts;
+  const int nblk = (rows + rpb - 1) / rpb;
+  hipLaunchKernelGGL(stn_x_colmax_kernel, dim3(nblk), dim3(288), 0, st, x, ldx, rows, rpb, partial);
+  hipLaunchKernelGGL(stn_x_shift_kernel, dim3(STN_N), dim3(256), 0, st, partial, nblk, xsh);
+  if (tail) hipLaunchKernelGGL(stn_split_x_tail_kernel, dim3(npieces), dim3(256), 0, st, x, ldx, xsh, lse, targets, rows, ximg);
+  else hipLaunchKernelGGL(stn_split_x_kernel, dim3(npieces), dim3(256), 0, st, x, ldx, xsh, ximg);
+  return xsh;
+}

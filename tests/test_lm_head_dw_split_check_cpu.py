@@ -1,4 +1,4 @@
-"""Builds tests/lm_head_dw_split_check.cpp -- a stand-alone program around pydynet_amd/csrc/lm_head_dw_split_index.h, the
+"""Builds tests/lm_head_dw_split_check.cpp -- a stand-alone program around pydynet_amd/csrc/split_tn_index.h, the
 header from which the split-fp16 lm_head weight-gradient kernel (csrc/lm_head_dw_split.hip) takes every address it forms --
 with the host compiler under AddressSanitizer and UndefinedBehaviorSanitizer, and runs it as a process of its own for the
 shapes of tests/test_lm_head_dw_split_gpu.py and the benchmark's 131072 x 32000.  The program walks every workgroup, wave,

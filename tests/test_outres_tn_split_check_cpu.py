@@ -1,4 +1,4 @@
-"""Builds tests/outres_tn_split_check.cpp -- a stand-alone program around pydynet_amd/csrc/outres_tn_split_index.h, the
+"""Builds tests/outres_tn_split_check.cpp -- a stand-alone program around pydynet_amd/csrc/split_tn_index.h, the
 header from which the split-fp16 kernel of the packed layer weight gradients (csrc/outres_tn_split.hip) takes every address
 it forms -- with the host compiler under AddressSanitizer and UndefinedBehaviorSanitizer, and runs it as a process of its own
 for the shapes of tests/test_outres_tn_split_gpu.py and the benchmark's 131072 x 864 and 131072 x 1536.  The program walks

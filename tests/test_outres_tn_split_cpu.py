@@ -4,7 +4,7 @@
 
     x[:, d] 2^s(d) = xh + xl / 2048        one power of two per column d, the largest |x[:, d]| into [2^8, 2^9)
     g 2^S = gh + gl / 2048                 S: the RUNNING exponent of a wave's sixteen columns (ots_next_scale of
-                                           csrc/outres_tn_split_index.h), found piece by piece, no pass over g
+                                           csrc/split_tn_index.h), found piece by piece, no pass over g
     dW 2^(S + s(d)) = xh gh + (xh gl + xl gh) / 2048        two fp32 running sums over pieces of 32 tokens
 
 Before the 32 x 16 values of a piece are split, their largest finite magnitude is taken; if that times 2^S would reach

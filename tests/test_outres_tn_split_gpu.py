@@ -119,7 +119,7 @@ class _Problem:
         return out[:, :D], (cnt[15], cnt[42])
 
     def _ranges(self):
-        """K ranges of the split form: ots_ranges / ots_k_per_split of csrc/outres_tn_split_index.h"""
+        """K ranges of the split form: ots_ranges / ots_k_per_split of csrc/split_tn_index.h"""
         cb, pieces = (self.n_all + 127) // 128, self.K // 32
         col_wgs = (self.n_all // 32 + 7) // 8
         plan = 256 // col_wgs

@@ -1,6 +1,6 @@
 """lm_head weight gradient with the cross-entropy gradient formed inside: the fp32 MFMA kernel (csrc/gemm_outres.hip,
-gemm_outres_tn_kernel<.., CE>) against the split-fp16 kernel (csrc/lm_head_dw_split.hip: the two passes over x and the
-product), and the split kernel's timing ablations (PDN_LMHEAD_DW_SPLIT_ABLATE: 1 = constant planes, no logits read -- MFMA
+gemm_outres_tn_kernel<.., CE>) against the split-fp16 kernel (csrc/lm_head_dw_split.hip: the passes over x of
+csrc/split_tn_planes.hip and the product), and the split kernel's timing ablations (PDN_LMHEAD_DW_SPLIT_ABLATE: 1 = constant planes, no logits read -- MFMA
 + LDS only; 2 = the logits fetched once -- no HBM stream, the split arithmetic stays).  Every figure is one call of
 pdn_linear_ce_backward_f32 with dx = NULL and includes the two slab reductions (dW and dbias), which both kernels share;
 the fp32 kernel is selected by the workspace size (include/pdn_hip.h).  The library reads the ablation switch once, so

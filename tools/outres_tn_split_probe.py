@@ -1,7 +1,7 @@
 """The packed layer weight gradients -- x^T (288 x K) against dq | dk | dv (K x 864 as three blocks) and dgate | dup
 (K x 1536 as two) -- on the fp32 MFMA kernel (csrc/gemm_outres.hip, gemm_outres_tn_kernel behind
-pdn_gemm_outres_tn_blocks_launch) against the split-fp16 kernel (csrc/outres_tn_split.hip: the three passes over x and the
-product), and the split kernel's timing ablations (PDN_OUTRES_TN_SPLIT_ABLATE: 1 = constant planes, g never read -- MFMA +
+pdn_gemm_outres_tn_blocks_launch) against the split-fp16 kernel (csrc/outres_tn_split.hip: the three passes over x of
+csrc/split_tn_planes.hip and the product), and the split kernel's timing ablations (PDN_OUTRES_TN_SPLIT_ABLATE: 1 = constant planes, g never read -- MFMA +
 LDS only; 2 = g fetched once -- no HBM stream, the split arithmetic stays).  Every figure is one call of pdn_gemm_f32 in the
 batched form of the backward pass with beta = 1 and includes the slab reduction, which both kernels share; the fp32 kernel
 is selected by the workspace size (include/pdn_hip.h).  The library reads the ablation switch once, so every variant runs
