@@ -219,7 +219,8 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *     15 (it IS the output-resident TN launch of the product)
  *  43 document-masked resident attention (the SEG kernels of csrc/attention.hip): pdns_attention_fwd_f32 and
  *     pdns_attention_bwd_f32 of include/pdn_segattn.h, either direction; also counts in 9 / 10 (it IS a resident launch)
- *  44 cross entropy with reduction='none' (csrc/row_loss.hip): once per pdnr_* entry of include/pdn_rowloss.h */
+ *  44 cross entropy with reduction='none' (csrc/row_loss.hip): once per pdnr_* entry of include/pdn_rowloss.h
+ *  45 cross entropy with label_smoothing / z_loss (csrc/smooth_loss.hip): once per pdnz_* entry of include/pdn_smoothloss.h */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores

@@ -191,8 +191,9 @@ def on_reshape(t, new_shape):
     return _linear(x.reshape(*shape[:-1], x.shape[-1]), w, b)
 
 
-def on_cross_entropy(y_pred, y_true, reduction, ignore_index=None):
-    """Hook of F.cross_entropy_loss (class-index targets, 2-D float32 predictions); `reduction` 'none' is passed through."""
+def on_cross_entropy(y_pred, y_true, reduction, ignore_index=None, label_smoothing=0.0, z_loss=0.0):
+    """Hook of F.cross_entropy_loss (class-index targets, 2-D float32 predictions); `reduction` 'none' is passed through, and
+    so are `label_smoothing` / `z_loss` where one of them is not 0."""
     if not (loss_chain.enabled and _pending_linear(y_pred) and y_pred.ndim == 2):
         return None
     x, w = y_pred._pending[0], y_pred._pending[1]
@@ -200,6 +201,8 @@ def on_cross_entropy(y_pred, y_true, reduction, ignore_index=None):
     if not _linear_ce.applicable(x, w, b, y_true, reduction, ignore_index):
         return None
     loss_chain.fused_built += 1
+    if label_smoothing != 0.0 or z_loss != 0.0:
+        return _linear_ce(x, w, b, y_true, reduction, ignore_index, label_smoothing, z_loss)
     if ignore_index is None:
         return _linear_ce(x, w, b, y_true, reduction)
     return _linear_ce(x, w, b, y_true, reduction, ignore_index)

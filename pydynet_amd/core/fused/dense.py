@@ -11,7 +11,7 @@ from ... import _lib
 from ...autograd import is_grad_enable
 from ..tensor import Tensor, _Operator
 from ._common import _hip, _L, _contig, _require_f32, _foldable, _beside, _is_leaf_f32, _Deferred, hip_f32
-from . import masked_loss, row_loss
+from . import masked_loss, row_loss, smooth_loss
 
 
 class linear(_Deferred, _Operator):
@@ -249,15 +249,70 @@ class cross_entropy(_Operator):
     reduction 'none' (an extension; the statement is core/fused/row_loss.py): the node's value is the (rows,) vector of row
     losses, 0 at ignored rows, and its backward takes a (rows,) float32 gradient -- dlogits_n = (softmax - onehot) * g_n,
     exactly 0 at ignored rows whatever g_n holds (`pdnr_cross_entropy_bwd_rows_f32` of include/pdn_rowloss.h).  No count and
-    no factor: normalisation is the caller's."""
+    no factor: normalisation is the caller's.
 
-    def __init__(self, logits, targets, reduction="mean", ignore_index=None):
+    `label_smoothing` eps / `z_loss` lam (extensions; both 0: off, exactly the node above; the statement is
+    core/fused/smooth_loss.py): row_n = lse - (1 - eps) x_n[t_n] - eps mean(x_n) + lam lse^2 under every reduction and with or
+    without `ignore_index`; 'mean' averages both terms over the same remaining rows.  On a HIP device the forward is one pass
+    per row for the maximum, the sum of exponentials and the sum (`pdnz_cross_entropy_fwd_f32` of include/pdn_smoothloss.h),
+    the backward `pdnz_cross_entropy_bwd_f32`; count and factor stay on the device."""
+
+    def __init__(self, logits, targets, reduction="mean", ignore_index=None, label_smoothing=0.0, z_loss=0.0):
         if reduction not in ("mean", "sum", "none"):
             raise ValueError("reduction must be mean, sum or none.")
         self.reduction = reduction
         self.ignore_index = None if ignore_index is None else int(ignore_index)
+        self.smooth = label_smoothing != 0.0 or z_loss != 0.0         # (both 0: nothing of smooth_loss.py runs)
+        self.label_smoothing, self.z_loss = smooth_loss.check_arguments(label_smoothing, z_loss) if self.smooth else (0.0, 0.0)
         self._t = targets.data if isinstance(targets, Tensor) else targets
         super().__init__(logits)
+
+    def _forward_smooth(self, x):
+        n, V = x.shape
+        eps, lam = self.label_smoothing, self.z_loss
+        if self.xp is np:
+            t = np.asarray(self._t).reshape(-1)
+            value = smooth_loss.value(x.data, t, eps, lam, self.ignore_index, self.reduction)
+            return np.asarray(value).astype(x.dtype)
+        _require_f32(self, x)
+        hp, L = _hip(), _L()
+        if not hasattr(self._t, "_ptr"):
+            self._t = hp.from_numpy(np.asarray(self._t).astype(np.int64))
+        self._x = _contig(x.data)
+        self._t = _contig(self._t)
+        loss_row = hp.empty((n,), np.float32)
+        self._lse = hp.empty((n,), np.float32)
+        by_rows = self.reduction == "none"
+        out = None if by_rows else hp.empty((1,), np.float32)
+        self._stats = None if by_rows else hp.empty((4,), np.float32)
+        masked = self.ignore_index is not None
+        L.call("pdnz_cross_entropy_fwd_f32", self._x._ptr, self._t._ptr, 1 if masked else 0, self.ignore_index if masked else 0,
+               n, V, ("none", "sum", "mean").index(self.reduction), eps, lam, loss_row._ptr, self._lse._ptr,
+               out._ptr if out is not None else None, self._stats._ptr if self._stats is not None else None,
+               hp.err_flag_ptr(), hp.stream())
+        return loss_row if by_rows else out.reshape(())
+
+    def _backward_smooth(self, g):
+        x = self.last[0]
+        n, V = x.shape
+        eps, lam = self.label_smoothing, self.z_loss
+        by_rows = self.reduction == "none"
+        if self.xp is np:
+            t = np.asarray(self._t).reshape(-1)
+            u = np.asarray(g, np.float64).reshape(-1) if by_rows else float(np.asarray(g))
+            return [smooth_loss.cross_entropy(x.data, t, eps, lam, self.ignore_index, self.reduction, u)[1].astype(x.dtype)]
+        hp, L = _hip(), _L()
+        g = _contig(g)
+        if by_rows:
+            g = g.reshape(-1)
+            if g.dtype != np.float32 or g.shape[0] != n:
+                raise TypeError(f"cross_entropy(reduction='none'): the upstream gradient must be ({n},) float32, got {g.shape} {g.dtype}")
+        dx = hp.empty((n, V), np.float32)
+        masked = self.ignore_index is not None
+        L.call("pdnz_cross_entropy_bwd_f32", self._x._ptr, self._t._ptr, 1 if masked else 0, self.ignore_index if masked else 0,
+               self._lse._ptr, g._ptr if by_rows else None, None if by_rows else g._ptr,
+               None if by_rows else self._stats._ptr, eps, lam, dx._ptr, n, V, hp.stream())
+        return [dx]
 
     def _forward_rows(self, x):
         """reduction 'none': the rows the forward entries leave anyway (every variant of them writes loss_row and lse_row)"""
@@ -309,6 +364,8 @@ class cross_entropy(_Operator):
 
     def forward_(self, x):
         n, V = x.shape
+        if self.smooth:
+            return self._forward_smooth(x)
         if self.reduction == "none":
             return self._forward_rows(x)
         if self.xp is np:
@@ -371,6 +428,8 @@ class cross_entropy(_Operator):
         return out.reshape(())
 
     def backward_all(self, g):
+        if self.smooth:
+            return self._backward_smooth(g)
         if self.reduction == "none":
             return self._backward_rows(g)
         x = self.last[0]
@@ -429,7 +488,16 @@ class linear_cross_entropy(_Operator):
     gscale 1, its rows scaled by u afterwards (ignored rows set to 0); dW = (diag(u / s) x)^T (s dz) from a scaled copy of x
     with s = max |u| as the product's device scalar; dbias, which the product can only sum unweighted, is one more pass over
     the saved logits, run only when the bias needs a gradient.  Nothing is read back, so the node replays from a
-    `hipnp.Graph` over changing targets and weights."""
+    `hipnp.Graph` over changing targets and weights.
+    `label_smoothing` eps / `z_loss` lam (both 0: off, exactly the node above; the statement is core/fused/smooth_loss.py):
+    the three products still stay the kernels they are and the two terms go around them (`pdnz_*` entries of
+    include/pdn_smoothloss.h).  Forward: the row sums of W once (mean_v z_n = (x_n . wsum + bsum) / V, no pass over the
+    logits) and a finish that takes the place of the others.  Backward: dz_n = u'_n (p - onehot) + c_n onehot - e_n with
+    u' = u a, a = 1 + 2 lam lse, c = u (2 lam lse + eps), e = u eps / V: the reduction='none' backward above runs unchanged
+    under the upstream vector u' (for 'mean' / 'sum' u is the upstream scalar times the device-resident factor), then
+    `pdnz_linear_ce_corrections_f32` adds c_n W[:, t_n] - e_n wsum to dx rows and, per class, the c-weighted sum of its x rows
+    minus sum_n e_n x_n to the columns of dW (a workgroup owns a range of classes and walks all targets in row order: no sort,
+    no atomics, two runs give the same bits), the same with x_n = 1 to dbias."""
 
     folds_existing = True
     enabled = True
@@ -456,7 +524,9 @@ class linear_cross_entropy(_Operator):
         return (rows // 32) * 37888 + 1152 if (rows >= 32768 and V >= 128) else 0
 
     @staticmethod
-    def applicable(x, w, b, targets, reduction="mean", ignore_index=None):
+    def applicable(x, w, b, targets, reduction="mean", ignore_index=None, label_smoothing=0.0, z_loss=0.0):
+        if label_smoothing != 0.0 or z_loss != 0.0:
+            smooth_loss.check_arguments(label_smoothing, z_loss)
         if not (linear_cross_entropy.enabled and x.device.is_hip and x.dtype == np.float32 and w.dtype == np.float32
                 and (b is None or b.dtype == np.float32) and reduction in ("mean", "sum", "none") and w.ndim == 2):
             return False
@@ -471,11 +541,13 @@ class linear_cross_entropy(_Operator):
                 and rows >= linear_cross_entropy.min_rows
                 and bool(_L().query("pdn_linear_ce_supported", rows, w.shape[1], w.shape[0])))
 
-    def __init__(self, x, weight, bias, targets, reduction="mean", ignore_index=None):
+    def __init__(self, x, weight, bias, targets, reduction="mean", ignore_index=None, label_smoothing=0.0, z_loss=0.0):
         if reduction not in ("mean", "sum", "none"):
             raise ValueError("reduction must be mean, sum or none.")
         self.reduction = reduction
         self.ignore_index = None if ignore_index is None else int(ignore_index)
+        self.smooth = label_smoothing != 0.0 or z_loss != 0.0         # (both 0: nothing of smooth_loss.py runs)
+        self.label_smoothing, self.z_loss = smooth_loss.check_arguments(label_smoothing, z_loss) if self.smooth else (0.0, 0.0)
         self.has_bias = bias is not None
         self._t = targets.data if isinstance(targets, Tensor) else targets
         super().__init__(*([x, weight] + ([bias] if self.has_bias else [])))
@@ -487,6 +559,10 @@ class linear_cross_entropy(_Operator):
             z = z + b.data.reshape(-1)
         n, V = z.shape
         t = np.asarray(self._t).reshape(-1)
+        if self.smooth:
+            self._saved = (x2, z, t)
+            value = smooth_loss.value(z, t, self.label_smoothing, self.z_loss, self.ignore_index, self.reduction)
+            return np.asarray(value).astype(z.dtype)
         if self.reduction == "none":
             row_loss.check_targets(t, self.ignore_index, V)
             valid = row_loss.valid_rows(t, self.ignore_index)
@@ -508,15 +584,21 @@ class linear_cross_entropy(_Operator):
     def _backward_np(self, g):
         x, w = self.last[0], self.last[1]
         b = self.last[2] if self.has_bias else None
-        x2, z, lse, valid, ts, factor = self._saved
-        self._saved = None
-        d = np.exp(z - lse)
-        d[np.arange(len(ts)), ts] -= 1
-        if self.reduction == "none":
-            d *= np.where(valid, np.asarray(g, z.dtype).reshape(-1), 0)[:, None]      # (an ignored row's g may hold anything)
+        if self.smooth:
+            x2, z, t = self._saved
+            u = np.asarray(g, np.float64).reshape(-1) if self.reduction == "none" else float(np.asarray(g))
+            d = smooth_loss.cross_entropy(z, t, self.label_smoothing, self.z_loss, self.ignore_index, self.reduction,
+                                          u)[1].astype(z.dtype)
         else:
-            d *= g * np.asarray(factor, z.dtype)
-        d[~valid] = 0
+            x2, z, lse, valid, ts, factor = self._saved
+            d = np.exp(z - lse)
+            d[np.arange(len(ts)), ts] -= 1
+            if self.reduction == "none":
+                d *= np.where(valid, np.asarray(g, z.dtype).reshape(-1), 0)[:, None]      # (an ignored row's g may hold anything)
+            else:
+                d *= g * np.asarray(factor, z.dtype)
+            d[~valid] = 0
+        self._saved = None
         grads = [None] * len(self.last)
         if x.requires_grad:
             grads[0] = (d @ w.data.T).reshape(x.shape)
@@ -536,6 +618,7 @@ class linear_cross_entropy(_Operator):
         n = x2.shape[0]
         masked = self.ignore_index is not None
         by_rows = self.reduction == "none"
+        smooth = self.smooth
         if not hasattr(self._t, "_ptr"):
             self._t = hp.from_numpy(np.asarray(self._t).astype(np.int64))
         self._t = _contig(self._t)
@@ -556,9 +639,25 @@ class linear_cross_entropy(_Operator):
             self._stats, self._t_safe = hp.empty((4,), np.float32), hp.empty((n,), np.int64)
         elif by_rows:
             self._t_safe = hp.empty((n,), np.int64)
+        if smooth:
+            self._t_safe = hp.empty((n,), np.int64)
+            if not masked and not by_rows:
+                self._stats = hp.empty((4,), np.float32)
+            # the row sums of W (and the sum of the bias) for mean_v z_n, formed once from the weights this forward reads
+            self._wsum = hp.empty((fin + 1,), np.float32) if self.label_smoothing != 0.0 else None
 
         def finish():
-            if by_rows:
+            if smooth:
+                wc = _contig(wd)
+                if self._wsum is not None:
+                    L.call("pdnz_weight_sums_f32", wc._ptr, bp, fin, V, self._wsum._ptr, hp.stream())
+                L.call("pdnz_linear_ce_finish_f32", logits._ptr, V, lse._ptr, self._t._ptr, 1 if masked else 0,
+                       self.ignore_index if masked else 0, x2._ptr, x2._strides[0],
+                       self._wsum._ptr if self._wsum is not None else None, n, V, fin,
+                       ("none", "sum", "mean").index(self.reduction), self.label_smoothing, self.z_loss, loss_row._ptr,
+                       None if by_rows else out._ptr, None if by_rows else self._stats._ptr, self._t_safe._ptr,
+                       hp.err_flag_ptr(), hp.stream())
+            elif by_rows:
                 # the masked finish without its reduction: loss_row is the node's value
                 L.call("pdnr_linear_ce_finish_rows_f32", logits._ptr, V, lse._ptr, self._t._ptr, 1 if masked else 0,
                        self.ignore_index if masked else 0, n, V, loss_row._ptr, self._t_safe._ptr, hp.err_flag_ptr(),
@@ -603,7 +702,7 @@ class linear_cross_entropy(_Operator):
             # (masked: unscaled -- 1 / count is not known yet and is applied with the upstream scalar; the kernel clamps the
             #  target whose column it subtracts, and the rows of ignored tokens are set to 0 in backward)
             L.call(dx_entry, logits._ptr, rowmax._ptr, parts, self._t._ptr,
-                   1.0 / n if (mean and not masked) else 1.0, wd._ptr, self._dxu._ptr, lse._ptr, n, V, fin, ws, wsb,
+                   1.0 / n if (mean and not masked and not smooth) else 1.0, wd._ptr, self._dxu._ptr, lse._ptr, n, V, fin, ws, wsb,
                    hp.stream())
             finish()
         elif self.stats_in_gemm:
@@ -622,7 +721,7 @@ class linear_cross_entropy(_Operator):
             hp.gemm(x2, wd, logits, bias=b.data.reshape(-1) if b is not None else None)
             L.call("pdn_cross_entropy_fwd_f32", logits._ptr, self._t._ptr, n, V, mean, loss_row._ptr, lse._ptr, out._ptr,
                    hp.err_flag_ptr(), hp.stream())
-            if by_rows:
+            if by_rows or smooth:
                 finish()
         self._saved = (x2, logits, lse)
         return loss_row if by_rows else out.reshape(())
@@ -645,6 +744,15 @@ class linear_cross_entropy(_Operator):
             if g.dtype != np.float32 or g.shape[0] != n:
                 raise TypeError(f"linear_cross_entropy(reduction='none'): the upstream gradient must be ({n},) float32, "
                                 f"got {g.shape} {g.dtype}")
+        smooth = self.smooth
+        if smooth:
+            # the row coefficients; from here on the node is the reduction='none' node under the upstream vector u'
+            up, cn = hp.empty((n,), np.float32), hp.empty((n,), np.float32)
+            en = hp.empty((n,), np.float32)
+            L.call("pdnz_row_coefficients_f32", lse._ptr, self._t_safe._ptr, g._ptr if by_rows else None,
+                   None if by_rows else g._ptr, None if by_rows else self._stats._ptr, self.label_smoothing, self.z_loss, n, V,
+                   up._ptr, cn._ptr, en._ptr, hp.stream())
+            g, by_rows = up, True
         grads = [None] * len(self.last)
         dx = ex = None
         dxu, self._dxu = self._dxu, None
@@ -689,6 +797,16 @@ class linear_cross_entropy(_Operator):
                    dw._ptr if dw is not None else None, dw_beta, db._ptr if db is not None else None, db_beta,
                    xs._ptr if xs is not None else None, s_dev._ptr if s_dev is not None else None, n, V, fin,
                    ws if wsb else None, wsb, ws if cneed else None, cneed, hp.stream())
+            if smooth:
+                # the target-column and the uniform term, added to what the call above left (dw_beta / db_beta are in it)
+                dxc = dxd if dxd is not None else dx
+                zneed = L.query("pdnz_linear_ce_corrections_workspace_bytes", n, V, fin) if self._wsum is not None else 0
+                zws, zwsb = hp.workspace(zneed) if zneed else (None, 0)
+                L.call("pdnz_linear_ce_corrections_f32", x2._ptr, x2._strides[0], _contig(w.data)._ptr,
+                       self._wsum._ptr if self._wsum is not None else None, self._t_safe._ptr, cn._ptr,
+                       en._ptr if self._wsum is not None else None, dxc._ptr if dxc is not None else None,
+                       dw._ptr if dw is not None else None, db._ptr if db is not None else None, n, V, fin, zws, zwsb,
+                       hp.stream())
             return grads
         need = L.query("pdn_linear_ce_workspace_bytes", n, V, fin) if (dw is not None or db is not None) else 0
         ws, wsb = hp.workspace(need) if need else (None, 0)

@@ -73,7 +73,8 @@ enum {
   PDN_CNT_ATT_SEG = 43,           // document-masked resident attention (the SEG kernels of csrc/attention.hip, include/pdn_segattn.h),
                                   // either direction: also counts in 9 / 10
   PDN_CNT_ROW_LOSS = 44,          // cross entropy with reduction='none' (csrc/row_loss.hip, include/pdn_rowloss.h): once per pdnr_* entry
-  PDN_CNT_SLOTS = 45
+  PDN_CNT_SMOOTH_LOSS = 45,       // cross entropy with label_smoothing / z_loss (csrc/smooth_loss.hip, include/pdn_smoothloss.h): once per pdnz_* entry
+  PDN_CNT_SLOTS = 46
 };
 void pdn_count(int slot);
 

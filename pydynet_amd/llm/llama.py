@@ -266,16 +266,31 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
             trainable, frozen = trainable + p.requires_grad, frozen + (not p.requires_grad)
         return trainable, frozen
 
-    def loss(self, input_ids, target_ids, criterion=None, start_pos: int = 0, ignore_index=None, segment_ids=None):
+    @staticmethod
+    def _smoothing(criterion, label_smoothing, z_loss):
+        """(label_smoothing, z_loss) from the keywords, or from a criterion that carries them -- not from both"""
+        if criterion is not None and (label_smoothing != 0.0 or z_loss != 0.0):
+            raise ValueError("pass label_smoothing / z_loss through the criterion (nn.CrossEntropyLoss(label_smoothing=..., "
+                             "z_loss=...)), not beside it")
+        if criterion is not None:
+            label_smoothing, z_loss = getattr(criterion, "label_smoothing", 0.0), getattr(criterion, "z_loss", 0.0)
+        return fused.smooth_loss.check_arguments(label_smoothing, z_loss) if (label_smoothing != 0.0 or z_loss != 0.0) else (0.0, 0.0)
+
+    def loss(self, input_ids, target_ids, criterion=None, start_pos: int = 0, ignore_index=None, segment_ids=None, *,
+             label_smoothing=0.0, z_loss=0.0):
         """Cross entropy of the next-token logits.  `segment_ids` ((B, L) integers, non-decreasing along a row; a NumPy
         array, or an int32 device array a captured step re-reads at every replay): the documents of packed rows -- every
         attention looks inside the query's document only (core/fused/segments.py; llm/packing.py builds such rows and
         their targets).  Training mode and start_pos 0 only.  `criterion.ignore_index` (nn.CrossEntropyLoss), or the `ignore_index`
         keyword when no criterion is given: targets equal to it -- a prompt region, right padding -- add nothing to the loss
         or the gradients and the mean runs over the remaining tokens (core/fused/masked_loss.py; 0, not NaN, when none
-        remains).  Under data parallel each rank divides by its own count."""
+        remains).  Under data parallel each rank divides by its own count.
+        `label_smoothing` (in [0, 1]) and `z_loss` (>= 0; adds z_loss * logsumexp^2 per token, which keeps the lm_head's
+        normaliser near 1), keywords or carried by the criterion likewise: core/fused/smooth_loss.py; with `ignore_index` both
+        terms are averaged over the same remaining tokens.  Both 0: the step of before."""
         if criterion is not None and ignore_index is not None:
             raise ValueError("pass ignore_index through the criterion (nn.CrossEntropyLoss(ignore_index=...)), not beside it")
+        eps, lam = self._smoothing(criterion, label_smoothing, z_loss)
         if criterion is not None:
             ignore_index = getattr(criterion, "ignore_index", None)
         h = self._forward_hidden(input_ids, start_pos) if segment_ids is None else \
@@ -290,21 +305,28 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         if ((criterion is None or type(criterion) is nn.CrossEntropyLoss) and type(head) is nn.Linear
                 and fused.linear_cross_entropy.applicable(h, head.weight, bias, targets, reduction, ignore_index)):
             # lm_head + cross entropy as one node: the (tokens, vocab) gradient of the logits is never written
+            if eps != 0.0 or lam != 0.0:
+                return fused.linear_cross_entropy(h, head.weight, bias, targets, reduction, ignore_index, eps, lam)
             if ignore_index is None:
                 return fused.linear_cross_entropy(h, head.weight, bias, targets, reduction)
             return fused.linear_cross_entropy(h, head.weight, bias, targets, reduction, ignore_index)
         logits = head(h)
         B, L, V = logits.shape
+        if criterion is None and (eps != 0.0 or lam != 0.0):
+            criterion = nn.CrossEntropyLoss(ignore_index=ignore_index, label_smoothing=eps, z_loss=lam)
         if criterion is None:
             criterion = nn.CrossEntropyLoss() if ignore_index is None else nn.CrossEntropyLoss(ignore_index=ignore_index)
         return criterion(logits.reshape(B * L, V), targets)
 
-    def token_losses(self, input_ids, target_ids, start_pos: int = 0, ignore_index=None, segment_ids=None):
+    def token_losses(self, input_ids, target_ids, start_pos: int = 0, ignore_index=None, segment_ids=None, *,
+                     label_smoothing=0.0, z_loss=0.0):
         """The cross entropy of every next-token prediction, a (B, L) tensor on the tape, 0 at tokens whose target equals
         `ignore_index`; nothing is counted or divided (core/fused/row_loss.py).  What follows plain SFT is built from it
         with plain operators -- `(token_losses * w).sum() / w.sum()` for per-token or per-document weights, a sum per row
         for sequence log-probabilities -- and still ends in the one lm_head + loss node, whose backward then takes a
-        different upstream gradient per token.  `segment_ids`: as in `loss`."""
+        different upstream gradient per token.  `segment_ids`, `label_smoothing`, `z_loss`: as in `loss` (the smoothed rows
+        are no log-probabilities: `sequence_logprobs` and `preference_step` do not take them)."""
+        eps, lam = self._smoothing(None, label_smoothing, z_loss)
         h = self._forward_hidden(input_ids, start_pos) if segment_ids is None else \
             self._forward_hidden(input_ids, start_pos, segment_ids=segment_ids)
         B, L = h.shape[0], h.shape[1]
@@ -315,10 +337,15 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         head = self.lm_head
         bias = getattr(head, "bias", None)
         if type(head) is nn.Linear and fused.linear_cross_entropy.applicable(h, head.weight, bias, targets, "none", ignore_index):
-            rows = fused.linear_cross_entropy(h, head.weight, bias, targets, "none", ignore_index)
+            if eps != 0.0 or lam != 0.0:
+                rows = fused.linear_cross_entropy(h, head.weight, bias, targets, "none", ignore_index, eps, lam)
+            else:
+                rows = fused.linear_cross_entropy(h, head.weight, bias, targets, "none", ignore_index)
         else:
             logits = head(h)
-            rows = nn.CrossEntropyLoss("none", ignore_index)(logits.reshape(B * L, logits.shape[-1]), targets)
+            crit = nn.CrossEntropyLoss("none", ignore_index, eps, lam) if (eps != 0.0 or lam != 0.0) else \
+                nn.CrossEntropyLoss("none", ignore_index)
+            rows = crit(logits.reshape(B * L, logits.shape[-1]), targets)
         return rows.reshape(B, L)
 
     def sequence_logprobs(self, input_ids, target_ids, start_pos: int = 0, ignore_index=None, segment_ids=None):
@@ -345,12 +372,16 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         return loss.item()
 
     def finetune_step(self, input_ids, target_ids, optimizer, criterion=None, start_pos: int = 0, ignore_index=None,
-                      segment_ids=None):
+                      segment_ids=None, *, label_smoothing=0.0, z_loss=0.0):
         """zero_grad -> forward -> cross entropy -> backward -> optimizer step; returns the loss.  `ignore_index`,
-        `segment_ids`: see `loss`."""
+        `segment_ids`, `label_smoothing`, `z_loss`: see `loss`."""
         self.train(True)
         optimizer.zero_grad()
-        if segment_ids is None:
+        if label_smoothing != 0.0 or z_loss != 0.0:
+            kw = {} if segment_ids is None else {"segment_ids": segment_ids}
+            loss = self.loss(input_ids, target_ids, criterion, start_pos, ignore_index, label_smoothing=label_smoothing,
+                             z_loss=z_loss, **kw)
+        elif segment_ids is None:
             loss = self.loss(input_ids, target_ids, criterion, start_pos, ignore_index)
         else:
             loss = self.loss(input_ids, target_ids, criterion, start_pos, ignore_index, segment_ids=segment_ids)

@@ -155,14 +155,43 @@ def nll_loss(y_pred, y_true, reduction='mean'):
     return _reduce(-y_pred * y_true, reduction)
 
 
-def cross_entropy_loss(y_pred, y_true, reduction='mean', ignore_index=None):
+def _smooth_cross_entropy(y_pred, y_true, reduction, ignore_index, eps, lam):
+    """float64 (any non-float32) predictions: core/fused/smooth_loss.py's row formula from plain operators"""
+    n, V = y_pred.shape
+    m = y_pred.max().item()
+    lse = (tensor.log(tensor.sum(tensor.exp(y_pred - m), 1, keepdims=True)) + m).reshape(n)
+    t = np.asarray(y_true.numpy() if isinstance(y_true, tensor.Tensor) else y_true).reshape(-1)
+    fused.row_loss.check_targets(t, ignore_index, V)
+    keep = np.ones(t.shape, bool) if ignore_index is None else t != int(ignore_index)
+    rows = lse - y_pred[range(n), np.where(keep, t, 0)] * (1.0 - eps) - tensor.sum(y_pred, 1) * (eps / V) + lse * lse * lam
+    if not keep.all():
+        rows = rows * tensor.Tensor(keep.astype(y_pred.dtype), dtype=y_pred.dtype, device=y_pred.device)
+    if reduction == 'none':
+        return rows
+    count = int(keep.sum())
+    return tensor.sum(rows) * ((1.0 / count if count else 0.0) if reduction == 'mean' else 1.0)
+
+
+def cross_entropy_loss(y_pred, y_true, reduction='mean', ignore_index=None, label_smoothing=0.0, z_loss=0.0):
     """`ignore_index` (an extension; None: off): rows whose class-index target equals it add nothing to the loss or to any
     gradient, and 'mean' divides by the number of remaining rows -- 0, not torch's NaN, when none remains (the contract and
     the reason are in core/fused/masked_loss.py).  Under data parallel each rank divides by its own count.
     reduction 'none' (an extension; class-index targets only): the (rows,) vector of row losses, 0 at ignored rows, on
-    the tape -- its backward takes one upstream number per row (core/fused/row_loss.py).  No count and no factor."""
+    the tape -- its backward takes one upstream number per row (core/fused/row_loss.py).  No count and no factor.
+    `label_smoothing` eps in [0, 1] and `z_loss` lam >= 0 (extensions; class-index targets only; both 0: off): each row
+    becomes lse - (1 - eps) z[t] - eps mean(z) + lam lse^2 (core/fused/smooth_loss.py).  Under 'mean' with `ignore_index` the
+    z-loss and the smoothing term are averaged over the same remaining rows as the cross entropy itself."""
     if reduction not in ('mean', 'sum', 'none'):
         raise ValueError("reduction must be mean, sum or none.")
+    if label_smoothing != 0.0 or z_loss != 0.0:
+        eps, lam = fused.smooth_loss.check_arguments(label_smoothing, z_loss)
+        if y_true.ndim != 1 or y_pred.ndim != 2:
+            raise ValueError("label_smoothing / z_loss need class-index targets (rows,) and (rows, classes) predictions, "
+                             "not one-hot or soft targets")
+        if y_pred.dtype != np.float32:
+            return _smooth_cross_entropy(y_pred, y_true, reduction, ignore_index, eps, lam)
+        r = fused.chain.on_cross_entropy(y_pred, y_true, reduction, ignore_index, eps, lam)
+        return r if r is not None else fused.cross_entropy(y_pred, y_true, reduction, ignore_index, eps, lam)
     if reduction == 'none':
         if y_true.ndim != 1 or y_pred.ndim != 2:
             raise ValueError("reduction 'none' needs class-index targets (rows,) and (rows, classes) predictions, "
