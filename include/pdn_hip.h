@@ -220,7 +220,10 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  43 document-masked resident attention (the SEG kernels of csrc/attention.hip): pdns_attention_fwd_f32 and
  *     pdns_attention_bwd_f32 of include/pdn_segattn.h, either direction; also counts in 9 / 10 (it IS a resident launch)
  *  44 cross entropy with reduction='none' (csrc/row_loss.hip): once per pdnr_* entry of include/pdn_rowloss.h
- *  45 cross entropy with label_smoothing / z_loss (csrc/smooth_loss.hip): once per pdnz_* entry of include/pdn_smoothloss.h */
+ *  45 cross entropy with label_smoothing / z_loss (csrc/smooth_loss.hip): once per pdnz_* entry of include/pdn_smoothloss.h
+ *  46 output-resident products on split-fp16 MFMA (csrc/outres_split.hip): no entry of its own, the form
+ *     pdn_gemm_outres_f32, pdn_gemm_outres_ws_f32 and pdn_gemm_outres_blocks_nt_f32 take at 65536 rows and more (see
+ *     there); also counts in 14 (it IS the output-resident launch of the product) */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -250,7 +253,9 @@ int pdn_gemm_rowtile_mode(int mode);
  * stays on the fp32 MFMA kernels.  xn and rms are left exactly as the fp32 form leaves them (to fp32 round-off). */
 /* dX (M x 288) = [d_1 | ... | d_nb] (M x nb * kb) [W_1 | ... | W_nb]^T (+ residual): the input gradient of projections
  * that share their input, the weights W_i (288 x kb, row-major, `b_block_stride` floats apart) read where they live
- * (csrc/gemm_outres.hip; `grad @ W^T` of tensor.py:670, one contraction over all projections) */
+ * (csrc/gemm_outres.hip; `grad @ W^T` of tensor.py:670, one contraction over all projections).
+ * At 65536 rows and more the product runs on split-fp16 MFMA at fp32 accuracy (csrc/outres_split.hip, counter slot 46 and
+ * 14 as before) under the conditions listed at pdn_gemm_outres_f32; `b_block_stride` a multiple of 4 is one of them. */
 int pdn_gemm_outres_blocks_supported(int M, int kb, int nb);
 int pdn_gemm_outres_blocks_nt_f32(const float* A, const float* W, int64_t b_block_stride, int kb, int nb, float* C,
                                   const float* residual, int M, int64_t lda, int64_t ldc, void* stream);
@@ -345,7 +350,17 @@ int pdn_gemm_f64(int M, int N, int K, double alpha, const double* A, int64_t a_r
  * residual, K a multiple of 32, A rows contiguous; B (K x 288) row-major or, with `b_trans`, the (288 x K)
  * row-major matrix whose transpose is meant.  A wave keeps 32 x 288 outputs in accumulators, A is read once
  * straight into MFMA operand registers, B streams through LDS (csrc/gemm_outres.hip).  pdn_gemm_f32 routes the
- * shapes it pays for here by itself; the entry point is exported for tests. */
+ * shapes it pays for here by itself; the entry point is exported for tests.
+ * The 65536-row split form (csrc/outres_split.hip, counter slot 46, and 14 as before): the product runs on split-fp16 MFMA
+ * at fp32 accuracy -- B as two fp16 planes with one power of two per output column (two small passes per call), A split in
+ * registers with a running power of two per ROW, three f16 products, the scale removed by one ldexp before bias and
+ * residual are added in fp32 -- when M >= 65536, K is a multiple of 32 in [256, 4096], no K split is planned, lda, ldb, ldc
+ * (and the block stride) are multiples of 4, A, B, C, bias and residual are 16-byte aligned, the stream is not being
+ * captured (the plane images of B, (K / 32) x 36864 bytes, with K / 32 x 1152 + 1152 bytes of column maxima and exponents,
+ * come from pdn_malloc and are rebuilt on every call) and PDN_OUTRES_SPLIT is not 0 (environment, read on EVERY call,
+ * announced on stderr the first time it is seen at 0; PDN_OUTRES_SPLIT_ABLATE = 1 / 2 / 3 and PDN_OUTRES_SPLIT_WGS are
+ * timing experiments, the former with WRONG results, announced too).  Everything else stays on the fp32 MFMA kernel and
+ * keeps its bits; the split form agrees with it to fp32 round-off. */
 int pdn_gemm_outres_supported(int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans);
 int pdn_gemm_outres_f32(const float* A, const float* B, float* C, const float* bias, const float* residual,
                         int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans, void* stream);

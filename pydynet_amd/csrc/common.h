@@ -38,7 +38,7 @@ enum {
                                   // split-fp16 kernel of csrc/lm_head_dx_split.hip (which counts in 39 as well)
   PDN_CNT_CE_DW = 13,             // gemm_outres_tn_kernel with the cross-entropy gradient formed inside, or the split-fp16
                                   // kernel of csrc/lm_head_dw_split.hip (which counts in 40 as well)
-  PDN_CNT_OUTRES = 14,            // gemm_outres_kernel, plain
+  PDN_CNT_OUTRES = 14,            // gemm_outres_kernel, plain, or the split-fp16 kernel of csrc/outres_split.hip (which counts in 46 as well)
   PDN_CNT_OUTRES_TN = 15,         // gemm_outres_tn_kernel, plain, or the split-fp16 kernel of csrc/outres_tn_split.hip
                                   // for the packed layer weight gradients (which counts in 42 as well)
   PDN_CNT_LINEAR_RELU_FWD = 16,   // tiled kernel with the relu + bit-mask store (pdn_linear_relu_fwd_f32)
@@ -74,7 +74,9 @@ enum {
                                   // either direction: also counts in 9 / 10
   PDN_CNT_ROW_LOSS = 44,          // cross entropy with reduction='none' (csrc/row_loss.hip, include/pdn_rowloss.h): once per pdnr_* entry
   PDN_CNT_SMOOTH_LOSS = 45,       // cross entropy with label_smoothing / z_loss (csrc/smooth_loss.hip, include/pdn_smoothloss.h): once per pdnz_* entry
-  PDN_CNT_SLOTS = 46
+  PDN_CNT_OUTRES_SPLIT = 46,      // layer input gradients / down projection (M x 288 = A B + bias + residual, 65536 rows and more) on
+                                  // split-fp16 MFMA (csrc/outres_split.hip): also counts in 14
+  PDN_CNT_SLOTS = 47
 };
 void pdn_count(int slot);
 

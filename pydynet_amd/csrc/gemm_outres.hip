@@ -503,6 +503,13 @@ extern "C" int pdn_gemm_outres_blocks_nt_f32(const float* A, const float* W, int
   return rc;
 }
 
+// csrc/outres_split.hip: the same product on split-fp16 MFMA (65536 rows and more, K in [256, 4096], no K split)
+int pdn_outres_split_takes(const float* A, const float* B, const float* C, const float* bias, const float* residual, int M,
+                           int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, int splits,
+                           void* stream);
+int pdn_outres_split_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int K,
+                            int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, void* stream);
+
 static int outres_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int N,
                          int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans, void* workspace,
                          int64_t workspace_bytes, void* stream, int kb, int64_t b_bstride) {
@@ -531,6 +538,12 @@ static int outres_launch(const float* A, const float* B, float* C, const float* 
     plan_nw = outres_unsplit_nw(M);
   }
   if (splits > 1) { p.kps = kps; p.slab = (float*)workspace; }
+  // many rows, a moderate K: three fp16 products at fp32 accuracy (csrc/outres_split.hip)
+  if (pdn_outres_split_takes(A, B, C, bias, residual, M, K, lda, ldb, ldc, b_trans, kb, b_bstride, splits, stream)) {
+    const int rc = pdn_outres_split_launch(A, B, C, bias, residual, M, K, lda, ldb, ldc, b_trans, kb, b_bstride, stream);
+    if (rc == PDN_OK) pdn_count(PDN_CNT_OUTRES);      // slot 14: "the output-resident product", whichever pipe ran it
+    return rc;
+  }
   static const int nw_env = getenv("PDN_OUTRES_NW") ? atoi(getenv("PDN_OUTRES_NW")) : 0;
   static const int stage_env = getenv("PDN_OUTRES_STAGE") ? atoi(getenv("PDN_OUTRES_STAGE")) : -1;
   static const int ablate = pdn_ablation_switch("PDN_OUTRES_ABLATE");
