@@ -223,7 +223,11 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  45 cross entropy with label_smoothing / z_loss (csrc/smooth_loss.hip): once per pdnz_* entry of include/pdn_smoothloss.h
  *  46 output-resident products on split-fp16 MFMA (csrc/outres_split.hip): no entry of its own, the form
  *     pdn_gemm_outres_f32, pdn_gemm_outres_ws_f32 and pdn_gemm_outres_blocks_nt_f32 take at 65536 rows and more (see
- *     there); also counts in 14 (it IS the output-resident launch of the product) */
+ *     there); also counts in 14 (it IS the output-resident launch of the product)
+ *  47 the 288 x 288 products of pdn_gemm_f32 (N = K = 288, NN or NT, bias and residual allowed, 65536 rows and more) on the
+ *     same split-fp16 output-resident kernel instead of the fp32 tile-piece kernel (slot 1): counts here ONLY, not in 1, 14
+ *     or 46.  Not taken under PDN_OUTRES_SPLIT=0, pdn_gemm_rowtile_mode(3), PDN_GEMM_NO_OUTRES / PDN_GEMM_NO_ROWRES, on a
+ *     stream that is being captured, or when A, B or the residual overlap C (a residual that IS C is taken) */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores

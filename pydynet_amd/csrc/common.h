@@ -76,7 +76,10 @@ enum {
   PDN_CNT_SMOOTH_LOSS = 45,       // cross entropy with label_smoothing / z_loss (csrc/smooth_loss.hip, include/pdn_smoothloss.h): once per pdnz_* entry
   PDN_CNT_OUTRES_SPLIT = 46,      // layer input gradients / down projection (M x 288 = A B + bias + residual, 65536 rows and more) on
                                   // split-fp16 MFMA (csrc/outres_split.hip): also counts in 14
-  PDN_CNT_SLOTS = 47
+  PDN_CNT_PROJ288_SPLIT = 47,    // the 288 x 288 products of pdn_gemm_f32 (M x 288 = A (M x 288) W (+ bias) (+ residual), NN or NT,
+                                  // 65536 rows and more) sent to the split-fp16 output-resident kernel (csrc/outres_split.hip)
+                                  // instead of the fp32 tile-piece kernel: counts HERE ONLY, not in 1, 14 or 46
+  PDN_CNT_SLOTS = 48
 };
 void pdn_count(int slot);
 

@@ -197,6 +197,14 @@ extern "C" int pdn_gemm_outres_f32(const float* A, const float* B, float* C, con
                                    int64_t ldc, int b_trans, void* stream);
 extern "C" int pdn_gemm_rowres_supported(int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans);
 int pdn_rowtile_plain_ok(int M, int N, int b_trans);
+extern "C" int pdn_gemm_rowtile_mode(int mode);                 // csrc/gemm_rowtile.hip; a negative mode only asks
+// csrc/outres_split.hip: the output-resident product on split-fp16 MFMA, here for the 288 x 288 products (slot 47)
+int pdn_outres_split_takes(const float* A, const float* B, const float* C, const float* bias, const float* residual, int M,
+                           int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, int splits,
+                           void* stream);
+int pdn_outres_split_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int K,
+                            int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, void* stream,
+                            int count_slot);
 extern "C" int pdn_gemm_rowres_f32(const float* A, const float* B, float* C, const float* bias,
                                    const float* residual, int M, int N, int K, int64_t lda, int64_t ldb,
                                    int64_t ldc, int b_trans, void* stream);
@@ -353,6 +361,31 @@ static int gemm_f32_impl(int M, int N, int K, float alpha, const float* A, int64
         g_prof.push_back(rec);
       }
       return PDN_OK;
+    }
+  }
+  // ---- tall A against a 288 x 288 weight (the attention output projection ctx Wo + x and its input gradient dz Wo^T), 65536
+  // rows and more: the same output-resident kernel on split-fp16 MFMA (csrc/outres_split.hip, nine pieces) in place of the
+  // fp32 tile-piece kernel, for exactly the calls that kernel would take.  At 131072 rows 214 (NN, residual) / 202 us (NT)
+  // on the fp32 pipe against 140 / 104 us here.  Kept away by PDN_OUTRES_SPLIT=0 (read on every call), pdn_gemm_rowtile_mode 3
+  // (the in-process A/B switch of the row-resident family), PDN_GEMM_NO_OUTRES / PDN_GEMM_NO_ROWRES, a captured stream, and
+  // operands that overlap C (a residual that IS C is fine: a lane reads its 16 bytes before it writes them).
+  if (nbatch == 1 && !ext_on && N == 288 && K == 288 && a_cs == 1 && alpha == 1.f && beta == 0.f && !b_colsum &&
+      !getenv("PDN_GEMM_NO_OUTRES") && !getenv("PDN_GEMM_NO_ROWRES") && pdn_gemm_rowtile_mode(-1) != 3) {
+    const int bt = (b_rs == 1 && b_cs != 1) ? 1 : 0;
+    const int64_t ldb = bt ? b_cs : b_rs;
+    auto overlaps_c = [&](const float* q, int64_t floats) {
+      return q && q < (const float*)C + (int64_t)M * ldc && (const float*)C < q + floats;
+    };
+    if ((bt || b_cs == 1) && pdn_rowtile_plain_ok(M, N, bt) && pdn_gemm_rowres_supported(M, N, K, a_rs, ldb, ldc, bt) &&
+        !overlaps_c(A, (int64_t)M * a_rs) && !overlaps_c(B, (int64_t)288 * ldb) &&
+        (residual == C || !overlaps_c(residual, (int64_t)M * ldc)) &&
+        pdn_outres_split_takes(A, B, C, bias, residual, M, K, a_rs, ldb, ldc, bt, 0, 0, 1, stream)) {
+      if (getenv("PDN_GEMM_DEBUG"))
+        fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> output-resident, split fp16 (%s)\n", M, N, K, bt ? "NT" : "NN");
+      const int tk = pdn_gemm_prof_begin(3, 2.0 * M * (double)N * (double)K, 0.0, stream);
+      const int rc = pdn_outres_split_launch(A, B, C, bias, residual, M, K, a_rs, ldb, ldc, bt, 0, 0, stream, PDN_CNT_PROJ288_SPLIT);
+      pdn_gemm_prof_end(tk, stream);
+      return rc;
     }
   }
   // A batch whose members share A and write side by side into one packed buffer (x against Wq | Wk | Wv,

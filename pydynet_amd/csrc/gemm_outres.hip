@@ -508,7 +508,8 @@ int pdn_outres_split_takes(const float* A, const float* B, const float* C, const
                            int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, int splits,
                            void* stream);
 int pdn_outres_split_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int K,
-                            int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, void* stream);
+                            int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, void* stream,
+                            int count_slot);
 
 static int outres_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int N,
                          int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans, void* workspace,
@@ -540,7 +541,8 @@ static int outres_launch(const float* A, const float* B, float* C, const float* 
   if (splits > 1) { p.kps = kps; p.slab = (float*)workspace; }
   // many rows, a moderate K: three fp16 products at fp32 accuracy (csrc/outres_split.hip)
   if (pdn_outres_split_takes(A, B, C, bias, residual, M, K, lda, ldb, ldc, b_trans, kb, b_bstride, splits, stream)) {
-    const int rc = pdn_outres_split_launch(A, B, C, bias, residual, M, K, lda, ldb, ldc, b_trans, kb, b_bstride, stream);
+    const int rc = pdn_outres_split_launch(A, B, C, bias, residual, M, K, lda, ldb, ldc, b_trans, kb, b_bstride, stream,
+                                           PDN_CNT_OUTRES_SPLIT);
     if (rc == PDN_OK) pdn_count(PDN_CNT_OUTRES);      // slot 14: "the output-resident product", whichever pipe ran it
     return rc;
   }

@@ -5,7 +5,7 @@
 // for the many-row calls of a training step that csrc/gemm_outres.hip ran on the fp32 pipe: the layer input gradients
 // dX = [dq | dk | dv] [Wq | Wk | Wv]^T and [dgate | dup] [Wg | Wu]^T (NT, the weights read as blocks where they live) and
 // the down projection h W_down + residual (NN).  outres_launch routes here (pdn_outres_split_takes); there is no entry of
-// its own.  The product is formed from fp16 operands like the lm_head input gradient (csrc/lm_head_dx_split.hip), whose
+// its own.  pdn_gemm_f32 sends the 288 x 288 products here as well (K = 288, nine pieces: ctx Wo + x and dz Wo^T, csrc/gemm.hip).  The product is formed from fp16 operands like the lm_head input gradient (csrc/lm_head_dx_split.hip), whose
 // main kernel this is without the exponential, Z, the targets and W^T:
 //
 //   B[:, d] 2^s(d) = wh + wl / 2048            one pass per call, one power of two per OUTPUT COLUMN d
@@ -88,13 +88,16 @@ __global__ __launch_bounds__(256) void ors_w_max_kernel(OrsWParams p) {
   }
 }
 
-// ---- W: the plane images, one workgroup per piece -------------------------------------------------------------------------
+// ---- W: the plane images, ORS_IMG_WGS workgroups per piece -------------------------------------------------------------------------
 template <bool NN>
 __global__ __launch_bounds__(256) void ors_w_img_kernel(OrsWParams p) {
   __shared__ float tile[NN ? ORS_KP * ORS_NN_LD : 1];
   if (NN) ors_w_stage_nn(p, tile);
   char* img = p.wimg + (int64_t)blockIdx.x * ORS_PIECE;
-  for (int i = threadIdx.x; i < ORS_N * 4; i += 256) {
+  // ONE unit per thread, the 1152 units of a piece over ORS_IMG_WGS workgroups (grid.y): with np workgroups of 4.5 units per
+  // thread the pass was a chain of five memory round trips on a tenth of the chip (NN: every workgroup stages the whole tile)
+  const int i = blockIdx.y * 256 + threadIdx.x;
+  if (i < ORS_N * 4) {
     const int d = i >> 2, q = i & 3;
     float amax = 0.f;
     for (int s = 0; s < p.np; ++s) amax = fmaxf(amax, p.pmax[(int64_t)s * ORS_N + d]);
@@ -164,6 +167,12 @@ __global__ __launch_bounds__(512, 1) void ors_main_kernel(OrsParams p) {
   const int np = p.np, nblk = p.nblk, grid = gridDim.x;
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
   constexpr bool STREAM = ABLATE == 0 || ABLATE == 3;
+  // for the drain: the 288 column exponents and the bias (-0 where there is none: x + -0 is x bit for bit, -0 included).
+  // Written here, read behind at least eight barriers.
+  __shared__ __attribute__((aligned(16))) int col_sh[ORS_N];
+  __shared__ __attribute__((aligned(16))) float col_bias[ORS_N];
+  if (tid < ORS_N) { col_sh[tid] = p.wsh[tid]; col_bias[tid] = p.bias ? p.bias[tid] : -0.f; }
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
   // W: the image of piece `piece` into slot `slot`, five instructions per wave
   const char* wsrc = p.wimg + lane * 16;
@@ -307,22 +316,45 @@ __global__ __launch_bounds__(512, 1) void ors_main_kernel(OrsParams p) {
 
     // ---- the block's rows: the lane's row, columns 16 j + 4 q .. + 3 of tile j -------------------------------------------
     const int64_t row = (int64_t)blk * ORS_WG_ROWS + wave * 16 + r;
+    // The exponents and the bias come out of LDS (col_sh / col_bias), so the only memory operations of the drain are the
+    // residual loads and the stores, and no load sits between two stores: a wait for a load would also wait for every store
+    // issued before it (both count in vmcnt, in order), which made each of the 18 tiles two or three memory round trips.
+    // The residual is requested ORS_DRAIN tiles at a time, one group ahead of the group being stored.
     if ((ABLATE != 3 || p.M < 0) && row < p.M) {
       float* out = p.C + row * p.ldc + 4 * q;
-      const float* res = p.residual ? p.residual + row * p.ldc + 4 * q : nullptr;
-      const float* bia = p.bias ? p.bias + 4 * q : nullptr;
-      const int* __restrict__ shp = p.wsh + 4 * q;
-#pragma unroll
-      for (int j = 0; j < ORS_NT; ++j) {
-        const int4 sv = *reinterpret_cast<const int4*>(shp + 16 * j);
+      auto tile_out = [&](int j) __attribute__((always_inline)) {
+        const int4 sv = *reinterpret_cast<const int4*>(__builtin_assume_aligned(col_sh + 16 * j + 4 * q, 16));
+        const float4 b4 = *reinterpret_cast<const float4*>(__builtin_assume_aligned(col_bias + 16 * j + 4 * q, 16));
         float4 o;
-        o.x = stn_unscale(acc1[j][0], acc0[j][0], S + sv.x);
-        o.y = stn_unscale(acc1[j][1], acc0[j][1], S + sv.y);
-        o.z = stn_unscale(acc1[j][2], acc0[j][2], S + sv.z);
-        o.w = stn_unscale(acc1[j][3], acc0[j][3], S + sv.w);
-        if (bia) { const float4 b4 = *reinterpret_cast<const float4*>(bia + 16 * j); o.x += b4.x; o.y += b4.y; o.z += b4.z; o.w += b4.w; }
-        if (res) { const float4 r4 = *reinterpret_cast<const float4*>(res + 16 * j); o.x += r4.x; o.y += r4.y; o.z += r4.z; o.w += r4.w; }
-        *reinterpret_cast<float4*>(out + 16 * j) = o;
+        o.x = stn_unscale(acc1[j][0], acc0[j][0], S + sv.x) + b4.x;
+        o.y = stn_unscale(acc1[j][1], acc0[j][1], S + sv.y) + b4.y;
+        o.z = stn_unscale(acc1[j][2], acc0[j][2], S + sv.z) + b4.z;
+        o.w = stn_unscale(acc1[j][3], acc0[j][3], S + sv.w) + b4.w;
+        return o;
+      };
+      if (p.residual) {
+        const float* res = p.residual + row * p.ldc + 4 * q;
+        float4 rq[2][ORS_DRAIN];
+#pragma unroll
+        for (int i = 0; i < ORS_DRAIN; ++i) rq[0][i] = *reinterpret_cast<const float4*>(res + 16 * i);
+#pragma unroll
+        for (int g = 0; g < ORS_NT / ORS_DRAIN; ++g) {
+          if (g + 1 < ORS_NT / ORS_DRAIN) {
+#pragma unroll
+            for (int i = 0; i < ORS_DRAIN; ++i) rq[(g + 1) & 1][i] = *reinterpret_cast<const float4*>(res + 16 * ((g + 1) * ORS_DRAIN + i));
+          }
+#pragma unroll
+          for (int i = 0; i < ORS_DRAIN; ++i) {
+            const int j = g * ORS_DRAIN + i;
+            float4 o = tile_out(j);
+            const float4 r4 = rq[g & 1][i];
+            o.x += r4.x; o.y += r4.y; o.z += r4.z; o.w += r4.w;
+            *reinterpret_cast<float4*>(out + 16 * j) = o;
+          }
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < ORS_NT; ++j) *reinterpret_cast<float4*>(out + 16 * j) = tile_out(j);
       }
     }
     // the stores are memory operations like the fetches: the count starts afresh (and behind the last block the repeated
@@ -370,7 +402,7 @@ int pdn_outres_split_takes(const float* A, const float* B, const float* C, const
     static bool s_told = false;
     if (!s_told) {
       s_told = true;
-      fprintf(stderr, "[pdnhip] WARNING: PDN_OUTRES_SPLIT=0 -- the layer input gradients and the down projection stay on the fp32 MFMA kernel\n");
+      fprintf(stderr, "[pdnhip] WARNING: PDN_OUTRES_SPLIT=0 -- the layer input gradients, the down projection and the 288 x 288 products stay on the fp32 MFMA kernels\n");
     }
     return 0;
   }
@@ -381,7 +413,8 @@ int pdn_outres_split_takes(const float* A, const float* B, const float* C, const
 }
 
 int pdn_outres_split_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int K,
-                            int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, void* stream) {
+                            int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, void* stream,
+                            int count_slot) {
   // both read on every call like PDN_OUTRES_SPLIT (tools/outres_split_probe.py alternates them in one process), the
   // ablation announced the first time it is seen
   const char* ea = getenv("PDN_OUTRES_SPLIT_ABLATE");
@@ -409,10 +442,10 @@ int pdn_outres_split_launch(const float* A, const float* B, float* C, const floa
   w.np = np; w.ppb = kb > 0 ? kb / ORS_KP : np; w.ldb = ldb; w.bstride = kb > 0 ? b_bstride : 0;
   if (b_trans) {
     hipLaunchKernelGGL(ors_w_max_kernel<false>, dim3(np), dim3(256), 0, st, w);
-    hipLaunchKernelGGL(ors_w_img_kernel<false>, dim3(np), dim3(256), 0, st, w);
+    hipLaunchKernelGGL(ors_w_img_kernel<false>, dim3(np, ORS_IMG_WGS), dim3(256), 0, st, w);
   } else {
     hipLaunchKernelGGL(ors_w_max_kernel<true>, dim3(np), dim3(256), 0, st, w);
-    hipLaunchKernelGGL(ors_w_img_kernel<true>, dim3(np), dim3(256), 0, st, w);
+    hipLaunchKernelGGL(ors_w_img_kernel<true>, dim3(np, ORS_IMG_WGS), dim3(256), 0, st, w);
   }
   OrsParams p;
   memset(&p, 0, sizeof(p));
@@ -424,7 +457,7 @@ int pdn_outres_split_launch(const float* A, const float* B, float* C, const floa
   const dim3 grid((unsigned)wgs);
   if (ablate == 3) hipLaunchKernelGGL(ors_main_kernel<3>, grid, dim3(512), 0, st, p);
   else STN_LAUNCH_ABLATE(ors_main_kernel, ablate, grid, stream, p);
-  pdn_count(PDN_CNT_OUTRES_SPLIT);
+  pdn_count(count_slot);            // 46 behind outres_launch, 47 for the 288 x 288 products of pdn_gemm_f32
   PDN_LAUNCH_CHECK();
   return PDN_OK;
 }

@@ -27,7 +27,9 @@
 #define ORS_RING 4                           // pieces of A per wave in LDS
 #define ORS_WG_ROWS 128
 #define ORS_RING0 (2 * ORS_PIECE)            // two W slots, then eight rings
-#define ORS_LDS (ORS_RING0 + 8 * ORS_RING * ORS_RAW)     // 136 KiB
+#define ORS_LDS (ORS_RING0 + 8 * ORS_RING * ORS_RAW)     // 136 KiB (the kernel adds 2 x 1152 bytes: column exponents and bias)
+#define ORS_IMG_WGS ((ORS_N * 4 + 255) / 256) // workgroups of 256 threads per piece in the image pass: one unit per thread
+#define ORS_DRAIN 6                         // tiles of the residual requested at a time by the drain (18 = 3 groups)
 #define ORS_MAX_WGS 256                      // one workgroup per CU
 #define ORS_MIN_ROWS 65536
 #define ORS_MIN_K 256                        // eight pieces: more than the ring holds, so a fetch is never two blocks ahead

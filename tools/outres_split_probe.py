@@ -5,6 +5,8 @@ two W passes and the persistent product), the split kernel with one workgroup pe
 ones (PDN_OUTRES_SPLIT_WGS=0), and its timing ablations (PDN_OUTRES_SPLIT_ABLATE: 1 = constant planes, A never read --
 MFMA + LDS only; 2 = A fetched once -- no HBM stream in; 3 = nothing stored).  The library reads these switches on every
 call, so all variants alternate in one process, `rounds` times; the table shows the median of each.
+Behind them the 288 x 288 products (K = 288, nine pieces: ctx Wo + x, NN with residual, and dz Wo^T, NT) through hipnp.gemm:
+the fp32 tile-piece kernel (pdn_gemm_rowtile_mode(3)) against the same split kernel and its variants (counter slot 47).
 usage: python tools/outres_split_probe.py [rows=131072] [rounds=5]"""
 import os
 import sys
@@ -65,6 +67,35 @@ def main():
             m = t[len(t) // 2]
             print(f"{M} x {K:4d} {name:18s} {v:40s} {m:8.1f} us (min {t[0]:7.1f}, max {t[-1]:7.1f})  {fl / m / 1e6:6.1f} TFLOP/s"
                   f"  {by / m / 1e6:5.2f} TB/s of A + C + residual", flush=True)
+
+    # ---- the 288 x 288 products through pdn_gemm_f32 (hipnp.gemm): the attention output projection ctx Wo + x (NN,
+    # residual) and its input gradient dz Wo^T (NT).  pdn_gemm_rowtile_mode(3) keeps the fp32 tile-piece kernel
+    # gemm_rowtile_kernel<.., 6 / 0>; the default sends them to the split kernel above (nine pieces). ------------------------
+    K = D
+    a = hp.from_numpy(1e-3 * rng.standard_normal((M, K), dtype=np.float32))
+    res = hp.from_numpy(rng.standard_normal((M, D), dtype=np.float32))
+    c = hp.empty((M, D), np.float32)
+    w = hp.from_numpy(0.05 * rng.standard_normal((K, D), dtype=np.float32))
+    variants = [("fp32 tile-piece kernel (mode 3)", 3, {})] + [(v, 1, env) for v, env in VARIANTS[1:]]
+    for name, fn, nbytes in (("ctx Wo + x (NN)", lambda: hp.gemm(a, w, c, residual=res), 4.0 * M * 3 * D),
+                             ("dz Wo^T (NT)", lambda: hp.gemm(a, w.T, c), 4.0 * M * 2 * D)):
+        us = {v: [] for v, _, _ in variants}
+        for _ in range(rounds):
+            for v, mode, env in variants:
+                for s in SWITCHES:
+                    os.environ.pop(s, None)
+                os.environ.update(env)
+                prev = L.query("pdn_gemm_rowtile_mode", mode)
+                us[v].append(timed(fn))
+                L.query("pdn_gemm_rowtile_mode", prev)
+        for s in SWITCHES:
+            os.environ.pop(s, None)
+        fl = 2.0 * M * D * K
+        for v, _, _ in variants:
+            t = sorted(us[v])
+            m = t[len(t) // 2]
+            print(f"{M} x {K:4d} {name:18s} {v:40s} {m:8.1f} us (min {t[0]:7.1f}, max {t[-1]:7.1f})  {fl / m / 1e6:6.1f} TFLOP/s"
+                  f"  {nbytes / m / 1e6:5.2f} TB/s of A + C (+ residual)", flush=True)
 
 
 if __name__ == "__main__":
