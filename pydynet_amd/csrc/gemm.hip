@@ -694,9 +694,20 @@ static int gemm_f32_impl(int M, int N, int K, float alpha, const float* A, int64
       if (sp >= 1 && (sp == 1 || ((int64_t)sp * M * N * nbatch <= ws_cap && !b_colsum && !ext_on))) best_splits = sp;
     }
   }
-  if (getenv("PDN_GEMM_DEBUG"))
-    fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d nb=%d akin=%d bkin=%d vec=%d -> %s cfg=%d splits=%d\n", M, N, K, nbatch,
-            (int)a_kin, (int)b_kin, (int)vec, use_stream ? "stream" : "tiled", best, best_splits);
+  if (getenv("PDN_GEMM_DEBUG")) {
+    if (use_stream) {
+      // the kernel the launch below picks (same tests, same order), its tile shape and the slabs it writes
+      const bool exact = M % 96 == 0 && N % 96 == 0;
+      const bool staged = vec && (sshape != 0 || !getenv("PDN_GEMM_STREAM_DIRECT"));
+      const char* kind = !staged ? (exact ? "direct" : "direct-edge")
+                         : (sshape != 0 || !exact) ? "lds-edge" : (getenv("PDN_GEMM_STREAM_NODMA") ? "lds" : "dma");
+      fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d nb=%d akin=%d bkin=%d vec=%d -> stream cfg=%d splits=%d sshape=%d kind=%s\n",
+              M, N, K, nbatch, (int)a_kin, (int)b_kin, (int)vec, best, p.splits, sshape, kind);
+    } else {
+      fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d nb=%d akin=%d bkin=%d vec=%d -> tiled cfg=%d splits=%d\n", M, N, K, nbatch,
+              (int)a_kin, (int)b_kin, (int)vec, best, best_splits);
+    }
+  }
   const TileCfg& cfg = kCfgs[best];
   const int BM = cfg.waves_m * cfg.wm * 32, BN = cfg.waves_n * cfg.wn * 32;
   if (!use_stream) {

@@ -24,6 +24,16 @@ class GemmMixin:
                      a1, a2, b1, b2, c1, c2, residual, colsum, colsum_acc, ws, wsb, stream):
         if M == 0 or N == 0 or nb1 == 0 or nb2 == 0:
             return 0
+        if colsum:
+            # csrc/gemm.hip: the fused column sums exist for the x^T @ g layout on the float4 path, unbatched, only
+            a_kin = not (a_rs == 1 and a_cs != 1) or M == 1
+            b_kin = b_rs == 1 and (b_cs != 1 or N == 1)
+            vec = (int(A) % 16 == 0 and int(B) % 16 == 0 and not any(s % 4 for s in (a1, a2, b1, b2, a_cs, b_rs, M, N))
+                   and a_rs == 1 and b_cs == 1)
+            if a_kin or b_kin or not vec or nb1 * nb2 != 1:
+                return -2
+        if nb1 * nb2 > 65535:                        # (the batch is the grid's y extent; the library refuses before any launch)
+            return -1
         a = view(A, (nb1, nb2, M, K), (a1, a2, a_rs, a_cs), np.float32)
         b = view(B, (nb1, nb2, K, N), (b1, b2, b_rs, b_cs), np.float32)
         c = view(C, (nb1, nb2, M, N), (c1, c2, ldc, 1), np.float32)
@@ -33,7 +43,6 @@ class GemmMixin:
         if residual:
             r = r + view(residual, (nb1, nb2, M, N), (c1, c2, ldc, 1), np.float32)
         if colsum:
-            assert nb1 * nb2 == 1 and a_rs == 1 and b_cs == 1, "b_colsum: x^T @ g layout only"
             cs = b[0, 0].sum(0)
             flat(colsum, N)[...] = flat(colsum, N) + cs if colsum_acc else cs
         if beta != 0.0:
