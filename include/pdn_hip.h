@@ -227,7 +227,9 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  47 the 288 x 288 products of pdn_gemm_f32 (N = K = 288, NN or NT, bias and residual allowed, 65536 rows and more) on the
  *     same split-fp16 output-resident kernel instead of the fp32 tile-piece kernel (slot 1): counts here ONLY, not in 1, 14
  *     or 46.  Not taken under PDN_OUTRES_SPLIT=0, pdn_gemm_rowtile_mode(3), PDN_GEMM_NO_OUTRES / PDN_GEMM_NO_ROWRES, on a
- *     stream that is being captured, or when A, B or the residual overlap C (a residual that IS C is taken) */
+ *     stream that is being captured, or when A, B or the residual overlap C (a residual that IS C is taken)
+ *  48 allowed sets, logit_bias and min_new_tokens of a decode step (csrc/logit_edit.hip): once per launch of
+ *     pdne_logit_edit_reset, pdne_logit_edit_step_f32 and pdne_logit_edit_rows_f32 of include/pdn_logitedit.h */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores

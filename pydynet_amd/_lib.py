@@ -29,6 +29,9 @@ ROWLOSS_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "pdn_row
 # cross entropy with label_smoothing / z_loss (prefix pdnz_, include/pdn_smoothloss.h): likewise, held to the rule by
 # tests/test_smoothloss_abi_cpu.py
 SMOOTH_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "pdn_smoothloss.h"),)
+# per-request logit edits of a decode step (prefix pdne_, include/pdn_logitedit.h): likewise, held to the rule by
+# tests/test_logitedit_abi_cpu.py
+EDIT_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "pdn_logitedit.h"),)
 
 _CTYPE = {
     "int": ctypes.c_int,
@@ -44,7 +47,7 @@ def parse_header(path: str = HEADER_PATH):
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     text = re.sub(r"//[^\n]*", "", text)
     protos = {}
-    for m in re.finditer(r"(const\s+char\s*\*|int64_t|int)\s+(pdn[xlsrz]?_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
+    for m in re.finditer(r"(const\s+char\s*\*|int64_t|int)\s+(pdn[xlsrze]?_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
         ret, name, args = m.group(1), m.group(2), m.group(3)
         restype = ctypes.c_char_p if "char" in ret else _CTYPE[ret]
         argtypes = []
@@ -80,7 +83,8 @@ class _Lib:
         # later by another package in the same process resolves to the same libamdhip64.
         self.cdll = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         self.protos = parse_header()
-        for path in EXT_HEADER_PATHS + LOSS_HEADER_PATHS + SEG_HEADER_PATHS + ROWLOSS_HEADER_PATHS + SMOOTH_HEADER_PATHS:
+        for path in (EXT_HEADER_PATHS + LOSS_HEADER_PATHS + SEG_HEADER_PATHS + ROWLOSS_HEADER_PATHS + SMOOTH_HEADER_PATHS
+                     + EDIT_HEADER_PATHS):
             self.protos.update(parse_header(path))
         self.fn = {}
         for name, (restype, argtypes) in self.protos.items():

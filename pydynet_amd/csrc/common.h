@@ -79,7 +79,9 @@ enum {
   PDN_CNT_PROJ288_SPLIT = 47,    // the 288 x 288 products of pdn_gemm_f32 (M x 288 = A (M x 288) W (+ bias) (+ residual), NN or NT,
                                   // 65536 rows and more) sent to the split-fp16 output-resident kernel (csrc/outres_split.hip)
                                   // instead of the fp32 tile-piece kernel: counts HERE ONLY, not in 1, 14 or 46
-  PDN_CNT_SLOTS = 48
+  PDN_CNT_LOGIT_EDIT = 48,        // allowed sets, logit_bias and min_new_tokens of a decode step (csrc/logit_edit.hip,
+                                  // include/pdn_logitedit.h): once per launching pdne_* entry
+  PDN_CNT_SLOTS = 49
 };
 void pdn_count(int slot);
 

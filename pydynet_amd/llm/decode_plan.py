@@ -8,6 +8,7 @@ import os
 
 import numpy as np
 
+from . import logit_edits as edit_np
 from . import logprobs as lp_np
 from . import penalties as pen_np
 from .sampling import params_bytes
@@ -23,6 +24,9 @@ _MIXED_ENTRIES = _WIDE_ENTRIES + ("pdn_decode_mixed_supported", "pdn_kv_append_r
 _SPEC_ENTRIES = _MIXED_ENTRIES + ("pdn_spec_draft_rows", "pdn_spec_verify_pick_tick_f32", "pdn_spec_verify_sample_tick_f32")
 # the entry points of the penalties (csrc/penalty.hip): without them every path applies the statement of llm/penalties.py
 _PEN_ENTRIES = ("pdn_penalty_chunks", "pdn_penalty_reset", "pdn_penalty_step_f32", "pdn_penalty_rows_f32")
+# the entry points of the logit edits (csrc/logit_edit.hip, include/pdn_logitedit.h): without them every path applies the
+# statement of llm/logit_edits.py
+_EDIT_ENTRIES = ("pdne_logit_edit_chunks", "pdne_logit_edit_reset", "pdne_logit_edit_step_f32", "pdne_logit_edit_rows_f32")
 # ring slots of the log-probability records of a decode plan (csrc/logprobs.hip): more than the steps ever in flight
 _LP_RING = 8
 
@@ -45,7 +49,8 @@ class DecodePlan:
         np.bitwise_or.at(mask, stops >> 5, np.uint32(1) << (stops & 31).astype(np.uint32))
         return mask.view(np.int32)
 
-    def _decode_plan(self, B, sampling=False, ragged=False, serve=False, beam=0, n_stops=0, penalty=False, n_lp=None):
+    def _decode_plan(self, B, sampling=False, ragged=False, serve=False, beam=0, n_stops=0, penalty=False, n_lp=None,
+                     edit=False):
         """Buffers and weight views of the graph-replayable decode step (csrc/decode.hip), or None when the
         model's shapes / layout are outside what those kernels take (then the generic launches below run).
         `sampling`: the step ends in the sample tick (csrc/sample.hip) instead of the greedy pick; its parameters live in
@@ -65,7 +70,12 @@ class DecodePlan:
         `cand_v` / `cand_i` then hold the candidates of that kernel.  None when the library lacks the entries.
         `n_lp` (generation with logprobs=n, csrc/logprobs.hip): pdn_logprobs_tick_f32 after the tick reads the logit rows
         (which every plan writes) and the token the tick stored, and writes each row's record into a ring of `_LP_RING`
-        slots of mapped host memory (`lp_box`, reached through the device pointer `lp_ptr`)."""
+        slots of mapped host memory (`lp_box`, reached through the device pointer `lp_ptr`).
+        `edit` (generation with allowed_token_ids / logit_bias / min_new_tokens, csrc/logit_edit.hip): the projection writes
+        full logit rows, and pdne_logit_edit_step_f32 edits them before the tick (after the penalty kernel); the rows'
+        allowed bits, bias tables and prompt lengths live in the plan (`edit_allow`, `edit_allow_on`, `edit_bias_ids`,
+        `edit_bias_val`, `edit_bias_n`, `edit_start`), min_new_tokens in `edit_params`.  A greedy plan's `cand_v` / `cand_i`
+        then hold the candidates of that kernel.  None when the library lacks the entries."""
         from .. import hipnp as hp, _lib
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
         st = getattr(self, "_decode_st", None)
@@ -77,6 +87,7 @@ class DecodePlan:
         key = (B, hp._state["device"], int(type(self).fused_decode or 0), os.environ.get("PDN_DECODE_SPLITS", ""),
                cache_len, tuple(ptrs), bool(sampling), wide,   # (the addresses: no hash to collide)
                (int(beam), int(n_stops), bool(penalty)), bool(ragged), bool(serve)) + (() if n_lp is None else (int(n_lp),))
+        key += ("edit",) if edit else ()
         if st is not None and st["key"] == key:
             return st if st["ok"] else None
         if st is not None:
@@ -88,6 +99,8 @@ class DecodePlan:
             # (the merge of the key-range partials happens in the output projection's load: at most 8 ranges)
             ok = int(os.environ.get("PDN_DECODE_SPLITS", "0") or 0) <= 8
         if penalty and not all(_lib.provides(n) for n in _PEN_ENTRIES):
+            ok = False
+        if edit and not all(_lib.provides(n) for n in _EDIT_ENTRIES):
             ok = False
         packs = []
         if ok:
@@ -102,8 +115,9 @@ class DecodePlan:
                 packs.append((qkv, gu))
             ok = ok and self.lm_head.weight.data.is_contiguous() and self.tok_embedding.weight.data.is_contiguous()
         st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged), "serve": bool(serve),
-              "wide": wide, "rows": bool(ragged or wide), "beam": int(beam), "full": bool(sampling or beam or penalty),
-              "pen": bool(penalty), "lp_n": n_lp}
+              "wide": wide, "rows": bool(ragged or wide), "beam": int(beam),
+              "full": bool(sampling or beam or penalty or edit),
+              "pen": bool(penalty), "lp_n": n_lp, "edit": bool(edit)}
         if ok:
             nblk = _lib.lib().query("pdn_decode_wide_blocks" if wide else "pdn_decode_gemv_blocks", V)
             # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
@@ -167,6 +181,15 @@ class DecodePlan:
                           start=hp.zeros((B,), np.int32), pen_params=hp.zeros((2,), np.int64), pen_val=None, pen_run=None)
                 if not sampling:
                     nc = _lib.lib().query("pdn_penalty_chunks", V)
+                    st.update(cand_v=hp.empty((B, nc), np.float32), cand_i=hp.empty((B, nc), np.int32))
+            if edit:
+                st.update(edit_allow=hp.zeros((B, -(-V // 32)), np.int32), edit_allow_on=hp.zeros((B,), np.int32),
+                          edit_bias_ids=hp.zeros((B, edit_np.MAX_BIAS), np.int32),
+                          edit_bias_val=hp.zeros((B, edit_np.MAX_BIAS), np.float32), edit_bias_n=hp.zeros((B,), np.int32),
+                          edit_start=hp.zeros((B,), np.int32), edit_params=hp.zeros((2,), np.int64), edit_val=None,
+                          edit_run=None)
+                if not sampling:
+                    nc = _lib.lib().query("pdne_logit_edit_chunks", V)
                     st.update(cand_v=hp.empty((B, nc), np.float32), cand_i=hp.empty((B, nc), np.int32))
             if n_lp is not None:
                 st.update(lp_ptr=hp.zeros((1,), np.int64), lp_box=None, lp_work=hp.zeros(
@@ -266,6 +289,7 @@ class DecodePlan:
             L.call("pdn_decode_gemv_sum_f32", xb, D, dparts, J, J * D, None, 0, self.norm.weight.data._ptr, self.norm.eps,
                    head.weight.data._ptr, V, V, 0, bias, logits, V, B, D, V, cv, ci, s)
             self._pen_step(st, s)
+            self._edit_step(st, s)
             self._decode_tick(st, s)
             self._lp_tick(st, s)
             return
@@ -294,6 +318,7 @@ class DecodePlan:
         L.call("pdn_decode_gemv_f32", x, D, self.norm.weight.data._ptr, self.norm.eps, head.weight.data._ptr, V, V, 0,
                bias, None, 0, logits, V, B, D, V, 0, 0, 0, cv, ci, s)
         self._pen_step(st, s)
+        self._edit_step(st, s)
         self._decode_tick(st, s)
         self._lp_tick(st, s)
 
@@ -327,6 +352,7 @@ class DecodePlan:
         L.call("pdn_decode_wide_gemm_f32", x, D, 1, self.norm.weight.data._ptr, self.norm.eps, 0, 0, head.weight.data._ptr,
                V, V, 0, bias, logits, V, 0 if st["full"] else 2, cv, ci, pos, B, D, V, work, s)
         self._pen_step(st, s)
+        self._edit_step(st, s)
         self._decode_tick(st, s)
         self._lp_tick(st, s)
 
@@ -350,10 +376,10 @@ class DecodePlan:
             st["lp_box"] = hp.Mailbox(_LP_RING, (st["B"], lp_np.record_words(st["lp_n"])), unset=lp_np.UNSET)
             st["lp_ptr"][...] = np.int64(st["lp_box"]._ptr)
 
-    def _run_values(self, st, sampling, pen=None):
+    def _run_values(self, st, sampling, pen=None, edit=None):
         """The values of a run, uploaded when they differ from those in the plan (stream ordered: earlier steps read the
         old ones): the sampling parameters, and for a run with penalties (`pen`: its llm/penalties.Rows) every row's
-        prompt with zero counts."""
+        prompt with zero counts; for a run with logit edits (`edit`: its llm/logit_edits.Rows) every row's request."""
         if st["params_val"] != sampling:
             if sampling is not None:
                 st["params"][...] = params_bytes(*sampling)
@@ -361,6 +387,9 @@ class DecodePlan:
         if pen is not None and st["pen_run"] is not pen:
             self._pen_reset(st, np.arange(st["B"]), pen.prompts, pen.values)
             st["pen_run"] = pen
+        if edit is not None and st["edit_run"] is not edit:
+            self._edit_reset(st, np.arange(st["B"]), edit.req, edit.start, edit.spec)
+            st["edit_run"] = edit
 
     def _lp_read(self, st, i):
         """The records of step i (a poll of its ring slot, then marked unwritten again) as Logprobs."""
@@ -376,9 +405,43 @@ class DecodePlan:
             return
         from .. import _lib
         V, B = self.vocab_size, st["B"]
-        cv, ci = (None, None) if st["sampling"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
+        # (the candidates: of the edit kernel when that one runs behind this one)
+        cv, ci = (None, None) if st["sampling"] or st["edit"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
         _lib.lib().call("pdn_penalty_step_f32", st["logits"]._ptr, V, B, V, st["pen_params"]._ptr, st["counts"]._ptr,
                         st["seen"]._ptr, st["start"]._ptr, st["ids"]._ptr, st["pos"]._ptr, int(st["rows"]), cv, ci, s)
+
+    def _edit_step(self, st, s):
+        """Edit plans: between the vocabulary projection (or the penalty kernel) and the tick, each live row's logits are
+        edited in place for its request (greedy plans: with the candidates the tick reduces, csrc/logit_edit.hip).  The
+        stop ids of min_new_tokens are the tick's own bitmask (the rectangular `generate` has neither)."""
+        if not st["edit"]:
+            return
+        from .. import _lib
+        V, B = self.vocab_size, st["B"]
+        cv, ci = (None, None) if st["sampling"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
+        stop = st["stop"]._ptr if st["ragged"] else None
+        _lib.lib().call("pdne_logit_edit_step_f32", st["logits"]._ptr, V, B, V, st["edit_params"]._ptr,
+                        st["edit_allow"]._ptr, st["edit_allow_on"]._ptr, st["edit_bias_ids"]._ptr, st["edit_bias_val"]._ptr,
+                        st["edit_bias_n"]._ptr, st["edit_start"]._ptr, st["pos"]._ptr, int(st["rows"]), stop, cv, ci, s)
+
+    def _edit_reset(self, st, rows, reqs, lens, spec):
+        """Rows `rows` of an edit plan take requests `reqs` of `spec` (llm/logit_edits.Edits) with prompt lengths `lens`
+        (allowed bits, bias tables, prompt lengths; one launch, stream ordered after every step queued before), and the
+        plan's min_new_tokens becomes the call's (stream ordered too)."""
+        from .. import hipnp as hp, _lib
+        if st["edit_val"] != spec.m:
+            st["edit_params"][...] = edit_np.params_bytes(spec.m)
+            st["edit_val"] = spec.m
+        rows = np.asarray(rows, np.int32).reshape(-1)
+        if not rows.size:
+            return
+        # (device copies held until the call has been issued; the allocator orders their reuse on the stream)
+        src = [None if a is None else hp.asarray(a) for a in spec.packed(reqs)]
+        d_rows, d_len = hp.asarray(rows), hp.asarray(np.asarray(lens, np.int32).reshape(-1))
+        _lib.lib().call("pdne_logit_edit_reset", st["edit_allow"]._ptr, st["edit_allow_on"]._ptr, st["edit_bias_ids"]._ptr,
+                        st["edit_bias_val"]._ptr, st["edit_bias_n"]._ptr, st["edit_start"]._ptr, st["B"], self.vocab_size,
+                        d_rows._ptr, int(rows.size), *(None if a is None else a._ptr for a in src), d_len._ptr,
+                        hp.stream())
 
     def _pen_reset(self, st, rows, prompts, penalty):
         """Rows `rows` of a penalty plan take `prompts` (zero counts, prompt bits, prompt lengths; stream ordered after
@@ -405,7 +468,7 @@ class DecodePlan:
         rows' arrival count -- the last row to finish advances the step, csrc/decode_wide.hip), the slot state (served
         plans: counter id and token budget per row, the history ring; per-row plans: the stop bitmask) and the output.
         `mixed` (the mixed step's buffers): always the wide slot tick, on its own arrival counter and -- unless the
-        penalty kernel left the plan's -- its own candidates."""
+        penalty or the edit kernel left the plan's -- its own candidates."""
         from .. import _lib
         emb, V, B = self.tok_embedding.weight.data, self.vocab_size, st["B"]
         if st["beam"]:
@@ -416,7 +479,7 @@ class DecodePlan:
         if st["sampling"]:
             src = (st["logits"]._ptr, V, B, V, st["params"]._ptr)
         else:
-            c = st if mixed is None or st["pen"] else mixed
+            c = st if mixed is None or st["pen"] or st["edit"] else mixed
             src = (c["cand_v"]._ptr, c["cand_i"]._ptr, B, c["cand_v"].shape[1])
         cnt = (st["pos"]._ptr,) + ((st["step"]._ptr,) if st["rows"] else ())
         if wide:

@@ -6,17 +6,20 @@ training mode, other dtypes) -- with the prompt passes and the generators that d
 import numpy as np
 
 from ..core import Tensor
+from . import logit_edits as edit_np
 from . import logprobs as lp_np
 from . import penalties as pen_np
-from .decode_plan import _PEN_ENTRIES
+from .decode_plan import _EDIT_ENTRIES, _PEN_ENTRIES
 from .sampling import params_buffer, sample_next, sample_next_rows
 
 
 class DecodeSteps:
-    def _generate(self, input_ids, max_new_tokens, sampling, penalty=None, n_lp=None):
+    def _generate(self, input_ids, max_new_tokens, sampling, penalty=None, n_lp=None, edit=None):
         B, L = input_ids.shape
         next_id = None
         pen = None
+        # (the rows' requests and prompt lengths: llm/logit_edits.py)
+        erows = None if edit is None else edit_np.Rows(B, edit, np.arange(B), np.full(B, L))
         if penalty is not None:                                   # (the rows' prompts and counts: llm/penalties.py)
             ids = np.asarray(input_ids.numpy() if isinstance(input_ids, Tensor) else input_ids).reshape(B, L)
             pen = pen_np.Rows(B, self.vocab_size, penalty, list(ids))
@@ -25,18 +28,22 @@ class DecodeSteps:
                 logits = self(input_ids, 0)[:, -1, :]             # prompt pass: fills the KV caches
                 if pen is not None:
                     logits = self._penalize_prompt(logits, pen.prompts, penalty)
+                if erows is not None:
+                    logits = self._edit_rows(logits, edit, erows.req, np.zeros(B, np.int64))
                 next_id = logits.argmax(-1, True) if sampling is None else sample_next(logits, pos, *sampling)
                 lp = None if n_lp is None else self._logprobs_rows(logits, next_id.numpy(), n_lp)
             elif self._fast_path(next_id.device):
                 # (`more`: another token will be asked for -- the step after this one may be queued ahead)
                 out = self._decode_step_hip(next_id.data, pos, more=pos + 1 < max_new_tokens, sampling=sampling,
-                                            pen=pen, n_lp=n_lp)
+                                            pen=pen, n_lp=n_lp, edit=erows)
                 out, lp = out if n_lp is not None else (out, None)
                 next_id = Tensor(out, dtype=np.int64, device=next_id.device, copy=False)
             else:
                 logits = self(next_id, pos)[:, -1, :]
                 if pen is not None:
                     logits = self._penalize_step(logits, pen, next_id.numpy(), np.full(B, pos))
+                if erows is not None:
+                    logits = self._edit_step_host(logits, erows, np.full(B, pos))
                 next_id = logits.argmax(-1, True) if sampling is None else sample_next(logits, pos, *sampling)
                 lp = None if n_lp is None else self._logprobs_rows(logits, next_id.numpy(), n_lp)
             yield next_id if n_lp is None else (next_id, lp_np.as_step(lp))
@@ -93,13 +100,57 @@ class DecodeSteps:
         pen.feed(ids, pos)
         return Tensor(pen.apply(np.asarray(logits.numpy(), np.float32)), dtype=np.float32, device=logits.device)
 
-    def _generate_ragged(self, rows, n, sampling, stops, penalty=None, n_lp=None):
+    def _edit_rows(self, logits, spec, reqs, generated, pos=None):
+        """The statement of llm/logit_edits.py on logit rows (R, V) (a Tensor or a device array) for requests reqs[i] of
+        `spec` (llm/logit_edits.Edits) that have generated[i] tokens; pos (R,) marks the rows to leave alone (-1; None:
+        none).  On a HIP device with the library's entries: pdne_logit_edit_rows_f32 in place (stream ordered, no plan);
+        elsewhere the statement.  Returns what it was given, a Tensor or a device array."""
+        from .. import _lib
+        V = self.vocab_size
+        x = logits.data if isinstance(logits, Tensor) else logits
+        reqs = np.asarray(reqs, np.int64).reshape(-1)
+        generated = np.asarray(generated, np.int64).reshape(-1)
+        pos = None if pos is None else np.asarray(pos, np.int64).reshape(-1)
+        if not isinstance(x, np.ndarray) and x.dtype == np.float32 and all(_lib.provides(n) for n in _EDIT_ENTRIES):
+            from .. import hipnp as hp
+            if x._strides[1] != 1 or x._strides[0] < V:
+                x = x.copy()
+            src = [None if a is None else hp.asarray(a) for a in spec.packed(np.maximum(reqs, 0))]
+            prm, gen = hp.asarray(edit_np.params_bytes(spec.m)), hp.asarray(generated.astype(np.int32))
+            skip = None if pos is None else hp.asarray(np.where((pos >= 0) & (reqs >= 0), 0, -1).astype(np.int32))
+            stop = hp.asarray(self._stop_mask(spec.stops)) if spec.m > 0 else None
+            _lib.lib().call("pdne_logit_edit_rows_f32", x._ptr, x._strides[0], x.shape[0], V, prm._ptr,
+                            *(None if a is None else a._ptr for a in src), gen._ptr,
+                            None if skip is None else skip._ptr, None if stop is None else stop._ptr, None, None,
+                            hp.stream())
+            return Tensor(x, dtype=np.float32, device=logits.device, copy=False) if isinstance(logits, Tensor) else x
+        z = np.asarray(logits.numpy() if isinstance(logits, Tensor) else x.get() if hasattr(x, "get") else x, np.float32)
+        live = np.flatnonzero(reqs >= 0 if pos is None else (pos >= 0) & (reqs >= 0))
+        z = np.array(z)
+        if live.size:
+            z[live] = edit_np.apply(z[live], spec.allow_rows(reqs[live]), spec.bias_rows(reqs[live]), generated[live],
+                                    spec.m, spec.stops)
+        if isinstance(logits, Tensor):
+            return Tensor(z, dtype=np.float32, device=logits.device)
+        if isinstance(x, np.ndarray):
+            return z
+        x[...] = z
+        return x
+
+    def _edit_step_host(self, logits, erows, pos):
+        """`_edit_rows` on a step of a path without the device state (`erows`: llm/logit_edits.Rows): every row's request
+        at positions pos (B,), -1 for a row that computes nothing."""
+        pos = np.asarray(pos, np.int64).reshape(-1)
+        return self._edit_rows(logits, erows.spec, erows.req, np.maximum(pos - erows.start, 0), pos)
+
+    def _generate_ragged(self, rows, n, sampling, stops, penalty=None, n_lp=None, edit=None):
         B = len(rows)
         lens = np.array([r.size for r in rows], np.int64)
         if n == 0:
             return
         pen = None if penalty is None else pen_np.Rows(B, self.vocab_size, penalty, rows)
-        nxt = self._prompt_rows(rows, lens, sampling, penalty, n_lp)
+        erows = None if edit is None else edit_np.Rows(B, edit, np.arange(B), lens)
+        nxt = self._prompt_rows(rows, lens, sampling, penalty, n_lp, edit)
         if n_lp is not None:
             nxt, lp = nxt
         live = np.ones(B, bool)
@@ -112,6 +163,7 @@ class DecodeSteps:
             # tokens by STEP: slot i holds step i of every row (-1 for a stopped row), so "not written yet" is its own
             # value; two slots beyond the last step for the runs of a graph capture
             run = {"lens": lens, "live": live, "sampling": sampling, "stop_mask": self._stop_mask(stops), "pen": pen,
+                   "edit": erows,
                    "hist": hp.Mailbox(n + 2, (B, 1), unset=np.iinfo(np.int64).min), "lp": n_lp}
         ids = nxt.data
         for i in range(1, n):
@@ -123,7 +175,8 @@ class DecodeSteps:
                 ids, lp = ids if n_lp is not None else (ids, None)
                 nxt = Tensor(ids, dtype=np.int64, device=nxt.device, copy=False)
             else:
-                nxt = self._step_module_rows(nxt, np.where(live, lens + i, -1), sampling, pen=pen, n_lp=n_lp)
+                nxt = self._step_module_rows(nxt, np.where(live, lens + i, -1), sampling, pen=pen, n_lp=n_lp,
+                                             edit=erows)
                 nxt, lp = nxt if n_lp is not None else (nxt, None)
             if stops.size:
                 yield nxt if n_lp is None else (nxt, lp_np.as_step(lp))
@@ -132,11 +185,12 @@ class DecodeSteps:
                 continue
             yield nxt if n_lp is None else (nxt, lp_np.as_step(lp))
 
-    def _prompt_rows(self, rows, lens, sampling, penalty=None, n_lp=None):
+    def _prompt_rows(self, rows, lens, sampling, penalty=None, n_lp=None, edit=None):
         """The prompt pass of a ragged generation: the prompts right-padded to the longest and run as one batched
         causal pass from position 0 (no real token attends to a pad after it); each row's logits at its last real token,
         gathered before lm_head.  The cache slots the pads wrote, [len_b, L_max) of row b, are put back as they were: a
-        row's cache is written at its own positions only.  `penalty`: the logits penalised for each row's prompt first.
+        row's cache is written at its own positions only.  `penalty`: the logits penalised for each row's prompt first;
+        `edit` (llm/logit_edits.Edits): then edited for request b in row b.
         Returns the first token of every row, (B, 1) int64 (`n_lp`: and their Logprobs)."""
         B, Lm, lo = len(rows), int(lens.max()), int(lens.min())
         ids = np.zeros((B, Lm), np.int64)
@@ -153,21 +207,26 @@ class DecodeSteps:
                 c.data[int(b), int(lens[b]):Lm] = keep[int(b), int(lens[b]) - lo:]
         if penalty is not None:
             logits = self._penalize_prompt(logits, rows, penalty)
+        if edit is not None:
+            logits = self._edit_rows(logits, edit, np.arange(B), np.zeros(B, np.int64))
         nxt = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, lens, *sampling)
         if n_lp is None:
             return nxt
         return nxt, self._logprobs_rows(logits, nxt.numpy(), n_lp)
 
-    def _step_module_rows(self, ids, pos, sampling, req=None, pen=None, n_lp=None):
+    def _step_module_rows(self, ids, pos, sampling, req=None, pen=None, n_lp=None, edit=None):
         """One ragged decode step on the tape-node operators (the `cpu` device, fast_decode = False, training mode,
         other dtypes): row b's token at position pos[b] (-1: a stopped row, which yields -1).  The NumPy statement of what
         the per-row kernels compute.  `req`: the counter id of each row (Llama.serve; default: the row).  `pen`
-        (llm/penalties.Rows): the fed tokens counted and the logits penalised before the pick.  `n_lp`: returns (ids,
+        (llm/penalties.Rows): the fed tokens counted and the logits penalised before the pick.  `edit`
+        (llm/logit_edits.Rows): then the rows' edits.  `n_lp`: returns (ids,
         Logprobs of the rows, none for rows at -1)."""
         p = np.maximum(pos, 0)
         logits = self._step_logits_rows(ids, pos)
         if pen is not None:
             logits = self._penalize_step(logits, pen, ids.numpy(), pos)
+        if edit is not None:
+            logits = self._edit_step_host(logits, edit, pos)
         nxt = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, p, *sampling, rows=req)
         if pos.min() < 0:
             out = nxt.numpy().reshape(-1, 1)
@@ -185,14 +244,15 @@ class DecodeSteps:
             h = layer.step_rows(h, pos, self.freqs_cos, self.freqs_sin)
         return self.lm_head(self.norm(h))[:, -1, :]
 
-    def _decode_step_hip(self, ids, pos: int, more: bool = False, sampling=None, pen=None, n_lp=None):
+    def _decode_step_hip(self, ids, pos: int, more: bool = False, sampling=None, pen=None, n_lp=None, edit=None):
         """One decode step (one new token per sequence) without building tape nodes.  ids: (B, 1) int64
         device array; returns the next ids, (B, 1) int64.  The step is ONE hipGraph replay: norm + projection,
         RoPE + cache append, decode attention, SwiGLU + down projection and the greedy pick all read the position
         from device memory (csrc/decode.hip), so nothing changes between replays but the data.  `sampling`: None =
         greedy, else (temperature, top_k, top_p, seed) and the step ends in the sample tick (csrc/sample.hip).  `pen`
         (llm/penalties.Rows of this generation, or None): a penalty plan; its rows are reset from the prompts when a new
-        generation begins.  `n_lp`: returns (ids, Logprobs of the step)."""
+        generation begins.  `edit` (llm/logit_edits.Rows of this generation, or None): an edit plan, reset likewise.
+        `n_lp`: returns (ids, Logprobs of the step)."""
         from .. import hipnp as hp
         B = ids.shape[0]
         cache = self.layers[0].attention.cache_k
@@ -204,13 +264,13 @@ class DecodeSteps:
                              f"(max_seq_len {cache.shape[1]}, {self.freqs_cos.shape[0]} RoPE rows)")
         if B > cache.shape[0]:
             raise ValueError(f"batch {B} exceeds the KV cache's max_batch_size {cache.shape[0]}")
-        st = self._decode_plan(B, sampling is not None, penalty=pen is not None, n_lp=n_lp)
+        st = self._decode_plan(B, sampling is not None, penalty=pen is not None, n_lp=n_lp, edit=edit is not None)
         if st is None:
-            return self._decode_step_generic(ids, pos, sampling, pen, n_lp)
+            return self._decode_step_generic(ids, pos, sampling, pen, n_lp, edit)
         ahead, st["ahead"] = st.get("ahead"), None
         if ahead is not None:
             if (ahead[0] == pos and ahead[1] is ids and st["params_val"] == sampling     # exactly this step, queued ahead
-                    and st.get("pen_run") is pen):
+                    and st.get("pen_run") is pen and st.get("edit_run") is edit):
                 out = st["last_out"] = ahead[2]
                 if more and pos + 1 < limit:
                     self._decode_ahead(st, pos + 1)
@@ -225,7 +285,7 @@ class DecodeSteps:
             # a new generation: its own history -- slots in mapped host memory the pick kernel stores into directly
             st["hist"] = hp.Mailbox(cache.shape[1], (B, 1))
             self._hist_begin(st, st["hist"])
-        self._run_values(st, sampling, pen)
+        self._run_values(st, sampling, pen, edit)
         if ids is not st["ids"] and ids is not st.get("last_out"):
             st["ids"][...] = ids                                 # (not the array the previous step returned: that
             self._decode_gather(st)                              # one's embedding row is already in x)
@@ -290,10 +350,11 @@ class DecodeSteps:
         L.call("pdn_swiglu_fwd_f32", g, u, sw, B * F, st)
         gemv(sw, F, f.down.weight, x, D, beta=1.0)                    # x += swiglu @ Wdown
 
-    def _eager_tail(self, ws, gemv, fed, pos, pen, draw, n_lp):
+    def _eager_tail(self, ws, gemv, fed, pos, pen, draw, n_lp, edit=None):
         """The end of an eager step: the final RMSNorm and the vocabulary projection; `pen` (llm/penalties.Rows): the
         statement of llm/penalties.py on the host counts, the tokens `fed` (device ids) at positions `pos` (host (B,), -1:
-        a stopped row) counted first; then the greedy pick, or `draw(out)`, which launches the draw into `out`.  Returns
+        a stopped row) counted first; `edit` (llm/logit_edits.Rows): the rows' edits (`_edit_rows`); then the greedy
+        pick, or `draw(out)`, which launches the draw into `out`.  Returns
         the ids, (B, 1) int64 (`n_lp`: and the rows' Logprobs, none for rows at -1)."""
         from .. import hipnp as hp, _lib
         D, V, B = self.embed_dim, self.vocab_size, ws["x"].shape[0]
@@ -303,6 +364,8 @@ class DecodeSteps:
         if pen is not None:
             pen.feed(fed.get(), pos)
             ws["logits"][...] = pen.apply(ws["logits"].get())
+        if edit is not None:
+            self._edit_step_host(ws["logits"], edit, pos)        # (contiguous rows: in place)
         if draw is None:
             out = ws["logits"].argmax(-1, keepdims=True)
         else:
@@ -314,7 +377,7 @@ class DecodeSteps:
         tok[pos < 0] = -1
         return out, self._logprobs_rows(ws["logits"], tok, n_lp)
 
-    def _decode_step_generic(self, ids, pos: int, sampling=None, pen=None, n_lp=None):
+    def _decode_step_generic(self, ids, pos: int, sampling=None, pen=None, n_lp=None, edit=None):
         """The same step from the library's generic entry points (skinny `pdn_gemm_f32`, RMSNorm, RoPE, decode
         attention, SwiGLU), ~77 launches from preallocated buffers: for shapes / layouts the graph path does not take."""
         from .. import hipnp as hp, _lib
@@ -347,7 +410,7 @@ class DecodeSteps:
 
         def draw(out):                                # (the sampled form of the pick: counter (pos, b))
             L.call("pdn_sample_rows_f32", ws["logits"]._ptr, V, B, V, params_buffer(*sampling)._ptr, pos, out._ptr, st)
-        return self._eager_tail(ws, gemv, ids, np.full(B, pos), pen, None if sampling is None else draw, n_lp)
+        return self._eager_tail(ws, gemv, ids, np.full(B, pos), pen, None if sampling is None else draw, n_lp, edit)
 
     # -- ragged decode (generate_ragged): every row at its own position ------------------------------
     def _decode_step_rows(self, ids, run, i: int, more: bool = False):
@@ -363,9 +426,10 @@ class DecodeSteps:
         limit = min(cache.shape[1], self.freqs_cos.shape[0])
         pos = np.where(live, lens + i, -1).astype(np.int32)
         n_lp = run.get("lp")
-        st = self._decode_plan(B, sampling is not None, ragged=True, penalty=run.get("pen") is not None, n_lp=n_lp)
+        st = self._decode_plan(B, sampling is not None, ragged=True, penalty=run.get("pen") is not None, n_lp=n_lp,
+                               edit=run.get("edit") is not None)
         if st is None:
-            out = self._decode_step_generic_rows(ids, pos, sampling, pen=run.get("pen"), n_lp=n_lp)
+            out = self._decode_step_generic_rows(ids, pos, sampling, pen=run.get("pen"), n_lp=n_lp, edit=run.get("edit"))
             out, lp = out if n_lp is not None else (out, None)
             if pos.min() < 0:
                 tok = out.get().reshape(B, 1)
@@ -387,7 +451,7 @@ class DecodeSteps:
             st["step"][...] = np.int32(i)
             st["stop"][...] = run["stop_mask"]
             self._hist_begin(st, run["hist"])
-        self._run_values(st, sampling, run.get("pen"))
+        self._run_values(st, sampling, run.get("pen"), run.get("edit"))
         if ids is not st["ids"] and ids is not st.get("last_out"):
             # (a stopped row's -1 is no token: any valid id stands in, its row computes nothing that is kept)
             st["ids"][...] = np.maximum(ids.get(), 0) if isinstance(ids, hp.readback_array) else ids
@@ -406,12 +470,13 @@ class DecodeSteps:
             st["host_step"] = i + 1
             st["ahead"] = ((id(run), i), st["last_out"], run["hist"].slot(i))
 
-    def _decode_step_generic_rows(self, ids, pos, sampling=None, req=None, pen=None, n_lp=None):
+    def _decode_step_generic_rows(self, ids, pos, sampling=None, req=None, pen=None, n_lp=None, edit=None):
         """`_decode_step_generic` with a position per row (pos: host int32, -1 = a stopped row: computed at position 0,
         no cache slot written): k / v are projected into scratch rows and written to each row's own slot, RoPE takes
         each row's own cos / sin row, and the attention runs over each row's own key count (pdn_attention_decode_rows_f32).
         `req` (Llama.serve): the counter id of each row, drawn by the slot tick (default: the row).  `pen`
-        (llm/penalties.Rows): the statement of the penalties on the host counts.  Returns the ids of every row, (B, 1)
+        (llm/penalties.Rows): the statement of the penalties on the host counts.  `edit` (llm/logit_edits.Rows): the rows'
+        edits.  Returns the ids of every row, (B, 1)
         int64 (`n_lp`: and the rows' Logprobs, none for rows at -1)."""
         from .. import hipnp as hp, _lib
         L, st = _lib.lib(), hp.stream()
@@ -459,4 +524,4 @@ class DecodeSteps:
             else:
                 L.call("pdn_decode_sample_tick_rows_f32", logits, V, B, V, params_buffer(*sampling)._ptr, out._ptr,
                        pd._ptr, step._ptr, None, None, None, 0, 0, None, st)
-        return self._eager_tail(ws, gemv, idc, pos, pen, None if sampling is None else draw, n_lp)
+        return self._eager_tail(ws, gemv, idc, pos, pen, None if sampling is None else draw, n_lp, edit)

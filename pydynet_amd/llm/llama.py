@@ -26,6 +26,7 @@ from ..special import zeros
 from . import beam as beam_np
 from . import chunked
 from . import logprobs as lp_np
+from . import logit_edits as edit_np
 from . import penalties as pen_np
 from . import prefix as prefix_np
 from . import speculative as spec_np
@@ -395,20 +396,24 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
     fast_decode = True      # class switch: False keeps every decode step on the generic tape-node path
 
     def generate(self, input_ids, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0,
-                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=None):
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=None, logit_bias=None,
+                 allowed_token_ids=None):
         """Yield the next ids, (B, 1) int64, for positions L .. max_new_tokens - 1.  temperature 0 (the default): the
         greedy pick of the reference (model.py:258-269); temperature > 0: drawn with top-k / top-p and the seeded
         counter-based generator of llm/sampling.py (token at position t of row b: Philox counter (t, b)).
         `repetition_penalty` / `presence_penalty` / `frequency_penalty` (defaults: off): the penalties of llm/penalties.py
         on each row's logits -- its prompt's tokens and the tokens it generated -- before the pick or the draw.
         `logprobs` = n (an int in [0, 20]; None: off): every step yields (ids, lp) instead, lp an llm/logprobs.Logprobs
-        of the row the pick or the draw read -- token (B, 1), top_ids (B, n), top_logprobs (B, n).  The arguments are
-        checked here, before anything runs."""
+        of the row the pick or the draw read -- token (B, 1), top_ids (B, n), top_logprobs (B, n).
+        `logit_bias` ({token id: bias}; -inf bans the token) / `allowed_token_ids` (the only tokens a row may produce):
+        the edits of llm/logit_edits.py, after the penalties and before the pick or the draw -- one value for every row,
+        or a sequence with one value (or None) per row.  The arguments are checked here, before anything runs."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
         penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty)
         n_lp = lp_np.check_n(logprobs)
+        edit = edit_np.check_args(logit_bias, allowed_token_ids, 0, self.vocab_size, input_ids.shape[0])
         return self._generate(input_ids, max_new_tokens, (temperature, top_k, top_p, seed) if temperature > 0 else None,
-                              penalty, n_lp)
+                              penalty, n_lp, edit)
 
     def score(self, input_ids, logprobs=0):
         """log p(x_t | x_<t) of given sequences: input_ids (B, L) int, L >= 2.  Returns llm/logprobs.Logprobs for
@@ -443,7 +448,7 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
 
     def generate_ragged(self, prompts, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
                         speculate=0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                        logprobs=None):
+                        logprobs=None, logit_bias=None, allowed_token_ids=None, min_new_tokens=0):
         """Generation for B prompts of different lengths, every row at its own position.  Yields a (B, 1) int64 Tensor
         per step: step i holds, for row b, the token at position len_b + i.  `max_new_tokens` is the number of NEW tokens
         per row -- `generate`'s second argument is an end position instead: for equal lengths L,
@@ -460,6 +465,9 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         `repetition_penalty` / `presence_penalty` / `frequency_penalty`: as in `generate` (llm/penalties.py), row b's
         prompt and generated tokens; not with speculate > 0.
         `logprobs` = n: as in `generate`, every step yields (ids, lp); a row that yields -1 has nan / -1 / nan.  Not with
+        speculate > 0.
+        `logit_bias` / `allowed_token_ids`: as in `generate` (llm/logit_edits.py), one value or one per prompt;
+        `min_new_tokens` = m: no row yields a stop id before it has produced m tokens (needs `stop_ids`).  Not with
         speculate > 0.
         Every argument is checked here (ValueError), before anything runs."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
@@ -491,12 +499,13 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         stops = np.asarray(sorted({int(t) for t in stop_ids}), np.int64)
         if stops.size and (stops.min() < 0 or stops.max() >= V):
             raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
+        edit = edit_np.check_args(logit_bias, allowed_token_ids, min_new_tokens, V, len(rows), stops, k)
         sampling = (temperature, top_k, top_p, seed) if temperature > 0 else None
         self.last_speculation = None if k == 0 else spec_np.counts()
         if k:
             return self._speculate([r.astype(np.int64) for r in rows], max_new_tokens, k, sampling, stops)
         return self._generate_ragged([r.astype(np.int64) for r in rows], max_new_tokens, sampling, stops, penalty,
-                                     n_lp)
+                                     n_lp, edit)
 
     # -- decode fast path -----------------------------------------------------------
     graph_decode = True     # class switch: False issues the step's launches one by one instead of replaying a hipGraph
@@ -508,7 +517,7 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
     # -- continuous batching (serve): a finished row takes the next waiting request -------------------------------
     def serve(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
               prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=None,
-              prefix_cache=False):
+              prefix_cache=False, logit_bias=None, allowed_token_ids=None, min_new_tokens=0):
         """Continuous batching: N requests (`prompts`, N may exceed max_batch_size) through `slots` decode rows
         (default min(N, max_batch_size)).  A row frees when its request yields a stop id or uses up its budget
         (`max_new_tokens`: one int, or one per request; 0 = the request yields nothing and never takes a row).  Before
@@ -537,7 +546,10 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         other path (a library without the mixed step, more than 8 key ranges, wide_decode off, the generic rows, the
         `cpu` device) a prompt completes with one whole pass from position 0, so every prompt is computed in full and
         steps and tokens are exactly those without the cache.  `self.prefix_stats` holds the run's figures (requests,
-        hits, prompt_tokens, reused_tokens, copies, launches) as it goes; with the cache off it is left alone."""
+        hits, prompt_tokens, reused_tokens, copies, launches) as it goes; with the cache off it is left alone.
+        `logit_bias` / `allowed_token_ids` (llm/logit_edits.py): one value for every request, or a sequence with one value
+        (or None) per request -- a request's edits follow it into whichever row it runs in; `min_new_tokens` = m: no
+        request yields a stop id before it has produced m tokens (needs `stop_ids`)."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
         penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty)
         n_lp = lp_np.check_n(logprobs)
@@ -574,20 +586,22 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         stops = np.asarray(sorted({int(t) for t in stop_ids}), np.int64)
         if stops.size and (stops.min() < 0 or stops.max() >= V):
             raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
+        edit = edit_np.check_args(logit_bias, allowed_token_ids, min_new_tokens, V, N, stops)
         sampling = (temperature, top_k, top_p, seed) if temperature > 0 else None
         C = chunked.check_chunk(prefill_chunk, slots)
         if C is not None:
             return self._serve_chunked([p.astype(np.int64) for p in rows], budgets, int(slots), C, sampling, stops,
-                                       penalty, n_lp, k_pre)
-        return self._serve([p.astype(np.int64) for p in rows], budgets, int(slots), sampling, stops, penalty, n_lp)
+                                       penalty, n_lp, k_pre, edit)
+        return self._serve([p.astype(np.int64) for p in rows], budgets, int(slots), sampling, stops, penalty, n_lp, edit)
 
     def serve_all(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
                   prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                  logprobs=None, prefix_cache=False):
+                  logprobs=None, prefix_cache=False, logit_bias=None, allowed_token_ids=None, min_new_tokens=0):
         """`serve` run to the end: a list of N int64 arrays, request r's generated tokens in order.  `logprobs` = n: a
         list of (tokens, Logprobs) instead, the arrays of length k / (k, n) for a request's k tokens."""
         it = self.serve(prompts, max_new_tokens, slots, temperature, top_k, top_p, seed, stop_ids, prefill_chunk,
-                        repetition_penalty, presence_penalty, frequency_penalty, logprobs, prefix_cache)
+                        repetition_penalty, presence_penalty, frequency_penalty, logprobs, prefix_cache, logit_bias,
+                        allowed_token_ids, min_new_tokens)
         out = [[] for _ in range(len(prompts))]
         lps = [[] for _ in range(len(prompts))]
         for step in it:
