@@ -588,7 +588,8 @@ int pdn_decode_argmax_tick_f32(const float* logits, int64_t row_stride, int B, i
  * u = (w >> 40) * 2^-24, w the first word of Philox4x64-10(counter (t, b, 0, 0), key (seed, 0)): the token is the
  * smallest kept id whose inclusive cumulative probability (ascending ids) is > u.  Deterministic: the same input gives
  * the same ids (the probability mass is summed as integers, 2^-40 units of the largest weight).  T <= 0: the argmax.
- * `params` is a DEVICE pointer, so a captured step can be replayed with new values.
+ * `params` is a DEVICE pointer, so a captured step can be replayed with new values.  The four bytes at offset 12 of the block
+ * hold min_p (0 = off), which only the per-row entries of include/pdn_persample.h read: callers of this header's write zeros.
  *   pdn_sample_rows_f32         row b -> out_ids[b] (int64) with counter (t, b); one workgroup per row.
  *   pdn_decode_sample_tick_f32  pdn_decode_pick_tick_f32 with full logit rows in place of the candidates: row b is
  *                               drawn with counter (*pos, b), stored to next_ids[b] and the history slot, its embedding

@@ -81,7 +81,9 @@ enum {
                                   // instead of the fp32 tile-piece kernel: counts HERE ONLY, not in 1, 14 or 46
   PDN_CNT_LOGIT_EDIT = 48,        // allowed sets, logit_bias and min_new_tokens of a decode step (csrc/logit_edit.hip,
                                   // include/pdn_logitedit.h): once per launching pdne_* entry
-  PDN_CNT_SLOTS = 49
+  PDN_CNT_PERSAMPLE = 49,         // sampling parameters per row (include/pdn_persample.h): once per pdnq_* entry, each of which
+                                  // also counts where its shared-parameter form counts
+  PDN_CNT_SLOTS = 50
 };
 void pdn_count(int slot);
 

@@ -386,7 +386,8 @@ __global__ __launch_bounds__(256) void wide_pick_tick_kernel(const float* __rest
   }
 }
 
-template <bool SLOTS>
+// PER (include/pdn_persample.h): row b uses parameter block prm[b] (a stopped row's is not read), else *prm.
+template <bool SLOTS, bool PER>
 __global__ __launch_bounds__(SMP_THREADS) void wide_sample_tick_kernel(
     const float* __restrict__ logits, int64_t rs, int B, int V, const SampleParams* __restrict__ prm,
     int64_t* __restrict__ ids, int* pos, int* step, int* arrive, const int* __restrict__ req, int* left, int ring,
@@ -397,7 +398,7 @@ __global__ __launch_bounds__(SMP_THREADS) void wide_sample_tick_kernel(
   const int pb = pos[b];
   int64_t tok = 0;
   if (pb >= 0) {                           // (uniform) the draw of sample.hip with counter (pos[b], req[b] or b)
-    tok = smp_row(logits + (int64_t)b * rs, V, *prm, (uint64_t)pb, (uint64_t)(SLOTS ? req[b] : b), s);
+    tok = smp_row<PER>(logits + (int64_t)b * rs, V, prm[PER ? b : 0], (uint64_t)pb, (uint64_t)(SLOTS ? req[b] : b), s);
     if (tid == 0) ids[b] = tok;
   }
   __syncthreads();                         // (every thread has read pos[b])
@@ -445,36 +446,38 @@ extern "C" int pdn_decode_wide_pick_tick_slots_f32(const float* blk_max, const i
   return PDN_OK;
 }
 
-extern "C" int pdn_decode_wide_sample_tick_rows_f32(const float* logits, int64_t row_stride, int B, int V,
-                                                    const void* params, int64_t* ids, int* pos, int* step, int* arrive,
-                                                    const unsigned* stop_mask, int64_t* const* history,
-                                                    const float* emb, int64_t emb_row_stride, int D, float* x_next,
-                                                    void* stream) {
+// PER: the pdnq_ forms of include/pdn_persample.h, `params` = B blocks.
+template <bool PER>
+static int wide_sample_tick_rows(const char* name, const float* logits, int64_t row_stride, int B, int V,
+                                 const void* params, int64_t* ids, int* pos, int* step, int* arrive,
+                                 const unsigned* stop_mask, int64_t* const* history, const float* emb,
+                                 int64_t emb_row_stride, int D, float* x_next, void* stream) {
   if (B == 0) return PDN_OK;
-  WD_TICK_CHECK("pdn_decode_wide_sample_tick_rows_f32");
-  PDN_CHECK_ARG(logits && params && V > 0 && V <= (1 << 23) && row_stride >= V,
-                "pdn_decode_wide_sample_tick_rows_f32: bad logits (V %d)", V);
-  hipLaunchKernelGGL(wide_sample_tick_kernel<false>, dim3(B), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
+  PDN_CHECK_ARG(ids && pos && step && arrive && B > 0 && B <= WD_MAX_B, "%s: bad arguments (B %d)", name, B);
+  PDN_CHECK_ARG(!emb || (x_next && D > 0), "%s: an embedding table needs x_next and D", name);
+  PDN_CHECK_ARG(logits && params && V > 0 && V <= (1 << 23) && row_stride >= V, "%s: bad logits (V %d)", name, V);
+  hipLaunchKernelGGL((wide_sample_tick_kernel<false, PER>), dim3(B), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
                      row_stride, B, V, (const SampleParams*)params, ids, pos, step, arrive, nullptr, nullptr, 1,
                      stop_mask, history, emb, emb_row_stride, D, x_next);
   PDN_LAUNCH_CHECK();
   pdn_count(PDN_CNT_DECODE_WIDE);
   pdn_count(PDN_CNT_SAMPLE);
   pdn_count(PDN_CNT_DECODE_ROWS);
+  if (PER) pdn_count(PDN_CNT_PERSAMPLE);
   return PDN_OK;
 }
 
-extern "C" int pdn_decode_wide_sample_tick_slots_f32(const float* logits, int64_t row_stride, int B, int V,
-                                                     const void* params, int64_t* ids, int* pos, int* step,
-                                                     int* arrive, const int* req, int* left, int ring,
-                                                     const unsigned* stop_mask, int64_t* const* history,
-                                                     const float* emb, int64_t emb_row_stride, int D, float* x_next,
-                                                     void* stream) {
+template <bool PER>
+static int wide_sample_tick_slots(const char* name, const float* logits, int64_t row_stride, int B, int V,
+                                  const void* params, int64_t* ids, int* pos, int* step, int* arrive, const int* req,
+                                  int* left, int ring, const unsigned* stop_mask, int64_t* const* history,
+                                  const float* emb, int64_t emb_row_stride, int D, float* x_next, void* stream) {
   if (B == 0) return PDN_OK;
-  WD_TICK_CHECK("pdn_decode_wide_sample_tick_slots_f32");
+  PDN_CHECK_ARG(ids && pos && step && arrive && B > 0 && B <= WD_MAX_B, "%s: bad arguments (B %d)", name, B);
+  PDN_CHECK_ARG(!emb || (x_next && D > 0), "%s: an embedding table needs x_next and D", name);
   PDN_CHECK_ARG(logits && params && req && left && ring > 0 && V > 0 && V <= (1 << 23) && row_stride >= V,
-                "pdn_decode_wide_sample_tick_slots_f32: bad arguments (V %d, ring %d)", V, ring);
-  hipLaunchKernelGGL(wide_sample_tick_kernel<true>, dim3(B), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
+                "%s: bad arguments (V %d, ring %d)", name, V, ring);
+  hipLaunchKernelGGL((wide_sample_tick_kernel<true, PER>), dim3(B), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
                      row_stride, B, V, (const SampleParams*)params, ids, pos, step, arrive, req, left, ring, stop_mask,
                      history, emb, emb_row_stride, D, x_next);
   PDN_LAUNCH_CHECK();
@@ -482,5 +485,26 @@ extern "C" int pdn_decode_wide_sample_tick_slots_f32(const float* logits, int64_
   pdn_count(PDN_CNT_SAMPLE);
   pdn_count(PDN_CNT_DECODE_ROWS);
   pdn_count(PDN_CNT_DECODE_SLOTS);
+  if (PER) pdn_count(PDN_CNT_PERSAMPLE);
   return PDN_OK;
 }
+
+#define WD_SAMPLE_ROWS_ENTRY(name, PER)                                                                                 \
+  extern "C" int name(const float* logits, int64_t row_stride, int B, int V, const void* params, int64_t* ids, int* pos, \
+                      int* step, int* arrive, const unsigned* stop_mask, int64_t* const* history, const float* emb,     \
+                      int64_t emb_row_stride, int D, float* x_next, void* stream) {                                     \
+    return wide_sample_tick_rows<PER>(#name, logits, row_stride, B, V, params, ids, pos, step, arrive, stop_mask,       \
+                                      history, emb, emb_row_stride, D, x_next, stream);                                 \
+  }
+#define WD_SAMPLE_SLOTS_ENTRY(name, PER)                                                                                \
+  extern "C" int name(const float* logits, int64_t row_stride, int B, int V, const void* params, int64_t* ids, int* pos, \
+                      int* step, int* arrive, const int* req, int* left, int ring, const unsigned* stop_mask,           \
+                      int64_t* const* history, const float* emb, int64_t emb_row_stride, int D, float* x_next,          \
+                      void* stream) {                                                                                   \
+    return wide_sample_tick_slots<PER>(#name, logits, row_stride, B, V, params, ids, pos, step, arrive, req, left,      \
+                                       ring, stop_mask, history, emb, emb_row_stride, D, x_next, stream);               \
+  }
+WD_SAMPLE_ROWS_ENTRY(pdn_decode_wide_sample_tick_rows_f32, false)
+WD_SAMPLE_ROWS_ENTRY(pdnq_decode_wide_sample_tick_rows_f32, true)
+WD_SAMPLE_SLOTS_ENTRY(pdn_decode_wide_sample_tick_slots_f32, false)
+WD_SAMPLE_SLOTS_ENTRY(pdnq_decode_wide_sample_tick_slots_f32, true)

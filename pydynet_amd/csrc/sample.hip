@@ -7,6 +7,8 @@
 //   2. p_i = exp((z_i - max z) / T) over the kept tokens, normalised;
 //   3. top-p: theta = the largest kept value whose mass of {kept i : z_i >= theta} is at least top_p; keep those
 //      (top_p >= 1: off);
+//   3b. min_p (the block's float at offset 12; 0: off; the per-row launches of include/pdn_persample.h only): a token kept
+//       so far stays iff exp((z_i - max z) / T) >= min_p;
 //   4. u = (w >> 40) * 2^-24 with w the first word of Philox4x64-10(counter (t, b, 0, 0), key (seed, 0)); the token is
 //      the smallest id whose inclusive cumulative probability (ascending ids, kept tokens only) is greater than u.
 //
@@ -23,11 +25,22 @@
 //     whose chunk holds the target walks it.
 #include "sample_row.h"
 
+// PER (include/pdn_persample.h): row b uses parameter block prm[b], is drawn with counter (pos[b], req ? req[b] : b) and
+// is left alone at pos[b] < 0 (its block is not read); else every row uses *prm and counter (t, b).
+template <bool PER>
 __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(const float* __restrict__ logits, int64_t rs, int V,
                                                                  const SampleParams* __restrict__ prm, int64_t t,
+                                                                 const int* __restrict__ pos, const int* __restrict__ req,
                                                                  int64_t* __restrict__ out) {
   __shared__ SmpShared s;
   const int b = blockIdx.x;
+  if (PER) {
+    const int pb = pos[b];
+    if (pb < 0) return;                              // (uniform)
+    const int tok = smp_row<true>(logits + (int64_t)b * rs, V, prm[b], (uint64_t)pb, (uint64_t)(req ? req[b] : b), s);
+    if (threadIdx.x == 0) out[b] = tok;
+    return;
+  }
   const int tok = smp_row(logits + (int64_t)b * rs, V, *prm, (uint64_t)t, (uint64_t)b, s);
   if (threadIdx.x == 0) out[b] = tok;
 }
@@ -38,10 +51,24 @@ extern "C" int pdn_sample_rows_f32(const float* logits, int64_t row_stride, int 
   PDN_CHECK_ARG(logits && params && out_ids && B > 0 && V > 0 && V <= (1 << 23) && row_stride >= V,
                 "pdn_sample_rows_f32: bad arguments (B %d, V %d, row stride %lld)", B, V, (long long)row_stride);
   PDN_CHECK_ARG(t >= 0, "pdn_sample_rows_f32: negative counter %lld", (long long)t);
-  hipLaunchKernelGGL(sample_rows_kernel, dim3(B), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits, row_stride, V,
-                     (const SampleParams*)params, t, out_ids);
+  hipLaunchKernelGGL(sample_rows_kernel<false>, dim3(B), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits, row_stride, V,
+                     (const SampleParams*)params, t, nullptr, nullptr, out_ids);
   PDN_LAUNCH_CHECK();
   pdn_count(PDN_CNT_SAMPLE);
+  return PDN_OK;
+}
+
+// include/pdn_persample.h: the standalone draw with a parameter block, a position and (req != NULL) a counter id per row
+extern "C" int pdnq_sample_rows_f32(const float* logits, int64_t row_stride, int B, int V, const void* params,
+                                    const int* pos, const int* req, int64_t* out_ids, void* stream) {
+  if (B == 0) return PDN_OK;
+  PDN_CHECK_ARG(logits && params && pos && out_ids && B > 0 && B <= 65535 && V > 0 && V <= (1 << 23) && row_stride >= V,
+                "pdnq_sample_rows_f32: bad arguments (B %d, V %d, row stride %lld)", B, V, (long long)row_stride);
+  hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(B), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits, row_stride, V,
+                     (const SampleParams*)params, (int64_t)0, pos, req, out_ids);
+  PDN_LAUNCH_CHECK();
+  pdn_count(PDN_CNT_SAMPLE);
+  pdn_count(PDN_CNT_PERSAMPLE);
   return PDN_OK;
 }
 
@@ -55,7 +82,9 @@ extern "C" int pdn_sample_rows_f32(const float* logits, int64_t row_stride, int 
 // SLOTS (with ROWS; Llama.serve): row b is drawn with counter (pos[b], req[b]) -- the request it holds, not the row --,
 // the history is a ring of `ring` steps, (*hist)[(*step % ring) * B + b], and left[b] counts the tokens row b may still
 // produce: a live row stores left[b] - 1 and stops once it reaches 0.
-template <bool ROWS, bool SLOTS = false>
+// PER (with ROWS; include/pdn_persample.h): row b uses parameter block prm[b], read by every thread before the barriers of
+// smp_row like pos[b]; a stopped row's block is not read.
+template <bool ROWS, bool SLOTS = false, bool PER = false>
 __global__ __launch_bounds__(SMP_THREADS) void decode_sample_tick_kernel(
     const float* __restrict__ logits, int64_t rs, int B, int V, const SampleParams* __restrict__ prm,
     int64_t* __restrict__ ids, int* __restrict__ pos, int64_t* const* __restrict__ hist, const float* __restrict__ emb,
@@ -64,7 +93,7 @@ __global__ __launch_bounds__(SMP_THREADS) void decode_sample_tick_kernel(
   __shared__ SmpShared s;
   const int tid = threadIdx.x;
   const int p = ROWS ? *step : (pos ? *pos : 0);
-  const SampleParams pr = *prm;
+  const SampleParams pr0 = PER ? SampleParams{} : *prm;
   int64_t* hrow = hist ? *hist + (int64_t)(SLOTS ? p % ring : p) * B : nullptr;
   for (int b = 0; b < B; ++b) {
     const int pb = ROWS ? pos[b] : p;      // (read by every thread before the barriers of smp_row)
@@ -72,7 +101,8 @@ __global__ __launch_bounds__(SMP_THREADS) void decode_sample_tick_kernel(
       if (tid == 0 && hrow) __hip_atomic_store(hrow + b, (int64_t)-1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       continue;
     }
-    const int64_t tok = smp_row(logits + (int64_t)b * rs, V, pr, (uint64_t)pb, (uint64_t)(SLOTS ? req[b] : b), s);
+    const SampleParams pr = PER ? prm[b] : pr0;
+    const int64_t tok = smp_row<PER>(logits + (int64_t)b * rs, V, pr, (uint64_t)pb, (uint64_t)(SLOTS ? req[b] : b), s);
     if (tid == 0) {
       ids[b] = tok;
       if (hrow) __hip_atomic_store(hrow + b, tok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (may be host memory)
@@ -115,41 +145,79 @@ extern "C" int pdn_decode_sample_tick_f32(const float* logits, int64_t row_strid
 }
 
 // The same with a position per row (decode_sample_tick_kernel<true>): pos (B,) and step (1,) int32 are required.
+// PER: the pdnq_ form, `params` = B blocks.
+template <bool PER>
+static int sample_tick_rows(const char* name, const float* logits, int64_t row_stride, int B, int V, const void* params,
+                            int64_t* next_ids, int* pos, int* step, const unsigned* stop_mask, int64_t* const* history,
+                            const float* emb, int64_t emb_row_stride, int D, float* x_next, void* stream) {
+  if (B == 0) return PDN_OK;
+  PDN_CHECK_ARG(logits && params && next_ids && pos && step && B > 0 && V > 0 && V <= (1 << 23) && row_stride >= V,
+                "%s: bad arguments (B %d, V %d)", name, B, V);
+  PDN_CHECK_ARG(!emb || (x_next && D > 0), "%s: an embedding table needs x_next and D", name);
+  hipLaunchKernelGGL((decode_sample_tick_kernel<true, false, PER>), dim3(1), dim3(SMP_THREADS), 0, (hipStream_t)stream,
+                     logits, row_stride, B, V, (const SampleParams*)params, next_ids, pos, history, emb, emb_row_stride, D,
+                     x_next, step, stop_mask, nullptr, nullptr, 0);
+  PDN_LAUNCH_CHECK();
+  pdn_count(PDN_CNT_SAMPLE);
+  pdn_count(PDN_CNT_DECODE_ROWS);
+  if (PER) pdn_count(PDN_CNT_PERSAMPLE);
+  return PDN_OK;
+}
+
 extern "C" int pdn_decode_sample_tick_rows_f32(const float* logits, int64_t row_stride, int B, int V, const void* params,
                                                int64_t* next_ids, int* pos, int* step, const unsigned* stop_mask,
                                                int64_t* const* history, const float* emb, int64_t emb_row_stride, int D,
                                                float* x_next, void* stream) {
-  if (B == 0) return PDN_OK;
-  PDN_CHECK_ARG(logits && params && next_ids && pos && step && B > 0 && V > 0 && V <= (1 << 23) && row_stride >= V,
-                "pdn_decode_sample_tick_rows_f32: bad arguments (B %d, V %d)", B, V);
-  PDN_CHECK_ARG(!emb || (x_next && D > 0), "pdn_decode_sample_tick_rows_f32: an embedding table needs x_next and D");
-  hipLaunchKernelGGL(decode_sample_tick_kernel<true>, dim3(1), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
-                     row_stride, B, V, (const SampleParams*)params, next_ids, pos, history, emb, emb_row_stride, D, x_next,
-                     step, stop_mask, nullptr, nullptr, 0);
-  PDN_LAUNCH_CHECK();
-  pdn_count(PDN_CNT_SAMPLE);
-  pdn_count(PDN_CNT_DECODE_ROWS);
-  return PDN_OK;
+  return sample_tick_rows<false>("pdn_decode_sample_tick_rows_f32", logits, row_stride, B, V, params, next_ids, pos, step,
+                                 stop_mask, history, emb, emb_row_stride, D, x_next, stream);
+}
+
+extern "C" int pdnq_decode_sample_tick_rows_f32(const float* logits, int64_t row_stride, int B, int V, const void* params,
+                                                int64_t* next_ids, int* pos, int* step, const unsigned* stop_mask,
+                                                int64_t* const* history, const float* emb, int64_t emb_row_stride, int D,
+                                                float* x_next, void* stream) {
+  return sample_tick_rows<true>("pdnq_decode_sample_tick_rows_f32", logits, row_stride, B, V, params, next_ids, pos, step,
+                                stop_mask, history, emb, emb_row_stride, D, x_next, stream);
 }
 
 // The per-row tick of a served batch (decode_sample_tick_kernel<true, true>): as pdn_decode_sample_tick_rows_f32, but
 // row b is drawn with counter (pos[b], req[b]), left (B,) int32 counts the tokens row b may still produce and the
 // history is a ring of `ring` steps, (*history)[(*step % ring) * B + b].
+// PER: the pdnq_ form, `params` = B blocks.
+template <bool PER>
+static int sample_tick_slots(const char* name, const float* logits, int64_t row_stride, int B, int V, const void* params,
+                             int64_t* next_ids, int* pos, int* step, const int* req, int* left, int ring,
+                             const unsigned* stop_mask, int64_t* const* history, const float* emb, int64_t emb_row_stride,
+                             int D, float* x_next, void* stream) {
+  if (B == 0) return PDN_OK;
+  PDN_CHECK_ARG(logits && params && next_ids && pos && step && req && left && ring > 0 && B > 0 && V > 0 &&
+                    V <= (1 << 23) && row_stride >= V,
+                "%s: bad arguments (B %d, V %d, ring %d)", name, B, V, ring);
+  PDN_CHECK_ARG(!emb || (x_next && D > 0), "%s: an embedding table needs x_next and D", name);
+  hipLaunchKernelGGL((decode_sample_tick_kernel<true, true, PER>), dim3(1), dim3(SMP_THREADS), 0, (hipStream_t)stream,
+                     logits, row_stride, B, V, (const SampleParams*)params, next_ids, pos, history, emb, emb_row_stride, D,
+                     x_next, step, stop_mask, req, left, ring);
+  PDN_LAUNCH_CHECK();
+  pdn_count(PDN_CNT_SAMPLE);
+  pdn_count(PDN_CNT_DECODE_SLOTS);
+  if (PER) pdn_count(PDN_CNT_PERSAMPLE);
+  return PDN_OK;
+}
+
 extern "C" int pdn_decode_sample_tick_slots_f32(const float* logits, int64_t row_stride, int B, int V, const void* params,
                                                 int64_t* next_ids, int* pos, int* step, const int* req, int* left,
                                                 int ring, const unsigned* stop_mask, int64_t* const* history,
                                                 const float* emb, int64_t emb_row_stride, int D, float* x_next,
                                                 void* stream) {
-  if (B == 0) return PDN_OK;
-  PDN_CHECK_ARG(logits && params && next_ids && pos && step && req && left && ring > 0 && B > 0 && V > 0 &&
-                    V <= (1 << 23) && row_stride >= V,
-                "pdn_decode_sample_tick_slots_f32: bad arguments (B %d, V %d, ring %d)", B, V, ring);
-  PDN_CHECK_ARG(!emb || (x_next && D > 0), "pdn_decode_sample_tick_slots_f32: an embedding table needs x_next and D");
-  hipLaunchKernelGGL((decode_sample_tick_kernel<true, true>), dim3(1), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
-                     row_stride, B, V, (const SampleParams*)params, next_ids, pos, history, emb, emb_row_stride, D, x_next,
-                     step, stop_mask, req, left, ring);
-  PDN_LAUNCH_CHECK();
-  pdn_count(PDN_CNT_SAMPLE);
-  pdn_count(PDN_CNT_DECODE_SLOTS);
-  return PDN_OK;
+  return sample_tick_slots<false>("pdn_decode_sample_tick_slots_f32", logits, row_stride, B, V, params, next_ids, pos,
+                                  step, req, left, ring, stop_mask, history, emb, emb_row_stride, D, x_next, stream);
+}
+
+extern "C" int pdnq_decode_sample_tick_slots_f32(const float* logits, int64_t row_stride, int B, int V, const void* params,
+                                                 int64_t* next_ids, int* pos, int* step, const int* req, int* left,
+                                                 int ring, const unsigned* stop_mask, int64_t* const* history,
+                                                 const float* emb, int64_t emb_row_stride, int D, float* x_next,
+                                                 void* stream) {
+  return sample_tick_slots<true>("pdnq_decode_sample_tick_slots_f32", logits, row_stride, B, V, params, next_ids, pos,
+                                 step, req, left, ring, stop_mask, history, emb, emb_row_stride, D, x_next, stream);
 }

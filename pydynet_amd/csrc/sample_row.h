@@ -11,9 +11,11 @@ struct SampleParams {
   float temperature;
   int top_k;
   float top_p;
+  float min_p;                                       // (the former padding: 0 = off; read by the per-row launches only)
   uint64_t seed;
 };
-static_assert(sizeof(SampleParams) == 24 && offsetof(SampleParams, seed) == 16, "pdn_sample_params layout");
+static_assert(sizeof(SampleParams) == 24 && offsetof(SampleParams, min_p) == 12 && offsetof(SampleParams, seed) == 16,
+              "pdn_sample_params layout");
 
 #define SMP_THREADS 1024
 #define SMP_WAVES (SMP_THREADS / 64)
@@ -131,7 +133,52 @@ __device__ __forceinline__ unsigned smp_select(const float* __restrict__ row, in
   return prefix;
 }
 
-// the sampled token of one row (every thread of the workgroup calls it and gets the token)
+// The draw of smp_row: chunk sums, block scan, the chunk holding the target is walked by its thread.  MINP: both the chunk
+// sums and the walk skip a token whose integer weight is below `wmin` (MINP = false is the draw of before min_p, instruction
+// for instruction).  `arg`: the row's first maximum, the token of a row whose kept mass is 0 (only with NaNs).
+template <bool MINP>
+__device__ __forceinline__ int smp_draw(const float* __restrict__ row, int V, unsigned floor, float mx, float T,
+                                        unsigned long long wmin, uint64_t t, uint64_t b, uint64_t seed, int arg,
+                                        SmpShared& s) {
+  const int tid = threadIdx.x;
+  const int C = (V + SMP_THREADS - 1) / SMP_THREADS;
+  const int lo = min(tid * C, V), hi = min(lo + C, V);
+  unsigned long long part = 0;
+  for (int i = lo; i < hi; ++i) {
+    const float z = row[i];
+    if (smp_key(z) >= floor) {
+      const unsigned long long w = smp_weight(z, mx, T);
+      if (!MINP || w >= wmin) part += w;
+    }
+  }
+  if (tid == 0) s.tok = arg;
+  unsigned long long W;
+  const unsigned long long incl = smp_scan(part, s, &W);
+  // u * W with u = r * 2^-24: the token is the first whose inclusive prefix exceeds floor(r * W / 2^24)
+  const unsigned long long r = smp_philox_w0(t, b, seed) >> 40;
+  const unsigned long long target = r * (W >> 24) + ((r * (W & 0xFFFFFFull)) >> 24);
+  const unsigned long long excl = incl - part;
+  if (W > 0 && excl <= target && target < incl) {
+    unsigned long long run = excl;
+    for (int i = lo; i < hi; ++i) {
+      const float z = row[i];
+      if (smp_key(z) >= floor) {
+        const unsigned long long w = smp_weight(z, mx, T);
+        if (!MINP || w >= wmin) {
+          run += w;
+          if (run > target) { s.tok = i; break; }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  return s.tok;
+}
+
+// the sampled token of one row (every thread of the workgroup calls it and gets the token).  MINP: the block's min_p is
+// honoured (the per-row launches of include/pdn_persample.h); MINP = false is the sampler of before, which never reads it
+// (the shared-parameter launches, whose callers write 0 there).
+template <bool MINP = false>
 __device__ __forceinline__ int smp_row(const float* __restrict__ row, int V, const SampleParams prm, uint64_t t,
                                        uint64_t b, SmpShared& s) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -156,37 +203,19 @@ __device__ __forceinline__ int smp_row(const float* __restrict__ row, int V, con
     if (s.fmax[w] > mx || (s.fmax[w] == mx && s.farg[w] < arg)) { mx = s.fmax[w]; arg = s.farg[w]; }
   if (arg == 0x7fffffff) arg = 0;                    // (a row of NaNs: token 0, as numpy.argmax)
   const float T = prm.temperature;
-  if (!(T > 0.f)) return arg;                         // (the host never asks: T = 0 is the greedy path)
+  if (!(T > 0.f)) {                                   // (uniform) a greedy request among sampled ones: its first maximum
+    __syncthreads();                                  // (fmax / farg are rewritten by the next row of a one-workgroup tick)
+    return arg;
+  }
 
   unsigned floor = 0;
   if (prm.top_k > 0 && prm.top_k < V) floor = smp_select<false>(row, V, 0u, mx, T, 1.f, (unsigned long long)prm.top_k, s);
   if (prm.top_p < 1.f) floor = smp_select<true>(row, V, floor, mx, T, prm.top_p, 0ull, s);
 
-  // draw: chunk sums, block scan, the chunk holding the target is walked by its thread
-  const int C = (V + SMP_THREADS - 1) / SMP_THREADS;
-  const int lo = min(tid * C, V), hi = min(lo + C, V);
-  unsigned long long part = 0;
-  for (int i = lo; i < hi; ++i) {
-    const float z = row[i];
-    if (smp_key(z) >= floor) part += smp_weight(z, mx, T);
-  }
-  if (tid == 0) s.tok = arg;                         // (kept mass 0: only with NaNs)
-  unsigned long long W;
-  const unsigned long long incl = smp_scan(part, s, &W);
-  // u * W with u = r * 2^-24: the token is the first whose inclusive prefix exceeds floor(r * W / 2^24)
-  const unsigned long long r = smp_philox_w0(t, b, prm.seed) >> 40;
-  const unsigned long long target = r * (W >> 24) + ((r * (W & 0xFFFFFFull)) >> 24);
-  const unsigned long long excl = incl - part;
-  if (W > 0 && excl <= target && target < incl) {
-    unsigned long long run = excl;
-    for (int i = lo; i < hi; ++i) {
-      const float z = row[i];
-      if (smp_key(z) >= floor) {
-        run += smp_weight(z, mx, T);
-        if (run > target) { s.tok = i; break; }
-      }
-    }
-  }
-  __syncthreads();
-  return s.tok;
+  // min_p (include/pdn_persample.h): of the tokens kept so far, those whose weight is below min_p times the largest (the
+  // maximum's, 2^40) leave the draw.  The threshold in the weights' integer units, once per row; min_p = 0 (off) takes the
+  // draw of before (uniform over the workgroup: every thread holds the same block).
+  if (MINP && prm.min_p > 0.f)
+    return smp_draw<true>(row, V, floor, mx, T, (unsigned long long)(prm.min_p * 1099511627776.f), t, b, prm.seed, arg, s);
+  return smp_draw<false>(row, V, floor, mx, T, 0ull, t, b, prm.seed, arg, s);
 }

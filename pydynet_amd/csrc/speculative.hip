@@ -92,6 +92,8 @@ __global__ __launch_bounds__(256) void spec_pick_kernel(const float* __restrict_
 }
 
 // grid B (k + 1), SMP_THREADS threads: the draw of sample.hip for each live query row, counter (its position, its row)
+// PER (include/pdn_persample.h): query row r uses parameter block prm[r / K1], its row's, else *prm.
+template <bool PER>
 __global__ __launch_bounds__(SMP_THREADS) void spec_sample_kernel(const float* __restrict__ logits, int64_t rs, int V,
                                                                   const SampleParams* __restrict__ prm, int K1,
                                                                   const int* __restrict__ qpos,
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(SMP_THREADS) void spec_sample_kernel(const float* _
   const int r = blockIdx.x;
   const int p = qpos[r];
   if (p < 0) return;                             // (uniform)
-  const int64_t t = smp_row(logits + (int64_t)r * rs, V, *prm, (uint64_t)p, (uint64_t)(r / K1), s);
+  const int64_t t = smp_row<PER>(logits + (int64_t)r * rs, V, prm[PER ? r / K1 : 0], (uint64_t)p, (uint64_t)(r / K1), s);
   if (threadIdx.x == 0) picks[r] = t;
 }
 
@@ -183,18 +185,40 @@ extern "C" int pdn_spec_verify_pick_tick_f32(const float* blk_max, const int* bl
   return PDN_OK;
 }
 
-extern "C" int pdn_spec_verify_sample_tick_f32(const float* logits, int64_t row_stride, int V, const void* params,
-                                               const int64_t* tokens, const int* qpos, int B, int k, int64_t* picks,
-                                               int* hist, int hist_stride, int* hist_len, int* pos, int* left,
-                                               const int* stop_mask, int* step, int64_t* const* mailbox, void* stream) {
-  SP_TICK_CHECK("pdn_spec_verify_sample_tick_f32");
-  PDN_CHECK_ARG(logits && params && V > 0 && row_stride >= V, "pdn_spec_verify_sample_tick_f32: bad logits (V %d)", V);
-  hipLaunchKernelGGL(spec_sample_kernel, dim3(B * (k + 1)), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
+// PER: the pdnq_ form of include/pdn_persample.h, `params` = B blocks.
+template <bool PER>
+static int spec_verify_sample_tick(const float* logits, int64_t row_stride, int V, const void* params,
+                                   const int64_t* tokens, const int* qpos, int B, int k, int64_t* picks, int* hist,
+                                   int hist_stride, int* hist_len, int* pos, int* left, const int* stop_mask, int* step,
+                                   int64_t* const* mailbox, void* stream) {
+  const char* name = PER ? "pdnq_spec_verify_sample_tick_f32" : "pdn_spec_verify_sample_tick_f32";
+  PDN_CHECK_ARG(tokens && qpos && picks && hist && hist_len && pos && left && step && B > 0 && k >= 0 && k <= SP_MAX_K &&
+                    (int64_t)B * (k + 1) <= 65535 && hist_stride > 0,
+                "%s: bad arguments (B %d, k %d, history stride %d)", name, B, k, hist_stride);
+  PDN_CHECK_ARG(logits && params && V > 0 && row_stride >= V, "%s: bad logits (V %d)", name, V);
+  hipLaunchKernelGGL(spec_sample_kernel<PER>, dim3(B * (k + 1)), dim3(SMP_THREADS), 0, (hipStream_t)stream, logits,
                      row_stride, V, (const SampleParams*)params, k + 1, qpos, picks);
   PDN_LAUNCH_CHECK();
   hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(SP_THREADS), 0, (hipStream_t)stream, tokens, qpos, picks, B, k,
                      hist, hist_stride, hist_len, pos, left, (const unsigned*)stop_mask, step, mailbox);
   PDN_LAUNCH_CHECK();
   pdn_count(PDN_CNT_SPECULATE);
+  if (PER) pdn_count(PDN_CNT_PERSAMPLE);
   return PDN_OK;
+}
+
+extern "C" int pdn_spec_verify_sample_tick_f32(const float* logits, int64_t row_stride, int V, const void* params,
+                                               const int64_t* tokens, const int* qpos, int B, int k, int64_t* picks,
+                                               int* hist, int hist_stride, int* hist_len, int* pos, int* left,
+                                               const int* stop_mask, int* step, int64_t* const* mailbox, void* stream) {
+  return spec_verify_sample_tick<false>(logits, row_stride, V, params, tokens, qpos, B, k, picks, hist, hist_stride,
+                                        hist_len, pos, left, stop_mask, step, mailbox, stream);
+}
+
+extern "C" int pdnq_spec_verify_sample_tick_f32(const float* logits, int64_t row_stride, int V, const void* params,
+                                                const int64_t* tokens, const int* qpos, int B, int k, int64_t* picks,
+                                                int* hist, int hist_stride, int* hist_len, int* pos, int* left,
+                                                const int* stop_mask, int* step, int64_t* const* mailbox, void* stream) {
+  return spec_verify_sample_tick<true>(logits, row_stride, V, params, tokens, qpos, B, k, picks, hist, hist_stride,
+                                       hist_len, pos, left, stop_mask, step, mailbox, stream);
 }

@@ -11,7 +11,7 @@ import numpy as np
 from . import logit_edits as edit_np
 from . import logprobs as lp_np
 from . import penalties as pen_np
-from .sampling import params_bytes
+from .sampling import Table, params_bytes
 
 
 # the entry points of the wide step: a library (or ABI stand-in) without them keeps B > 8 on the generic step
@@ -27,6 +27,11 @@ _PEN_ENTRIES = ("pdn_penalty_chunks", "pdn_penalty_reset", "pdn_penalty_step_f32
 # the entry points of the logit edits (csrc/logit_edit.hip, include/pdn_logitedit.h): without them every path applies the
 # statement of llm/logit_edits.py
 _EDIT_ENTRIES = ("pdne_logit_edit_chunks", "pdne_logit_edit_reset", "pdne_logit_edit_step_f32", "pdne_logit_edit_rows_f32")
+# the per-row sampled launches (include/pdn_persample.h): without them a run with a parameter table leaves the graph path and
+# every draw applies the statement of llm/sampling.py row by row
+_PERSAMPLE_ENTRIES = ("pdnq_sample_rows_f32", "pdnq_decode_sample_tick_rows_f32", "pdnq_decode_sample_tick_slots_f32",
+                      "pdnq_decode_wide_sample_tick_rows_f32", "pdnq_decode_wide_sample_tick_slots_f32",
+                      "pdnq_spec_verify_sample_tick_f32")
 # ring slots of the log-probability records of a decode plan (csrc/logprobs.hip): more than the steps ever in flight
 _LP_RING = 8
 
@@ -50,7 +55,7 @@ class DecodePlan:
         return mask.view(np.int32)
 
     def _decode_plan(self, B, sampling=False, ragged=False, serve=False, beam=0, n_stops=0, penalty=False, n_lp=None,
-                     edit=False):
+                     edit=False, per_row=False):
         """Buffers and weight views of the graph-replayable decode step (csrc/decode.hip), or None when the
         model's shapes / layout are outside what those kernels take (then the generic launches below run).
         `sampling`: the step ends in the sample tick (csrc/sample.hip) instead of the greedy pick; its parameters live in
@@ -75,7 +80,10 @@ class DecodePlan:
         full logit rows, and pdne_logit_edit_step_f32 edits them before the tick (after the penalty kernel); the rows'
         allowed bits, bias tables and prompt lengths live in the plan (`edit_allow`, `edit_allow_on`, `edit_bias_ids`,
         `edit_bias_val`, `edit_bias_n`, `edit_start`), min_new_tokens in `edit_params`.  A greedy plan's `cand_v` / `cand_i`
-        then hold the candidates of that kernel.  None when the library lacks the entries."""
+        then hold the candidates of that kernel.  None when the library lacks the entries.
+        `per_row` (a sampled run of generate_ragged / serve with a parameter table, llm/sampling.Table; with `ragged`):
+        `params` holds a block per row, (B, 3) int64, and the step ends in the pdnq_ tick of include/pdn_persample.h, where
+        row b is drawn with block b.  None when the library lacks the entries."""
         from .. import hipnp as hp, _lib
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
         st = getattr(self, "_decode_st", None)
@@ -88,6 +96,7 @@ class DecodePlan:
                cache_len, tuple(ptrs), bool(sampling), wide,   # (the addresses: no hash to collide)
                (int(beam), int(n_stops), bool(penalty)), bool(ragged), bool(serve)) + (() if n_lp is None else (int(n_lp),))
         key += ("edit",) if edit else ()
+        key += ("per_row",) if per_row else ()
         if st is not None and st["key"] == key:
             return st if st["ok"] else None
         if st is not None:
@@ -101,6 +110,8 @@ class DecodePlan:
         if penalty and not all(_lib.provides(n) for n in _PEN_ENTRIES):
             ok = False
         if edit and not all(_lib.provides(n) for n in _EDIT_ENTRIES):
+            ok = False
+        if per_row and not all(_lib.provides(n) for n in _PERSAMPLE_ENTRIES):
             ok = False
         packs = []
         if ok:
@@ -117,7 +128,7 @@ class DecodePlan:
         st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged), "serve": bool(serve),
               "wide": wide, "rows": bool(ragged or wide), "beam": int(beam),
               "full": bool(sampling or beam or penalty or edit),
-              "pen": bool(penalty), "lp_n": n_lp, "edit": bool(edit)}
+              "pen": bool(penalty), "lp_n": n_lp, "edit": bool(edit), "per_row": bool(per_row)}
         if ok:
             nblk = _lib.lib().query("pdn_decode_wide_blocks" if wide else "pdn_decode_gemv_blocks", V)
             # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
@@ -130,7 +141,8 @@ class DecodePlan:
                       # only ITS address), so arrays returned earlier are never rewritten
                       hist_ptr=hp.zeros((1,), np.int64), hist=None,
                       # pdn_sample_params of the current generation (written before its first step; sampling plans only)
-                      params=hp.zeros((3,), np.int64) if sampling else None, params_val=None,
+                      # (a plan with a parameter table: a block per row)
+                      params=hp.zeros((B, 3) if per_row else (3,), np.int64) if sampling else None, params_val=None,
                       **{n: hp.empty((B, w), np.float32) for n, w in
                          (("x", D), ("qkv", 3 * D), ("att", ns * H * (4 + D // H)), ("gu", 2 * F), ("logits", V))})
             # three launches per layer (csrc/decode_layer.hip): the output / down projections leave per-head /
@@ -378,10 +390,14 @@ class DecodePlan:
 
     def _run_values(self, st, sampling, pen=None, edit=None):
         """The values of a run, uploaded when they differ from those in the plan (stream ordered: earlier steps read the
-        old ones): the sampling parameters, and for a run with penalties (`pen`: its llm/penalties.Rows) every row's
+        old ones): the sampling parameters (a llm/sampling.Table: row b takes request b's block; a served plan's rows take
+        theirs at admission, `_params_rows`), and for a run with penalties (`pen`: its llm/penalties.Rows) every row's
         prompt with zero counts; for a run with logit edits (`edit`: its llm/logit_edits.Rows) every row's request."""
         if st["params_val"] != sampling:
-            if sampling is not None:
+            if isinstance(sampling, Table):
+                if not st.get("serve"):
+                    self._params_rows(st, sampling, np.arange(st["B"]))
+            elif sampling is not None:
                 st["params"][...] = params_bytes(*sampling)
             st["params_val"] = sampling
         if pen is not None and st["pen_run"] is not pen:
@@ -390,6 +406,12 @@ class DecodePlan:
         if edit is not None and st["edit_run"] is not edit:
             self._edit_reset(st, np.arange(st["B"]), edit.req, edit.start, edit.spec)
             st["edit_run"] = edit
+
+    @staticmethod
+    def _params_rows(st, table, reqs):
+        """The rows of a plan with a parameter table take the blocks of requests `reqs` (B,) (< 0: a free row, whose block
+        is never read); stream ordered, so only while no step is queued that may still read the old ones."""
+        st["params"][...] = table.blocks(reqs)
 
     def _lp_read(self, st, i):
         """The records of step i (a poll of its ring slot, then marked unwritten again) as Logprobs."""
@@ -487,8 +509,9 @@ class DecodePlan:
         slot = (st["req"]._ptr, st["left"]._ptr, st["ring"]) if st["serve"] else ()
         if st["rows"]:
             slot += (st["stop"]._ptr,)
-        name = "pdn_decode%s_%s_tick%s_f32" % ("_wide" if wide else "", "sample" if st["sampling"] else "pick",
-                                               "_slots" if st["serve"] else "_rows" if st["rows"] else "")
+        name = "pdn%s_decode%s_%s_tick%s_f32" % ("q" if st["per_row"] else "", "_wide" if wide else "",
+                                                 "sample" if st["sampling"] else "pick",
+                                                 "_slots" if st["serve"] else "_rows" if st["rows"] else "")
         _lib.lib().call(name, *src, st["ids"]._ptr, *cnt, *slot, st["hist_ptr"]._ptr, emb._ptr, emb._strides[0],
                         self.embed_dim, st["x"]._ptr, s)
 

@@ -9,7 +9,8 @@ import numpy as np
 from ..core import Tensor
 from . import beam as beam_np
 from . import speculative as spec_np
-from .decode_plan import _SPEC_ENTRIES
+from .decode_plan import _PERSAMPLE_ENTRIES, _SPEC_ENTRIES
+from .sampling import Table
 
 
 class SearchEngine:
@@ -86,10 +87,12 @@ class SearchEngine:
     def _spec_begin(self, R, k, sampling):
         """The plan of the speculative pass (buffers, weight views, its graph), kept across calls while the model's arrays
         and (B, k, sampling) stay; then this run's row state uploaded.  None when the library or the model's layout
-        refuses it."""
+        refuses it.  `sampling` a llm/sampling.Table: a parameter block per row and the pdnq_ verify tick (include/
+        pdn_persample.h); None when the library lacks those entries."""
         from .. import hipnp as hp, _lib
         B = len(R.out)
-        if not self._spec_ok(B, k):
+        per_row = isinstance(sampling, Table)
+        if not self._spec_ok(B, k) or (per_row and not all(_lib.provides(n) for n in _PERSAMPLE_ENTRIES)):
             return None
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
         cache_len = self.layers[0].attention.cache_k.shape[1]
@@ -97,6 +100,7 @@ class SearchEngine:
         if ns > 8:
             return None
         key = (B, k, bool(sampling), hp._state["device"], ns, cache_len, tuple(self._weight_ptrs()))
+        key += ("per_row",) if per_row else ()
         st = getattr(self, "_spec_st", None)
         if st is not None and st["pending"]:
             hp.synchronize()                             # (an abandoned run's passes: done before its buffers change)
@@ -121,10 +125,10 @@ class SearchEngine:
                        for a, b in ((D, 3 * D), (D, D), (F, D), (D, 2 * F), (D, V)))
             nblk = L.query("pdn_decode_wide_blocks", V)
             st = {"key": key, "B": B, "k": k, "R": Rq, "ns": ns, "hw": hw, "packs": packs, "graph": None, "nograph": False,
-                  "pending": 0, "sampling": bool(sampling), "params_val": None,
+                  "pending": 0, "sampling": bool(sampling), "params_val": None, "per_row": per_row,
                   "work": hp.zeros((max(work, 4),), np.float32),
                   "cand_v": hp.empty((Rq, nblk), np.float32), "cand_i": hp.empty((Rq, nblk), np.int32),
-                  "logits": hp.empty((Rq, V), np.float32), "params": hp.zeros((3,), np.int64),
+                  "logits": hp.empty((Rq, V), np.float32), "params": hp.zeros((B, 3) if per_row else (3,), np.int64),
                   # the rows' state (written before a run, then only by the device): history, its length, the position
                   # of the next pass, the budget; the pass counter and the address of the run's mailbox
                   "hist": hp.zeros((B, hw), np.int32), "hlen": hp.zeros((B,), np.int32), "pos": hp.zeros((B,), np.int32),
@@ -173,7 +177,8 @@ class SearchEngine:
         row = (p["tok"], p["qpos"], B, k, p["picks"], p["hist"], st["hw"], p["hlen"], p["pos"], p["left"], p["stop"],
                p["step"], p["mbox_ptr"], s)
         if full:
-            L.call("pdn_spec_verify_sample_tick_f32", p["logits"], V, V, st["params"]._ptr, *row)
+            L.call("pdnq_spec_verify_sample_tick_f32" if st["per_row"] else "pdn_spec_verify_sample_tick_f32", p["logits"], V,
+                   V, st["params"]._ptr, *row)
         else:
             L.call("pdn_spec_verify_pick_tick_f32", p["cand_v"], p["cand_i"], st["cand_v"].shape[1], *row)
 

@@ -11,7 +11,7 @@ from . import logprobs as lp_np
 from . import penalties as pen_np
 from . import prefix as prefix_np
 from .decode_plan import _MIXED_ENTRIES
-from .sampling import sample_next_rows
+from .sampling import Table, draw_rows
 
 
 class ServeEngine:
@@ -120,14 +120,15 @@ class ServeEngine:
         the token of position p - 1), which in a fresh cache holds zeros.  No pad position and no other row is written.
         `penalty`: the logits penalised for each prompt first; `edit` (llm/logit_edits.Edits): then edited for each
         request (no token generated yet).  Returns the first token of each request (counter (len_i,
-        reqs[i]) when sampled), host int64 (`n_lp`: and their Logprobs)."""
+        reqs[i]) when sampled; `sampling` a llm/sampling.Table: with request reqs[i]'s own values, through the per-row
+        standalone entry), host int64 (`n_lp`: and their Logprobs)."""
         logits = self._prefill_rows(prompts, rows)
         if penalty is not None:
             logits = self._penalize_prompt(logits, prompts, penalty)
         if edit is not None:
             logits = self._edit_rows(logits, edit, reqs, np.zeros(len(prompts), np.int64))
         lens = np.array([p.size for p in prompts], np.int64)
-        first = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, lens, *sampling, rows=reqs)
+        first = logits.argmax(-1, True) if sampling is None else draw_rows(logits, lens, sampling, reqs, rows=reqs)
         first = np.asarray(first.numpy()).reshape(-1).astype(np.int64)
         return first if n_lp is None else (first, self._logprobs_rows(logits, first, n_lp))
 
@@ -182,9 +183,10 @@ class ServeEngine:
     def _serve_begin(self, S, sampling, stops, penalty=None, n_lp=None, edit=None):
         from .. import hipnp as hp
         st = self._decode_plan(S, sampling is not None, ragged=True, serve=True, penalty=penalty is not None, n_lp=n_lp,
-                               edit=edit is not None)
+                               edit=edit is not None, per_row=isinstance(sampling, Table))
         if st is None:
             return None
+        st["table"] = sampling if st["per_row"] else None        # (the rows' blocks: written with their requests)
         if st["pending"]:
             hp.synchronize()                                     # (an abandoned run's queued steps)
         st["hist"] = hp.Mailbox(st["ring"], (S, 1), unset=np.iinfo(np.int64).min)
@@ -237,9 +239,12 @@ class ServeEngine:
 
     def _serve_write(self, st, req, pos, left, last):
         """After an admission (no step queued): the rows' state as the host keeps it -- positions (-1: free), counter
-        ids, budgets and last tokens -- written in stream order, and x = the embedding rows of those tokens."""
+        ids, budgets and last tokens -- written in stream order, and x = the embedding rows of those tokens.  A plan with a
+        parameter table: each row's block becomes its request's."""
         st["pos"][...] = pos.astype(np.int32)
         st["req"][...] = np.maximum(req, 0).astype(np.int32)
+        if st["table"] is not None:
+            self._params_rows(st, st["table"], req)
         st["left"][...] = left.astype(np.int32)
         st["ids"][...] = last.reshape(-1, 1)
         self._decode_gather(st)
@@ -418,6 +423,8 @@ class ServeEngine:
         pos[comp] = lens[comp]
         st["pos"][...] = pos.astype(np.int32)
         st["req"][...] = np.maximum(sch.req, 0).astype(np.int32)
+        if st["table"] is not None:
+            self._params_rows(st, st["table"], sch.req)
         st["left"][...] = np.where(inc | comp, sch.left, 0).astype(np.int32)
         M["qpos"][...] = qpos
         M["runs"][...] = runs

@@ -10,7 +10,7 @@ from . import logit_edits as edit_np
 from . import logprobs as lp_np
 from . import penalties as pen_np
 from .decode_plan import _EDIT_ENTRIES, _PEN_ENTRIES
-from .sampling import params_buffer, sample_next, sample_next_rows
+from .sampling import Table, draw_rows, params_buffer, sample_next, sample_next_table
 
 
 class DecodeSteps:
@@ -209,7 +209,7 @@ class DecodeSteps:
             logits = self._penalize_prompt(logits, rows, penalty)
         if edit is not None:
             logits = self._edit_rows(logits, edit, np.arange(B), np.zeros(B, np.int64))
-        nxt = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, lens, *sampling)
+        nxt = logits.argmax(-1, True) if sampling is None else draw_rows(logits, lens, sampling, np.arange(B))
         if n_lp is None:
             return nxt
         return nxt, self._logprobs_rows(logits, nxt.numpy(), n_lp)
@@ -227,7 +227,9 @@ class DecodeSteps:
             logits = self._penalize_step(logits, pen, ids.numpy(), pos)
         if edit is not None:
             logits = self._edit_step_host(logits, edit, pos)
-        nxt = logits.argmax(-1, True) if sampling is None else sample_next_rows(logits, p, *sampling, rows=req)
+        # (`sampling` a llm/sampling.Table: row b with the values of the request it holds)
+        nxt = logits.argmax(-1, True) if sampling is None else draw_rows(
+            logits, p, sampling, np.arange(len(p)) if req is None else req, rows=req)
         if pos.min() < 0:
             out = nxt.numpy().reshape(-1, 1)
             out[pos < 0] = -1
@@ -427,7 +429,7 @@ class DecodeSteps:
         pos = np.where(live, lens + i, -1).astype(np.int32)
         n_lp = run.get("lp")
         st = self._decode_plan(B, sampling is not None, ragged=True, penalty=run.get("pen") is not None, n_lp=n_lp,
-                               edit=run.get("edit") is not None)
+                               edit=run.get("edit") is not None, per_row=isinstance(sampling, Table))
         if st is None:
             out = self._decode_step_generic_rows(ids, pos, sampling, pen=run.get("pen"), n_lp=n_lp, edit=run.get("edit"))
             out, lp = out if n_lp is not None else (out, None)
@@ -516,6 +518,12 @@ class DecodeSteps:
             self._eager_ffn(layer, ws, gemv)
 
         def draw(out):                                # (counter (pos[b], b): the per-row tick on scratch copies)
+            if isinstance(sampling, Table):           # (a block per row: the per-row standalone entry, or the statement)
+                rq = np.arange(B) if req is None else np.asarray(req, np.int64).reshape(B)
+                dev = self.tok_embedding.weight.device
+                got = sample_next_table(Tensor(ws["logits"], dtype=np.float32, device=dev, copy=False), p, sampling, rq, rq)
+                out[...] = got.data
+                return
             pd, step = hp.asarray(p.astype(np.int32)), hp.zeros((1,), np.int32)
             if req is not None:                       # (counter (pos[b], req[b]): the slot tick, a budget of one token)
                 rq, left = hp.asarray(np.asarray(req, np.int32).reshape(B)), hp.asarray(np.ones(B, np.int32))

@@ -34,7 +34,7 @@ from .decode_plan import DecodePlan
 from .decode_search import SearchEngine
 from .decode_serve import ServeEngine
 from .decode_steps import DecodeSteps
-from .sampling import check_args as check_sampling_args
+from .sampling import active as active_sampling, check_args as check_sampling_args, check_request_args
 
 
 def compute_cos_sin_cache(head_dim: int, max_seq_len: int, base: int = 10000, dtype=None):
@@ -448,7 +448,7 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
 
     def generate_ragged(self, prompts, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
                         speculate=0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                        logprobs=None, logit_bias=None, allowed_token_ids=None, min_new_tokens=0):
+                        logprobs=None, logit_bias=None, allowed_token_ids=None, min_new_tokens=0, min_p=0.0):
         """Generation for B prompts of different lengths, every row at its own position.  Yields a (B, 1) int64 Tensor
         per step: step i holds, for row b, the token at position len_b + i.  `max_new_tokens` is the number of NEW tokens
         per row -- `generate`'s second argument is an end position instead: for equal lengths L,
@@ -469,8 +469,12 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         `logit_bias` / `allowed_token_ids`: as in `generate` (llm/logit_edits.py), one value or one per prompt;
         `min_new_tokens` = m: no row yields a stop id before it has produced m tokens (needs `stop_ids`).  Not with
         speculate > 0.
+        `min_p` (llm/sampling.py; 0 = off): after top-k and top-p, only tokens whose probability is at least min_p times
+        the largest stay in the draw.  Each of `temperature`, `top_k`, `top_p`, `seed` and `min_p` is one value or a
+        sequence with one value per row, mixed freely: row b is then drawn with its own values, key (seed_b, 0) and
+        counter (t, b); a row with temperature 0 in a run that samples takes the first maximum of its logits, and a run
+        whose temperatures are all 0 is the greedy run.  The penalties stay one set of values for every row.
         Every argument is checked here (ValueError), before anything runs."""
-        temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
         V = self.vocab_size
         if int(max_new_tokens) != max_new_tokens or max_new_tokens < 0:
             raise ValueError(f"max_new_tokens must be a non-negative integer, got {max_new_tokens}")
@@ -479,6 +483,7 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         cache = self.layers[0].attention.cache_k
         if not rows:
             raise ValueError("generate_ragged needs at least one prompt")
+        sampling = active_sampling(check_request_args(temperature, top_k, top_p, seed, min_p, len(rows), "row"))
         k = spec_np.check_speculate(speculate, len(rows))
         penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty, k)
         n_lp = lp_np.check_n(logprobs)
@@ -500,7 +505,6 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         if stops.size and (stops.min() < 0 or stops.max() >= V):
             raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
         edit = edit_np.check_args(logit_bias, allowed_token_ids, min_new_tokens, V, len(rows), stops, k)
-        sampling = (temperature, top_k, top_p, seed) if temperature > 0 else None
         self.last_speculation = None if k == 0 else spec_np.counts()
         if k:
             return self._speculate([r.astype(np.int64) for r in rows], max_new_tokens, k, sampling, stops)
@@ -517,7 +521,7 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
     # -- continuous batching (serve): a finished row takes the next waiting request -------------------------------
     def serve(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
               prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=None,
-              prefix_cache=False, logit_bias=None, allowed_token_ids=None, min_new_tokens=0):
+              prefix_cache=False, logit_bias=None, allowed_token_ids=None, min_new_tokens=0, min_p=0.0):
         """Continuous batching: N requests (`prompts`, N may exceed max_batch_size) through `slots` decode rows
         (default min(N, max_batch_size)).  A row frees when its request yields a stop id or uses up its budget
         (`max_new_tokens`: one int, or one per request; 0 = the request yields nothing and never takes a row).  Before
@@ -549,8 +553,13 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         hits, prompt_tokens, reused_tokens, copies, launches) as it goes; with the cache off it is left alone.
         `logit_bias` / `allowed_token_ids` (llm/logit_edits.py): one value for every request, or a sequence with one value
         (or None) per request -- a request's edits follow it into whichever row it runs in; `min_new_tokens` = m: no
-        request yields a stop id before it has produced m tokens (needs `stop_ids`)."""
-        temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
+        request yields a stop id before it has produced m tokens (needs `stop_ids`).
+        `temperature` / `top_k` / `top_p` / `seed` / `min_p` (llm/sampling.py): each one value for every request, or a
+        sequence with one value per request, mixed freely -- a greedy request (temperature 0) shares the batch with
+        sampled ones, and two requests may differ in temperature or seed.  The promise above holds per request: request
+        r's tokens are those of row r of `generate_ragged(prompts, max(budgets), <r's own values for every row>)`, drawn
+        with key (seed_r, 0) and counter (t, r), whichever row it runs in and whatever the other requests' values are.
+        The penalties are not per request: they stay one set of values for the call."""
         penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty)
         n_lp = lp_np.check_n(logprobs)
         k_pre = prefix_np.check_arg(prefix_cache, prefill_chunk)
@@ -559,6 +568,7 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         if not rows:
             raise ValueError("serve needs at least one prompt")
         N = len(rows)
+        sampling = active_sampling(check_request_args(temperature, top_k, top_p, seed, min_p, N))
         budgets = [max_new_tokens] * N if np.ndim(max_new_tokens) == 0 else list(max_new_tokens)
         if len(budgets) != N:
             raise ValueError(f"max_new_tokens: {len(budgets)} budgets for {N} prompts")
@@ -587,7 +597,6 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         if stops.size and (stops.min() < 0 or stops.max() >= V):
             raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
         edit = edit_np.check_args(logit_bias, allowed_token_ids, min_new_tokens, V, N, stops)
-        sampling = (temperature, top_k, top_p, seed) if temperature > 0 else None
         C = chunked.check_chunk(prefill_chunk, slots)
         if C is not None:
             return self._serve_chunked([p.astype(np.int64) for p in rows], budgets, int(slots), C, sampling, stops,
@@ -596,12 +605,13 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
 
     def serve_all(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
                   prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                  logprobs=None, prefix_cache=False, logit_bias=None, allowed_token_ids=None, min_new_tokens=0):
+                  logprobs=None, prefix_cache=False, logit_bias=None, allowed_token_ids=None, min_new_tokens=0,
+                  min_p=0.0):
         """`serve` run to the end: a list of N int64 arrays, request r's generated tokens in order.  `logprobs` = n: a
         list of (tokens, Logprobs) instead, the arrays of length k / (k, n) for a request's k tokens."""
         it = self.serve(prompts, max_new_tokens, slots, temperature, top_k, top_p, seed, stop_ids, prefill_chunk,
                         repetition_penalty, presence_penalty, frequency_penalty, logprobs, prefix_cache, logit_bias,
-                        allowed_token_ids, min_new_tokens)
+                        allowed_token_ids, min_new_tokens, min_p)
         out = [[] for _ in range(len(prompts))]
         lps = [[] for _ in range(len(prompts))]
         for step in it:
