@@ -128,7 +128,14 @@ int pdn_comm_allgather(void* comm, const void* send, void* recv, int64_t bytes_p
  *       switch says: behind the 64 slabs (64 * 288 * N * nbatch * 4 bytes), at the next multiple of 256 bytes,
  *       (K / 32) * 36864 + 1152 bytes.  A caller that passes the size less those bytes gets the fp32 kernel, silently and
  *       correctly: the in-process A/B switch.
- * Nothing is allocated inside the call (it may run on a capturing stream).  Counter slot 42, and 15 as before. */
+ * Nothing is allocated inside the call (it may run on a capturing stream).  Counter slot 42, and 15 as before.
+ * The down-projection weight gradient -- one batch, A = h^T (M x K, a_rs 1, a_cs >= M), B = g2 (K x 288, b_cs 1), N == 288,
+ * M a multiple of 16 from 512 to 1024, K >= 32768 a multiple of 32, alpha 1, any beta, no bias, residual or b_colsum, a_cs
+ * and b_rs multiples of 4, 16-byte aligned operands and workspace -- takes the same split-fp16 kernel with the roles swapped
+ * (g2 as the plane images, h under the running exponent; the kernel stores the transpose, so its slabs are M x 288
+ * row-major) under the same two conditions: (a) as above, (b) the same extra region, (K / 32) * 36864 + 1152 bytes at the
+ * next multiple of 256 bytes behind the 64 slabs (64 * M * 288 * 4 bytes), which pdn_gemm_f32_workspace_bytes(M, 288, K, 1)
+ * includes for these shapes.  With the slabs only the wave-streaming fp32 kernel runs.  Counter slot 50 only. */
 int pdn_gemm_f32(int M, int N, int K, float alpha, const float* A, int64_t a_rs, int64_t a_cs,
                  const float* B, int64_t b_rs, int64_t b_cs, float beta, float* C, int64_t ldc,
                  const float* bias, int nb1, int nb2, int64_t a_bs1, int64_t a_bs2,
@@ -229,7 +236,11 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *     or 46.  Not taken under PDN_OUTRES_SPLIT=0, pdn_gemm_rowtile_mode(3), PDN_GEMM_NO_OUTRES / PDN_GEMM_NO_ROWRES, on a
  *     stream that is being captured, or when A, B or the residual overlap C (a residual that IS C is taken)
  *  48 allowed sets, logit_bias and min_new_tokens of a decode step (csrc/logit_edit.hip): once per launch of
- *     pdne_logit_edit_reset, pdne_logit_edit_step_f32 and pdne_logit_edit_rows_f32 of include/pdn_logitedit.h */
+ *     pdne_logit_edit_reset, pdne_logit_edit_step_f32 and pdne_logit_edit_rows_f32 of include/pdn_logitedit.h
+ *  49 sampling parameters per row (include/pdn_persample.h): once per pdnq_* entry
+ *  50 down-projection weight gradient on split-fp16 MFMA (csrc/outres_tn_split.hip, transposed store): no entry of its own,
+ *     the form pdn_gemm_f32 takes for h^T (M x K) against g2 (K x 288), M = 512 .. 1024, at 32768 tokens and more (see
+ *     there): counts here ONLY, not in 15 or 42 */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores

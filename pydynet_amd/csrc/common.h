@@ -83,7 +83,9 @@ enum {
                                   // include/pdn_logitedit.h): once per launching pdne_* entry
   PDN_CNT_PERSAMPLE = 49,         // sampling parameters per row (include/pdn_persample.h): once per pdnq_* entry, each of which
                                   // also counts where its shared-parameter form counts
-  PDN_CNT_SLOTS = 50
+  PDN_CNT_DOWN_DW_SPLIT = 50,     // down-projection weight gradient (M x 288 = h^T g2, M = 512 .. 1024, K >= 32768) of pdn_gemm_f32 on
+                                  // split-fp16 MFMA (csrc/outres_tn_split.hip, transposed store): counts HERE ONLY, not in 15 or 42
+  PDN_CNT_SLOTS = 51
 };
 void pdn_count(int slot);
 

@@ -215,9 +215,10 @@ extern "C" int64_t pdn_gemm_f32_workspace_bytes(int M, int N, int K, int nbatch)
   // Enough for up to 64 splits of one output; pdn_gemm_f32 never uses more than it is given.
   // [64 slabs | the shapes of the split-fp16 packed weight gradients (288 rows, two or more blocks, K >= 32768): x's fp16
   //  plane images and 288 exponents, LAST, at the next multiple of 256 bytes: (K / 32) * 36864 + 1152 bytes, whatever
-  //  PDN_OUTRES_TN_SPLIT says]
+  //  PDN_OUTRES_TN_SPLIT says; the same region for the down-projection weight gradient: one batch, N == 288, M = 512 .. 1024
+  //  a multiple of 16, K >= 32768 a multiple of 32]
   const int64_t base = (int64_t)64 * M * N * (int64_t)nbatch * 4;
-  if (!pdn_outres_tn_split_supported(M, N, nbatch, K)) return base;
+  if (!pdn_outres_tn_split_supported(M, N, nbatch, K) && !(nbatch == 1 && pdn_down_dw_split_supported(M, N, K))) return base;
   return ((base + 255) & ~(int64_t)255) + pdn_outres_tn_split_extra_bytes(K);
 }
 
@@ -538,6 +539,34 @@ static int gemm_f32_impl(int M, int N, int K, float alpha, const float* A, int64
         }
         return PDN_OK;
       }
+    }
+  }
+  // ---- the down-projection weight gradient dW_down (M x 288) = h^T (M x K) g2 (K x 288), M = 512 .. 1024 in whole waves,
+  // from 32768 tokens on: the split-fp16 TN kernel with the roles swapped (g2 the plane-image operand, h the raw one) and a
+  // transposed store (csrc/outres_tn_split.hip), its slabs combined (with beta) by the reduce below.  Taken when switched on
+  // (PDN_OUTRES_TN_SPLIT), with 16-byte aligned operands and a workspace that holds the extra region behind the 64 slabs; a
+  // caller that passes only the slabs gets the wave-streaming fp32 kernel (the in-process A/B switch).
+  if (nbatch == 1 && !ext_on && a_rs == 1 && b_cs == 1 && alpha == 1.f && !b_colsum && !bias && !residual &&
+      pdn_down_dw_split_supported(M, N, K) && a_cs >= M && b_rs >= N && m4(a_cs) && m4(b_rs) && al16(A) && al16(B) && workspace &&
+      al16(workspace) && pdn_outres_tn_split_enabled() && !getenv("PDN_GEMM_NO_OUTRES")) {
+    const int64_t xoff = (((int64_t)64 * M * N * 4 + 255) & ~(int64_t)255);
+    const int ranges = pdn_down_dw_split_ranges(M, K);
+    const int kps = ((K / 32 + ranges - 1) / ranges) * 32;
+    const int splits = (K + kps - 1) / kps;
+    if (workspace_bytes >= xoff + pdn_outres_tn_split_extra_bytes(K) && splits > 1 && splits <= 64) {
+      if (getenv("PDN_GEMM_DEBUG"))
+        fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> output-resident TN, split-fp16, transposed (splits %d)\n", M, N, K, splits);
+      const int tk = pdn_gemm_prof_begin(4, 2.0 * M * (double)N * (double)K, 0.0, stream);
+      const int rc = pdn_down_dw_split_launch(B, A, (float*)workspace, M, K, b_rs, a_cs, kps, (char*)workspace + xoff, stream);
+      if (rc) { pdn_gemm_prof_end(tk, stream); return rc; }
+      p.splits = splits;
+      const int64_t total = (int64_t)M * N;
+      const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+      const int rvec = (ldc % 4 == 0) && al16(C);
+      hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, p, 1, rvec);
+      PDN_LAUNCH_CHECK();
+      pdn_gemm_prof_end(tk, stream);
+      return PDN_OK;
     }
   }
   // ---- weight-gradient form (small output, long K): wave-streaming kernel --------------------

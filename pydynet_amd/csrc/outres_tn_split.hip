@@ -72,7 +72,9 @@ __device__ __forceinline__ void ots_form2(float g0, float g1, int S, unsigned& h
 
 // ABLATE (timing experiments, PDN_OUTRES_TN_SPLIT_ABLATE; the results are WRONG): 1 = the planes of g are constants, g is
 // never read (MFMA + LDS only); 2 = g is fetched once, before the loop (no HBM stream).
-template <int ABLATE>
+// TSTORE: one block, the slabs hold the TRANSPOSE (n_all rows of 288 floats; a lane's four registers of a tile are sixteen
+// consecutive bytes of its column's row): dW_down^T = g2^T h, whose slabs are then dW_down's, row-major.
+template <int ABLATE, bool TSTORE = false>
 __global__ __launch_bounds__(512, 1) void ots_main_kernel(OtsParams p) {
   __shared__ __attribute__((aligned(1024))) char smem[stn_lds(OTS_XKIB)];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -197,10 +199,17 @@ __global__ __launch_bounds__(512, 1) void ots_main_kernel(OtsParams p) {
   for (int j = 0; j < STN_NT; ++j) {
     const int4 sv = *reinterpret_cast<const int4*>(shp + 16 * j);
     const int sh[4] = {sv.x, sv.y, sv.z, sv.w};
+    if (TSTORE) {
+      float4 o;
+      o.x = stn_unscale(acc1[j][0], acc0[j][0], Se + sh[0]); o.y = stn_unscale(acc1[j][1], acc0[j][1], Se + sh[1]);
+      o.z = stn_unscale(acc1[j][2], acc0[j][2], Se + sh[2]); o.w = stn_unscale(acc1[j][3], acc0[j][3], Se + sh[3]);
+      *reinterpret_cast<float4*>(p.C + ots_out_elem_t(by, p.slab, stn_out_row(j, q, 0), col)) = o;
+    } else {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-      p.C[ots_out_elem(by, p.slab, p.blk_stride, p.nb_cols, stn_out_row(j, q, i), col)] =
-          stn_unscale(acc1[j][i], acc0[j][i], Se + sh[i]);
+      for (int i = 0; i < 4; ++i)
+        p.C[ots_out_elem(by, p.slab, p.blk_stride, p.nb_cols, stn_out_row(j, q, i), col)] =
+            stn_unscale(acc1[j][i], acc0[j][i], Se + sh[i]);
+    }
   }
 }
 
@@ -244,6 +253,37 @@ int pdn_outres_tn_split_launch(const float* X, const float* G, float* C, int n_a
   // slot 15 as well: "packed weight gradient on the output-resident TN kernel" is what bench.py asks for, whichever pipe ran it
   pdn_count(PDN_CNT_OUTRES_TN);
   pdn_count(PDN_CNT_OUTRES_TN_SPLIT);
+  PDN_LAUNCH_CHECK();
+  return PDN_OK;
+}
+
+// ---- the down-projection weight gradient: dW_down (M x 288) = h^T g2 as (g2^T h)^T, one block, transposed store ----------
+// g2 (K x 288) is the plane-image operand with one exponent per column, h (K x M) the raw one under the per-wave running
+// exponent.  M in whole waves from 512 to 1024 columns (four to eight column workgroups: 32 .. 64 K ranges in one round;
+// narrower outputs have too few columns to pay for the passes, wider ones would get fewer, longer ranges than any measured).
+int pdn_down_dw_split_supported(int M, int N, int K) {
+  return (N == STN_N && M % 16 == 0 && M >= 512 && M <= 1024 && K >= OTS_MIN_K && K % STN_KP == 0) ? 1 : 0;
+}
+int pdn_down_dw_split_ranges(int M, int K) { return ots_t_ranges(M, K / STN_KP); }
+
+// slabs: K range s at C + s * M * 288, M rows of 288 floats.  `extra`: stn_extra_bytes(K, OTS_XKIB) bytes, 16-byte aligned.
+int pdn_down_dw_split_launch(const float* G2, const float* H, float* C, int M, int K, int64_t ldx, int64_t ldg, int k_per_split,
+                             void* extra, void* stream) {
+  PDN_CHECK_ARG(pdn_down_dw_split_supported(M, STN_N, K) && k_per_split > 0 && k_per_split % STN_KP == 0 &&
+                    ((((uintptr_t)G2 | (uintptr_t)H | (uintptr_t)extra | (uintptr_t)C) & 15) == 0) && (ldx & 3) == 0 &&
+                    (ldg & 3) == 0 && ldx >= STN_N && ldg >= M,
+                "pdn_down_dw_split_launch: unsupported shape or alignment (K %d, rows %d)", K, M);
+  const int ranges = (K + k_per_split - 1) / k_per_split;
+  PDN_CHECK_ARG(ranges <= OTS_MAX_RANGES, "pdn_down_dw_split_launch: %d K ranges", ranges);
+  OtsParams p;
+  memset(&p, 0, sizeof(p));
+  p.g = H; p.ximg = static_cast<const char*>(extra); p.xsh = stn_x_planes_launch(G2, ldx, K, extra, nullptr, nullptr, stream);
+  p.C = C;
+  p.n_all = M; p.nb_cols = M; p.K = K; p.k_per_split = k_per_split;
+  p.ldg = ldg; p.slab = (int64_t)STN_N * M; p.blk_stride = 0;
+  hipLaunchKernelGGL((ots_main_kernel<0, true>), dim3((unsigned)((M + STN_COLS - 1) / STN_COLS), (unsigned)ranges), dim3(512), 0,
+                     (hipStream_t)stream, p);
+  pdn_count(PDN_CNT_DOWN_DW_SPLIT);                 // here only: slots 15 and 42 stay the packed products'
   PDN_LAUNCH_CHECK();
   return PDN_OK;
 }

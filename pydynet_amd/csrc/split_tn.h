@@ -18,6 +18,12 @@ int64_t pdn_outres_tn_split_extra_bytes(int K);
 int pdn_outres_tn_split_ranges(int n_all, int K, int plan);
 int pdn_outres_tn_split_launch(const float* X, const float* G, float* C, int n_all, int K, int64_t ldx, int64_t ldg,
                                int nb_cols, int k_per_split, void* extra, void* stream);
+// ... and the down-projection weight gradient dW_down (M x 288) = h^T g2 on the same kernel with the roles swapped and a
+// transposed store (one block; slabs M x 288 row-major)
+int pdn_down_dw_split_supported(int M, int N, int K);
+int pdn_down_dw_split_ranges(int M, int K);
+int pdn_down_dw_split_launch(const float* G2, const float* H, float* C, int M, int K, int64_t ldx, int64_t ldg, int k_per_split,
+                             void* extra, void* stream);
 // csrc/lm_head_dw_split.hip: the lm_head weight gradient on split-fp16 MFMA, same slabs and column-sum slabs as
 // pdn_outres_ce_dw_launch
 int pdn_outres_ce_dw_split_enabled();

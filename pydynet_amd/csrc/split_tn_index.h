@@ -1,6 +1,7 @@
 // Index arithmetic of the split-fp16 TN pipeline (csrc/split_tn.h) and of its two users, the lm_head weight gradient
 // (csrc/lm_head_dw_split.hip, LDW_ / ldw_) and the packed layer weight gradients (csrc/outres_tn_split.hip, OTS_ / ots_),
-// shared by the kernels and two host checkers (tests/lm_head_dw_split_check.cpp, tests/outres_tn_split_check.cpp) that walk
+// shared by the kernels and the host checkers (tests/lm_head_dw_split_check.cpp, tests/outres_tn_split_check.cpp,
+// tests/down_dw_split_check.cpp: the transposed one-block form and the plane pass) that walk
 // every workgroup, wave, lane and piece: which global bytes a DMA or a store touches, where they land in LDS, and the
 // swizzles.  Nothing here depends on HIP.
 //
@@ -70,6 +71,23 @@ STN_HD int stn_x_frag(int j, int r, int q) { return j * 1024 + (r * 4 + (q ^ ((r
 STN_HD int stn_x_dma_kib(int e, int wave, int xkib) { return stn_min_i(e * 8 + wave, xkib - 1); }
 STN_HD int64_t stn_x_dma_src(int64_t piece, int I, int lane, int xkib) { return piece * stn_xpiece(xkib) + I * 1024 + lane * 16; }   // byte in the image region
 STN_HD int stn_x_dma_lds(int slot, int I, int lane, int xkib) { return slot * stn_xpiece(xkib) + I * 1024 + lane * 16; }
+// The plane pass (csrc/split_tn_planes.hip), 256 threads per piece.  Load item i (nine per thread) is the 16 bytes of token
+// row i / 72, float4 chunk i % 72 of the piece, staged raw in LDS: token t, column d at float stn_pass_lds(t, d), its chunk
+// moved on by four per quarter of the piece (modulo the row's 72), so that the sixteen columns x four quarters a wave reads
+// back sit in 64 different banks (a row is 4.5 x 64 banks: rows of one parity begin at the same bank).  Store item u (4.5
+// per thread) is unit u of either plane in IMAGE order, bytes 16 u ..: a wave stores 1 KiB of whole lines.
+#define STN_PASS_THREADS 256
+#define STN_PASS_LOADS (STN_KP * STN_N / 4 / STN_PASS_THREADS)      // 9
+STN_HD int stn_pass_row(int i) { return i / (STN_N / 4); }
+STN_HD int stn_pass_chunk(int i) { return i % (STN_N / 4); }
+STN_HD int stn_pass_lds(int t, int d) {
+  const int c = (d >> 2) + 4 * (t >> 3);
+  return t * STN_N + 4 * (c >= STN_N / 4 ? c - STN_N / 4 : c) + (d & 3);
+}
+STN_HD int stn_pass_unit_d(int u) { return u >> 2; }
+STN_HD int stn_pass_unit_q(int u) { return (u & 3) ^ ((u >> 4) & 3); }      // stn_x_unit(d, q) == 16 u
+static_assert(STN_PASS_LOADS * STN_PASS_THREADS * 4 == STN_KP * STN_N, "nine whole load items per thread");
+
 STN_HD int ldw_tail_nl(int slot, int t) { return slot * stn_xpiece(LDW_XKIB) + LDW_TAIL + 4 * t; }
 STN_HD int ldw_tail_tg(int slot, int t) { return slot * stn_xpiece(LDW_XKIB) + LDW_TAIL + 128 + 4 * t; }
 
@@ -124,6 +142,18 @@ STN_HD int ots_ranges(int n_all, int plan, int pieces) {
   return r < 1 ? 1 : r;
 }
 STN_HD int ots_k_per_split(int pieces, int ranges) { return ((pieces + ranges - 1) / ranges) * STN_KP; }
+// The one-block TRANSPOSED form (dW_down^T = g2^T h, M = 512 .. 1024 columns of h): ONE round of workgroups, as many ranges
+// as 256 workgroups hold with ceil(M / 128) column blocks (768 columns: 6 x 42 = 252, 98 pieces each at 131072 tokens, the
+// length of the fp32 running sums the 1536-column packed product already has; 6 x 64 = 384 would be two rounds of 64).
+STN_HD int ots_t_ranges(int n_all, int pieces) {
+  const int cb = (n_all + STN_COLS - 1) / STN_COLS;
+  int r = stn_min_i(OTS_MAX_RANGES, 256 / cb);
+  if (r > pieces) r = pieces;
+  return r < 1 ? 1 : r;
+}
+// its store: the lane's registers i = 0 .. 3 of tile j are rows 16 j + 4 q + i of ONE column, sixteen bytes of row `col` of
+// the (n_all x 288) slab of K range `by`: element (col, d) at
+STN_HD int64_t ots_out_elem_t(int by, int64_t slab, int d, int col) { return (int64_t)by * slab + (int64_t)col * STN_N + d; }
 // accumulator register i of tile j in lane (r, q): row 16 j + 4 q + i of dW, column 16 w + r of the block
 STN_HD int stn_out_row(int j, int q, int i) { return 16 * j + 4 * q + i; }
 // lm_head: slab of K range `by`, rows of V floats

@@ -52,21 +52,39 @@ template <int XKIB, bool TAIL>
 __device__ __forceinline__ void stn_split_x(const float* __restrict__ x, int64_t ldx, const int* __restrict__ xsh,
                                             const float* __restrict__ lse, const int64_t* __restrict__ targets, int rows,
                                             char* __restrict__ ximg) {
+  __shared__ __attribute__((aligned(16))) float raw[STN_KP * STN_N];
   char* img = ximg + (int64_t)blockIdx.x * stn_xpiece(XKIB);
   const float* xp = x + (int64_t)blockIdx.x * STN_KP * ldx;
-  for (int i = threadIdx.x; i < STN_N * 4; i += 256) {
-    const int d = i % STN_N, q = i / STN_N;
-    const int sh = xsh[d];
-    f16x8 hv, lv;
+  // the piece by 16-byte loads, all nine of a thread in flight, staged raw in LDS (the chunks of a row rotated per quarter)
+  float4 v[STN_PASS_LOADS];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      _Float16 h, l;
-      ls_split(xp[(int64_t)(8 * q + k) * ldx + d], sh, h, l);
-      hv[k] = h; lv[k] = l;
+  for (int e = 0; e < STN_PASS_LOADS; ++e) {
+    const int i = threadIdx.x + STN_PASS_THREADS * e;
+    v[e] = *reinterpret_cast<const float4*>(xp + (int64_t)stn_pass_row(i) * ldx + 4 * stn_pass_chunk(i));
+  }
+#pragma unroll
+  for (int e = 0; e < STN_PASS_LOADS; ++e) {
+    const int i = threadIdx.x + STN_PASS_THREADS * e;
+    *reinterpret_cast<float4*>(raw + stn_pass_lds(stn_pass_row(i), 4 * stn_pass_chunk(i))) = v[e];
+  }
+  __syncthreads();
+  // the units in image order: a wave's store instruction is 1 KiB of whole lines in either plane
+#pragma unroll
+  for (int e = 0; e < (STN_N * 4 + STN_PASS_THREADS - 1) / STN_PASS_THREADS; ++e) {
+    const int u = threadIdx.x + STN_PASS_THREADS * e;
+    if (u < STN_N * 4) {
+      const int d = stn_pass_unit_d(u), q = stn_pass_unit_q(u);
+      const int sh = xsh[d];
+      f16x8 hv, lv;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        _Float16 h, l;
+        ls_split(raw[stn_pass_lds(8 * q + k, d)], sh, h, l);
+        hv[k] = h; lv[k] = l;
+      }
+      *reinterpret_cast<f16x8*>(img + 16 * u) = hv;
+      *reinterpret_cast<f16x8*>(img + STN_PLANE + 16 * u) = lv;
     }
-    char* dst = img + stn_x_unit(d, q);
-    *reinterpret_cast<f16x8*>(dst) = hv;
-    *reinterpret_cast<f16x8*>(dst + STN_PLANE) = lv;
   }
   // tail: 1 KiB = 256 dwords; dwords 0..31 -lse log2 e, 32..63 the targets, the rest zero
   if (TAIL) {
