@@ -43,33 +43,11 @@
 #include "gemm_stream.h"   // gemm_tn_stream_{,lds_,dma_}kernel, gemm_skinny_kernel
 #include "split_tn.h"      // host entry points of the split-fp16 weight gradients (pdn_outres_tn_split_*, pdn_outres_ce_dw_split_*)
 
+#include "gemm_select.h"   // TileCfg / kCfgs, the operand layout and the tiled / streaming selector (host-only)
+#include "gemm_prof.h"     // pdn_gemm_prof_begin / end, GemmProfScope
+#include "gemm_routes.h"   // what pdn_gemm_f32 routes to in the other GEMM files
+
 // ---- host side ----------------------------------------------------------------------
-struct TileCfg {
-  int waves_m, waves_n, wm, wn, bk;
-  float eff;  // relative efficiency of the tile shape (operand bytes per MFMA, barrier rate)
-};
-static const TileCfg kCfgs[] = {
-    // eff values are fitted to the round-1 tile sweep on MI355X (tools/gemm_bench.py, profiles/)
-    {2, 2, 2, 2, 32, 1.00f},  // 0: 128 x 128
-    {4, 1, 1, 3, 32, 0.97f},  // 1: 128 x  96   (N = 288 = 3*96)
-    {1, 4, 3, 1, 32, 0.95f},  // 2:  96 x 128   (M = 288, weight gradients)
-    {4, 1, 1, 2, 32, 0.85f},  // 3: 128 x  64
-    {1, 4, 2, 1, 32, 0.90f},  // 4:  64 x 128
-    {2, 2, 1, 1, 32, 0.60f},  // 5:  64 x  64
-    {2, 2, 4, 2, 16, 0.85f},  // 6: 256 x 128
-    {2, 2, 2, 4, 16, 1.10f},  // 7: 128 x 256   (only offered to very wide outputs, see below)
-    {4, 1, 2, 3, 16, 0.99f},  // 8: 256 x  96
-    {1, 4, 3, 2, 16, 0.70f},  // 9:  96 x 256
-    {2, 1, 1, 3, 32, 0.78f},  // 10: 64 x  96   (2 waves: finer quantisation for N = 288)
-    {1, 2, 3, 1, 32, 0.70f},  // 11: 96 x  64
-    {4, 1, 1, 3, 16, 1.15f},  // 12: 128 x 96, BK 16: 51 KB of LDS -> three workgroups per CU (offered selectively)
-    // (tried in round 2: {4, 1, 1, 9, 16} = 128 x 288, the whole 288-wide row panel in one workgroup so that the
-    //  65536 x 32000 dlogits operand of the lm_head input gradient is read from HBM once instead of 1.76 times
-    //  (PMC: FETCH 14.8 GB vs 8.4 GB algorithmic) -- 10.45 ms against 9.79 ms for the 96 x 128 tile: the product is
-    //  matrix-pipe bound, the re-reads are L2 / MALL hits that cost nothing; not kept)
-};
-static const int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-static const int kScalarCfg = 5;
 
 template <int WMV, int WNV, int WM, int WN, int BK, bool VEC, bool MASKS = false>
 static void launch_layout(const GemmParams& p, bool a_kin, bool b_kin, dim3 grid, hipStream_t st) {
@@ -181,36 +159,6 @@ extern "C" int pdn_gemm_prof_collect(double* total_ms, double* total_flops, int6
   return PDN_OK;
 }
 
-int pdn_gemm_outres_tn_plan(int N, int K, int* nw_out, int* k_per_split_out);
-int pdn_gemm_outres_tn_launch(const float* X, const float* G, float* C, int N, int K, int64_t ldx, int64_t ldg,
-                              int64_t ldc, int64_t slab, int nw, int k_per_split, void* stream);
-int pdn_gemm_outres_tn_blocks_launch(const float* X, const float* G, float* C, int N, int K, int64_t ldx, int64_t ldg,
-                                     int nb_cols, int nw, int k_per_split, void* stream);
-extern "C" int64_t pdn_gemm_outres_workspace_bytes(int M, int K);
-extern "C" int pdn_gemm_outres_plan(int M, int K, int* nw, int* kps);
-extern "C" int pdn_gemm_outres_ws_f32(const float* A, const float* B, float* C, const float* bias, const float* residual,
-                                      int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans,
-                                      void* workspace, int64_t workspace_bytes, void* stream);
-extern "C" int pdn_gemm_outres_supported(int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans);
-extern "C" int pdn_gemm_outres_f32(const float* A, const float* B, float* C, const float* bias,
-                                   const float* residual, int M, int N, int K, int64_t lda, int64_t ldb,
-                                   int64_t ldc, int b_trans, void* stream);
-extern "C" int pdn_gemm_rowres_supported(int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans);
-int pdn_rowtile_plain_ok(int M, int N, int b_trans);
-extern "C" int pdn_gemm_rowtile_mode(int mode);                 // csrc/gemm_rowtile.hip; a negative mode only asks
-// csrc/outres_split.hip: the output-resident product on split-fp16 MFMA, here for the 288 x 288 products (slot 47)
-int pdn_outres_split_takes(const float* A, const float* B, const float* C, const float* bias, const float* residual, int M,
-                           int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, int splits,
-                           void* stream);
-int pdn_outres_split_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int K,
-                            int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, void* stream,
-                            int count_slot);
-extern "C" int pdn_gemm_rowres_f32(const float* A, const float* B, float* C, const float* bias,
-                                   const float* residual, int M, int N, int K, int64_t lda, int64_t ldb,
-                                   int64_t ldc, int b_trans, void* stream);
-int pdn_gemm_rowres_blocks(const float* A, const float* B, float* C, int M, int N, int K, int64_t lda, int64_t ldb,
-                           int64_t ldc, int b_trans, int nblocks, int64_t b_block_stride, void* stream);
-
 extern "C" int64_t pdn_gemm_f32_workspace_bytes(int M, int N, int K, int nbatch) {
   // Enough for up to 64 splits of one output; pdn_gemm_f32 never uses more than it is given.
   // [64 slabs | the shapes of the split-fp16 packed weight gradients (288 rows, two or more blocks, K >= 32768): x's fp16
@@ -222,571 +170,295 @@ extern "C" int64_t pdn_gemm_f32_workspace_bytes(int M, int N, int K, int nbatch)
   return ((base + 255) & ~(int64_t)255) + pdn_outres_tn_split_extra_bytes(K);
 }
 
-// csrc/gemm_narrow.hip: products with at most 16 output columns (bandwidth kernels)
-bool pdn_gemm_narrow_nn_ok(int M, int N, int K, int64_t a_rs, int64_t a_cs, const void* A);
-int pdn_gemm_narrow_nn_launch(const float* A, int64_t lda, const float* B, int64_t b_rs, int64_t b_cs, const float* bias,
-                              float* C, int64_t ldc, int M, int N, int K, void* stream);
-int pdn_gemm_narrow_tn_plan(int Mc, int N, int K, int64_t a_rs, int64_t a_cs, int64_t b_cs, const void* A, int64_t ws_cap_floats,
-                            int* kps);
-int pdn_gemm_narrow_tn_launch(const float* A, int64_t a_cs, const float* B, int64_t b_rs, float* slabs, int Mc, int N, int K,
-                              int kps, int splits, void* stream);
+// ---- pdn_gemm_f32 proper: one call record, one function per route ---------------------------------------------------------
+// A call of pdn_gemm_f32 / pdn_linear_relu_fwd_f32 / pdn_linear_dx_masked_f32: its arguments (those the kernels read are in
+// `p`) and the facts the routes derive from them, once.  `relu_mask` / `grad_mask` (GemmParams) are the one-bit-per-element
+// epilogues of pdn_linear_relu_fwd_f32 / pdn_linear_dx_masked_f32: with either (`ext_on`), the product goes to the tiled
+// kernel unsplit.
+struct GemmCall {
+  GemmParams p;              // operands, extents, strides, alpha / beta; the launching route sets splits, k_per_split, tiles
+  int nb1, nbatch;
+  bool ext_on, mask_colsum;
+  GemmLayout lay;            // a_kin, b_kin, vec (gemm_select.h)
+  int bt;                    // B as the kernels with a row stride and a transpose flag take it: bt = 1: (N x K) row-major
+  int64_t ldb;
+  void* workspace;           // as passed
+  int64_t workspace_bytes;
+  int64_t ws_bytes, ws_floats;   // its capacity: 0 without a workspace
+  void* stream;
+  hipStream_t st;
+};
+// what a route returns when the call is not its own: the next route is tried
+constexpr int kNotTaken = -0x7fffffff - 1;
 
-// pdn_gemm_f32 proper.  `relu_mask` / `grad_mask` (GemmParams) are the one-bit-per-element epilogues of
-// pdn_linear_relu_fwd_f32 / pdn_linear_dx_masked_f32: with either, the product goes to the tiled kernel unsplit.
-static int gemm_f32_impl(int M, int N, int K, float alpha, const float* A, int64_t a_rs,
-                         int64_t a_cs, const float* B, int64_t b_rs, int64_t b_cs, float beta,
-                         float* C, int64_t ldc, const float* bias, int nb1, int nb2,
-                         int64_t a_bs1, int64_t a_bs2, int64_t b_bs1, int64_t b_bs2,
-                         int64_t c_bs1, int64_t c_bs2, const float* residual,
-                         float* b_colsum, int colsum_accumulate, void* workspace,
-                         int64_t workspace_bytes, void* stream, uint32_t* relu_mask, const uint32_t* grad_mask,
-                         float* mask_colsum = nullptr) {
-  const bool ext_on = relu_mask || grad_mask;
-  PDN_CHECK_ARG(!ext_on || (nb1 == 1 && nb2 == 1 && N % 32 == 0 && !b_colsum),
-                "pdn_gemm_f32: the mask epilogues need one batch and N a multiple of 32 (N = %d)", N);
-  PDN_CHECK_ARG(M >= 0 && N >= 0 && K >= 0 && nb1 >= 0 && nb2 >= 0, "pdn_gemm_f32: negative extent");
-  if (M == 0 || N == 0 || nb1 == 0 || nb2 == 0) return PDN_OK;
-  PDN_CHECK_ARG(A && B && C, "pdn_gemm_f32: null operand");
-  PDN_CHECK_ARG(ldc >= N, "pdn_gemm_f32: ldc (%lld) < N (%d)", (long long)ldc, N);
-  hipStream_t st = (hipStream_t)stream;
-  const int nbatch = nb1 * nb2;
+static inline bool al16(const void* q) { return gemm_al16((uintptr_t)q); }
 
-  GemmParams p;
-  p.A = A; p.B = B; p.C = C; p.bias = bias; p.ws = (float*)workspace;
-  p.residual = residual; p.colsum = b_colsum; p.colsum_acc = colsum_accumulate;
-  p.relu_mask = relu_mask; p.grad_mask = grad_mask; p.mask_colsum = grad_mask ? mask_colsum : nullptr;
-  p.M = M; p.N = N; p.K = K;
-  p.a_rs = a_rs; p.a_cs = a_cs; p.b_rs = b_rs; p.b_cs = b_cs; p.ldc = ldc;
-  p.nb2 = nb2;
-  p.a_bs1 = a_bs1; p.a_bs2 = a_bs2; p.b_bs1 = b_bs1; p.b_bs2 = b_bs2; p.c_bs1 = c_bs1; p.c_bs2 = c_bs2;
-  p.alpha = alpha; p.beta = beta;
+// the deterministic sum of `p.splits` slabs in p.ws into C (alpha, bias, residual, beta * C applied); `rvec`: 16-byte
+// accesses, which every site decides for its own operands
+static int reduce_slabs(const GemmParams& p, int64_t total, int nbatch, int rvec, hipStream_t st) {
+  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, p, nbatch, rvec);
+  PDN_LAUNCH_CHECK();
+  return PDN_OK;
+}
 
-  // LDS layout per operand: contraction-contiguous (KIN) unless the m/n index is the unit stride.
-  const bool a_kin = !(a_rs == 1 && a_cs != 1) || M == 1;
-  const bool b_kin = (b_rs == 1 && b_cs != 1) || (b_rs == 1 && N == 1);
-  auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-  auto m4 = [](int64_t v) { return (v & 3) == 0; };
-  // float4 path: unit stride on the staged-contiguous index, every row start 16B aligned,
-  // extents along the contiguous index multiples of 4.
-  bool vec = al16(A) && al16(B) && m4(a_bs1) && m4(a_bs2) && m4(b_bs1) && m4(b_bs2);
-  if (a_kin) vec = vec && a_cs == 1 && m4(a_rs) && m4(K);
-  else vec = vec && a_rs == 1 && m4(a_cs) && m4(M);
-  if (b_kin) vec = vec && b_rs == 1 && m4(b_cs) && m4(K);
-  else vec = vec && b_cs == 1 && m4(b_rs) && m4(N);
+// ---- 1: one to four output rows (decode): stream the weight matrix once ----------------------
+// (a workgroup walks ALL of K for its 128 columns: right when the weight matrix is wide, wrong for a
+//  long-K / narrow-N product such as the input-weight gradient of an RNN with one input feature)
+static int route_skinny(const GemmCall& c) {
+  const GemmParams& p = c.p;
+  if (!(p.M <= 4 && !c.ext_on && c.nbatch == 1 && !p.colsum && p.b_cs == 1 && p.a_cs == 1 && gemm_m4(p.N) && gemm_m4(p.b_rs) &&
+        gemm_m4(p.ldc) && al16(p.B) && al16(p.C) && (!p.bias || al16(p.bias)) && (!p.residual || al16(p.residual)) && p.K > 0 &&
+        (p.K <= 4096 || (int64_t)p.K <= 4ll * p.N)))
+    return kNotTaken;
+  const dim3 g((p.N + 127) / 128);
+  switch (p.M) {
+    case 1: hipLaunchKernelGGL((gemm_skinny_kernel<1>), g, dim3(256), 0, c.st, p); break;
+    case 2: hipLaunchKernelGGL((gemm_skinny_kernel<2>), g, dim3(256), 0, c.st, p); break;
+    case 3: hipLaunchKernelGGL((gemm_skinny_kernel<3>), g, dim3(256), 0, c.st, p); break;
+    default: hipLaunchKernelGGL((gemm_skinny_kernel<4>), g, dim3(256), 0, c.st, p); break;
+  }
+  PDN_LAUNCH_CHECK();
+  return PDN_OK;
+}
 
-  if (b_colsum) {
-    // fused column sums need B staged n-contiguous, A m-contiguous (the dW = x^T @ g form), the
-    // float4 path, a single batch and no k-split (each column is summed by exactly one block)
-    if (a_kin || b_kin || !vec || nbatch != 1) {
-      pdn_set_error("pdn_gemm_f32: b_colsum needs the x^T @ g layout (A m-contiguous, B n-contiguous, aligned, unbatched)");
-      return PDN_EUNSUPPORTED;
-    }
+// ---- 2: a handful of output columns (a classifier head): bandwidth kernels (gemm_narrow.hip) ----
+static int route_narrow(GemmCall& c) {
+  GemmParams& p = c.p;
+  const int M = p.M, N = p.N, K = p.K;
+  if (!(c.nbatch == 1 && !c.ext_on && N <= 16 && p.alpha == 1.f && !p.residual && !p.colsum && !getenv("PDN_GEMM_NO_NARROW")))
+    return kNotTaken;
+  if (p.beta == 0.f && pdn_gemm_narrow_nn_ok(M, N, K, p.a_rs, p.a_cs, p.A)) {
+    if (getenv("PDN_GEMM_DEBUG")) fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> narrow NN\n", M, N, K);
+    return pdn_gemm_narrow_nn_launch(p.A, p.a_rs, p.B, p.b_rs, p.b_cs, p.bias, p.C, p.ldc, M, N, K, c.stream);
   }
-  // ---- one to four output rows (decode): stream the weight matrix once ----------------------
-  // (a workgroup walks ALL of K for its 128 columns: right when the weight matrix is wide, wrong for a
-  //  long-K / narrow-N product such as the input-weight gradient of an RNN with one input feature)
-  if (M <= 4 && !ext_on && nbatch == 1 && !b_colsum && b_cs == 1 && a_cs == 1 && m4(N) && m4(b_rs) && m4(ldc) &&
-      al16(B) && al16(C) && (!bias || al16(bias)) && (!residual || al16(residual)) && K > 0 &&
-      (K <= 4096 || (int64_t)K <= 4ll * N)) {
-    const dim3 g((N + 127) / 128);
-    switch (M) {
-      case 1: hipLaunchKernelGGL((gemm_skinny_kernel<1>), g, dim3(256), 0, st, p); break;
-      case 2: hipLaunchKernelGGL((gemm_skinny_kernel<2>), g, dim3(256), 0, st, p); break;
-      case 3: hipLaunchKernelGGL((gemm_skinny_kernel<3>), g, dim3(256), 0, st, p); break;
-      default: hipLaunchKernelGGL((gemm_skinny_kernel<4>), g, dim3(256), 0, st, p); break;
-    }
-    PDN_LAUNCH_CHECK();
-    return PDN_OK;
-  }
-  // ---- a handful of output columns (a classifier head): bandwidth kernels (gemm_narrow.hip) ----
-  if (nbatch == 1 && !ext_on && N <= 16 && alpha == 1.f && !residual && !b_colsum && !getenv("PDN_GEMM_NO_NARROW")) {
-    if (beta == 0.f && pdn_gemm_narrow_nn_ok(M, N, K, a_rs, a_cs, A)) {
-      if (getenv("PDN_GEMM_DEBUG")) fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> narrow NN\n", M, N, K);
-      return pdn_gemm_narrow_nn_launch(A, a_rs, B, b_rs, b_cs, bias, C, ldc, M, N, K, stream);
-    }
-    int kps = 0;
-    const int64_t cap = (workspace && workspace_bytes > 0 && al16(workspace)) ? workspace_bytes / 4 : 0;
-    const int sp = !bias ? pdn_gemm_narrow_tn_plan(M, N, K, a_rs, a_cs, b_cs, A, cap, &kps) : 0;
-    if (sp > 0) {
-      if (getenv("PDN_GEMM_DEBUG")) fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> narrow TN (%d slabs)\n", M, N, K, sp);
-      const int rc = pdn_gemm_narrow_tn_launch(A, a_cs, B, b_rs, (float*)workspace, M, N, K, kps, sp, stream);
-      if (rc) return rc;
-      p.splits = sp;
-      const int64_t total = (int64_t)M * N;
-      const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-      const int rvec = (N % 4 == 0) && (ldc % 4 == 0) && al16(C);
-      hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, p, 1, rvec);
-      PDN_LAUNCH_CHECK();
-      return PDN_OK;
-    }
-  }
-  // ---- tall A, contraction 288, wide-enough output: rows of A resident in registers (gemm_rowres.hip) ----
-  // measured against the tiled kernel at 65536 rows: N 864 +19 %, 1536 +14 %, 768 (either B orientation)
-  // +11..14 %, 32000 +4 %; N 288 equal (left to the tiled kernel); with a residual the tiled epilogue wins
-  // ---- tall A, output exactly the model width (288), longer contraction: outputs resident in accumulators
-  // (gemm_outres.hip).  Measured against the tiled kernel at 65536 rows: K 768 +6 %, 864 +17 %, 1536 +20 %,
-  // 32000 +15 % (91.7 % of the matrix peak); at 32768 rows (4-wave workgroups, one wave per SIMD) K >= 1536 only.
-  if (nbatch == 1 && !ext_on && N == 288 && a_cs == 1 && alpha == 1.f && beta == 0.f && !b_colsum && K >= 768 &&
-      al16(A) && al16(B) && !getenv("PDN_GEMM_NO_OUTRES")) {
-    const int bt = (b_rs == 1 && b_cs != 1) ? 1 : 0;
-    const int64_t ldb = bt ? b_cs : b_rs;
-    const bool big = (M + 255) / 256 >= 224, mid = (M + 127) / 128 >= 224 && K >= 1536;
-    // fewer rows than that: K cut into ranges over grid.y (slabs in the workspace), when K is long enough
-    int pl_nw, pl_kps;
-    const int64_t or_ws = (workspace && workspace_bytes > 0) ? workspace_bytes : 0;
-    // (the plan may also cut K where unsplit 4-wave workgroups would fill the chip: 8-wave ones over two ranges)
-    const bool cut = !big && M >= 8192 && K >= 1536 && pdn_gemm_outres_plan(M, K, &pl_nw, &pl_kps) > 1 &&
-                     or_ws >= pdn_gemm_outres_workspace_bytes(M, K);
-    if ((big || mid || cut) && (bt || b_cs == 1) && pdn_gemm_outres_supported(M, N, K, a_rs, ldb, ldc, bt)) {
-      bool prof;
-      ProfRec rec;
-      {
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        prof = g_prof_on;
-      }
-      if (prof) {
-        PDN_HIP(hipEventCreate(&rec.e0));
-        PDN_HIP(hipEventCreate(&rec.e1));
-        rec.flops = 2.0 * M * (double)N * (double)K;
-        rec.family = 3;
-        PDN_HIP(hipEventRecord(rec.e0, st));
-      }
-      if (getenv("PDN_GEMM_DEBUG"))
-        fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> output-resident (%s)\n", M, N, K, bt ? "NT" : "NN");
-      const int rc = cut ? pdn_gemm_outres_ws_f32(A, B, C, bias, residual, M, N, K, a_rs, ldb, ldc, bt, workspace, or_ws, stream)
-                         : pdn_gemm_outres_f32(A, B, C, bias, residual, M, N, K, a_rs, ldb, ldc, bt, stream);
-      if (rc) return rc;
-      if (prof) {
-        PDN_HIP(hipEventRecord(rec.e1, st));
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        g_prof.push_back(rec);
-      }
-      return PDN_OK;
-    }
-  }
-  // ---- tall A against a 288 x 288 weight (the attention output projection ctx Wo + x and its input gradient dz Wo^T), 65536
-  // rows and more: the same output-resident kernel on split-fp16 MFMA (csrc/outres_split.hip, nine pieces) in place of the
-  // fp32 tile-piece kernel, for exactly the calls that kernel would take.  At 131072 rows 214 (NN, residual) / 202 us (NT)
-  // on the fp32 pipe against 140 / 104 us here.  Kept away by PDN_OUTRES_SPLIT=0 (read on every call), pdn_gemm_rowtile_mode 3
-  // (the in-process A/B switch of the row-resident family), PDN_GEMM_NO_OUTRES / PDN_GEMM_NO_ROWRES, a captured stream, and
-  // operands that overlap C (a residual that IS C is fine: a lane reads its 16 bytes before it writes them).
-  if (nbatch == 1 && !ext_on && N == 288 && K == 288 && a_cs == 1 && alpha == 1.f && beta == 0.f && !b_colsum &&
-      !getenv("PDN_GEMM_NO_OUTRES") && !getenv("PDN_GEMM_NO_ROWRES") && pdn_gemm_rowtile_mode(-1) != 3) {
-    const int bt = (b_rs == 1 && b_cs != 1) ? 1 : 0;
-    const int64_t ldb = bt ? b_cs : b_rs;
-    auto overlaps_c = [&](const float* q, int64_t floats) {
-      return q && q < (const float*)C + (int64_t)M * ldc && (const float*)C < q + floats;
-    };
-    if ((bt || b_cs == 1) && pdn_rowtile_plain_ok(M, N, bt) && pdn_gemm_rowres_supported(M, N, K, a_rs, ldb, ldc, bt) &&
-        !overlaps_c(A, (int64_t)M * a_rs) && !overlaps_c(B, (int64_t)288 * ldb) &&
-        (residual == C || !overlaps_c(residual, (int64_t)M * ldc)) &&
-        pdn_outres_split_takes(A, B, C, bias, residual, M, K, a_rs, ldb, ldc, bt, 0, 0, 1, stream)) {
-      if (getenv("PDN_GEMM_DEBUG"))
-        fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> output-resident, split fp16 (%s)\n", M, N, K, bt ? "NT" : "NN");
-      const int tk = pdn_gemm_prof_begin(3, 2.0 * M * (double)N * (double)K, 0.0, stream);
-      const int rc = pdn_outres_split_launch(A, B, C, bias, residual, M, K, a_rs, ldb, ldc, bt, 0, 0, stream, PDN_CNT_PROJ288_SPLIT);
-      pdn_gemm_prof_end(tk, stream);
-      return rc;
-    }
-  }
-  // A batch whose members share A and write side by side into one packed buffer (x against Wq | Wk | Wv,
-  // x against Wg | Wu: core/fused/) is ONE such product with B in equally spaced column blocks.
-  {
-    const bool one_dim = nb1 == 1 || nb2 == 1;
-    const int64_t a_bs = nb1 == 1 ? a_bs2 : a_bs1, b_bs = nb1 == 1 ? b_bs2 : b_bs1, c_bs = nb1 == 1 ? c_bs2 : c_bs1;
-    const bool blocks = nbatch > 1 && one_dim && a_bs == 0 && c_bs == N && ldc >= (int64_t)nbatch * N && !bias &&
-                        N % 96 == 0 && (b_bs & 3) == 0;
-    const int64_t n_all = (int64_t)N * (blocks ? nbatch : 1);
-    // (round 5: the tile-piece kernel also takes what the chunk kernel lost to the tiled one -- outputs narrower than 768
-    //  columns, i.e. the 288 x 288 products of the attention output projection, and a residual added in the store)
-    const int bt0 = (b_rs == 1 && b_cs != 1) ? 1 : 0;
-    const bool tilepiece = nbatch == 1 && K == 288 && n_all >= 96 && n_all % 32 == 0 && M >= 8192 &&
-                           pdn_rowtile_plain_ok(M, (int)n_all, bt0);
-    if ((nbatch == 1 || blocks) && !ext_on && K == 288 && a_cs == 1 && alpha == 1.f && beta == 0.f && !b_colsum &&
-        (tilepiece || (!residual && n_all >= 768)) && n_all < (1 << 30) && M >= 8192 && al16(A) && al16(B) &&
-        (!residual || al16(residual)) && !getenv("PDN_GEMM_NO_ROWRES")) {
-      const int bt = (b_rs == 1 && b_cs != 1) ? 1 : 0;
-      const int64_t ldb = bt ? b_cs : b_rs;
-      if ((bt || b_cs == 1) && pdn_gemm_rowres_supported(M, N, K, a_rs, ldb, ldc, bt)) {
-        bool prof;
-        ProfRec rec;
-        {
-          std::lock_guard<std::mutex> lk(g_prof_mu);
-          prof = g_prof_on;
-        }
-        if (prof) {
-          PDN_HIP(hipEventCreate(&rec.e0));
-          PDN_HIP(hipEventCreate(&rec.e1));
-          rec.flops = 2.0 * M * (double)n_all * (double)K;
-          rec.family = 2;
-          PDN_HIP(hipEventRecord(rec.e0, st));
-        }
-        if (getenv("PDN_GEMM_DEBUG"))
-          fprintf(stderr, "pdn_gemm_f32 M=%d N=%lld K=%d -> row-resident (%s, %d block%s)\n", M, (long long)n_all, K,
-                  bt ? "NT" : "NN", blocks ? nbatch : 1, blocks ? "s" : "");
-        const int rc = blocks ? pdn_gemm_rowres_blocks(A, B, C, M, (int)n_all, K, a_rs, ldb, ldc, bt, nbatch, b_bs, stream)
-                              : pdn_gemm_rowres_f32(A, B, C, bias, residual, M, N, K, a_rs, ldb, ldc, bt, stream);
-        if (rc) return rc;
-        if (prof) {
-          PDN_HIP(hipEventRecord(rec.e1, st));
-          std::lock_guard<std::mutex> lk(g_prof_mu);
-          g_prof.push_back(rec);
-        }
-        return PDN_OK;
-      }
-    }
-  }
-  const int64_t ws_cap = (workspace && workspace_bytes > 0) ? workspace_bytes / 4 : 0;
-  // ---- weight gradient of a wide layer out of the model width: C (288 x N) = x^T (288 x K) g (K x N), K = tokens --
-  // (the lm_head: N = 32000).  Output-resident over the 288 rows, g read once straight into MFMA operands
-  // (gemm_outres_tn_kernel); K split so that the grid fills the chip once, slabs combined (with beta) below.
-  if (nbatch == 1 && !ext_on && M == 288 && a_rs == 1 && a_cs >= 288 && b_cs == 1 && alpha == 1.f && !b_colsum && !bias && !residual &&
-      N >= 8192 && N % 32 == 0 && K % 32 == 0 && K >= 4096 && m4(a_cs) && m4(b_rs) && al16(A) && al16(B) &&
-      (int64_t)288 * ldc < (1ll << 30) && (int64_t)32 * b_rs < (1ll << 30) && !getenv("PDN_GEMM_NO_OUTRES")) {
-    int nw = 8, kps = K;
-    const int splits = pdn_gemm_outres_tn_plan(N, K, &nw, &kps);
-    const bool direct = splits == 1 && beta == 0.f;
-    if (direct || (int64_t)splits * M * N <= ws_cap) {
-      bool prof;
-      ProfRec rec;
-      {
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        prof = g_prof_on;
-      }
-      if (prof) {
-        PDN_HIP(hipEventCreate(&rec.e0));
-        PDN_HIP(hipEventCreate(&rec.e1));
-        rec.flops = 2.0 * M * (double)N * (double)K;
-        rec.family = 4;
-        PDN_HIP(hipEventRecord(rec.e0, st));
-      }
-      if (getenv("PDN_GEMM_DEBUG"))
-        fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> output-resident TN (splits %d)\n", M, N, K, splits);
-      int rc = direct ? pdn_gemm_outres_tn_launch(A, B, C, N, K, a_cs, b_rs, ldc, 0, nw, kps, stream)
-                      : pdn_gemm_outres_tn_launch(A, B, (float*)workspace, N, K, a_cs, b_rs, N, (int64_t)M * N, nw, kps, stream);
-      if (rc) return rc;
-      if (!direct) {
-        p.splits = splits;
-        const int64_t total = (int64_t)M * N;
-        const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-        const int rvec = (ldc % 4 == 0) && al16(C) && al16(workspace);
-        hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, p, 1, rvec);
-        PDN_LAUNCH_CHECK();
-      }
-      if (prof) {
-        PDN_HIP(hipEventRecord(rec.e1, st));
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        g_prof.push_back(rec);
-      }
-      return PDN_OK;
-    }
-  }
-  // ---- the packed weight gradients of a transformer block out of the model width: x^T (288 x K) against dq | dk | dv
-  // (three 288-column blocks of one (K x 864) matrix) or dgate | dup (two 768-column blocks), one output per block.
-  // The same output-resident TN kernel, K split 40-64 ways so that the grid fills the chip, slabs in the batched
-  // layout of the split-K reduce (which adds beta * C).  Against the wave-streaming kernel: 864 columns -16 %,
-  // 1536 columns -11 % (60 instead of 170 operand bytes per MFMA; the slab pass costs 30-40 us).
-  {
-    const bool one_dim = nb1 == 1 || nb2 == 1;
-    const int64_t a_bs = nb1 == 1 ? a_bs2 : a_bs1, b_bs = nb1 == 1 ? b_bs2 : b_bs1;
-    const int64_t n_all = (int64_t)N * nbatch;
-    if (nbatch > 1 && one_dim && M == 288 && a_bs == 0 && b_bs == N && a_rs == 1 && a_cs >= 288 && b_cs == 1 &&
-        b_rs >= n_all && alpha == 1.f && !b_colsum && !bias && !residual && N % 32 == 0 && n_all >= 768 && n_all <= 8192 &&
-        K % 32 == 0 && K >= 16384 && m4(a_cs) && m4(b_rs) && al16(A) && al16(B) && !getenv("PDN_GEMM_NO_OUTRES")) {
-      int nw = 8, kps = K;
-      int splits = pdn_gemm_outres_tn_plan((int)n_all, K, &nw, &kps);
-      // split-fp16 form (csrc/outres_tn_split.hip): switched on, a shape it takes, 16-byte aligned operands, and a workspace
-      // that holds its extra region behind the 64 slabs (a caller that passes only the slabs selects the fp32 kernel: the
-      // in-process A/B switch).  It cuts K into its own number of ranges, at most 64.
-      const int64_t xoff = (((int64_t)64 * M * n_all * 4 + 255) & ~(int64_t)255);
-      const bool split16 = pdn_outres_tn_split_supported(M, N, nbatch, K) && pdn_outres_tn_split_enabled() && workspace &&
-                           workspace_bytes >= xoff + pdn_outres_tn_split_extra_bytes(K) && al16(workspace);
-      if (split16) {
-        kps = ((K / 32 + pdn_outres_tn_split_ranges((int)n_all, K, splits) - 1) / pdn_outres_tn_split_ranges((int)n_all, K, splits)) * 32;
-        splits = (K + kps - 1) / kps;
-      }
-      if (splits > 1 && (int64_t)splits * M * n_all <= ws_cap && nbatch * splits <= 65535) {
-        bool prof;
-        ProfRec rec;
-        {
-          std::lock_guard<std::mutex> lk(g_prof_mu);
-          prof = g_prof_on;
-        }
-        if (prof) {
-          PDN_HIP(hipEventCreate(&rec.e0));
-          PDN_HIP(hipEventCreate(&rec.e1));
-          rec.flops = 2.0 * M * (double)n_all * (double)K;
-          rec.family = 4;
-          PDN_HIP(hipEventRecord(rec.e0, st));
-        }
-        if (getenv("PDN_GEMM_DEBUG"))
-          fprintf(stderr, "pdn_gemm_f32 M=%d N=%lld K=%d -> output-resident TN%s (%d blocks, splits %d)\n", M,
-                  (long long)n_all, K, split16 ? ", split-fp16" : "", nbatch, splits);
-        int rc = split16 ? pdn_outres_tn_split_launch(A, B, (float*)workspace, (int)n_all, K, a_cs, b_rs, N, kps,
-                                                      (char*)workspace + xoff, stream)
-                         : pdn_gemm_outres_tn_blocks_launch(A, B, (float*)workspace, (int)n_all, K, a_cs, b_rs, N, nw, kps, stream);
-        if (rc) return rc;
-        p.splits = splits;
-        const int64_t total = (int64_t)M * n_all;
-        const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-        const int rvec = (ldc % 4 == 0) && al16(C) && m4(c_bs1) && m4(c_bs2) && al16(workspace);
-        hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, p, nbatch, rvec);
-        PDN_LAUNCH_CHECK();
-        if (prof) {
-          PDN_HIP(hipEventRecord(rec.e1, st));
-          std::lock_guard<std::mutex> lk(g_prof_mu);
-          g_prof.push_back(rec);
-        }
-        return PDN_OK;
-      }
-    }
-  }
-  // ---- the down-projection weight gradient dW_down (M x 288) = h^T (M x K) g2 (K x 288), M = 512 .. 1024 in whole waves,
-  // from 32768 tokens on: the split-fp16 TN kernel with the roles swapped (g2 the plane-image operand, h the raw one) and a
-  // transposed store (csrc/outres_tn_split.hip), its slabs combined (with beta) by the reduce below.  Taken when switched on
-  // (PDN_OUTRES_TN_SPLIT), with 16-byte aligned operands and a workspace that holds the extra region behind the 64 slabs; a
-  // caller that passes only the slabs gets the wave-streaming fp32 kernel (the in-process A/B switch).
-  if (nbatch == 1 && !ext_on && a_rs == 1 && b_cs == 1 && alpha == 1.f && !b_colsum && !bias && !residual &&
-      pdn_down_dw_split_supported(M, N, K) && a_cs >= M && b_rs >= N && m4(a_cs) && m4(b_rs) && al16(A) && al16(B) && workspace &&
-      al16(workspace) && pdn_outres_tn_split_enabled() && !getenv("PDN_GEMM_NO_OUTRES")) {
-    const int64_t xoff = (((int64_t)64 * M * N * 4 + 255) & ~(int64_t)255);
-    const int ranges = pdn_down_dw_split_ranges(M, K);
-    const int kps = ((K / 32 + ranges - 1) / ranges) * 32;
-    const int splits = (K + kps - 1) / kps;
-    if (workspace_bytes >= xoff + pdn_outres_tn_split_extra_bytes(K) && splits > 1 && splits <= 64) {
-      if (getenv("PDN_GEMM_DEBUG"))
-        fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> output-resident TN, split-fp16, transposed (splits %d)\n", M, N, K, splits);
-      const int tk = pdn_gemm_prof_begin(4, 2.0 * M * (double)N * (double)K, 0.0, stream);
-      const int rc = pdn_down_dw_split_launch(B, A, (float*)workspace, M, K, b_rs, a_cs, kps, (char*)workspace + xoff, stream);
-      if (rc) { pdn_gemm_prof_end(tk, stream); return rc; }
-      p.splits = splits;
-      const int64_t total = (int64_t)M * N;
-      const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-      const int rvec = (ldc % 4 == 0) && al16(C);
-      hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, p, 1, rvec);
-      PDN_LAUNCH_CHECK();
-      pdn_gemm_prof_end(tk, stream);
-      return PDN_OK;
-    }
-  }
-  // ---- weight-gradient form (small output, long K): wave-streaming kernel --------------------
-  constexpr int SNW = 8;                                  // waves per streaming workgroup
-  bool use_stream = false;
-  int sshape = 0;
-  // Which weight gradients it takes (tools/gemm_fc_sweep.py, same process, warm clocks, K = 4096 ... 65536):
-  //   * outputs BELOW 2^20 elements: at 1024 x 1024 -- config 2's second layer -- the tiled kernel with its k-split measured
-  //     1065 us against 1144 us, and the MLP step 5.44 -> 5.32 ms (PDN_GEMM_STREAM_MAX overrides the bound);
-  //   * from 2^18 elements on only where the tiled kernel's 128 / 96-wide tiles would PAD the output by more than 4 %:
-  //     784 x 1024 (config 2's first layer: 9 x 8 tiles of 96 x 128 = +10 %) 954 us here against 1030-1080 us tiled, but
-  //     512 x 512 and 512 x 1536 (the Transformer example, the dim-512 Llama) 38 / 85 us tiled against 45 / 109 us here at
-  //     K = 5632 and 280 / 804 against 330 / 890 us at K = 65536; below 2^18 (288 x 288, 288 x 768) this kernel wins at every K.
-  bool stream_fits = (int64_t)M * N * nbatch <= (getenv("PDN_GEMM_STREAM_MAX") ? atol(getenv("PDN_GEMM_STREAM_MAX")) : (1 << 20) - 1);
-  if (stream_fits && (int64_t)M * N * nbatch >= (1 << 18) && !getenv("PDN_GEMM_STREAM_MAX")) {
-    static const int kPadTiles[3][2] = {{128, 128}, {128, 96}, {96, 128}};
-    double pad = 1e30;
-    for (const auto& t : kPadTiles)
-      pad = std::min(pad, (double)(cdiv64(M, t[0]) * t[0]) * (double)(cdiv64(N, t[1]) * t[1]) / ((double)M * N));
-    stream_fits = pad > 1.04;
-  }
-  if (!ext_on && !a_kin && !b_kin && a_rs == 1 && b_cs == 1 && !b_colsum && K >= 2048 && stream_fits && nbatch <= 64 &&
-      !getenv("PDN_GEMM_NO_STREAM")) {
-    // tile shape of the LDS-staged kernel (in 32-row / 32-column MFMA tiles): 3 x 3 unless another one pads the output
-    // less (784 x 1024: 9 x 11 tiles of 96 x 96 = 912 K accumulators, 5 x 16 of 160 x 64 = 819 K)
-    static const int kShapes[5][2] = {{3, 3}, {5, 2}, {2, 5}, {4, 2}, {2, 4}};
-    // time per accumulator of the padded output relative to 3 x 3 (tools/mlp_dw_probe.py, 65536 tokens: 784 x 1024,
-    // 1024 x 1024, 768 x 768, 512 x 2048); an exact 3 x 3 tiling takes the DMA-staged kernel
-    static const double kShapeCost[5] = {1.0, 1.05, 1.08, 1.07, 1.02};
-    sshape = 0;
-    if (vec) {
-      double best_area = (double)cdiv64(M, 96) * cdiv64(N, 96) * 96 * 96 * ((M % 96 == 0 && N % 96 == 0) ? 0.975 : 1.0);
-      for (int c = 1; c < 5; ++c) {
-        const int th = kShapes[c][0] * 32, tw = kShapes[c][1] * 32;
-        const double area = (double)cdiv64(M, th) * cdiv64(N, tw) * th * tw * kShapeCost[c];
-        if (area < best_area) { best_area = area; sshape = c; }
-      }
-      if (const char* e = getenv("PDN_GEMM_STREAM_SHAPE")) { const int c = atoi(e); if (c >= 0 && c < 5) sshape = c; }
-    }
-    const int sth = kShapes[sshape][0] * 32, stw = kShapes[sshape][1] * 32;
-    const int tm = (int)cdiv64(M, sth), tn = (int)cdiv64(N, stw), tiles = tm * tn * nbatch;
-    if (tiles <= 256) {
-      // one 8-wave workgroup per CU (2 waves / SIMD): rounds of 256 blocks; each extra slab costs a
-      // write + read of the output in the reduce pass (~1.7 KB/clk), plus its launch
-      double best_cost = 1e300;
-      int best_kps = 0, best_sp = 1;
-      const int smax = (int)std::min<int64_t>(64, K / (SNW * 16));
-      for (int s = 1; s <= smax; ++s) {
-        if (s > 1 && (int64_t)s * M * N * nbatch > ws_cap) break;
-        const int kw = (int)cdiv64(cdiv64(K, (int64_t)s * SNW), 8) * 8;
-        const int kps = kw * SNW, sp = (int)cdiv64(K, kps);
-        const double rounds = (double)cdiv64((int64_t)tiles * sp, 256);
-        double cost = rounds * (kw * 0.5 * (kShapes[sshape][0] * kShapes[sshape][1]) * 64 * (SNW / 4.0) + 6000.0);
-        if (sp > 1) cost += (double)sp * M * N * nbatch * 8.0 / 1700.0 + 5000.0;
-        if (cost < best_cost) { best_cost = cost; best_kps = kps; best_sp = sp; }
-      }
-      if (const char* e = getenv("PDN_GEMM_STREAM_SPLITS")) {     // tuning override
-        const int s = atoi(e);
-        if (s >= 1 && (s == 1 || (int64_t)s * M * N * nbatch <= ws_cap)) {
-          const int kw = (int)cdiv64(cdiv64(K, (int64_t)s * SNW), 8) * 8;
-          best_kps = kw * SNW; best_sp = (int)cdiv64(K, best_kps);
-        }
-      }
-      use_stream = true;
-      p.tiles_m = tm; p.tiles_n = tn; p.k_per_split = best_kps; p.splits = best_sp;
-    }
-  }
+  int kps = 0;
+  const int64_t cap = al16(c.workspace) ? c.ws_floats : 0;
+  const int sp = !p.bias ? pdn_gemm_narrow_tn_plan(M, N, K, p.a_rs, p.a_cs, p.b_cs, p.A, cap, &kps) : 0;
+  if (sp <= 0) return kNotTaken;
+  if (getenv("PDN_GEMM_DEBUG")) fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> narrow TN (%d slabs)\n", M, N, K, sp);
+  const int rc = pdn_gemm_narrow_tn_launch(p.A, p.a_cs, p.B, p.b_rs, (float*)c.workspace, M, N, K, kps, sp, c.stream);
+  if (rc) return rc;
+  p.splits = sp;
+  return reduce_slabs(p, (int64_t)M * N, 1, (N % 4 == 0) && (p.ldc % 4 == 0) && al16(p.C), c.st);
+}
 
-  // ---- pick tile shape and k-split with a small cost model -----------------------------
-  // The matrix pipes of a CU are shared by its resident workgroups, so MFMA throughput is
-  // counted per CU (256), not per residency slot: n blocks take ceil(n/256) block-times until
-  // the grid is large enough (>= 4 rounds) for the dispatcher to even the load out.
-  int best = -1, best_splits = 1;
-  double best_cost = 1e300;
-  static const bool no_fixed = getenv("PDN_GEMM_NO_FIXED") != nullptr;      // A/B switch for the residency-round term
-  for (int c = 0; c < kNumCfgs && !use_stream; ++c) {
-    if (!vec && c != kScalarCfg) continue;  // scalar staging: 64x64 only
-    if (ext_on && !(c == 0 || c == 3 || c == 6 || c == 7 || c == 8 || c == kScalarCfg)) continue;   // the tile shapes built with MASKS
-    if (mask_colsum && c == 8) continue;    // (a lane keeps its columns over a band only when 64 % (8 WN) == 0)
-    // 128 x 256: very wide outputs -- and (round 6) the 1024-wide Linear + ReLU layers of config 2 at chip-filling row
-    // counts, where it measures 0.86 of the fp32-MFMA peak against 0.71-0.80 for 128 x 128 (tools/gemm_fc_sweep.py)
-    if (c == 7 && N < 2048 && !(ext_on && N >= 1024 && N % 256 == 0 && M >= 16384)) continue;
-    if (c == 6 && ext_on && !(N >= 1024 && M >= 16384)) continue;
-    if (c == 8 && N < 768) continue;        // 256-row tiles lose on narrow outputs (one block per CU)
-    const int BM = kCfgs[c].waves_m * kCfgs[c].wm * 32, BN = kCfgs[c].waves_n * kCfgs[c].wn * 32;
-    const int bk = kCfgs[c].bk;
-    const int64_t tiles = cdiv64(M, BM) * cdiv64(N, BN) * nbatch;
-    // 128x96 with BK 16 keeps THREE workgroups per CU: worth it exactly when two-per-CU would
-    // leave a half-empty last round of short blocks (measured: 73 -> 58 us on 32768x288x288)
-    if (c == 12 && !(tiles > 512 && tiles <= 768 && K <= 1024 && a_kin && !b_kin)) continue;
-    const int ktiles = (int)cdiv64(K > 0 ? K : 1, bk);
-    for (int s = 1; s <= 64; s *= 2) {
-      if (s > 1 && (b_colsum || ext_on)) break;
-      if (s > 1) {
-        if (ktiles * bk / s < 128) break;
-        if ((int64_t)s * M * N * nbatch > ws_cap) break;
-      }
-      const int kps = (int)cdiv64(ktiles, s);
-      // Model (fitted to tools/gemm_sweep_dw.py and the tile sweep): a block keeps `waves_pb`
-      // SIMDs busy for BM*BN*K/waves_pb MFMA-cycles; blocks are dealt round-robin over the 256
-      // CUs, so a grid needs ceil(blocks/slots) rounds until it is large enough to even out; a CU
-      // with at least two resident blocks hides their barriers/prologues behind each other
-      // (~0.7 -> 1.0 matrix-pipe duty), which is why ~480 blocks beat 240 longer ones.
-      const double waves_pb = kCfgs[c].waves_m * kCfgs[c].waves_n;
-      const double blocks = (double)tiles * s;
-      const double slots = 256.0 * (4.0 / waves_pb);
-      const double rounds = blocks >= 4 * slots ? blocks / slots : (double)cdiv64((int64_t)blocks, (int64_t)slots);
-      const double wps = blocks * waves_pb / 1024.0;   // resident waves per SIMD in a round
-      const double util = wps >= 1.875 ? 1.0 : (wps > 1.0 ? 0.7 + 0.3 * (wps - 1.0) / 0.875 : 0.7);
-      const double eff = kCfgs[c].eff;
-      double cost = rounds * ((double)BM * BN * (kps * bk + 64) / waves_pb * 4.0 / (eff * util));
-      // ... plus what a block costs besides its MFMAs (first tiles in, accumulators out: ~25k cycles = 10 us, fitted at
-      // 16384 x 288 x {288, 768, 864}: 38 us for 384 blocks of 128 x 96 against 46 us for 768 of 64 x 128), paid once
-      // per RESIDENCY round -- co-resident blocks overlap theirs -- which is what makes few fat blocks win on short
-      // products even when they leave CUs half loaded (round 3; the unit is 1/156 matrix-pipe cycle)
-      if (!no_fixed) {
-        const double per_cu = c == 12 ? 3.0 : 2.0;
-        cost += (double)cdiv64((int64_t)blocks, (int64_t)(256.0 * per_cu)) * 3.9e6;
-      }
-      if (s > 1) cost += (double)M * N * nbatch * (s + 1) * 0.5 + 1.0e6;   // slab pass + extra launch
-      if (cost < best_cost) { best_cost = cost; best = c; best_splits = s; }
-    }
+// ---- 3: tall A, output exactly the model width (288), longer contraction: outputs resident in accumulators
+// (gemm_outres.hip).  Measured against the tiled kernel at 65536 rows: K 768 +6 %, 864 +17 %, 1536 +20 %,
+// 32000 +15 % (91.7 % of the matrix peak); at 32768 rows (4-wave workgroups, one wave per SIMD) K >= 1536 only.
+static int route_outres(const GemmCall& c) {
+  const GemmParams& p = c.p;
+  const int M = p.M, N = p.N, K = p.K;
+  if (!(c.nbatch == 1 && !c.ext_on && N == 288 && p.a_cs == 1 && p.alpha == 1.f && p.beta == 0.f && !p.colsum && K >= 768 &&
+        al16(p.A) && al16(p.B) && !getenv("PDN_GEMM_NO_OUTRES")))
+    return kNotTaken;
+  const bool big = (M + 255) / 256 >= 224, mid = (M + 127) / 128 >= 224 && K >= 1536;
+  // fewer rows than that: K cut into ranges over grid.y (slabs in the workspace), when K is long enough
+  int pl_nw, pl_kps;
+  // (the plan may also cut K where unsplit 4-wave workgroups would fill the chip: 8-wave ones over two ranges)
+  const bool cut = !big && M >= 8192 && K >= 1536 && pdn_gemm_outres_plan(M, K, &pl_nw, &pl_kps) > 1 &&
+                   c.ws_bytes >= pdn_gemm_outres_workspace_bytes(M, K);
+  if (!((big || mid || cut) && (c.bt || p.b_cs == 1) && pdn_gemm_outres_supported(M, N, K, p.a_rs, c.ldb, p.ldc, c.bt)))
+    return kNotTaken;
+  GemmProfScope prof(3, 2.0 * M * (double)N * (double)K, 0.0, c.stream);
+  if (getenv("PDN_GEMM_DEBUG"))
+    fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> output-resident (%s)\n", M, N, K, c.bt ? "NT" : "NN");
+  return cut ? pdn_gemm_outres_ws_f32(p.A, p.B, p.C, p.bias, p.residual, M, N, K, p.a_rs, c.ldb, p.ldc, c.bt, c.workspace, c.ws_bytes,
+                                      c.stream)
+             : pdn_gemm_outres_f32(p.A, p.B, p.C, p.bias, p.residual, M, N, K, p.a_rs, c.ldb, p.ldc, c.bt, c.stream);
+}
+
+// ---- 4: tall A against a 288 x 288 weight (the attention output projection ctx Wo + x and its input gradient dz Wo^T), 65536
+// rows and more: the same output-resident kernel on split-fp16 MFMA (csrc/outres_split.hip, nine pieces) in place of the
+// fp32 tile-piece kernel, for exactly the calls that kernel would take.  At 131072 rows 214 (NN, residual) / 202 us (NT)
+// on the fp32 pipe against 140 / 104 us here.  Kept away by PDN_OUTRES_SPLIT=0 (read on every call), pdn_gemm_rowtile_mode 3
+// (the in-process A/B switch of the row-resident family), PDN_GEMM_NO_OUTRES / PDN_GEMM_NO_ROWRES, a captured stream, and
+// operands that overlap C (a residual that IS C is fine: a lane reads its 16 bytes before it writes them).
+static int route_outres_split288(const GemmCall& c) {
+  const GemmParams& p = c.p;
+  const int M = p.M, N = p.N, K = p.K;
+  if (!(c.nbatch == 1 && !c.ext_on && N == 288 && K == 288 && p.a_cs == 1 && p.alpha == 1.f && p.beta == 0.f && !p.colsum &&
+        !getenv("PDN_GEMM_NO_OUTRES") && !getenv("PDN_GEMM_NO_ROWRES") && pdn_gemm_rowtile_mode(-1) != 3))
+    return kNotTaken;
+  auto overlaps_c = [&](const float* q, int64_t floats) {
+    return q && q < (const float*)p.C + (int64_t)M * p.ldc && (const float*)p.C < q + floats;
+  };
+  if (!((c.bt || p.b_cs == 1) && pdn_rowtile_plain_ok(M, N, c.bt) && pdn_gemm_rowres_supported(M, N, K, p.a_rs, c.ldb, p.ldc, c.bt) &&
+        !overlaps_c(p.A, (int64_t)M * p.a_rs) && !overlaps_c(p.B, (int64_t)288 * c.ldb) &&
+        (p.residual == p.C || !overlaps_c(p.residual, (int64_t)M * p.ldc)) &&
+        pdn_outres_split_takes(p.A, p.B, p.C, p.bias, p.residual, M, K, p.a_rs, c.ldb, p.ldc, c.bt, 0, 0, 1, c.stream)))
+    return kNotTaken;
+  if (getenv("PDN_GEMM_DEBUG"))
+    fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> output-resident, split fp16 (%s)\n", M, N, K, c.bt ? "NT" : "NN");
+  GemmProfScope prof(3, 2.0 * M * (double)N * (double)K, 0.0, c.stream);
+  return pdn_outres_split_launch(p.A, p.B, p.C, p.bias, p.residual, M, K, p.a_rs, c.ldb, p.ldc, c.bt, 0, 0, c.stream, PDN_CNT_PROJ288_SPLIT);
+}
+
+// ---- 5: tall A, contraction 288, wide-enough output: rows of A resident in registers (gemm_rowres.hip) ----
+// measured against the tiled kernel at 65536 rows: N 864 +19 %, 1536 +14 %, 768 (either B orientation)
+// +11..14 %, 32000 +4 %; N 288 equal (left to the tiled kernel); with a residual the tiled epilogue wins
+// A batch whose members share A and write side by side into one packed buffer (x against Wq | Wk | Wv,
+// x against Wg | Wu: core/fused/) is ONE such product with B in equally spaced column blocks.
+static int route_rowres(const GemmCall& c) {
+  const GemmParams& p = c.p;
+  const int M = p.M, N = p.N, K = p.K, nbatch = c.nbatch;
+  const bool one_dim = c.nb1 == 1 || p.nb2 == 1;
+  const int64_t a_bs = c.nb1 == 1 ? p.a_bs2 : p.a_bs1, b_bs = c.nb1 == 1 ? p.b_bs2 : p.b_bs1, c_bs = c.nb1 == 1 ? p.c_bs2 : p.c_bs1;
+  const bool blocks = nbatch > 1 && one_dim && a_bs == 0 && c_bs == N && p.ldc >= (int64_t)nbatch * N && !p.bias &&
+                      N % 96 == 0 && (b_bs & 3) == 0;
+  const int64_t n_all = (int64_t)N * (blocks ? nbatch : 1);
+  // (round 5: the tile-piece kernel also takes what the chunk kernel lost to the tiled one -- outputs narrower than 768
+  //  columns, i.e. the 288 x 288 products of the attention output projection, and a residual added in the store)
+  const bool tilepiece = nbatch == 1 && K == 288 && n_all >= 96 && n_all % 32 == 0 && M >= 8192 &&
+                         pdn_rowtile_plain_ok(M, (int)n_all, c.bt);
+  if (!((nbatch == 1 || blocks) && !c.ext_on && K == 288 && p.a_cs == 1 && p.alpha == 1.f && p.beta == 0.f && !p.colsum &&
+        (tilepiece || (!p.residual && n_all >= 768)) && n_all < (1 << 30) && M >= 8192 && al16(p.A) && al16(p.B) &&
+        (!p.residual || al16(p.residual)) && !getenv("PDN_GEMM_NO_ROWRES")))
+    return kNotTaken;
+  if (!((c.bt || p.b_cs == 1) && pdn_gemm_rowres_supported(M, N, K, p.a_rs, c.ldb, p.ldc, c.bt))) return kNotTaken;
+  GemmProfScope prof(2, 2.0 * M * (double)n_all * (double)K, 0.0, c.stream);
+  if (getenv("PDN_GEMM_DEBUG"))
+    fprintf(stderr, "pdn_gemm_f32 M=%d N=%lld K=%d -> row-resident (%s, %d block%s)\n", M, (long long)n_all, K,
+            c.bt ? "NT" : "NN", blocks ? nbatch : 1, blocks ? "s" : "");
+  return blocks ? pdn_gemm_rowres_blocks(p.A, p.B, p.C, M, (int)n_all, K, p.a_rs, c.ldb, p.ldc, c.bt, nbatch, b_bs, c.stream)
+                : pdn_gemm_rowres_f32(p.A, p.B, p.C, p.bias, p.residual, M, N, K, p.a_rs, c.ldb, p.ldc, c.bt, c.stream);
+}
+
+// ---- 6: weight gradient of a wide layer out of the model width: C (288 x N) = x^T (288 x K) g (K x N), K = tokens --
+// (the lm_head: N = 32000).  Output-resident over the 288 rows, g read once straight into MFMA operands
+// (gemm_outres_tn_kernel); K split so that the grid fills the chip once, slabs combined (with beta) by the reduce.
+static int route_outres_tn(GemmCall& c) {
+  GemmParams& p = c.p;
+  const int M = p.M, N = p.N, K = p.K;
+  if (!(c.nbatch == 1 && !c.ext_on && M == 288 && p.a_rs == 1 && p.a_cs >= 288 && p.b_cs == 1 && p.alpha == 1.f && !p.colsum &&
+        !p.bias && !p.residual && N >= 8192 && N % 32 == 0 && K % 32 == 0 && K >= 4096 && gemm_m4(p.a_cs) && gemm_m4(p.b_rs) &&
+        al16(p.A) && al16(p.B) && (int64_t)288 * p.ldc < (1ll << 30) && (int64_t)32 * p.b_rs < (1ll << 30) &&
+        !getenv("PDN_GEMM_NO_OUTRES")))
+    return kNotTaken;
+  int nw = 8, kps = K;
+  const int splits = pdn_gemm_outres_tn_plan(N, K, &nw, &kps);
+  const bool direct = splits == 1 && p.beta == 0.f;
+  if (!(direct || (int64_t)splits * M * N <= c.ws_floats)) return kNotTaken;
+  GemmProfScope prof(4, 2.0 * M * (double)N * (double)K, 0.0, c.stream);
+  if (getenv("PDN_GEMM_DEBUG"))
+    fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> output-resident TN (splits %d)\n", M, N, K, splits);
+  const int rc = direct ? pdn_gemm_outres_tn_launch(p.A, p.B, p.C, N, K, p.a_cs, p.b_rs, p.ldc, 0, nw, kps, c.stream)
+                        : pdn_gemm_outres_tn_launch(p.A, p.B, (float*)c.workspace, N, K, p.a_cs, p.b_rs, N, (int64_t)M * N, nw, kps,
+                                                    c.stream);
+  if (rc || direct) return rc;
+  p.splits = splits;
+  return reduce_slabs(p, (int64_t)M * N, 1, (p.ldc % 4 == 0) && al16(p.C) && al16(c.workspace), c.st);
+}
+
+// ---- 7: the packed weight gradients of a transformer block out of the model width: x^T (288 x K) against dq | dk | dv
+// (three 288-column blocks of one (K x 864) matrix) or dgate | dup (two 768-column blocks), one output per block.
+// The same output-resident TN kernel, K split 40-64 ways so that the grid fills the chip, slabs in the batched
+// layout of the split-K reduce (which adds beta * C).  Against the wave-streaming kernel: 864 columns -16 %,
+// 1536 columns -11 % (60 instead of 170 operand bytes per MFMA; the slab pass costs 30-40 us).
+static int route_outres_tn_blocks(GemmCall& c) {
+  GemmParams& p = c.p;
+  const int M = p.M, N = p.N, K = p.K, nbatch = c.nbatch;
+  const bool one_dim = c.nb1 == 1 || p.nb2 == 1;
+  const int64_t a_bs = c.nb1 == 1 ? p.a_bs2 : p.a_bs1, b_bs = c.nb1 == 1 ? p.b_bs2 : p.b_bs1;
+  const int64_t n_all = (int64_t)N * nbatch;
+  if (!(nbatch > 1 && one_dim && M == 288 && a_bs == 0 && b_bs == N && p.a_rs == 1 && p.a_cs >= 288 && p.b_cs == 1 &&
+        p.b_rs >= n_all && p.alpha == 1.f && !p.colsum && !p.bias && !p.residual && N % 32 == 0 && n_all >= 768 && n_all <= 8192 &&
+        K % 32 == 0 && K >= 16384 && gemm_m4(p.a_cs) && gemm_m4(p.b_rs) && al16(p.A) && al16(p.B) && !getenv("PDN_GEMM_NO_OUTRES")))
+    return kNotTaken;
+  int nw = 8, kps = K;
+  int splits = pdn_gemm_outres_tn_plan((int)n_all, K, &nw, &kps);
+  // split-fp16 form (csrc/outres_tn_split.hip): switched on, a shape it takes, 16-byte aligned operands, and a workspace
+  // that holds its extra region behind the 64 slabs (a caller that passes only the slabs selects the fp32 kernel: the
+  // in-process A/B switch).  It cuts K into its own number of ranges, at most 64.
+  const int64_t xoff = (((int64_t)64 * M * n_all * 4 + 255) & ~(int64_t)255);
+  const bool split16 = pdn_outres_tn_split_supported(M, N, nbatch, K) && pdn_outres_tn_split_enabled() && c.workspace &&
+                       c.workspace_bytes >= xoff + pdn_outres_tn_split_extra_bytes(K) && al16(c.workspace);
+  if (split16) {
+    kps = ((K / 32 + pdn_outres_tn_split_ranges((int)n_all, K, splits) - 1) / pdn_outres_tn_split_ranges((int)n_all, K, splits)) * 32;
+    splits = (K + kps - 1) / kps;
   }
-  PDN_CHECK_ARG(best >= 0 || use_stream, "pdn_gemm_f32: no tile configuration");
-  if (!use_stream && best_splits == 1 && !b_colsum && !ext_on && K >= 8192) {
-    // 2-4 very long blocks per CU: the last one of each CU runs without a co-resident partner to
-    // hide its barriers behind; halving the blocks evens that out (measured -3..4 % on the
-    // 32768 x 288 x 32000 and 288 x 32000 x 32768 products, slab pass included)
-    const int BMb = kCfgs[best].waves_m * kCfgs[best].wm * 32, BNb = kCfgs[best].waves_n * kCfgs[best].wn * 32;
-    const int64_t blocks = cdiv64(M, BMb) * cdiv64(N, BNb) * nbatch;
-    if (blocks > 512 && blocks < 1024 && (int64_t)2 * M * N * nbatch <= ws_cap) best_splits = 2;
-  }
-  // Mid-size products that 128 x 128 tiles cannot spread over the chip (fewer than 256 of them) or whose contraction is
-  // short (K <= 512): 64 x 64 tiles with a k-split.  Config 3's fully connected layers (4096 x 3200 x 500 in its three
-  // forms) measured inside the step: 1.390 -> 1.335 ms with `5,8` for all of them, every other choice in between
-  // (round 6; the cost model above prices a block's fixed cost too high for these).
-  // The k-split pays in the weight-gradient form only (long contraction over the rows): with the rows on the output side
-  // 5632 x 512 over K = 1536 measured 85 us unsplit against 94 / 96 / 103 us split 2 / 4 / 8 ways, 8192 x 1024 over 1024
-  // 143 against 161 / 177 / 233 us (tools/gemm_fc_sweep.py) -- and the Linear + ReLU products (mask epilogues: no split) take
-  // the same tiles: 5632 x 512 -> 1536 with its ReLU 104 -> 8x us.
-  if (!use_stream && !b_colsum && vec && nbatch == 1 && (int64_t)M * N >= (1 << 20) && (int64_t)M * N <= (1 << 24) &&
-      K <= 4096 && K >= 128 && (cdiv64(M, 128) * cdiv64(N, 128) < 256 || K <= 512)) {
-    int sp = (a_kin || ext_on) ? 1 : 8;
-    while (sp > 1 && (K / sp < 64 || (int64_t)sp * M * N > ws_cap)) sp >>= 1;
-    best = kScalarCfg;
-    best_splits = sp;
-  }
-  if (use_stream) best = 0;
-  else if (const char* e = getenv("PDN_GEMM_CFG")) {            // tuning override: "<cfg>[,<splits>]"
-    int c = -1, sp = 0;
-    if (sscanf(e, "%d,%d", &c, &sp) >= 1 && c >= 0 && c < kNumCfgs && vec &&
-        (!ext_on || c == 0 || c == 3 || c == 6 || c == 7 || (c == 8 && !mask_colsum) || c == kScalarCfg)) {
-      best = c;
-      if (sp >= 1 && (sp == 1 || ((int64_t)sp * M * N * nbatch <= ws_cap && !b_colsum && !ext_on))) best_splits = sp;
-    }
-  }
+  if (!(splits > 1 && (int64_t)splits * M * n_all <= c.ws_floats && nbatch * splits <= 65535)) return kNotTaken;
+  GemmProfScope prof(4, 2.0 * M * (double)n_all * (double)K, 0.0, c.stream);
+  if (getenv("PDN_GEMM_DEBUG"))
+    fprintf(stderr, "pdn_gemm_f32 M=%d N=%lld K=%d -> output-resident TN%s (%d blocks, splits %d)\n", M,
+            (long long)n_all, K, split16 ? ", split-fp16" : "", nbatch, splits);
+  const int rc = split16 ? pdn_outres_tn_split_launch(p.A, p.B, (float*)c.workspace, (int)n_all, K, p.a_cs, p.b_rs, N, kps,
+                                                      (char*)c.workspace + xoff, c.stream)
+                         : pdn_gemm_outres_tn_blocks_launch(p.A, p.B, (float*)c.workspace, (int)n_all, K, p.a_cs, p.b_rs, N, nw, kps,
+                                                            c.stream);
+  if (rc) return rc;
+  p.splits = splits;
+  return reduce_slabs(p, (int64_t)M * n_all, nbatch,
+                      (p.ldc % 4 == 0) && al16(p.C) && gemm_m4(p.c_bs1) && gemm_m4(p.c_bs2) && al16(c.workspace), c.st);
+}
+
+// ---- 8: the down-projection weight gradient dW_down (M x 288) = h^T (M x K) g2 (K x 288), M = 512 .. 1024 in whole waves,
+// from 32768 tokens on: the split-fp16 TN kernel with the roles swapped (g2 the plane-image operand, h the raw one) and a
+// transposed store (csrc/outres_tn_split.hip), its slabs combined (with beta) by the reduce.  Taken when switched on
+// (PDN_OUTRES_TN_SPLIT), with 16-byte aligned operands and a workspace that holds the extra region behind the 64 slabs; a
+// caller that passes only the slabs gets the wave-streaming fp32 kernel (the in-process A/B switch).
+static int route_down_dw_split(GemmCall& c) {
+  GemmParams& p = c.p;
+  const int M = p.M, N = p.N, K = p.K;
+  if (!(c.nbatch == 1 && !c.ext_on && p.a_rs == 1 && p.b_cs == 1 && p.alpha == 1.f && !p.colsum && !p.bias && !p.residual &&
+        pdn_down_dw_split_supported(M, N, K) && p.a_cs >= M && p.b_rs >= N && gemm_m4(p.a_cs) && gemm_m4(p.b_rs) && al16(p.A) &&
+        al16(p.B) && c.workspace && al16(c.workspace) && pdn_outres_tn_split_enabled() && !getenv("PDN_GEMM_NO_OUTRES")))
+    return kNotTaken;
+  const int64_t xoff = (((int64_t)64 * M * N * 4 + 255) & ~(int64_t)255);
+  const int ranges = pdn_down_dw_split_ranges(M, K);
+  const int kps = ((K / 32 + ranges - 1) / ranges) * 32;
+  const int splits = (K + kps - 1) / kps;
+  if (!(c.workspace_bytes >= xoff + pdn_outres_tn_split_extra_bytes(K) && splits > 1 && splits <= 64)) return kNotTaken;
+  if (getenv("PDN_GEMM_DEBUG"))
+    fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d -> output-resident TN, split-fp16, transposed (splits %d)\n", M, N, K, splits);
+  GemmProfScope prof(4, 2.0 * M * (double)N * (double)K, 0.0, c.stream);
+  const int rc = pdn_down_dw_split_launch(p.B, p.A, (float*)c.workspace, M, K, p.b_rs, p.a_cs, kps, (char*)c.workspace + xoff, c.stream);
+  if (rc) return rc;
+  p.splits = splits;
+  return reduce_slabs(p, (int64_t)M * N, 1, (p.ldc % 4 == 0) && al16(p.C), c.st);
+}
+
+// ---- 9: everything else: the wave-streaming weight-gradient kernels or the tiled kernel, as gemm_select.h chooses -------
+static int route_stream_or_tiled(GemmCall& c) {
+  GemmParams& p = c.p;
+  const int M = p.M, N = p.N, K = p.K, nbatch = c.nbatch;
+  const bool a_kin = c.lay.a_kin, b_kin = c.lay.b_kin, vec = c.lay.vec;
+  const GemmChoice ch = gemm_select(M, N, K, nbatch, p.a_rs, p.b_cs, c.lay, c.ext_on, p.colsum != nullptr, c.mask_colsum, c.ws_floats);
+  PDN_CHECK_ARG(ch.cfg >= 0, "pdn_gemm_f32: no tile configuration");
   if (getenv("PDN_GEMM_DEBUG")) {
-    if (use_stream) {
-      // the kernel the launch below picks (same tests, same order), its tile shape and the slabs it writes
-      const bool exact = M % 96 == 0 && N % 96 == 0;
-      const bool staged = vec && (sshape != 0 || !getenv("PDN_GEMM_STREAM_DIRECT"));
-      const char* kind = !staged ? (exact ? "direct" : "direct-edge")
-                         : (sshape != 0 || !exact) ? "lds-edge" : (getenv("PDN_GEMM_STREAM_NODMA") ? "lds" : "dma");
-      fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d nb=%d akin=%d bkin=%d vec=%d -> stream cfg=%d splits=%d sshape=%d kind=%s\n",
-              M, N, K, nbatch, (int)a_kin, (int)b_kin, (int)vec, best, p.splits, sshape, kind);
-    } else {
-      fprintf(stderr, "pdn_gemm_f32 M=%d N=%d K=%d nb=%d akin=%d bkin=%d vec=%d -> tiled cfg=%d splits=%d\n", M, N, K, nbatch,
-              (int)a_kin, (int)b_kin, (int)vec, best, best_splits);
-    }
+    char line[256];
+    gemm_route_line(line, sizeof(line), M, N, K, nbatch, c.lay, ch);
+    fputs(line, stderr);
   }
-  const TileCfg& cfg = kCfgs[best];
-  const int BM = cfg.waves_m * cfg.wm * 32, BN = cfg.waves_n * cfg.wn * 32;
-  if (!use_stream) {
-    p.tiles_m = (int)cdiv64(M, BM);
-    p.tiles_n = (int)cdiv64(N, BN);
-    const int ktiles = (int)cdiv64(K > 0 ? K : 1, cfg.bk);
-    p.k_per_split = (int)cdiv64(ktiles, best_splits) * cfg.bk;
-    p.splits = (int)cdiv64(K > 0 ? K : 1, p.k_per_split);
-    if (p.splits < 1) p.splits = 1;
-  }
+  p.tiles_m = ch.tiles_m; p.tiles_n = ch.tiles_n; p.k_per_split = ch.k_per_split; p.splits = ch.splits;
   PDN_CHECK_ARG((int64_t)nbatch * p.splits <= 65535, "pdn_gemm_f32: batch*splits too large (%d)",
                 nbatch * p.splits);
   dim3 grid(p.tiles_m * p.tiles_n, nbatch * p.splits);
+  hipStream_t st = c.st;
 
-  bool prof;
-  ProfRec rec;
-  {
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    prof = g_prof_on;
-  }
-  if (prof) {
-    PDN_HIP(hipEventCreate(&rec.e0));
-    PDN_HIP(hipEventCreate(&rec.e1));
-    rec.flops = 2.0 * M * N * (double)K * nbatch;
-    rec.family = use_stream ? 1 : 0;
-    PDN_HIP(hipEventRecord(rec.e0, st));
-  }
-
-  if (use_stream) {
+  GemmProfScope prof(ch.use_stream ? 1 : 0, 2.0 * M * N * (double)K * nbatch, 0.0, c.stream);
+  if (ch.use_stream) {
+    constexpr int SNW = kStreamWaves;
     const dim3 sgrid(p.tiles_m * p.tiles_n * p.splits, nbatch);
-    const bool exact = M % 96 == 0 && N % 96 == 0;
-    if (vec && sshape != 0) {                            // (set for aligned operands only)
-      switch (sshape) {
-        case 1: hipLaunchKernelGGL((gemm_tn_stream_lds_kernel<5, 2, SNW, true>), sgrid, dim3(SNW * 64), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((gemm_tn_stream_lds_kernel<2, 5, SNW, true>), sgrid, dim3(SNW * 64), 0, st, p); break;
-        case 3: hipLaunchKernelGGL((gemm_tn_stream_lds_kernel<4, 2, SNW, true>), sgrid, dim3(SNW * 64), 0, st, p); break;
-        default: hipLaunchKernelGGL((gemm_tn_stream_lds_kernel<2, 4, SNW, true>), sgrid, dim3(SNW * 64), 0, st, p); break;
-      }
-    } else if (vec && !getenv("PDN_GEMM_STREAM_DIRECT")) {      // 16-byte loads staged through LDS
-      if (exact && !getenv("PDN_GEMM_STREAM_NODMA"))
-        hipLaunchKernelGGL((gemm_tn_stream_dma_kernel<3, 3, SNW>), sgrid, dim3(SNW * 64), 0, st, p);
-      else if (exact) hipLaunchKernelGGL((gemm_tn_stream_lds_kernel<3, 3, SNW, false>), sgrid, dim3(SNW * 64), 0, st, p);
-      else hipLaunchKernelGGL((gemm_tn_stream_lds_kernel<3, 3, SNW, true>), sgrid, dim3(SNW * 64), 0, st, p);
-    } else {                                             // unaligned operands: dword loads, no LDS
-      if (exact) hipLaunchKernelGGL((gemm_tn_stream_kernel<3, 3, SNW, false>), sgrid, dim3(SNW * 64), 0, st, p);
-      else hipLaunchKernelGGL((gemm_tn_stream_kernel<3, 3, SNW, true>), sgrid, dim3(SNW * 64), 0, st, p);
+    switch (ch.kind) {
+      case kStreamLdsEdge:                                 // 16-byte loads staged through LDS, edge tests
+        switch (ch.sshape) {
+          case 0: hipLaunchKernelGGL((gemm_tn_stream_lds_kernel<3, 3, SNW, true>), sgrid, dim3(SNW * 64), 0, st, p); break;
+          case 1: hipLaunchKernelGGL((gemm_tn_stream_lds_kernel<5, 2, SNW, true>), sgrid, dim3(SNW * 64), 0, st, p); break;
+          case 2: hipLaunchKernelGGL((gemm_tn_stream_lds_kernel<2, 5, SNW, true>), sgrid, dim3(SNW * 64), 0, st, p); break;
+          case 3: hipLaunchKernelGGL((gemm_tn_stream_lds_kernel<4, 2, SNW, true>), sgrid, dim3(SNW * 64), 0, st, p); break;
+          default: hipLaunchKernelGGL((gemm_tn_stream_lds_kernel<2, 4, SNW, true>), sgrid, dim3(SNW * 64), 0, st, p); break;
+        }
+        break;
+      case kStreamDma: hipLaunchKernelGGL((gemm_tn_stream_dma_kernel<3, 3, SNW>), sgrid, dim3(SNW * 64), 0, st, p); break;
+      case kStreamLds: hipLaunchKernelGGL((gemm_tn_stream_lds_kernel<3, 3, SNW, false>), sgrid, dim3(SNW * 64), 0, st, p); break;
+      // unaligned operands: dword loads, no LDS
+      case kStreamDirect: hipLaunchKernelGGL((gemm_tn_stream_kernel<3, 3, SNW, false>), sgrid, dim3(SNW * 64), 0, st, p); break;
+      case kStreamDirectEdge: hipLaunchKernelGGL((gemm_tn_stream_kernel<3, 3, SNW, true>), sgrid, dim3(SNW * 64), 0, st, p); break;
     }
-  } else if (ext_on) {
+  } else if (c.ext_on) {
     if (!vec) launch_layout<2, 2, 1, 1, 32, false, true>(p, a_kin, b_kin, grid, st);
-    else switch (best) {
+    else switch (ch.cfg) {
       case 0: launch_layout<2, 2, 2, 2, 32, true, true>(p, a_kin, b_kin, grid, st); break;
       case 3: launch_layout<4, 1, 1, 2, 32, true, true>(p, a_kin, b_kin, grid, st); break;
       case 6: launch_layout<2, 2, 4, 2, 16, true, true>(p, a_kin, b_kin, grid, st); break;
@@ -795,7 +467,7 @@ static int gemm_f32_impl(int M, int N, int K, float alpha, const float* A, int64
       default: launch_layout<2, 2, 1, 1, 32, true, true>(p, a_kin, b_kin, grid, st); break;
     }
   } else if (vec) {
-    switch (best) {
+    switch (ch.cfg) {
       case 0: launch_layout<2, 2, 2, 2, 32, true>(p, a_kin, b_kin, grid, st); break;
       case 1: launch_layout<4, 1, 1, 3, 32, true>(p, a_kin, b_kin, grid, st); break;
       case 2: launch_layout<1, 4, 3, 1, 32, true>(p, a_kin, b_kin, grid, st); break;
@@ -814,20 +486,67 @@ static int gemm_f32_impl(int M, int N, int K, float alpha, const float* A, int64
     launch_layout<2, 2, 1, 1, 32, false>(p, a_kin, b_kin, grid, st);
   }
   PDN_LAUNCH_CHECK();
-  if (p.splits > 1) {
-    const int64_t total = (int64_t)M * N * nbatch;
-    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    const int rvec = (N % 4 == 0) && (ldc % 4 == 0) && al16(C) && m4(c_bs1) && m4(c_bs2) && (!bias || al16(bias)) &&
-                     (!residual || al16(residual)) && al16(workspace);
-    hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, p, nbatch, rvec);
-    PDN_LAUNCH_CHECK();
+  if (p.splits <= 1) return PDN_OK;
+  return reduce_slabs(p, (int64_t)M * N * nbatch, nbatch,
+                      (N % 4 == 0) && (p.ldc % 4 == 0) && al16(p.C) && gemm_m4(p.c_bs1) && gemm_m4(p.c_bs2) &&
+                          (!p.bias || al16(p.bias)) && (!p.residual || al16(p.residual)) && al16(c.workspace), st);
+}
+
+static int gemm_f32_impl(int M, int N, int K, float alpha, const float* A, int64_t a_rs,
+                         int64_t a_cs, const float* B, int64_t b_rs, int64_t b_cs, float beta,
+                         float* C, int64_t ldc, const float* bias, int nb1, int nb2,
+                         int64_t a_bs1, int64_t a_bs2, int64_t b_bs1, int64_t b_bs2,
+                         int64_t c_bs1, int64_t c_bs2, const float* residual,
+                         float* b_colsum, int colsum_accumulate, void* workspace,
+                         int64_t workspace_bytes, void* stream, uint32_t* relu_mask, const uint32_t* grad_mask,
+                         float* mask_colsum = nullptr) {
+  const bool ext_on = relu_mask || grad_mask;
+  PDN_CHECK_ARG(!ext_on || (nb1 == 1 && nb2 == 1 && N % 32 == 0 && !b_colsum),
+                "pdn_gemm_f32: the mask epilogues need one batch and N a multiple of 32 (N = %d)", N);
+  PDN_CHECK_ARG(M >= 0 && N >= 0 && K >= 0 && nb1 >= 0 && nb2 >= 0, "pdn_gemm_f32: negative extent");
+  if (M == 0 || N == 0 || nb1 == 0 || nb2 == 0) return PDN_OK;
+  PDN_CHECK_ARG(A && B && C, "pdn_gemm_f32: null operand");
+  PDN_CHECK_ARG(ldc >= N, "pdn_gemm_f32: ldc (%lld) < N (%d)", (long long)ldc, N);
+
+  GemmCall c;
+  GemmParams& p = c.p;
+  p.A = A; p.B = B; p.C = C; p.bias = bias; p.ws = (float*)workspace;
+  p.residual = residual; p.colsum = b_colsum; p.colsum_acc = colsum_accumulate;
+  p.relu_mask = relu_mask; p.grad_mask = grad_mask; p.mask_colsum = grad_mask ? mask_colsum : nullptr;
+  p.M = M; p.N = N; p.K = K;
+  p.a_rs = a_rs; p.a_cs = a_cs; p.b_rs = b_rs; p.b_cs = b_cs; p.ldc = ldc;
+  p.nb2 = nb2;
+  p.a_bs1 = a_bs1; p.a_bs2 = a_bs2; p.b_bs1 = b_bs1; p.b_bs2 = b_bs2; p.c_bs1 = c_bs1; p.c_bs2 = c_bs2;
+  p.alpha = alpha; p.beta = beta;
+  c.nb1 = nb1; c.nbatch = nb1 * nb2;
+  c.ext_on = ext_on; c.mask_colsum = mask_colsum != nullptr;
+  c.lay = gemm_layout(M, N, K, a_rs, a_cs, b_rs, b_cs, a_bs1, a_bs2, b_bs1, b_bs2, (uintptr_t)A, (uintptr_t)B);
+  c.bt = (b_rs == 1 && b_cs != 1) ? 1 : 0;
+  c.ldb = c.bt ? b_cs : b_rs;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.ws_bytes = (workspace && workspace_bytes > 0) ? workspace_bytes : 0;
+  c.ws_floats = c.ws_bytes / 4;
+  c.stream = stream; c.st = (hipStream_t)stream;
+
+  if (b_colsum) {
+    // fused column sums need B staged n-contiguous, A m-contiguous (the dW = x^T @ g form), the
+    // float4 path, a single batch and no k-split (each column is summed by exactly one block)
+    if (c.lay.a_kin || c.lay.b_kin || !c.lay.vec || c.nbatch != 1) {
+      pdn_set_error("pdn_gemm_f32: b_colsum needs the x^T @ g layout (A m-contiguous, B n-contiguous, aligned, unbatched)");
+      return PDN_EUNSUPPORTED;
+    }
   }
-  if (prof) {
-    PDN_HIP(hipEventRecord(rec.e1, st));
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    g_prof.push_back(rec);
-  }
-  return PDN_OK;
+  // the routes in their order: the first that takes the call launches it
+  int rc;
+  if ((rc = route_skinny(c)) != kNotTaken) return rc;
+  if ((rc = route_narrow(c)) != kNotTaken) return rc;
+  if ((rc = route_outres(c)) != kNotTaken) return rc;
+  if ((rc = route_outres_split288(c)) != kNotTaken) return rc;
+  if ((rc = route_rowres(c)) != kNotTaken) return rc;
+  if ((rc = route_outres_tn(c)) != kNotTaken) return rc;
+  if ((rc = route_outres_tn_blocks(c)) != kNotTaken) return rc;
+  if ((rc = route_down_dw_split(c)) != kNotTaken) return rc;
+  return route_stream_or_tiled(c);
 }
 
 extern "C" int pdn_gemm_f32(int M, int N, int K, float alpha, const float* A, int64_t a_rs,
@@ -949,7 +668,7 @@ extern "C" int pdn_gateup_swiglu_tiled_fwd_f32(const float* x, int64_t ldx, cons
   GemmParams p;
   p.A = x; p.B = packed; p.C = gu; p.a_rs = ldx; p.a_cs = 1; p.b_rs = Np; p.b_cs = 1; p.ldc = 2 * (int64_t)F;
   p.swi_h = h; p.swi_gu = nullptr; p.swi_ldh = F; p.swi_F = F;
-  int tok = pdn_gemm_prof_begin(0, 2.0 * M * 2.0 * F * K, 0.0, stream);
+  GemmProfScope prof(0, 2.0 * M * 2.0 * F * K, 0.0, stream);
   if (Np >= 2048) {                                            // 128 x 256 tiles
     swiglu_params(p, M, Np, K, 128, 256, 16);
     hipLaunchKernelGGL((gemm_f32_mfma_kernel<2, 2, 2, 4, 16, true, false, true, false, false, 1>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
@@ -958,7 +677,6 @@ extern "C" int pdn_gateup_swiglu_tiled_fwd_f32(const float* x, int64_t ldx, cons
     hipLaunchKernelGGL((gemm_f32_mfma_kernel<2, 2, 2, 2, 32, true, false, true, false, false, 1>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
   }
   PDN_LAUNCH_CHECK();
-  pdn_gemm_prof_end(tok, stream);
   pdn_count(PDN_CNT_TILED_SWIGLU_FWD);
   return PDN_OK;
 }
@@ -978,11 +696,10 @@ extern "C" int pdn_swiglu_bwd_tiled_f32(const float* dy, int64_t ldy, const floa
   GemmParams p;
   p.A = dy; p.B = w_down; p.C = dgu; p.a_rs = ldy; p.a_cs = 1; p.b_rs = 1; p.b_cs = K; p.ldc = 2 * (int64_t)F;
   p.swi_h = nullptr; p.swi_gu = gu; p.swi_ldh = 0; p.swi_F = F;
-  int tok = pdn_gemm_prof_begin(0, 2.0 * M * (double)F * K, 0.0, stream);
+  GemmProfScope prof(0, 2.0 * M * (double)F * K, 0.0, stream);
   swiglu_params(p, M, F, K, 128, 128, 32);
   hipLaunchKernelGGL((gemm_f32_mfma_kernel<2, 2, 2, 2, 32, true, true, true, false, false, 2>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
   PDN_LAUNCH_CHECK();
-  pdn_gemm_prof_end(tok, stream);
   pdn_count(PDN_CNT_TILED_SWIGLU_BWD);
   return PDN_OK;
 }
@@ -997,20 +714,6 @@ extern "C" int pdn_swiglu_bwd_tiled_f32(const float* dy, int64_t ldy, const floa
 // in = 288 (output-resident kernels, csrc/gemm_outres.hip).  The cross-entropy pass then only reads the logits
 // (row statistics) instead of reading them and writing a gradient of the same size.
 // ======================================================================================
-int pdn_outres_ce_dx_launch(const float* logits, int64_t ldl, const float* lse, const int64_t* targets, float gscale,
-                            const float* gdev, const float* W, int64_t ldw, float* dx, int64_t ldc,
-                            const float* residual, int M, int V, void* workspace, int64_t workspace_bytes, void* stream);
-int pdn_outres_ce_dw_launch(const float* X, const float* logits, float* C, int N, int K, int64_t ldx, int64_t ldg,
-                            int64_t ldc, int64_t slab, int nw, int k_per_split, const float* lse,
-                            const int64_t* targets, float gscale, const float* gdev, float* colsum, void* stream);
-// (the same product on split-fp16 MFMA, csrc/lm_head_dw_split.hip: pdn_outres_ce_dw_split_* of split_tn.h)
-
-int pdn_outres_ce_dx_deferred_launch(const float* logits, int64_t ldl, const float* rowmax, int max_parts,
-                                     const int64_t* targets, float gscale, const float* W, int64_t ldw, float* dx,
-                                     int64_t ldc, float* lse_out, int M, int V, void* workspace, int64_t workspace_bytes,
-                                     void* stream);
-extern "C" int pdn_linear_ce_dx_deferred_supported(int64_t M, int V, int K);
-
 // Input gradient of `linear -> cross entropy` from the logits and their ROW MAXIMA (pdn_linear_rowmax_fwd_f32: `max_parts`
 // vectors of `rows` maxima), leaving the rows' log-sum-exp as a by-product:
 //   dx[t] = gscale * (sum_v exp(l[t][v] - max[t]) W[:, v] / Z[t] - W[:, target[t]]),  Z[t] = sum_v exp(l[t][v] - max[t]),
@@ -1029,11 +732,9 @@ extern "C" int pdn_linear_ce_dx_deferred_f32(const float* logits, const float* r
     return PDN_EUNSUPPORTED;
   }
   PDN_CHECK_ARG(((((uintptr_t)logits | (uintptr_t)W) & 15) == 0), "pdn_linear_ce_dx_deferred_f32: 16-byte alignment required");
-  const int tk = pdn_gemm_prof_begin(3, 2.0 * (double)rows * (double)V * (double)in_features, 0.0, stream);
-  const int rc = pdn_outres_ce_dx_deferred_launch(logits, V, rowmax, max_parts, targets, gscale, W, V, dx, in_features, lse,
-                                                  (int)rows, V, workspace, workspace_bytes, stream);
-  pdn_gemm_prof_end(tk, stream);
-  return rc;
+  GemmProfScope prof(3, 2.0 * (double)rows * (double)V * (double)in_features, 0.0, stream);
+  return pdn_outres_ce_dx_deferred_launch(logits, V, rowmax, max_parts, targets, gscale, W, V, dx, in_features, lse,
+                                          (int)rows, V, workspace, workspace_bytes, stream);
 }
 
 extern "C" int pdn_linear_ce_supported(int64_t rows, int V, int in_features) {
@@ -1068,29 +769,10 @@ extern "C" int pdn_linear_ce_backward_f32(const float* x, int64_t ldx, const flo
   PDN_CHECK_ARG((ldx & 3) == 0 && ldx >= in_features && ((((uintptr_t)x | (uintptr_t)logits | (uintptr_t)W) & 15) == 0),
                 "pdn_linear_ce_backward_f32: 16-byte alignment required");
   hipStream_t st = (hipStream_t)stream;
-  bool prof;
-  {
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    prof = g_prof_on;
-  }
   // the two products count as launches of the output-resident family in the GEMM profile (bench.py roofline)
-  auto prof_begin = [&](ProfRec& rec) {
-    if (!prof) return;
-    (void)hipEventCreate(&rec.e0);
-    (void)hipEventCreate(&rec.e1);
-    rec.flops = 2.0 * (double)rows * (double)V * (double)in_features;
-    rec.family = 3;
-    (void)hipEventRecord(rec.e0, st);
-  };
-  auto prof_end = [&](ProfRec& rec) {
-    if (!prof) return;
-    (void)hipEventRecord(rec.e1, st);
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    g_prof.push_back(rec);
-  };
+  const double flops = 2.0 * (double)rows * (double)V * (double)in_features;
   if (dx) {
-    ProfRec rec;
-    prof_begin(rec);
+    GemmProfScope prof(3, flops, 0.0, stream);
     int nw_, kps_;
     const int64_t dw_bytes = (int64_t)pdn_gemm_outres_tn_plan(V, (int)rows, &nw_, &kps_) * (in_features + 1) * V * 4;
     const int64_t dx_bytes = pdn_gemm_outres_workspace_bytes((int)rows, V);
@@ -1098,11 +780,9 @@ extern "C" int pdn_linear_ce_backward_f32(const float* x, int64_t ldx, const flo
     int rc = pdn_outres_ce_dx_launch(logits, V, lse, targets, gscale, upstream, W, V, dx, in_features, dx_residual,
                                      (int)rows, V, dx_ws, dx_ws ? dx_bytes : 0, stream);
     if (rc) return rc;
-    prof_end(rec);
   }
-  ProfRec rec_w;
-  if (dW || dbias) { prof_begin(rec_w); rec_w.family = 4; }
   if (dW || dbias) {
+    GemmProfScope prof(4, flops, 0.0, stream);
     int nw, kps;
     const int splits = pdn_gemm_outres_tn_plan(V, (int)rows, &nw, &kps);
     const int64_t need = (int64_t)splits * (in_features + 1) * V * 4;
@@ -1124,20 +804,14 @@ extern "C" int pdn_linear_ce_backward_f32(const float* x, int64_t ldx, const flo
     p.N = V; p.nb2 = 1; p.splits = splits;
     if (dW) {
       p.M = in_features; p.C = dW; p.ldc = V; p.ws = slabs; p.beta = dw_beta;
-      const int64_t total = (int64_t)p.M * V;
-      const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-      const int rvec = ((uintptr_t)dW & 15) == 0 && ((uintptr_t)slabs & 15) == 0;
-      hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, p, 1, rvec);
-      PDN_LAUNCH_CHECK();
+      rc = reduce_slabs(p, (int64_t)p.M * V, 1, al16(dW) && al16(slabs), st);
+      if (rc) return rc;
     }
     if (dbias) {
       p.M = 1; p.C = dbias; p.ldc = V; p.ws = cs; p.beta = db_beta;
-      const int blocks = (V + 255) / 256 < 2048 ? (V + 255) / 256 : 2048;
-      const int rvec = ((uintptr_t)dbias & 15) == 0 && ((uintptr_t)cs & 15) == 0;
-      hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, p, 1, rvec);
-      PDN_LAUNCH_CHECK();
+      rc = reduce_slabs(p, V, 1, al16(dbias) && al16(cs), st);
+      if (rc) return rc;
     }
-    prof_end(rec_w);
   }
   return PDN_OK;
 }

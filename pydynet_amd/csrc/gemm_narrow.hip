@@ -15,6 +15,7 @@
 //    rows of the output and walks its share of the tokens.  Waves of a workgroup are combined through LDS, workgroups
 //    through the split-K slabs of csrc/gemm.hip (fixed order: deterministic).
 #include "common.h"
+#include "gemm_routes.h"
 #include <stdint.h>
 #include <algorithm>
 

@@ -21,6 +21,8 @@
 // The k-order of every output element is that of csrc/gemm.hip (k = 8t + 4h + j inside an MFMA group, groups
 // ascending), so the results are bit-identical to the tiled kernel's when that one does not split K.
 #include "common.h"
+#include "gemm_prof.h"
+#include "gemm_routes.h"
 #include <stdlib.h>
 
 // Timing-ablation switches (tools/*_probe.py): read ONCE per process; a non-zero value makes kernels skip work and return
@@ -475,9 +477,6 @@ extern "C" int pdn_gemm_outres_ws_f32(const float* A, const float* B, float* C, 
   return outres_launch(A, B, C, bias, residual, M, N, K, lda, ldb, ldc, b_trans, workspace, workspace_bytes, stream);
 }
 
-int pdn_gemm_prof_begin(int family, double flops, double bytes, void* stream);    // csrc/gemm.hip
-void pdn_gemm_prof_end(int token, void* stream);
-
 // dX (M x 288) = [d_1 | ... | d_nb] (M x nb * kb) * [W_1 | ... | W_nb]^T (+ residual), W_i (288 x kb) row-major and
 // `b_block_stride` floats apart -- the input gradient of projections that share their input (q | k | v, gate | up:
 // llm/llama/model.py:93-104, 56-58; `grad @ W^T` of tensor.py:670 summed over the projections by ONE contraction)
@@ -502,14 +501,6 @@ extern "C" int pdn_gemm_outres_blocks_nt_f32(const float* A, const float* W, int
   pdn_gemm_prof_end(tk, stream);
   return rc;
 }
-
-// csrc/outres_split.hip: the same product on split-fp16 MFMA (65536 rows and more, K in [256, 4096], no K split)
-int pdn_outres_split_takes(const float* A, const float* B, const float* C, const float* bias, const float* residual, int M,
-                           int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, int splits,
-                           void* stream);
-int pdn_outres_split_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int K,
-                            int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, void* stream,
-                            int count_slot);
 
 static int outres_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int N,
                          int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans, void* workspace,

@@ -25,6 +25,8 @@
 // group, groups ascending), so both kernels give bit-identical results.
 #include "common.h"
 #include "gemm_rowtile.h"
+#include "gemm_prof.h"
+#include "gemm_routes.h"
 #include <stdlib.h>
 
 // Timing-ablation switches (tools/*_probe.py): read ONCE per process; a non-zero value makes kernels skip work and return
@@ -668,8 +670,6 @@ extern "C" int pdn_gemm_rowres_supported(int M, int N, int K, int64_t lda, int64
 // B as `nblocks` matrices side by side (block b at B + b * b_block_stride floats; NN: each (K x N / nblocks),
 // NT: each (N / nblocks x K)); nblocks > 1 needs N / nblocks to be a multiple of 96.
 // `epi` (may be null): fused epilogue request, EPI of the kernel template + its operands.
-int pdn_gemm_prof_begin(int family, double flops, double bytes, void* stream);    // csrc/gemm.hip: bench.py's per-family timing
-void pdn_gemm_prof_end(int token, void* stream);
 struct RowResEpi {
   int kind;                 // 1 SwiGLU forward, 2 SwiGLU backward, 3 RoPE
   float* H; int64_t ldh;    // 1

@@ -29,6 +29,7 @@
 // k-group, groups ascending): results are bit-identical to both.
 #include "common.h"
 #include "gemm_rowtile.h"
+#include "gemm_routes.h"
 #include <stdlib.h>
 #include <type_traits>
 

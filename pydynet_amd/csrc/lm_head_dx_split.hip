@@ -34,6 +34,7 @@
 // stay in flight and are never waited for earlier than two pieces after their issue.
 // Deterministic: fixed order, no atomics.
 #include "split_tn.h"
+#include "gemm_prof.h"
 
 #define LD_N 288                          // output columns: 18 tiles of 16
 #define LD_NT 18
@@ -293,8 +294,6 @@ __global__ __launch_bounds__(512, 1) void ldx_main_kernel(LdxParams p) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-int pdn_gemm_prof_begin(int family, double flops, double bytes, void* stream);    // csrc/gemm.hip: bench.py's per-family timing
-void pdn_gemm_prof_end(int token, void* stream);
 int pdn_outres_wt_transpose_launch(const float* W, int64_t ldw, int V, float* Wt, void* stream);   // csrc/gemm_outres.hip
 
 // PDN_LMHEAD_DX_SPLIT=0: the fp32 kernel at every size (A/B switch; read once, announced)

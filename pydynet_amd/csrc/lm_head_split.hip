@@ -34,6 +34,7 @@
 // Deterministic: fixed order, no atomics.
 #include "common.h"
 #include "lm_head_split.h"
+#include "gemm_prof.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -301,8 +302,6 @@ __global__ __launch_bounds__(512, 1) void ls_main_kernel(LsParams p) {
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-int pdn_gemm_prof_begin(int family, double flops, double bytes, void* stream);    // csrc/gemm.hip: bench.py's per-family timing
-void pdn_gemm_prof_end(int token, void* stream);
 
 static void ls_plan(int64_t M, int V, int* tpw, int* parts) {
   const int nt = V / 32;

@@ -32,6 +32,7 @@
 // operands in LDS already.  Deterministic: fixed order, no atomics.
 #include "split_tn.h"
 #include "outres_split_index.h"
+#include "gemm_routes.h"
 
 extern "C" int pdn_malloc(void** ptr, int64_t bytes);
 extern "C" int pdn_free(void* ptr);

@@ -6,7 +6,8 @@ csrc/gemm_stream.h.  A case whose route is not the one it was written for fails.
 
 Every check is one `_run_case`; each GPU test (`-m gpu`) has a twin that runs the same case list on the NumPy emulation of
 the C ABI, which has no dispatch: the twin checks the harness, the float64 statements (tests/gemm_variants_ref.py) and the
-operand plumbing.  The `test_harness_notices_*` tests show that `_run_case` fails on an entry with one defect.
+operand plumbing (the selection itself, csrc/gemm_select.h, is held to the same pinned routes without a GPU by
+tests/test_gemm_select_cpu.py).  The `test_harness_notices_*` tests show that `_run_case` fails on an entry with one defect.
 
 Criteria, per case:
   * exact pass: operands, bias, residual and prior C are integers in [-4, 4], alpha in {1, 0.5, 2}, beta in {0, 1, 2},
@@ -43,12 +44,12 @@ EINVAL, EUNSUPPORTED = -1, -2
 ROUTING_VARS = ("PDN_GEMM_CFG", "PDN_GEMM_STREAM_SHAPE", "PDN_GEMM_STREAM_SPLITS", "PDN_GEMM_STREAM_DIRECT",
                 "PDN_GEMM_STREAM_NODMA", "PDN_GEMM_STREAM_MAX", "PDN_GEMM_NO_STREAM", "PDN_GEMM_NO_NARROW", "PDN_GEMM_DEBUG")
 
-# kCfgs of csrc/gemm.hip: (waves_m, waves_n, wm, wn, BK); BM = 32 waves_m wm, BN = 32 waves_n wn
+# kCfgs of csrc/gemm_select.h: (waves_m, waves_n, wm, wn, BK); BM = 32 waves_m wm, BN = 32 waves_n wn
 KCFGS = ((2, 2, 2, 2, 32), (4, 1, 1, 3, 32), (1, 4, 3, 1, 32), (4, 1, 1, 2, 32), (1, 4, 2, 1, 32), (2, 2, 1, 1, 32),
          (2, 2, 4, 2, 16), (2, 2, 2, 4, 16), (4, 1, 2, 3, 16), (1, 4, 3, 2, 16), (2, 1, 1, 3, 32), (1, 2, 3, 1, 32),
          (4, 1, 1, 3, 16))
 MASK_CFGS = (0, 3, 5, 6, 7, 8)               # the tile shapes built with MASKS
-STREAM_SHAPES = ((3, 3), (5, 2), (2, 5), (4, 2), (2, 4))      # kShapes of csrc/gemm.hip, in 32-row / 32-column tiles
+STREAM_SHAPES = ((3, 3), (5, 2), (2, 5), (4, 2), (2, 4))      # kShapes of csrc/gemm_select.h, in 32-row / 32-column tiles
 LAYOUTS = (("NN", False, False), ("NT", False, True), ("TN", True, False), ("TT", True, True))
 
 
@@ -603,8 +604,8 @@ _register("stream_batches_and_length_threshold", stream_batch_and_threshold_case
 # the tables say what they claim (CPU)
 # =====================================================================================================================
 def test_tile_table_matches_the_library_source():
-    """KCFGS and STREAM_SHAPES restate kCfgs / kShapes of csrc/gemm.hip."""
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pydynet_amd", "csrc", "gemm.hip")).read()
+    """KCFGS and STREAM_SHAPES restate kCfgs / kShapes of csrc/gemm_select.h (the selector of csrc/gemm.hip)."""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pydynet_amd", "csrc", "gemm_select.h")).read()
     body = src[src.index("static const TileCfg kCfgs[]"):src.index("static const int kNumCfgs")]
     rows = re.findall(r"^\s*\{(\d+), (\d+), (\d+), (\d+), (\d+), [\d.]+f\},", body, flags=re.M)
     assert tuple(tuple(int(x) for x in r) for r in rows) == KCFGS
