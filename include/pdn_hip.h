@@ -240,7 +240,9 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  49 sampling parameters per row (include/pdn_persample.h): once per pdnq_* entry
  *  50 down-projection weight gradient on split-fp16 MFMA (csrc/outres_tn_split.hip, transposed store): no entry of its own,
  *     the form pdn_gemm_f32 takes for h^T (M x K) against g2 (K x 288), M = 512 .. 1024, at 32768 tokens and more (see
- *     there): counts here ONLY, not in 15 or 42 */
+ *     there): counts here ONLY, not in 15 or 42
+ *  51 dh + SwiGLU backward on split-fp16 MFMA (csrc/rowtile_split.hip): no entry of its own, the form
+ *     pdn_swiglu_bwd_gemm_f32 takes at 16384 rows and more; counts in 3 as well, not in 41 */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores
@@ -267,7 +269,10 @@ int pdn_gemm_rowtile_mode(int mode);
  * not being captured (the tile images of W, (3D / 32 or 2F / 32) x 37120 bytes, come from pdn_malloc and are rebuilt on
  * every call), PDN_ROWTILE_SPLIT is not 0 (environment, read once, announced on stderr when 0; PDN_ROWTILE_SPLIT_ABLATE =
  * 1 / 2 are timing experiments with WRONG results, announced too) and pdn_gemm_rowtile_mode is not 3.  Everything else
- * stays on the fp32 MFMA kernels.  xn and rms are left exactly as the fp32 form leaves them (to fp32 round-off). */
+ * stays on the fp32 MFMA kernels.  xn and rms are left exactly as the fp32 form leaves them (to fp32 round-off).
+ * pdn_swiglu_bwd_gemm_f32 takes the same form (counter slot 51) under the same conditions when F is a multiple of 32 and dgu
+ * overlaps neither gu nor dy: dh on split fp16, the SwiGLU backward in fp32 exactly as the fp32 kernel forms it.
+ * PDN_ROWTILE_SPLIT_ABLATE = 4 (the gu rows are not read) is a timing experiment of this form only. */
 /* dX (M x 288) = [d_1 | ... | d_nb] (M x nb * kb) [W_1 | ... | W_nb]^T (+ residual): the input gradient of projections
  * that share their input, the weights W_i (288 x kb, row-major, `b_block_stride` floats apart) read where they live
  * (csrc/gemm_outres.hip; `grad @ W^T` of tensor.py:670, one contraction over all projections).

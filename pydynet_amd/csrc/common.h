@@ -24,7 +24,7 @@ enum {
   PDN_CNT_ROWRES_CHUNK = 0,       // gemm_rowres_kernel (chunk kernel), any epilogue
   PDN_CNT_ROWTILE_PLAIN = 1,      // gemm_rowtile_kernel<EPI 0>
   PDN_CNT_ROWTILE_SWIGLU_FWD = 2, // EPI 1: gate | up + SwiGLU (gemm_rowtile_kernel, or the split-fp16 kernel of csrc/rowtile_split.hip: 41 as well)
-  PDN_CNT_ROWTILE_SWIGLU_BWD = 3, // EPI 2: dh + SwiGLU backward
+  PDN_CNT_ROWTILE_SWIGLU_BWD = 3, // EPI 2: dh + SwiGLU backward (gemm_rowtile_kernel, or the split-fp16 kernel: 51 as well)
   PDN_CNT_ROWTILE_ROPE = 4,       // EPI 3: q | k | v + RoPE (likewise)
   PDN_CNT_ROWTILE_ROWMAX = 5,     // vocabulary projection + row maxima: gemm_rowtile_kernel<EPI 5>, or the split-fp16
                                   // kernel of csrc/lm_head_split.hip (which counts in 37 as well)
@@ -85,7 +85,9 @@ enum {
                                   // also counts where its shared-parameter form counts
   PDN_CNT_DOWN_DW_SPLIT = 50,     // down-projection weight gradient (M x 288 = h^T g2, M = 512 .. 1024, K >= 32768) of pdn_gemm_f32 on
                                   // split-fp16 MFMA (csrc/outres_tn_split.hip, transposed store): counts HERE ONLY, not in 15 or 42
-  PDN_CNT_SLOTS = 51
+  PDN_CNT_ROWTILE_BWD_SPLIT = 51, // dh + SwiGLU backward on split-fp16 MFMA (rts_main_kernel<2> of csrc/rowtile_split.hip): also counts in 3,
+                                  // NOT in 41
+  PDN_CNT_SLOTS = 52
 };
 void pdn_count(int slot);
 

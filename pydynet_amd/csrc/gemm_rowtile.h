@@ -31,7 +31,8 @@ struct RowTileArgs {
 // workgroup -- with the columns split over grid.y if need be)
 int pdn_rowtile_takes(const RowTileArgs& a);
 int pdn_rowtile_launch(const RowTileArgs& a, void* stream);
-// The split-fp16 form of epilogues 1 and 3 for 16384 rows and more (csrc/rowtile_split.hip), which pdn_rowtile_launch takes
-// unless the mode is 3, PDN_ROWTILE_SPLIT is 0, the shape is not its own or the stream is being captured (it allocates)
+// The split-fp16 form of epilogues 1, 2 and 3 for 16384 rows and more (csrc/rowtile_split.hip), which pdn_rowtile_launch
+// takes unless the mode is 3, PDN_ROWTILE_SPLIT is 0, the shape is not its own or the stream is being captured (it
+// allocates).  Epilogue 2 (b_trans, N = F, ldc >= 2F): F a multiple of 32, ldb >= 288, C apart from GU and A.
 int pdn_rowtile_split_takes(const RowTileArgs& a, void* stream);
 int pdn_rowtile_split_launch(const RowTileArgs& a, void* stream);

@@ -527,7 +527,7 @@ static void rowtile_plan(const RowTileArgs& a, int* pieces, int* ppw, int* nspli
 
 // 0 = never (the chunk kernel of gemm_rowres.hip runs), 1 = when every CU gets an 8-wave workgroup (default), 2 = whenever
 // the shape is valid (tests: small and ragged shapes on this kernel), 3 = as 1, but never the split-fp16 form of the
-// q | k | v and gate | up projections (csrc/rowtile_split.hip): the in-process A/B switch.  PDN_ROWTILE sets the initial value.
+// q | k | v, gate | up and dh + SwiGLU backward products (csrc/rowtile_split.hip): the in-process A/B switch.  PDN_ROWTILE sets the initial value.
 static int g_rowtile_mode = getenv("PDN_ROWTILE") ? atoi(getenv("PDN_ROWTILE")) : 1;
 extern "C" int pdn_gemm_rowtile_mode(int mode) {
   const int prev = g_rowtile_mode;

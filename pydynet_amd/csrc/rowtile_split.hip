@@ -1,19 +1,23 @@
-// q | k | v + RoPE and gate | up + SwiGLU on split-fp16 MFMA at fp32 accuracy (gfx950 only), for 16384 rows and more:
+// q | k | v + RoPE, gate | up + SwiGLU and dh + SwiGLU backward on split-fp16 MFMA at fp32 accuracy (gfx950 only), for 16384
+// rows and more:
 //
 //   qkv (M x 3D) = rmsnorm(x) [Wq | Wk | Wv], RoPE on the q and k blocks          (llm/llama/model.py:23-44, 93-104)
 //   gu (M x 2F)  = rmsnorm(x) [Wg | Wu],  h = silu(gate) * up                     (model.py:56-58)
+//   dgu (M x 2F) = SwiGLU'(gu) o (g2 W_down^T)                                    (model.py:56-58 backwards)
 //
-// the contracts of gemm_rowtile_kernel<false, 3 / 1, ., NORM> (csrc/gemm_rowtile.hip), whose launch routes here
+// the contracts of gemm_rowtile_kernel<false, 3 / 1, ., NORM> and <true, 2> (csrc/gemm_rowtile.hip), whose launch routes here
 // (pdn_rowtile_launch: no entry of its own).  It is the product of csrc/lm_head_split.hip -- tall A, contraction exactly
 // 288, A rows resident in registers as two fp16 planes, an N-sweep over 32-column tile images of W in a ring of three LDS
 // slots, transposed accumulators (a lane owns a ROW), the finished tile leaving row-wise through a per-wave LDS area in the
 // shadow of the next tile's MFMAs -- with two differences:
-//   * no pass over x: the wave reads its 32 rows itself, TWICE.  Sweep 1 forms the sum of squares (the RMSNorm's) and the
-//     largest |x w| of the row, from which the row's power of two follows (max |xn| = max |x w| / r up to round-off, which
-//     moves the planes' top bit by at most one place); sweep 2 reads the rows again (from L2, or from memory once more
-//     rows are in flight than it holds), normalises with the arithmetic of the fp32 kernel (x * (1 / r) * w), stores xn and
-//     splits, three k-steps at a time: 144 fp32 values and 144 plane registers are never alive together.  Only the
-//     workgroups of the first column range (blockIdx.y == 0) write xn / rms.
+//   * no pass over x: the wave reads its 32 rows itself, ONCE and by whole 128-byte lines (eight lanes per row; 36
+//     instructions, 144 registers).  From them it forms the sum of squares (the RMSNorm's) and the largest |x w| of each
+//     row, from which the row's power of two follows (max |xn| = max |x w| / r up to round-off, which moves the planes'
+//     top bit by at most one place).  Then, a chunk of 32 columns at a time, it normalises with the arithmetic of the fp32
+//     kernel (x * (1 / r) * w), stores xn as whole lines, passes the 32 x 32 chunk through its staging area and reads it
+//     back as the B fragments of two k-steps, which are split: 16 fp32 registers die as 16 plane registers are born, so
+//     the 144 fp32 values and the 144 plane registers are never alive together.  Only the workgroups of the first column
+//     range (blockIdx.y == 0) write xn / rms.
 //   * the epilogues run in the drain, AFTER the scale is removed (one ldexp with the sum of the two integer exponents):
 //     RoPE rotates the pairs inside a lane's four columns with the table entries of its own row (the two EVEN columns'
 //     entries serve both members of a pair), requested three or four slots ahead into four registers; SwiGLU meets
@@ -21,6 +25,10 @@
 //     followed by their 16 up columns (rowtile_split_index.h).  h is formed from
 //     the still-scaled registers a second time (8 ldexp) rather than kept, and passes through the same LDS area once the
 //     gu rows have left it.
+//   * dh + SwiGLU backward (EPI 2): a tile is 32 dh columns = 32 rows of W_down (the W pass reads them along k).  Its
+//     row-wise store step meets, per lane, the 16 bytes of gate and of up at its row and columns of gu and writes dgate
+//     and dup there: whole 128-byte lines in all four streams.  The gu values of two row steps are held at a time (16
+//     registers), requested behind the staging loads of the tile before or in front of those of slot 6 (run_tile).
 // One small launch per call (rts_w_kernel) builds the tile images from the weights where they live; the optimiser changes
 // them every step.  Every address comes from rowtile_split_index.h, which tests/rowtile_split_check.cpp walks on the host.
 // Deterministic: fixed order, no atomics.
@@ -51,11 +59,25 @@ __global__ __launch_bounds__(256) void rts_w_kernel(RtsWParams p) {
   const int tid = threadIdx.x, c = tid & 31, kq = tid >> 5, tile = blockIdx.x;
   float amax = 0.f;
   bool bad = false;
-  for (int k = kq; k < RTS_K; k += 8) {
-    const float f = p.B[rts_w_src(p.kind, tile, c, k, p.nper, p.ldb, p.bstride, p.g_off, p.u_off)];
-    sm[k * 33 + c] = f;
-    amax = fmaxf(amax, fabsf(f));
-    bad |= !(fabsf(f) < INFINITY);
+  if (p.kind == 2) {
+    // transposed source (the rows of W_down are the tile's columns): read along k, 288 contiguous floats per column
+    for (int i = tid; i < 32 * RTS_K; i += 256) {
+      const int n = rts_w_t_n(i), k = rts_w_t_k(i);
+      sm[k * 33 + n] = p.B[rts_w_src_t(tile, n, k, p.ldb)];
+    }
+    __syncthreads();
+    for (int k = kq; k < RTS_K; k += 8) {
+      const float f = sm[k * 33 + c];
+      amax = fmaxf(amax, fabsf(f));
+      bad |= !(fabsf(f) < INFINITY);
+    }
+  } else {
+    for (int k = kq; k < RTS_K; k += 8) {
+      const float f = p.B[rts_w_src(p.kind, tile, c, k, p.nper, p.ldb, p.bstride, p.g_off, p.u_off)];
+      sm[k * 33 + c] = f;
+      amax = fmaxf(amax, fabsf(f));
+      bad |= !(fabsf(f) < INFINITY);
+    }
   }
   smax[kq * 32 + c] = bad ? INFINITY : amax;
   __syncthreads();
@@ -90,6 +112,7 @@ struct RtsParams {
   const char* wimg;
   float* C;
   float* H;
+  const float* GU;                // EPI 2: the saved [gate | up] rows, leading dimension ldc
   unsigned ldc, ldh;
   const float* rope;
   int L, hd, rope_tiles;
@@ -102,7 +125,7 @@ struct RtsParams {
   float norm_eps;
   int M, ntiles, tpw;
   int ablate;                     // PDN_ROWTILE_SPLIT_ABLATE (timing experiments; 0 in the library): 1 = no stores,
-                                  // 2 = constant planes (the rows of x are not read)
+                                  // 2 = constant planes (the rows of x are not read), 4 = EPI 2: the gu rows are not read
 };
 
 template <int V> using rts_ic = std::integral_constant<int, V>;
@@ -111,11 +134,12 @@ __device__ __forceinline__ float rts_sigmoid(float g) {     // rt_sigmoid of csr
   return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * g));
 }
 
-// EPI: 1 SwiGLU, 3 RoPE.  GUARD: M is not a multiple of 256 (row test in every store).  NORM: A holds the rows BEFORE
+// EPI: 1 SwiGLU, 2 SwiGLU backward (W transposed, NORM never), 3 RoPE.  GUARD: M is not a multiple of 256 (row test in every store).  NORM: A holds the rows BEFORE
 // the RMSNorm.  LDS: the ring of three tile images and the eight staging areas of ls_main_kernel.
 template <int EPI, bool GUARD, bool NORM>
 __global__ __launch_bounds__(512, 1) void rts_main_kernel(RtsParams p) {
-  static_assert(EPI == 1 || EPI == 3, "SwiGLU or RoPE");
+  static_assert(EPI == 1 || EPI == 2 || EPI == 3, "SwiGLU, SwiGLU backward or RoPE");
+  static_assert(EPI != 2 || !NORM, "SwiGLU backward: no RMSNorm in front");
   __shared__ __attribute__((aligned(16))) char smem[RTS_LDS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -141,6 +165,7 @@ __global__ __launch_bounds__(512, 1) void rts_main_kernel(RtsParams p) {
     stage_park(0, 0, t0); stage_park(0, 1, t1); stage_park(0, 2, t2); stage_park(0, 3, t3); stage_park(0, 4, t4);
   }
   // ---- the wave's 32 rows: statistics, then normalise / store / split ------------------------------------------------
+  char* stg0 = smem + 3 * RTS_TILE + wave * RTS_STG;
   f16x8 xh[RTS_KS], xl[RTS_KS];
   int nexv = 0;
   if (p.ablate & 2) {
@@ -149,64 +174,84 @@ __global__ __launch_bounds__(512, 1) void rts_main_kernel(RtsParams p) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) { xh[s][j] = (_Float16)1.f; xl[s][j] = (_Float16)0.5f; }
   } else {
-    const char* ap = reinterpret_cast<const char*>(p.A + rts_a_row(m0, li, p.M) * p.lda + rts_a_col(0, lh));
-    const char* wp = reinterpret_cast<const char*>(p.norm_w + rts_a_col(0, lh));
-    float ss = 0.f, am = 0.f;
-    bool bad = false;
-#pragma unroll 6
-    for (int s = 0; s < RTS_KS; ++s) {
-      const float4 a = *reinterpret_cast<const float4*>(ap + 64 * s), b = *reinterpret_cast<const float4*>(ap + 64 * s + 16);
-      float4 wa = make_float4(1.f, 1.f, 1.f, 1.f), wb = wa;
-      if (NORM) { wa = *reinterpret_cast<const float4*>(wp + 64 * s); wb = *reinterpret_cast<const float4*>(wp + 64 * s + 16); }
-      ss += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
-      ss += (b.x * b.x + b.y * b.y) + (b.z * b.z + b.w * b.w);
-      const float f0 = fabsf(a.x * wa.x), f1 = fabsf(a.y * wa.y), f2 = fabsf(a.z * wa.z), f3 = fabsf(a.w * wa.w);
-      const float f4 = fabsf(b.x * wb.x), f5 = fabsf(b.y * wb.y), f6 = fabsf(b.z * wb.z), f7 = fabsf(b.w * wb.w);
-      const float fm = fmaxf(fmaxf(fmaxf(f0, f1), fmaxf(f2, f3)), fmaxf(fmaxf(f4, f5), fmaxf(f6, f7)));
-      am = fmaxf(am, fm);
-      // Inf or NaN anywhere (fmaxf alone would drop a NaN): the sum is then non-finite too
-      bad |= !(((f0 + f1) + (f2 + f3)) + ((f4 + f5) + (f6 + f7)) < INFINITY);
+    // whole 128-byte lines: instruction (c, i) takes columns 32 c + 4 (lane & 7) .. + 3 of row 8 i + (lane >> 3), eight
+    // lanes per row and line; every element of the 32 rows is read ONCE and stays in registers until its chunk is split
+    const char* arow[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      arow[i] = reinterpret_cast<const char*>(p.A + rts_a_row(m0, rts_pl_row(lane, i), p.M) * p.lda + rts_pl_col(lane, 0));
+    const char* wp = reinterpret_cast<const char*>(p.norm_w + rts_pl_col(lane, 0));
+    float4 xa[RTS_CHUNKS][4];
+#pragma unroll
+    for (int c = 0; c < RTS_CHUNKS; ++c)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) xa[c][i] = *reinterpret_cast<const float4*>(arow[i] + 128 * c);
+    // statistics of the lane's four rows: sum of squares, max |x w| (INFINITY once an Inf or NaN was seen: fmaxf alone
+    // would drop a NaN, the sum of the four does not)
+    float ss[4] = {0.f, 0.f, 0.f, 0.f}, am[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < RTS_CHUNKS; ++c) {
+      float4 w = make_float4(1.f, 1.f, 1.f, 1.f);
+      if (NORM) w = *reinterpret_cast<const float4*>(wp + 128 * c);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float4 a = xa[c][i];
+        ss[i] += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
+        const float f0 = fabsf(a.x * w.x), f1 = fabsf(a.y * w.y), f2 = fabsf(a.z * w.z), f3 = fabsf(a.w * w.w);
+        am[i] = fmaxf(am[i], fmaxf(fmaxf(f0, f1), fmaxf(f2, f3)));
+        if (!((f0 + f1) + (f2 + f3) < INFINITY)) am[i] = INFINITY;
+      }
     }
-    ss += __shfl_xor(ss, 32, 64);
-    am = fmaxf(am, __shfl_xor(am, 32, 64));
-    bad = bad || (__shfl_xor(bad ? 1 : 0, 32, 64) != 0);
-    float inv = 1.f;
-    const bool row_w = (!GUARD || m0 + li < p.M) && blockIdx.y == 0 && !(p.ablate & 1);
-    if (NORM) {
-      const float r = sqrtf(ss / 288.f + p.norm_eps);
-      inv = 1.f / r;
-      if (lh == 0 && row_w) p.rms[m0 + li] = r;
+    // the eight lanes of a row, in a fixed order; then every one of them has the row's r, 1 / r and shift
+    float inv[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int d = 1; d < 8; d <<= 1) {
+        ss[i] += __shfl_xor(ss[i], d, 64);
+        am[i] = fmaxf(am[i], __shfl_xor(am[i], d, 64));
+      }
+      float r = 1.f;
+      inv[i] = 1.f;
+      if (NORM) { r = sqrtf(ss[i] / 288.f + p.norm_eps); inv[i] = 1.f / r; }
+      const float amax = NORM ? am[i] * inv[i] : am[i];
+      const int sh_i = ls_shift(!(amax < INFINITY) ? INFINITY : amax);      // a non-finite row keeps scale 1 and comes out NaN
+      // to the lanes that own the row's fragments, through the wave's staging area (free before the first tile leaves)
+      if ((lane & 7) == 0)
+        *reinterpret_cast<float2*>(__builtin_assume_aligned(stg0 + rts_pl_stat(rts_pl_row(lane, i)), 8)) = make_float2(r, __int_as_float(sh_i));
     }
-    const float amax = NORM ? am * inv : am;
-    const int sh = ls_shift((bad || !(amax < INFINITY)) ? INFINITY : amax);   // a non-finite row keeps scale 1 and comes out NaN
+    const float2 st = *reinterpret_cast<const float2*>(__builtin_assume_aligned(stg0 + rts_pl_stat(li), 8));
+    const int sh = __float_as_int(st.y);
     nexv = -sh;
-    char* xp = reinterpret_cast<char*>(p.xn + rts_a_row(m0, li, p.M) * p.ldxn + rts_a_col(0, lh));
-    asm volatile("" : "+v"(ap));                    // (read again: the rows of sweep 1 must not stay in registers)
+    const bool wr_on = blockIdx.y == 0 && !(p.ablate & 1);
+    if (NORM && lh == 0 && wr_on && (!GUARD || m0 + li < p.M)) p.rms[m0 + li] = st.x;
+    char* xrow[4];
 #pragma unroll
-    for (int s0 = 0; s0 < RTS_KS; s0 += 3) {
-      float4 xa[3], xb[3], wa[3], wb[3];
+    for (int i = 0; i < 4; ++i)
+      xrow[i] = reinterpret_cast<char*>(p.xn + rts_a_row(m0, rts_pl_row(lane, i), p.M) * p.ldxn + rts_pl_col(lane, 0));
+    char* pw = stg0 + rts_pl_stg_w(lane, 0);        // row step i: 8 i rows further on
+    const char* pf = stg0 + rts_pl_stg_r(li, lh, 0, 0);
+    // a chunk of 32 columns (two k-steps): normalise where it was loaded, xn leaves as whole lines, the 32 x 32 chunk
+    // passes through the staging area (row pitch 144) and comes back as the B fragments k = 16 s + 8 lh .. + 7 of row li
 #pragma unroll
-      for (int e = 0; e < 3; ++e) {
-        xa[e] = *reinterpret_cast<const float4*>(ap + 64 * (s0 + e));
-        xb[e] = *reinterpret_cast<const float4*>(ap + 64 * (s0 + e) + 16);
+    for (int c = 0; c < RTS_CHUNKS; ++c) {
+      float4 w = make_float4(1.f, 1.f, 1.f, 1.f);
+      if (NORM) w = *reinterpret_cast<const float4*>(wp + 128 * c);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float4 v = xa[c][i];
         if (NORM) {
-          wa[e] = *reinterpret_cast<const float4*>(wp + 64 * (s0 + e));
-          wb[e] = *reinterpret_cast<const float4*>(wp + 64 * (s0 + e) + 16);
+          v.x = v.x * inv[i] * w.x; v.y = v.y * inv[i] * w.y; v.z = v.z * inv[i] * w.z; v.w = v.w * inv[i] * w.w;
+          if (wr_on && (!GUARD || m0 + rts_pl_row(lane, i) < p.M)) *reinterpret_cast<float4*>(xrow[i] + 128 * c) = v;
         }
+        *reinterpret_cast<float4*>(__builtin_assume_aligned(pw + i * (8 * 144), 16)) = v;
       }
 #pragma unroll
-      for (int e = 0; e < 3; ++e) {
-        const int s = s0 + e;
-        float v[8] = {xa[e].x, xa[e].y, xa[e].z, xa[e].w, xb[e].x, xb[e].y, xb[e].z, xb[e].w};
-        if (NORM) {
-          const float w[8] = {wa[e].x, wa[e].y, wa[e].z, wa[e].w, wb[e].x, wb[e].y, wb[e].z, wb[e].w};
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = v[j] * inv * w[j];
-          if (row_w) {
-            *reinterpret_cast<float4*>(xp + 64 * s) = make_float4(v[0], v[1], v[2], v[3]);
-            *reinterpret_cast<float4*>(xp + 64 * s + 16) = make_float4(v[4], v[5], v[6], v[7]);
-          }
-        }
+      for (int e = 0; e < 2; ++e) {
+        const int s = 2 * c + e;
+        const float4 va = *reinterpret_cast<const float4*>(__builtin_assume_aligned(pf + 64 * e, 16));
+        const float4 vb = *reinterpret_cast<const float4*>(__builtin_assume_aligned(pf + 64 * e + 16, 16));
+        const float v[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           _Float16 h, l;
@@ -225,7 +270,7 @@ __global__ __launch_bounds__(512, 1) void rts_main_kernel(RtsParams p) {
 
   const int fr_even = rts_frag_base(li, lh, 0), fr_odd = rts_frag_base(li, lh, 1);
   const int tail_lane = RTS_TAIL + 4 * rts_reg_col(0, lh);   // group g: 32 g bytes further on
-  char* stg = smem + 3 * RTS_TILE + wave * RTS_STG;
+  char* stg = stg0;
   char* stg_w = stg + rts_stg_w(li, lh, 0);         // group g: 32 g bytes further on
   const char* stg_r = stg + rts_stg_r(lane, 0);     // store j: 8 j rows further on
   const char* stgh_r = stg + rts_h_r(lane, 0);      // h store j: 16 j rows further on
@@ -237,6 +282,11 @@ __global__ __launch_bounds__(512, 1) void rts_main_kernel(RtsParams p) {
                                 : 4u * (unsigned)rts_st_col(lane));
   const unsigned obh = 4u * (unsigned)rts_h_row(lane, 0) * p.ldh + 16u * (unsigned)(lane & 3);
   const unsigned ldc32 = 32u * p.ldc, ldh64 = 64u * p.ldh;   // eight rows of C / sixteen rows of H, in bytes
+  const unsigned Fb = 4u * (unsigned)p.F;           // EPI 2: dup / up lie F floats after dgate / gate
+  const bool gu_on = !(p.ablate & 4);
+  // EPI 2: the saved gate / up values of two row steps (rows 8 j + (lane >> 3), columns 4 (lane & 7) .. + 3 of the tile)
+  float4 pg[2], pu[2];
+  pg[0] = pg[1] = pu[0] = pu[1] = make_float4(1.f, 1.f, 1.f, 1.f);
   const unsigned tab_lane = 8u * (unsigned)rts_rope_pos(m0, li, p.L) * (unsigned)p.hd;   // this lane's row of the table, in bytes
 
   // the table entries of the two even columns of group g of tile t: (cos, -sin, cos', -sin')
@@ -285,6 +335,32 @@ __global__ __launch_bounds__(512, 1) void rts_main_kernel(RtsParams p) {
     if (st_all && (!GUARD || hrow + 16 * j < p.M))
       *reinterpret_cast<float4*>(reinterpret_cast<char*>(Hd) + obh + (unsigned)j * ldh64) = v;
   };
+  // EPI 2: gate and up of row step j of the tile whose first gate column is at Gd: a whole 128-byte line per eight lanes each
+  auto gu_ld = [&](int j, const float* Gd, float4& g, float4& u) __attribute__((always_inline)) {
+    if (gu_on && (!GUARD || srow + 8 * j < p.M)) {
+      const char* src = reinterpret_cast<const char*>(Gd) + ob + (unsigned)j * ldc32;
+      g = *reinterpret_cast<const float4*>(src);
+      u = *reinterpret_cast<const float4*>(src + Fb);
+    }
+  };
+  // EPI 2 store j: dh of rows 8 j .. 8 j + 7 from the staging area, the arithmetic of gemm_rowtile_kernel<., 2>
+  auto store_bwd = [&](int j, float* Cd, const float4& g, const float4& u) __attribute__((always_inline)) {
+    const float4 d = *reinterpret_cast<const float4*>(__builtin_assume_aligned(stg_r + j * (8 * 144), 16));
+    const float dh[4] = {d.x, d.y, d.z, d.w}, gv[4] = {g.x, g.y, g.z, g.w}, uv[4] = {u.x, u.y, u.z, u.w};
+    float dg[4], du[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float s = rts_sigmoid(gv[i]), sl = gv[i] * s;
+      const float dsl = fmaf(sl, 1.f - s, s);       // silu'(g) = s (1 + g (1 - s))
+      dg[i] = dh[i] * uv[i] * dsl; du[i] = dh[i] * sl;
+    }
+    if (st_all && (!GUARD || srow + 8 * j < p.M)) {
+      char* dst = reinterpret_cast<char*>(Cd) + ob + (unsigned)j * ldc32;
+      *reinterpret_cast<float4*>(dst) = make_float4(dg[0], dg[1], dg[2], dg[3]);
+      *reinterpret_cast<float4*>(dst + Fb) = make_float4(du[0], du[1], du[2], du[3]);
+    }
+  };
+  auto g_of = [&](int t) -> const float* { return p.GU + (int64_t)m0 * p.ldc + 32 * t; };
   auto c_of = [&](int t) -> float* { return p.C + (int64_t)m0 * p.ldc + (EPI == 1 ? 16 : 32) * t; };
   auto h_of = [&](int t) -> float* { return p.H + (int64_t)m0 * p.ldh + 16 * t; };
 
@@ -295,6 +371,9 @@ __global__ __launch_bounds__(512, 1) void rts_main_kernel(RtsParams p) {
   //   RoPE:   the table entries of group g are requested in slots 0, 4, 8, 12 (four registers) and the group is drained
   //           in 4, 8, 12, 15; row stores in 16, 17
   //   SwiGLU: groups drained in 1, 3, 5, 7; gu row stores in 8 .. 11; h formed in 12, 13 and stored in 14, 15
+  //   SwiGLU backward: groups drained in 0 .. 3; row steps 0, 1 leave in 4, 5 with the gate / up values requested in slot
+  //           13 of the tile BEFORE (behind that tile's last staging load, long arrived); the values of row steps 2, 3 are
+  //           requested in slot 6 into the same registers, in front of the staging loads of that slot, and used in 11, 12
   auto run_tile = [&](auto firstc, int t, int cur, int prv, int nxt) __attribute__((always_inline)) {
     constexpr bool FIRST = decltype(firstc)::value != 0;
     lds_barrier();
@@ -318,6 +397,7 @@ __global__ __launch_bounds__(512, 1) void rts_main_kernel(RtsParams p) {
       if (s + 1 < RTS_KS) { RTS_LOADH((s + 1) & 1, s + 1) }
       // which group leaves for the LDS area in this slot (-1: none), and which h group is formed
       const int dg = EPI == 1 ? (((s & 1) && s < 8) ? (s >> 1) : -1)
+                     : EPI == 2 ? (s < 4 ? s : -1)
                               : (s == 4 ? 0 : s == 8 ? 1 : s == 12 ? 2 : s == 15 ? 3 : -1);
       const int hg = EPI == 1 ? (s == 12 ? 0 : s == 13 ? 1 : -1) : -1;
       if (!FIRST && dg >= 0) ne = *reinterpret_cast<const int4*>(__builtin_assume_aligned(tl + 32 * dg, 16));
@@ -339,9 +419,13 @@ __global__ __launch_bounds__(512, 1) void rts_main_kernel(RtsParams p) {
       if (s == 17) stage_park(nxt, 4, r0);
       if (!FIRST && dg >= 0) drain_group(dg, ne, tb, rot);
       if (EPI == 3 && !FIRST && (s == 0 || s == 4 || s == 8 || s == 12)) rope_ld(t - 1, s >> 2, tb);
+      if (EPI == 2 && !FIRST && (s == 4 || s == 5)) store_bwd(s - 4, Cd, pg[s - 4], pu[s - 4]);
+      if (EPI == 2 && !FIRST && s == 6) { gu_ld(2, g_of(t - 1), pg[0], pu[0]); gu_ld(3, g_of(t - 1), pg[1], pu[1]); }
+      if (EPI == 2 && !FIRST && (s == 11 || s == 12)) store_bwd(s - 9, Cd, pg[s - 11], pu[s - 11]);
       if (s == 0) { stage_ld(nb, 0, r0); stage_ld(nb, 1, r1); }
       if (s == 6) { stage_ld(nb, 2, r0); stage_ld(nb, 3, r1); }
       if (s == 12) stage_ld(nb, 4, r0);
+      if (EPI == 2 && s == 13) { gu_ld(0, g_of(t), pg[0], pu[0]); gu_ld(1, g_of(t), pg[1], pu[1]); }   // of THIS tile: it leaves next
       if (EPI == 3 && !FIRST && s >= 16) { store_rows(2 * (s - 16), Cd); store_rows(2 * (s - 16) + 1, Cd); }
       if (EPI == 1 && !FIRST && s >= 8 && s < 12) store_rows(s - 8, Cd);
       if (!FIRST && hg >= 0) h_group(hg, ne, nu);
@@ -371,14 +455,22 @@ __global__ __launch_bounds__(512, 1) void rts_main_kernel(RtsParams p) {
       tb[g] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (EPI == 3) rope_ld(T1 - 1, g, tb[g]);
     }
+    float4 lg[2], lu[2];                            // EPI 2: row steps 2, 3 (0, 1 were requested in slot 13)
+    lg[0] = lg[1] = lu[0] = lu[1] = make_float4(1.f, 1.f, 1.f, 1.f);
+    if (EPI == 2) { gu_ld(2, g_of(T1 - 1), lg[0], lu[0]); gu_ld(3, g_of(T1 - 1), lg[1], lu[1]); }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int4 ne = *reinterpret_cast<const int4*>(__builtin_assume_aligned(tl + 32 * g, 16));
       drain_group(g, ne, tb[g], rot);
     }
     __builtin_amdgcn_sched_barrier(0);
+    if (EPI == 2) {
+      store_bwd(0, Cd, pg[0], pu[0]); store_bwd(1, Cd, pg[1], pu[1]);
+      store_bwd(2, Cd, lg[0], lu[0]); store_bwd(3, Cd, lg[1], lu[1]);
+    } else {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) store_rows(j, Cd);
+      for (int j = 0; j < 4; ++j) store_rows(j, Cd);
+    }
     if (EPI == 1) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -414,14 +506,23 @@ static int rts_tiles(const RowTileArgs& a) { return a.epi == 1 ? a.F / 16 : a.N 
 
 // PDN_ROWTILE_SPLIT=0: the fp32 kernel at every size (A/B switch; read once, announced)
 int pdn_rowtile_split_takes(const RowTileArgs& a, void* stream) {
-  static const int s_on = ls_env_switch("PDN_ROWTILE_SPLIT", 1, "the q | k | v and gate | up projections stay on the fp32 MFMA kernel");
-  if (!s_on || (a.epi != 1 && a.epi != 3) || a.M < RTS_MIN_ROWS || a.b_trans || a.bias || a.residual) return 0;
+  static const int s_on = ls_env_switch("PDN_ROWTILE_SPLIT", 1, "the q | k | v and gate | up projections and dh + SwiGLU backward stay on the fp32 MFMA kernel");
+  if (!s_on || (a.epi != 1 && a.epi != 2 && a.epi != 3) || a.M < RTS_MIN_ROWS || a.bias || a.residual) return 0;
+  if ((a.epi == 2) != (a.b_trans != 0)) return 0;
   if (a.N < 32 || a.N % 32 != 0 || a.nblocks < 1 || (a.N / a.nblocks) * a.nblocks != a.N || (a.N / a.nblocks) % 32 != 0) return 0;
-  if ((a.lda & 3) || (a.ldc & 3) || a.lda < RTS_K || a.ldc < a.N || a.ldc >= (1 << 24) || a.ldb < a.N / a.nblocks) return 0;
+  if ((a.lda & 3) || (a.ldc & 3) || a.lda < RTS_K || a.ldc < a.N || a.ldc >= (1 << 24) || a.ldb < (a.b_trans ? RTS_K : a.N / a.nblocks)) return 0;
   if (((uintptr_t)a.A | (uintptr_t)a.C) & 15) return 0;
   if (a.epi == 1 && (a.F < 16 || a.F % 16 != 0 || a.N != 2 * a.F || a.nblocks != 2 || !a.H || (a.ldh & 3) || a.ldh < a.F ||
                      a.ldh >= (1 << 24) || ((uintptr_t)a.H & 15)))
     return 0;
+  if (a.epi == 2) {
+    // dgu (M x 2F) = SwiGLU'(gu) o (A W_down^T): W_down (F x 288) row-major, gu and dgu packed [gate | up] with ldc; an
+    // in-place caller (C over GU) never comes here (gemm_rowres.hip), and this kernel reads gu rows after it wrote others
+    if (a.F < 32 || a.F % 32 != 0 || a.N != a.F || a.nblocks != 1 || a.ldc < 2 * (int64_t)a.F || !a.GU || ((uintptr_t)a.GU & 15)) return 0;
+    const float* ce = a.C + (int64_t)a.M * a.ldc;
+    if ((const float*)a.C < a.GU + (int64_t)a.M * a.ldc && a.GU < ce) return 0;
+    if ((const float*)a.C < a.A + (int64_t)a.M * a.lda && a.A < ce) return 0;
+  }
   if (a.epi == 3 && (!a.rope || a.hd < 4 || a.hd % 4 != 0 || a.L < 1 || a.rope_cols % 32 != 0 || a.rope_cols > a.N ||
                      (int64_t)a.L * a.hd >= (1 << 27) || ((uintptr_t)a.rope & 7)))
     return 0;
@@ -433,7 +534,7 @@ int pdn_rowtile_split_takes(const RowTileArgs& a, void* stream) {
 }
 
 int pdn_rowtile_split_launch(const RowTileArgs& a, void* stream) {
-  static const int s_ablate = ls_env_switch("PDN_ROWTILE_SPLIT_ABLATE", 0, "timing ablation active, the results of the split q | k | v and gate | up kernels are WRONG");
+  static const int s_ablate = ls_env_switch("PDN_ROWTILE_SPLIT_ABLATE", 0, "timing ablation active, the results of the split q | k | v, gate | up and dh + SwiGLU backward kernels are WRONG");
   const int nt = rts_tiles(a);
   RtsTemp img;
   const int rc = img.get((int64_t)nt * RTS_TILE, stream);
@@ -446,7 +547,7 @@ int pdn_rowtile_split_launch(const RowTileArgs& a, void* stream) {
   hipLaunchKernelGGL(rts_w_kernel, dim3(nt), dim3(256), 0, st, w);
   RtsParams p;
   memset(&p, 0, sizeof(p));
-  p.A = a.A; p.lda = a.lda; p.wimg = w.wimg; p.C = a.C; p.H = a.H; p.ldc = (unsigned)a.ldc; p.ldh = (unsigned)a.ldh;
+  p.A = a.A; p.lda = a.lda; p.wimg = w.wimg; p.C = a.C; p.H = a.H; p.GU = a.GU ? a.GU : a.A; p.ldc = (unsigned)a.ldc; p.ldh = (unsigned)a.ldh;
   p.rope = a.rope ? a.rope : a.A; p.L = a.L > 0 ? a.L : 1; p.hd = a.hd > 0 ? a.hd : 32; p.rope_tiles = a.rope_cols / 32;
   p.hd_magic = rts_rope_magic(p.hd);
   p.F = a.F; p.norm_w = a.norm_w ? a.norm_w : a.A; p.xn = a.xn ? a.xn : a.C; p.rms = a.rms; p.ldxn = a.ldxn; p.norm_eps = a.norm_eps;
@@ -460,12 +561,16 @@ int pdn_rowtile_split_launch(const RowTileArgs& a, void* stream) {
                else hipLaunchKernelGGL((rts_main_kernel<EPI_, true, false>), grid, block, 0, st, p); }        \
   else { if (norm) hipLaunchKernelGGL((rts_main_kernel<EPI_, false, true>), grid, block, 0, st, p);           \
          else hipLaunchKernelGGL((rts_main_kernel<EPI_, false, false>), grid, block, 0, st, p); }
-  if (a.epi == 1) { RTS_LAUNCH(1) } else { RTS_LAUNCH(3) }
+  if (a.epi == 1) { RTS_LAUNCH(1) }
+  else if (a.epi == 3) { RTS_LAUNCH(3) }
+  else if (guard) hipLaunchKernelGGL((rts_main_kernel<2, true, false>), grid, block, 0, st, p);
+  else hipLaunchKernelGGL((rts_main_kernel<2, false, false>), grid, block, 0, st, p);
 #undef RTS_LAUNCH
   // slots 2 / 4 as well: "gate | up + SwiGLU" and "q | k | v + RoPE" on the tile kernel are what bench.py's path check asks
   // for, whichever pipe ran them
+  // (dh + SwiGLU backward: slot 3, and its own slot 51 rather than 41)
   pdn_count(PDN_CNT_ROWTILE_PLAIN + a.epi);
-  pdn_count(PDN_CNT_ROWTILE_SPLIT);
+  pdn_count(a.epi == 2 ? PDN_CNT_ROWTILE_BWD_SPLIT : PDN_CNT_ROWTILE_SPLIT);
   PDN_LAUNCH_CHECK();
   return PDN_OK;
 }

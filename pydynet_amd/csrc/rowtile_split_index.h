@@ -51,6 +51,11 @@ RTS_HD int64_t rts_w_src(int kind, int tile, int n, int k, int nper, int64_t ldb
   const int c = 32 * tile + n, b = c / nper;
   return (int64_t)b * bstride + (int64_t)k * ldb + (c - b * nper);
 }
+// dh + SwiGLU backward (kind 2): the tile's columns are ROWS 32 t .. 32 t + 31 of W_down (F x 288, row-major, ldb floats
+// between rows); the W pass reads element i = 0 .. 32 * 288 - 1 of a tile along k: (n, k) = (rts_w_t_n(i), rts_w_t_k(i))
+RTS_HD int64_t rts_w_src_t(int tile, int n, int k, int64_t ldb) { return (int64_t)(32 * tile + n) * ldb + k; }
+RTS_HD int rts_w_t_n(int i) { return i / RTS_K; }
+RTS_HD int rts_w_t_k(int i) { return i % RTS_K; }
 // byte offset, inside a plane, of unit u (k = 8 u .. 8 u + 7) of tile column n: with a row stride of 36 units the sixteen
 // lanes a ds_read_b128 serves together fall on sixteen different 16-byte slots
 RTS_HD int rts_img_unit(int n, int u) { return (n * 36 + (u ^ ((n >> 2) & 3))) * 16; }
@@ -66,6 +71,20 @@ RTS_HD bool rts_stage_on(int q, int tid) { return rts_stage_unit(q, tid) < RTS_U
 RTS_HD int rts_a_col(int s, int lh) { return 16 * s + 8 * lh; }
 RTS_HD int64_t rts_a_row(int64_t m0, int li, int64_t M) { return m0 + li < M ? m0 + li : M - 1; }
 
+// The kernel no longer loads A through rts_a_col (it still clamps rows with rts_a_row, and its W fragments still meet
+// k = rts_a_col(s, lh)): it reads whole 128-byte lines.  Load (c, i) of a lane, c = 0 .. RTS_CHUNKS - 1 (a chunk = 32
+// columns = two k-steps), i = 0 .. 3: row rts_pl_row(lane, i) of the wave's 32, columns rts_pl_col(lane, c) .. + 3; the
+// eight lanes 8 r .. 8 r + 7 cover one line.  xn leaves from the same places.  The rows' (r, shift) pass from the lanes
+// (lane & 7) == 0 to the fragment-owning lanes through rts_pl_stat(row) of the wave's staging area; then chunk c is written
+// there at rts_pl_stg_w(lane, i) (row pitch 144 bytes) and k = 32 c + 16 e + 8 lh + 4 half .. + 3 of row li read back from
+// rts_pl_stg_r(li, lh, e, half): e = the k-step's parity, the two halves are the fragment's eight values.
+#define RTS_CHUNKS 9
+RTS_HD int rts_pl_row(int lane, int i) { return (lane >> 3) + 8 * i; }
+RTS_HD int rts_pl_col(int lane, int c) { return 32 * c + 4 * (lane & 7); }
+RTS_HD int rts_pl_stat(int row) { return row * 16; }
+RTS_HD int rts_pl_stg_w(int lane, int i) { return rts_pl_row(lane, i) * 144 + (lane & 7) * 16; }
+RTS_HD int rts_pl_stg_r(int li, int lh, int e, int half) { return li * 144 + 64 * e + 32 * lh + 16 * half; }
+
 // ---- the leaving tile: registers -> the wave's staging area -> memory, ROW-wise -----------------------------------------
 // group g (registers 4 g .. 4 g + 3 of lane (li, lh)) = tile columns 8 g + 4 lh .. + 3 of row li
 RTS_HD int rts_reg_col(int g, int lh) { return 8 * g + 4 * lh; }
@@ -76,6 +95,11 @@ RTS_HD int rts_st_row(int lane, int j) { return (lane >> 3) + 8 * j; }
 RTS_HD int rts_st_col(int lane) { return 4 * (lane & 7); }
 // output column of tile column c: q | k | v: 32 t + c; gate | up (packed [gate | up], F columns each): 16 t + c, F + 16 t + c - 16
 RTS_HD int rts_out_col(int kind, int tile, int c, int F) { return kind == 1 ? (c < 16 ? 16 * tile + c : F + 16 * tile + c - 16) : 32 * tile + c; }
+// dh + SwiGLU backward: tile column c is dh column 32 t + c; store j of a lane (rts_st_row, rts_st_col) reads gate and up
+// and writes dgate and dup at the SAME row and these columns of the packed (M x 2F) [gate | up] matrices: eight lanes
+// cover one 128-byte line in each of the four streams
+RTS_HD int rts_bwd_gate_col(int tile, int c) { return 32 * tile + c; }
+RTS_HD int rts_bwd_up_col(int tile, int c, int F) { return F + 32 * tile + c; }
 // h = silu(gate) up of a gate | up tile (16 columns): group g (0, 1) of lane (li, lh) = h columns 8 g + 4 lh .. + 3 from
 // registers 4 g .. + 3 (gate) and 4 g + 8 .. + 3 (up); it passes through the first 64 bytes of the staging rows AFTER the
 // gu stores have read them; store j (0, 1): lane reads row 16 j + (lane >> 2), h columns 4 (lane & 3) .. + 3
