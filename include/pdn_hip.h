@@ -242,7 +242,9 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *     the form pdn_gemm_f32 takes for h^T (M x K) against g2 (K x 288), M = 512 .. 1024, at 32768 tokens and more (see
  *     there): counts here ONLY, not in 15 or 42
  *  51 dh + SwiGLU backward on split-fp16 MFMA (csrc/rowtile_split.hip): no entry of its own, the form
- *     pdn_swiglu_bwd_gemm_f32 takes at 16384 rows and more; counts in 3 as well, not in 41 */
+ *     pdn_swiglu_bwd_gemm_f32 takes at 16384 rows and more; counts in 3 as well, not in 41
+ *  52 token-FSM constrained decoding of a decode step (csrc/token_fsm.hip): once per launch of pdnf_fsm_reset,
+ *     pdnf_fsm_step_f32 and pdnf_fsm_rows_f32 of include/pdn_fsm.h */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores

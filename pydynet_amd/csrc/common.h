@@ -87,7 +87,9 @@ enum {
                                   // split-fp16 MFMA (csrc/outres_tn_split.hip, transposed store): counts HERE ONLY, not in 15 or 42
   PDN_CNT_ROWTILE_BWD_SPLIT = 51, // dh + SwiGLU backward on split-fp16 MFMA (rts_main_kernel<2> of csrc/rowtile_split.hip): also counts in 3,
                                   // NOT in 41
-  PDN_CNT_SLOTS = 52
+  PDN_CNT_TOKEN_FSM = 52,         // token-FSM constrained decoding of a decode step (csrc/token_fsm.hip, include/pdn_fsm.h): once
+                                  // per launching pdnf_* entry
+  PDN_CNT_SLOTS = 53
 };
 void pdn_count(int slot);
 

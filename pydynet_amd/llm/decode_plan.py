@@ -11,6 +11,7 @@ import numpy as np
 from . import logit_edits as edit_np
 from . import logprobs as lp_np
 from . import penalties as pen_np
+from . import token_fsm as fsm_np
 from .sampling import Table, params_bytes
 
 
@@ -27,6 +28,9 @@ _PEN_ENTRIES = ("pdn_penalty_chunks", "pdn_penalty_reset", "pdn_penalty_step_f32
 # the entry points of the logit edits (csrc/logit_edit.hip, include/pdn_logitedit.h): without them every path applies the
 # statement of llm/logit_edits.py
 _EDIT_ENTRIES = ("pdne_logit_edit_chunks", "pdne_logit_edit_reset", "pdne_logit_edit_step_f32", "pdne_logit_edit_rows_f32")
+# the entry points of the token FSM (csrc/token_fsm.hip, include/pdn_fsm.h): without them every path applies the statement of
+# llm/token_fsm.py
+_FSM_ENTRIES = ("pdnf_fsm_chunks", "pdnf_fsm_reset", "pdnf_fsm_step_f32", "pdnf_fsm_rows_f32")
 # the per-row sampled launches (include/pdn_persample.h): without them a run with a parameter table leaves the graph path and
 # every draw applies the statement of llm/sampling.py row by row
 _PERSAMPLE_ENTRIES = ("pdnq_sample_rows_f32", "pdnq_decode_sample_tick_rows_f32", "pdnq_decode_sample_tick_slots_f32",
@@ -55,7 +59,7 @@ class DecodePlan:
         return mask.view(np.int32)
 
     def _decode_plan(self, B, sampling=False, ragged=False, serve=False, beam=0, n_stops=0, penalty=False, n_lp=None,
-                     edit=False, per_row=False):
+                     edit=False, per_row=False, fsm=False):
         """Buffers and weight views of the graph-replayable decode step (csrc/decode.hip), or None when the
         model's shapes / layout are outside what those kernels take (then the generic launches below run).
         `sampling`: the step ends in the sample tick (csrc/sample.hip) instead of the greedy pick; its parameters live in
@@ -83,7 +87,14 @@ class DecodePlan:
         then hold the candidates of that kernel.  None when the library lacks the entries.
         `per_row` (a sampled run of generate_ragged / serve with a parameter table, llm/sampling.Table; with `ragged`):
         `params` holds a block per row, (B, 3) int64, and the step ends in the pdnq_ tick of include/pdn_persample.h, where
-        row b is drawn with block b.  None when the library lacks the entries."""
+        row b is drawn with block b.  None when the library lacks the entries.
+        `fsm` (generation with token_fsm, csrc/token_fsm.hip; False, or the (states, edges) capacity of the call's merged
+        machines, llm/token_fsm.Machines.caps): the projection writes full logit rows, and pdnf_fsm_step_f32 advances each
+        row's state by the token it is fed and masks its logits between the penalty kernel and the edit kernel; the tables
+        live in the plan at that capacity (`fsm_off`, `fsm_tok`, `fsm_next`, `fsm_dflt`: a later call's machines of similar
+        size are uploaded into the same arrays), the rows' state words, start states and prompt lengths in `fsm_state`,
+        `fsm_start_state`, `fsm_start`.  A greedy plan's `cand_v` / `cand_i` then hold the candidates of the last of the
+        three kernels.  None when the library lacks the entries."""
         from .. import hipnp as hp, _lib
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
         st = getattr(self, "_decode_st", None)
@@ -97,6 +108,7 @@ class DecodePlan:
                (int(beam), int(n_stops), bool(penalty)), bool(ragged), bool(serve)) + (() if n_lp is None else (int(n_lp),))
         key += ("edit",) if edit else ()
         key += ("per_row",) if per_row else ()
+        key += ("fsm",) + tuple(int(c) for c in fsm) if fsm else ()
         if st is not None and st["key"] == key:
             return st if st["ok"] else None
         if st is not None:
@@ -113,6 +125,8 @@ class DecodePlan:
             ok = False
         if per_row and not all(_lib.provides(n) for n in _PERSAMPLE_ENTRIES):
             ok = False
+        if fsm and not all(_lib.provides(n) for n in _FSM_ENTRIES):
+            ok = False
         packs = []
         if ok:
             for layer in self.layers:
@@ -127,8 +141,8 @@ class DecodePlan:
             ok = ok and self.lm_head.weight.data.is_contiguous() and self.tok_embedding.weight.data.is_contiguous()
         st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged), "serve": bool(serve),
               "wide": wide, "rows": bool(ragged or wide), "beam": int(beam),
-              "full": bool(sampling or beam or penalty or edit),
-              "pen": bool(penalty), "lp_n": n_lp, "edit": bool(edit), "per_row": bool(per_row)}
+              "full": bool(sampling or beam or penalty or edit or fsm),
+              "pen": bool(penalty), "lp_n": n_lp, "edit": bool(edit), "per_row": bool(per_row), "fsm": bool(fsm)}
         if ok:
             nblk = _lib.lib().query("pdn_decode_wide_blocks" if wide else "pdn_decode_gemv_blocks", V)
             # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
@@ -202,6 +216,15 @@ class DecodePlan:
                           edit_run=None)
                 if not sampling:
                     nc = _lib.lib().query("pdne_logit_edit_chunks", V)
+                    st.update(cand_v=hp.empty((B, nc), np.float32), cand_i=hp.empty((B, nc), np.int32))
+            if fsm:
+                S_cap, E_cap = (int(c) for c in fsm)
+                st.update(fsm_off=hp.zeros((S_cap + 1,), np.int32), fsm_tok=hp.zeros((E_cap,), np.int32),
+                          fsm_next=hp.zeros((E_cap,), np.int32), fsm_dflt=hp.zeros((S_cap,), np.int32),
+                          fsm_state=hp.zeros((B,), np.int64), fsm_start_state=hp.zeros((B,), np.int32),
+                          fsm_start=hp.zeros((B,), np.int32), fsm_caps=(S_cap, E_cap), fsm_val=None, fsm_run=None)
+                if not sampling and not edit:
+                    nc = _lib.lib().query("pdnf_fsm_chunks", V)
                     st.update(cand_v=hp.empty((B, nc), np.float32), cand_i=hp.empty((B, nc), np.int32))
             if n_lp is not None:
                 st.update(lp_ptr=hp.zeros((1,), np.int64), lp_box=None, lp_work=hp.zeros(
@@ -301,6 +324,7 @@ class DecodePlan:
             L.call("pdn_decode_gemv_sum_f32", xb, D, dparts, J, J * D, None, 0, self.norm.weight.data._ptr, self.norm.eps,
                    head.weight.data._ptr, V, V, 0, bias, logits, V, B, D, V, cv, ci, s)
             self._pen_step(st, s)
+            self._fsm_step(st, s)
             self._edit_step(st, s)
             self._decode_tick(st, s)
             self._lp_tick(st, s)
@@ -330,6 +354,7 @@ class DecodePlan:
         L.call("pdn_decode_gemv_f32", x, D, self.norm.weight.data._ptr, self.norm.eps, head.weight.data._ptr, V, V, 0,
                bias, None, 0, logits, V, B, D, V, 0, 0, 0, cv, ci, s)
         self._pen_step(st, s)
+        self._fsm_step(st, s)
         self._edit_step(st, s)
         self._decode_tick(st, s)
         self._lp_tick(st, s)
@@ -364,6 +389,7 @@ class DecodePlan:
         L.call("pdn_decode_wide_gemm_f32", x, D, 1, self.norm.weight.data._ptr, self.norm.eps, 0, 0, head.weight.data._ptr,
                V, V, 0, bias, logits, V, 0 if st["full"] else 2, cv, ci, pos, B, D, V, work, s)
         self._pen_step(st, s)
+        self._fsm_step(st, s)
         self._edit_step(st, s)
         self._decode_tick(st, s)
         self._lp_tick(st, s)
@@ -388,11 +414,12 @@ class DecodePlan:
             st["lp_box"] = hp.Mailbox(_LP_RING, (st["B"], lp_np.record_words(st["lp_n"])), unset=lp_np.UNSET)
             st["lp_ptr"][...] = np.int64(st["lp_box"]._ptr)
 
-    def _run_values(self, st, sampling, pen=None, edit=None):
+    def _run_values(self, st, sampling, pen=None, edit=None, fsm=None):
         """The values of a run, uploaded when they differ from those in the plan (stream ordered: earlier steps read the
         old ones): the sampling parameters (a llm/sampling.Table: row b takes request b's block; a served plan's rows take
         theirs at admission, `_params_rows`), and for a run with penalties (`pen`: its llm/penalties.Rows) every row's
-        prompt with zero counts; for a run with logit edits (`edit`: its llm/logit_edits.Rows) every row's request."""
+        prompt with zero counts; for a run with logit edits (`edit`: its llm/logit_edits.Rows) every row's request; for a
+        run with machines (`fsm`: its llm/token_fsm.Rows) the tables and every row's start state."""
         if st["params_val"] != sampling:
             if isinstance(sampling, Table):
                 if not st.get("serve"):
@@ -406,6 +433,9 @@ class DecodePlan:
         if edit is not None and st["edit_run"] is not edit:
             self._edit_reset(st, np.arange(st["B"]), edit.req, edit.start, edit.spec)
             st["edit_run"] = edit
+        if fsm is not None and st["fsm_run"] is not fsm:
+            self._fsm_reset(st, np.arange(st["B"]), fsm.req, fsm.start, fsm.spec)
+            st["fsm_run"] = fsm
 
     @staticmethod
     def _params_rows(st, table, reqs):
@@ -427,10 +457,43 @@ class DecodePlan:
             return
         from .. import _lib
         V, B = self.vocab_size, st["B"]
-        # (the candidates: of the edit kernel when that one runs behind this one)
-        cv, ci = (None, None) if st["sampling"] or st["edit"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
+        # (the candidates: of the FSM or the edit kernel when one of them runs behind this one)
+        cv, ci = (None, None) if st["sampling"] or st["edit"] or st["fsm"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
         _lib.lib().call("pdn_penalty_step_f32", st["logits"]._ptr, V, B, V, st["pen_params"]._ptr, st["counts"]._ptr,
                         st["seen"]._ptr, st["start"]._ptr, st["ids"]._ptr, st["pos"]._ptr, int(st["rows"]), cv, ci, s)
+
+    def _fsm_step(self, st, s):
+        """FSM plans: between the penalty kernel (or the vocabulary projection) and the edit kernel (or the tick), each
+        live row's state is advanced by the token it is fed and its logits are masked in place (greedy plans without
+        edits: with the candidates the tick reduces, csrc/token_fsm.hip)."""
+        if not st["fsm"]:
+            return
+        from .. import _lib
+        V, B = self.vocab_size, st["B"]
+        cv, ci = (None, None) if st["sampling"] or st["edit"] else (st["cand_v"]._ptr, st["cand_i"]._ptr)
+        S_cap, E_cap = st["fsm_caps"]
+        _lib.lib().call("pdnf_fsm_step_f32", st["logits"]._ptr, V, B, V, st["fsm_off"]._ptr, st["fsm_tok"]._ptr,
+                        st["fsm_next"]._ptr, st["fsm_dflt"]._ptr, S_cap, E_cap, st["fsm_state"]._ptr,
+                        st["fsm_start_state"]._ptr, st["fsm_start"]._ptr, st["ids"]._ptr, st["pos"]._ptr, int(st["rows"]),
+                        cv, ci, s)
+
+    def _fsm_reset(self, st, rows, reqs, lens, spec):
+        """Rows `rows` of an FSM plan take requests `reqs` of `spec` (llm/token_fsm.Machines) with prompt lengths `lens`
+        (start states, prompt lengths, state words; one launch, stream ordered after every step queued before), and the
+        plan's tables become the call's (stream ordered too)."""
+        from .. import hipnp as hp, _lib
+        if st["fsm_val"] is not spec:
+            for name, a in zip(("fsm_off", "fsm_tok", "fsm_next", "fsm_dflt"), fsm_np.padded(spec.tables, *st["fsm_caps"])):
+                st[name][...] = a
+            st["fsm_val"] = spec
+        rows = np.asarray(rows, np.int32).reshape(-1)
+        if not rows.size:
+            return
+        # (device copies held until the call has been issued; the allocator orders their reuse on the stream)
+        d_rows, d_state = hp.asarray(rows), hp.asarray(spec.start_states(reqs))
+        d_len = hp.asarray(np.asarray(lens, np.int32).reshape(-1))
+        _lib.lib().call("pdnf_fsm_reset", st["fsm_state"]._ptr, st["fsm_start_state"]._ptr, st["fsm_start"]._ptr, st["B"],
+                        d_rows._ptr, int(rows.size), d_state._ptr, d_len._ptr, hp.stream())
 
     def _edit_step(self, st, s):
         """Edit plans: between the vocabulary projection (or the penalty kernel) and the tick, each live row's logits are
@@ -490,7 +553,7 @@ class DecodePlan:
         rows' arrival count -- the last row to finish advances the step, csrc/decode_wide.hip), the slot state (served
         plans: counter id and token budget per row, the history ring; per-row plans: the stop bitmask) and the output.
         `mixed` (the mixed step's buffers): always the wide slot tick, on its own arrival counter and -- unless the
-        penalty or the edit kernel left the plan's -- its own candidates."""
+        penalty, the FSM or the edit kernel left the plan's -- its own candidates."""
         from .. import _lib
         emb, V, B = self.tok_embedding.weight.data, self.vocab_size, st["B"]
         if st["beam"]:
@@ -501,7 +564,7 @@ class DecodePlan:
         if st["sampling"]:
             src = (st["logits"]._ptr, V, B, V, st["params"]._ptr)
         else:
-            c = st if mixed is None or st["pen"] or st["edit"] else mixed
+            c = st if mixed is None or st["pen"] or st["edit"] or st["fsm"] else mixed
             src = (c["cand_v"]._ptr, c["cand_i"]._ptr, B, c["cand_v"].shape[1])
         cnt = (st["pos"]._ptr,) + ((st["step"]._ptr,) if st["rows"] else ())
         if wide:
@@ -533,7 +596,7 @@ class DecodePlan:
         runs write the KV cache slots of the next two steps with exactly what the real steps will write there, and they
         advance ids, positions and counters.  `keep` maps the plan arrays to put back afterwards to their values: a host
         value, or None for a device copy taken before the capture.  A penalty plan's `counts` are always kept (the runs
-        count their fed tokens too).
+        count their fed tokens too), and an FSM plan's state words (the runs advance them).
         `redirect` = (name, mailbox[, slots]): the runs' tick stores its tokens through the device pointer st[name],
         which points at a SCRATCH twin of `mailbox` meanwhile, so that the real one's slots stay "not written" until the
         real steps store there (a later step with other ids would otherwise read the capture's token as its own).  The
@@ -550,6 +613,8 @@ class DecodePlan:
         if g is None and capture and type(self).graph_decode:
             if st.get("pen"):
                 keep = dict(keep, counts=None)
+            if st.get("fsm"):
+                keep = dict(keep, fsm_state=None)
             saved = {n: st[n].copy() if v is None else v for n, v in keep.items()}
             moved = [redirect] if redirect else []
             if st.get("lp_n") is not None:

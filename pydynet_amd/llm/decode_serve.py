@@ -10,18 +10,20 @@ from . import logit_edits as edit_np
 from . import logprobs as lp_np
 from . import penalties as pen_np
 from . import prefix as prefix_np
+from . import token_fsm as fsm_np
 from .decode_plan import _MIXED_ENTRIES
 from .sampling import Table, draw_rows
 
 
 class ServeEngine:
-    def _serve(self, rows, budgets, S, sampling, stops, penalty=None, n_lp=None, edit=None):
+    def _serve(self, rows, budgets, S, sampling, stops, penalty=None, n_lp=None, edit=None, fsm=None):
         """The scheduler of `serve`.  Per step: the rows holding a request decode one token, then the rows freed by the
         previous step take the waiting requests in order through one prompt pass (`_serve_prefill`), then the step is
         yielded.  The host keeps, per row, the request, the position of its next decode step, the tokens it may still
         produce and its last token; on the graph path the device keeps the same in the served plan (`_serve_begin`) and
         the host writes it only after an admission, when every queued step has been read.  `edit` (llm/logit_edits.Edits):
-        request r's edits follow it into the row that takes it, as its prompt set and counts do with penalties."""
+        request r's edits follow it into the row that takes it, as its prompt set and counts do with penalties; `fsm`
+        (llm/token_fsm.Machines): likewise request r's machine, from its start state."""
         lens = np.array([r.size for r in rows], np.int64)
         queue = [r for r in range(len(rows)) if budgets[r] > 0]   # FIFO by index; a budget of 0 never takes a row
         req = np.full(S, -1, np.int64)
@@ -29,9 +31,10 @@ class ServeEngine:
         left = np.zeros(S, np.int64)
         last = np.zeros(S, np.int64)
         hip = self._fast_path(self.tok_embedding.weight.device)
-        st = self._serve_begin(S, sampling, stops, penalty, n_lp, edit) if hip else None  # None: the plan refuses -> generic
+        st = self._serve_begin(S, sampling, stops, penalty, n_lp, edit, fsm) if hip else None  # None: the plan refuses -> generic
         pen = None if penalty is None or st is not None else pen_np.Rows(S, self.vocab_size, penalty)   # (host counts)
         erows = None if edit is None or st is not None else edit_np.Rows(S, edit)                        # (host state)
+        frows = None if fsm is None or st is not None else fsm_np.Rows(S, fsm)                           # (host state)
         q = 0
         try:
             while True:
@@ -54,10 +57,10 @@ class ServeEngine:
                             self._serve_ahead(st, int(nxt.max()))    # the next step, queued before this one is read
                         toks[run] = self._serve_read(st, lpv, run)[run]
                 elif run.any():
-                    toks[run] = self._serve_step_eager(hip, last, p, req, run, sampling, pen, n_lp, lpv, erows)[run]
+                    toks[run] = self._serve_step_eager(hip, last, p, req, run, sampling, pen, n_lp, lpv, erows, frows)[run]
                 shown = req.copy()
                 if adm.size:
-                    first = self._serve_prefill([rows[r] for r in new], adm, new, sampling, penalty, n_lp, edit)
+                    first = self._serve_prefill([rows[r] for r in new], adm, new, sampling, penalty, n_lp, edit, fsm)
                     if n_lp is not None:
                         first, lpf = first
                         lp_np.merge(lpv, adm, lpf)
@@ -65,6 +68,8 @@ class ServeEngine:
                         pen.reset(adm, [rows[r] for r in new])
                     if erows is not None:
                         erows.reset(adm, new, lens[new])
+                    if frows is not None:
+                        frows.reset(adm, new, lens[new])
                     if st is not None and st["pending"]:
                         d = self._serve_read(st, lpv, run)       # (stream order: that step ran before the prefill)
                         toks[run] = d[run]
@@ -84,6 +89,8 @@ class ServeEngine:
                         self._pen_reset(st, adm, [rows[r] for r in new], penalty)
                     if st["edit"]:
                         self._edit_reset(st, adm, new, lens[new], edit)
+                    if st["fsm"]:
+                        self._fsm_reset(st, adm, new, lens[new], fsm)
                     if (req >= 0).any():
                         self._serve_ahead(st, int(np.where(req >= 0, pos, -1).max()))
                 yield (shown, toks) if n_lp is None else (shown, toks, lpv)
@@ -93,7 +100,7 @@ class ServeEngine:
                 hp.synchronize()                                 # (queued steps store into this run's history)
                 st["pending"] = 0
 
-    def _serve_step_eager(self, hip, last, p, req, on, sampling, pen, n_lp, lpv, edit=None):
+    def _serve_step_eager(self, hip, last, p, req, on, sampling, pen, n_lp, lpv, edit=None, fsm=None):
         """One decode step of the served rows off the graph path: rows `on` (bool) fed their last tokens `last` at
         positions `p` (-1: a row that does not decode) with the counter ids `req` -- the generic rows step on a HIP device
         (`hip`), the tape-node step elsewhere.  Returns the tokens of every row, host (S,); `n_lp`: the records of rows
@@ -102,29 +109,32 @@ class ServeEngine:
         if hip:
             from .. import hipnp as hp
             out = self._decode_step_generic_rows(hp.asarray(ids), p.astype(np.int32), sampling, rq, pen=pen, n_lp=n_lp,
-                                                 edit=edit)
+                                                 edit=edit, fsm=fsm)
         else:
             dev = self.tok_embedding.weight.device
             out = self._step_module_rows(Tensor(ids, dtype=np.int64, device=dev), p, sampling, rq, pen=pen, n_lp=n_lp,
-                                         edit=edit)
+                                         edit=edit, fsm=fsm)
         if n_lp is not None:
             out, lpr = out
             lp_np.merge(lpv, np.flatnonzero(on), lp_np.Logprobs(*(a[on] for a in lpr)))
         return (out.get() if hip else out.numpy()).reshape(-1)
 
-    def _serve_prefill(self, prompts, rows, reqs, sampling, penalty=None, n_lp=None, edit=None):
+    def _serve_prefill(self, prompts, rows, reqs, sampling, penalty=None, n_lp=None, edit=None, fsm=None):
         """Admit requests `reqs` (their prompts) into decode rows `rows`: the prompts right-padded to the longest run as one
         batched causal pass from position 0 into a staging cache (the layers' caches point at it meanwhile), then
         pdn_kv_store_slots_f32 puts prompt i's keys / values, positions [0, len_i), into cache row rows[i] and zeroes
         position len_i there -- the slot a decode step attends to but never writes (`generate`'s step at position p feeds
         the token of position p - 1), which in a fresh cache holds zeros.  No pad position and no other row is written.
-        `penalty`: the logits penalised for each prompt first; `edit` (llm/logit_edits.Edits): then edited for each
+        `penalty`: the logits penalised for each prompt first; `fsm` (llm/token_fsm.Machines): then masked for each
+        request's start state; `edit` (llm/logit_edits.Edits): then edited for each
         request (no token generated yet).  Returns the first token of each request (counter (len_i,
         reqs[i]) when sampled; `sampling` a llm/sampling.Table: with request reqs[i]'s own values, through the per-row
         standalone entry), host int64 (`n_lp`: and their Logprobs)."""
         logits = self._prefill_rows(prompts, rows)
         if penalty is not None:
             logits = self._penalize_prompt(logits, prompts, penalty)
+        if fsm is not None:
+            logits = self._fsm_rows(logits, fsm, fsm.start_states(reqs))
         if edit is not None:
             logits = self._edit_rows(logits, edit, reqs, np.zeros(len(prompts), np.int64))
         lens = np.array([p.size for p in prompts], np.int64)
@@ -180,10 +190,11 @@ class ServeEngine:
 
     # (graph path of `serve`: the served plan holds the rows' state on the device; steps are issued, queued ahead and
     #  read in order, through a ring of `ring` history slots)
-    def _serve_begin(self, S, sampling, stops, penalty=None, n_lp=None, edit=None):
+    def _serve_begin(self, S, sampling, stops, penalty=None, n_lp=None, edit=None, fsm=None):
         from .. import hipnp as hp
         st = self._decode_plan(S, sampling is not None, ragged=True, serve=True, penalty=penalty is not None, n_lp=n_lp,
-                               edit=edit is not None, per_row=isinstance(sampling, Table))
+                               edit=edit is not None, per_row=isinstance(sampling, Table),
+                               fsm=False if fsm is None else fsm.caps)
         if st is None:
             return None
         st["table"] = sampling if st["per_row"] else None        # (the rows' blocks: written with their requests)
@@ -202,6 +213,9 @@ class ServeEngine:
         if edit is not None:                                     # (likewise: here only min_new_tokens is uploaded)
             self._edit_reset(st, [], [], [], edit)
             st["edit_run"] = None
+        if fsm is not None:                                      # (likewise: here only the tables are uploaded)
+            self._fsm_reset(st, [], [], [], fsm)
+            st["fsm_run"] = None
         st["pending"], st["read"] = 0, 0
         return st
 
@@ -250,7 +264,8 @@ class ServeEngine:
         self._decode_gather(st)
 
     # -- chunked prefill (serve(prefill_chunk=C)): prompts fed C tokens per step (statement: llm/chunked.py) -----------
-    def _serve_chunked(self, rows, budgets, S, C, sampling, stops, penalty=None, n_lp=None, prefix=None, edit=None):
+    def _serve_chunked(self, rows, budgets, S, C, sampling, stops, penalty=None, n_lp=None, prefix=None, edit=None,
+                       fsm=None):
         """The scheduler of `serve` with a chunk: llm/chunked.Schedule decides, per step, which rows decode and which
         prompt tokens are fed.  Graph path (`_mixed_begin`): a step with prompt tokens runs the mixed step (the decode
         rows and the chunks as query rows of the wide product, csrc/extend.hip), a step without runs the served step.
@@ -261,7 +276,7 @@ class ServeEngine:
         their prefill starts at fed = n; every other path starts every prompt at 0 (the schedule with reuse forced off)."""
         lens = np.array([r.size for r in rows], np.int64)
         hip = self._fast_path(self.tok_embedding.weight.device)
-        st = self._mixed_begin(S, C, sampling, stops, penalty, n_lp, edit) if hip else None
+        st = self._mixed_begin(S, C, sampling, stops, penalty, n_lp, edit, fsm) if hip else None
         if prefix is None:
             sch = chunked.Schedule(lens, budgets, S, C)
         else:
@@ -271,6 +286,7 @@ class ServeEngine:
                 st.pop("prefix", None)                          # (the cache pointer table: built by the run's first copy)
         pen = None if penalty is None or st is not None else pen_np.Rows(S, self.vocab_size, penalty)   # (host counts)
         erows = None if edit is None or st is not None else edit_np.Rows(S, edit)                        # (host state)
+        frows = None if fsm is None or st is not None else fsm_np.Rows(S, fsm)                           # (host state)
         dirty = False                                           # (the device's row state differs from the host's)
         try:
             while True:
@@ -290,6 +306,11 @@ class ServeEngine:
                         self._edit_reset(st, adm, new, lens[new], edit)
                     else:
                         erows.reset(adm, new, lens[new])
+                if adm.size and fsm is not None:                # (likewise)
+                    if st is not None:
+                        self._fsm_reset(st, adm, new, lens[new], fsm)
+                    else:
+                        frows.reset(adm, new, lens[new])
                 if not sch.busy():
                     return
                 n, dec, comp = sch.plan()
@@ -322,11 +343,11 @@ class ServeEngine:
                 else:
                     if dec.any():
                         toks[dec] = self._serve_step_eager(hip, sch.last, np.where(dec, sch.pos, -1), sch.req, dec,
-                                                           sampling, pen, n_lp, lpv, erows)[dec]
+                                                           sampling, pen, n_lp, lpv, erows, frows)[dec]
                     if comp.any():
                         b = np.flatnonzero(comp)
                         first = self._serve_prefill([rows[r] for r in sch.req[b]], b, sch.req[b], sampling, penalty,
-                                                    n_lp, edit)
+                                                    n_lp, edit, fsm)
                         if n_lp is not None:
                             first, lpf = first
                             lp_np.merge(lpv, b, lpf)
@@ -371,12 +392,12 @@ class ServeEngine:
         return bool(type(self).wide_decode and S + C <= 256 and all(_lib.provides(n) for n in _MIXED_ENTRIES)
                     and L.query("pdn_decode_mixed_supported", D, H, D // H, F, V, cache_len))
 
-    def _mixed_begin(self, S, C, sampling, stops, penalty=None, n_lp=None, edit=None):
+    def _mixed_begin(self, S, C, sampling, stops, penalty=None, n_lp=None, edit=None, fsm=None):
         """The served plan (`_serve_begin`) plus the buffers of the mixed step (`mixed`), or None when either refuses."""
         from .. import hipnp as hp, _lib
         if not self._mixed_ok(S, C):
             return None
-        st = self._serve_begin(S, sampling, stops, penalty, n_lp, edit)
+        st = self._serve_begin(S, sampling, stops, penalty, n_lp, edit, fsm)
         if st is None or st["ns"] > 8:
             return None
         M = st.get("mixed")
@@ -458,15 +479,17 @@ class ServeEngine:
         self._mixed_layers(M, st["packs"], S, C, R, ns, s)
         xe = M["xe"]._ptr
         L.call("pdn_embedding_gather_f32", x, R, D, D, M["emit"]._ptr, S, xe, hp.err_flag_ptr(), s)
-        full = st["sampling"] or st["pen"] or st["edit"]
+        full = st["sampling"] or st["pen"] or st["edit"] or st["fsm"]
         cv, ci = (None, None) if full else (M["cand_v"]._ptr, M["cand_i"]._ptr)
         L.call("pdn_decode_wide_gemm_f32", xe, D, 1, self.norm.weight.data._ptr, self.norm.eps, 0, 0,
                self.lm_head.weight.data._ptr, V, V, 0, self._head_bias(), st["logits"]._ptr, V, 0 if full else 2, cv, ci,
                st["pos"]._ptr, S, D, V, work, s)
         # (penalty plans: a row completing its prompt here is at position len = start and counts nothing; greedy: the
         #  plan's candidates are those of the penalty kernel.  Edit plans: that row has generated no token; the
-        #  candidates are those of the edit kernel)
+        #  candidates are those of the edit kernel.  FSM plans: that row is in its start state, which the kernel takes at
+        #  g = 0 whatever the row's word holds)
         self._pen_step(st, s)
+        self._fsm_step(st, s)
         self._edit_step(st, s)
         self._decode_tick(st, s, mixed=M)
         self._lp_tick(st, s)

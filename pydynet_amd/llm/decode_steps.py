@@ -9,17 +9,20 @@ from ..core import Tensor
 from . import logit_edits as edit_np
 from . import logprobs as lp_np
 from . import penalties as pen_np
-from .decode_plan import _EDIT_ENTRIES, _PEN_ENTRIES
+from . import token_fsm as fsm_np
+from .decode_plan import _EDIT_ENTRIES, _FSM_ENTRIES, _PEN_ENTRIES
 from .sampling import Table, draw_rows, params_buffer, sample_next, sample_next_table
 
 
 class DecodeSteps:
-    def _generate(self, input_ids, max_new_tokens, sampling, penalty=None, n_lp=None, edit=None):
+    def _generate(self, input_ids, max_new_tokens, sampling, penalty=None, n_lp=None, edit=None, fsm=None):
         B, L = input_ids.shape
         next_id = None
         pen = None
         # (the rows' requests and prompt lengths: llm/logit_edits.py)
         erows = None if edit is None else edit_np.Rows(B, edit, np.arange(B), np.full(B, L))
+        # (the rows' machines, states and prompt lengths: llm/token_fsm.py)
+        frows = None if fsm is None else fsm_np.Rows(B, fsm, np.arange(B), np.full(B, L))
         if penalty is not None:                                   # (the rows' prompts and counts: llm/penalties.py)
             ids = np.asarray(input_ids.numpy() if isinstance(input_ids, Tensor) else input_ids).reshape(B, L)
             pen = pen_np.Rows(B, self.vocab_size, penalty, list(ids))
@@ -28,6 +31,8 @@ class DecodeSteps:
                 logits = self(input_ids, 0)[:, -1, :]             # prompt pass: fills the KV caches
                 if pen is not None:
                     logits = self._penalize_prompt(logits, pen.prompts, penalty)
+                if frows is not None:
+                    logits = self._fsm_rows(logits, fsm, frows.start_state)
                 if erows is not None:
                     logits = self._edit_rows(logits, edit, erows.req, np.zeros(B, np.int64))
                 next_id = logits.argmax(-1, True) if sampling is None else sample_next(logits, pos, *sampling)
@@ -35,13 +40,15 @@ class DecodeSteps:
             elif self._fast_path(next_id.device):
                 # (`more`: another token will be asked for -- the step after this one may be queued ahead)
                 out = self._decode_step_hip(next_id.data, pos, more=pos + 1 < max_new_tokens, sampling=sampling,
-                                            pen=pen, n_lp=n_lp, edit=erows)
+                                            pen=pen, n_lp=n_lp, edit=erows, fsm=frows)
                 out, lp = out if n_lp is not None else (out, None)
                 next_id = Tensor(out, dtype=np.int64, device=next_id.device, copy=False)
             else:
                 logits = self(next_id, pos)[:, -1, :]
                 if pen is not None:
                     logits = self._penalize_step(logits, pen, next_id.numpy(), np.full(B, pos))
+                if frows is not None:
+                    logits = self._fsm_step_host(logits, frows, next_id.numpy(), np.full(B, pos))
                 if erows is not None:
                     logits = self._edit_step_host(logits, erows, np.full(B, pos))
                 next_id = logits.argmax(-1, True) if sampling is None else sample_next(logits, pos, *sampling)
@@ -100,6 +107,43 @@ class DecodeSteps:
         pen.feed(ids, pos)
         return Tensor(pen.apply(np.asarray(logits.numpy(), np.float32)), dtype=np.float32, device=logits.device)
 
+    def _fsm_rows(self, logits, spec, states, pos=None):
+        """The mask of llm/token_fsm.py on logit rows (R, V) (a Tensor or a device array) for rows in the states
+        `states` (R,) of `spec` (llm/token_fsm.Machines; -1: off); pos (R,) marks the rows to leave alone (-1; None: none).
+        On a HIP device with the library's entries: pdnf_fsm_rows_f32 in place (stream ordered, no plan); elsewhere the
+        statement.  Returns what it was given, a Tensor or a device array."""
+        from .. import _lib
+        V = self.vocab_size
+        x = logits.data if isinstance(logits, Tensor) else logits
+        states = np.asarray(states, np.int64).reshape(-1)
+        if pos is not None:
+            states = np.where(np.asarray(pos, np.int64).reshape(-1) >= 0, states, -1)
+        if not isinstance(x, np.ndarray) and x.dtype == np.float32 and all(_lib.provides(n) for n in _FSM_ENTRIES):
+            from .. import hipnp as hp
+            if x._strides[1] != 1 or x._strides[0] < V:
+                x = x.copy()
+            off, tok, _, dfl = (hp.asarray(a) for a in fsm_np.padded(spec.tables, *spec.caps))
+            d_states = hp.asarray(states.astype(np.int32))
+            _lib.lib().call("pdnf_fsm_rows_f32", x._ptr, x._strides[0], x.shape[0], V, off._ptr, tok._ptr, dfl._ptr,
+                            spec.caps[0], spec.caps[1], d_states._ptr, None, None, None, hp.stream())
+            return Tensor(x, dtype=np.float32, device=logits.device, copy=False) if isinstance(logits, Tensor) else x
+        z = np.asarray(logits.numpy() if isinstance(logits, Tensor) else x.get() if hasattr(x, "get") else x, np.float32)
+        z = fsm_np.apply(z, spec.tables, states)
+        if isinstance(logits, Tensor):
+            return Tensor(z, dtype=np.float32, device=logits.device)
+        if isinstance(x, np.ndarray):
+            return z
+        x[...] = z
+        return x
+
+    def _fsm_step_host(self, logits, frows, ids, pos):
+        """`_fsm_rows` on a step of a path without the device state (`frows`: llm/token_fsm.Rows): every row's state
+        advanced by the token it is fed (ids (B,), host or device) at positions pos (B,), -1 for a row that computes nothing."""
+        pos = np.asarray(pos, np.int64).reshape(-1)
+        ids = np.asarray(ids.get() if hasattr(ids, "get") else ids, np.int64).reshape(-1)
+        cur, frows.word = fsm_np.step_states(frows.spec.tables, frows.word, frows.start_state, frows.start, ids, pos)
+        return self._fsm_rows(logits, frows.spec, cur, pos)
+
     def _edit_rows(self, logits, spec, reqs, generated, pos=None):
         """The statement of llm/logit_edits.py on logit rows (R, V) (a Tensor or a device array) for requests reqs[i] of
         `spec` (llm/logit_edits.Edits) that have generated[i] tokens; pos (R,) marks the rows to leave alone (-1; None:
@@ -143,14 +187,15 @@ class DecodeSteps:
         pos = np.asarray(pos, np.int64).reshape(-1)
         return self._edit_rows(logits, erows.spec, erows.req, np.maximum(pos - erows.start, 0), pos)
 
-    def _generate_ragged(self, rows, n, sampling, stops, penalty=None, n_lp=None, edit=None):
+    def _generate_ragged(self, rows, n, sampling, stops, penalty=None, n_lp=None, edit=None, fsm=None):
         B = len(rows)
         lens = np.array([r.size for r in rows], np.int64)
         if n == 0:
             return
         pen = None if penalty is None else pen_np.Rows(B, self.vocab_size, penalty, rows)
         erows = None if edit is None else edit_np.Rows(B, edit, np.arange(B), lens)
-        nxt = self._prompt_rows(rows, lens, sampling, penalty, n_lp, edit)
+        frows = None if fsm is None else fsm_np.Rows(B, fsm, np.arange(B), lens)
+        nxt = self._prompt_rows(rows, lens, sampling, penalty, n_lp, edit, fsm)
         if n_lp is not None:
             nxt, lp = nxt
         live = np.ones(B, bool)
@@ -163,7 +208,7 @@ class DecodeSteps:
             # tokens by STEP: slot i holds step i of every row (-1 for a stopped row), so "not written yet" is its own
             # value; two slots beyond the last step for the runs of a graph capture
             run = {"lens": lens, "live": live, "sampling": sampling, "stop_mask": self._stop_mask(stops), "pen": pen,
-                   "edit": erows,
+                   "edit": erows, "fsm": frows,
                    "hist": hp.Mailbox(n + 2, (B, 1), unset=np.iinfo(np.int64).min), "lp": n_lp}
         ids = nxt.data
         for i in range(1, n):
@@ -176,7 +221,7 @@ class DecodeSteps:
                 nxt = Tensor(ids, dtype=np.int64, device=nxt.device, copy=False)
             else:
                 nxt = self._step_module_rows(nxt, np.where(live, lens + i, -1), sampling, pen=pen, n_lp=n_lp,
-                                             edit=erows)
+                                             edit=erows, fsm=frows)
                 nxt, lp = nxt if n_lp is not None else (nxt, None)
             if stops.size:
                 yield nxt if n_lp is None else (nxt, lp_np.as_step(lp))
@@ -185,12 +230,13 @@ class DecodeSteps:
                 continue
             yield nxt if n_lp is None else (nxt, lp_np.as_step(lp))
 
-    def _prompt_rows(self, rows, lens, sampling, penalty=None, n_lp=None, edit=None):
+    def _prompt_rows(self, rows, lens, sampling, penalty=None, n_lp=None, edit=None, fsm=None):
         """The prompt pass of a ragged generation: the prompts right-padded to the longest and run as one batched
         causal pass from position 0 (no real token attends to a pad after it); each row's logits at its last real token,
         gathered before lm_head.  The cache slots the pads wrote, [len_b, L_max) of row b, are put back as they were: a
         row's cache is written at its own positions only.  `penalty`: the logits penalised for each row's prompt first;
-        `edit` (llm/logit_edits.Edits): then edited for request b in row b.
+        `fsm` (llm/token_fsm.Machines): then masked for request b's start state; `edit` (llm/logit_edits.Edits): then
+        edited for request b in row b.
         Returns the first token of every row, (B, 1) int64 (`n_lp`: and their Logprobs)."""
         B, Lm, lo = len(rows), int(lens.max()), int(lens.min())
         ids = np.zeros((B, Lm), np.int64)
@@ -207,6 +253,8 @@ class DecodeSteps:
                 c.data[int(b), int(lens[b]):Lm] = keep[int(b), int(lens[b]) - lo:]
         if penalty is not None:
             logits = self._penalize_prompt(logits, rows, penalty)
+        if fsm is not None:
+            logits = self._fsm_rows(logits, fsm, fsm.start_states(np.arange(B)))
         if edit is not None:
             logits = self._edit_rows(logits, edit, np.arange(B), np.zeros(B, np.int64))
         nxt = logits.argmax(-1, True) if sampling is None else draw_rows(logits, lens, sampling, np.arange(B))
@@ -214,17 +262,20 @@ class DecodeSteps:
             return nxt
         return nxt, self._logprobs_rows(logits, nxt.numpy(), n_lp)
 
-    def _step_module_rows(self, ids, pos, sampling, req=None, pen=None, n_lp=None, edit=None):
+    def _step_module_rows(self, ids, pos, sampling, req=None, pen=None, n_lp=None, edit=None, fsm=None):
         """One ragged decode step on the tape-node operators (the `cpu` device, fast_decode = False, training mode,
         other dtypes): row b's token at position pos[b] (-1: a stopped row, which yields -1).  The NumPy statement of what
         the per-row kernels compute.  `req`: the counter id of each row (Llama.serve; default: the row).  `pen`
         (llm/penalties.Rows): the fed tokens counted and the logits penalised before the pick.  `edit`
-        (llm/logit_edits.Rows): then the rows' edits.  `n_lp`: returns (ids,
+        (llm/logit_edits.Rows): then the rows' edits; `fsm` (llm/token_fsm.Rows): between the two, the rows' machines
+        advanced by the fed tokens and their masks.  `n_lp`: returns (ids,
         Logprobs of the rows, none for rows at -1)."""
         p = np.maximum(pos, 0)
         logits = self._step_logits_rows(ids, pos)
         if pen is not None:
             logits = self._penalize_step(logits, pen, ids.numpy(), pos)
+        if fsm is not None:
+            logits = self._fsm_step_host(logits, fsm, ids.numpy(), pos)
         if edit is not None:
             logits = self._edit_step_host(logits, edit, pos)
         # (`sampling` a llm/sampling.Table: row b with the values of the request it holds)
@@ -246,14 +297,15 @@ class DecodeSteps:
             h = layer.step_rows(h, pos, self.freqs_cos, self.freqs_sin)
         return self.lm_head(self.norm(h))[:, -1, :]
 
-    def _decode_step_hip(self, ids, pos: int, more: bool = False, sampling=None, pen=None, n_lp=None, edit=None):
+    def _decode_step_hip(self, ids, pos: int, more: bool = False, sampling=None, pen=None, n_lp=None, edit=None,
+                         fsm=None):
         """One decode step (one new token per sequence) without building tape nodes.  ids: (B, 1) int64
         device array; returns the next ids, (B, 1) int64.  The step is ONE hipGraph replay: norm + projection,
         RoPE + cache append, decode attention, SwiGLU + down projection and the greedy pick all read the position
         from device memory (csrc/decode.hip), so nothing changes between replays but the data.  `sampling`: None =
         greedy, else (temperature, top_k, top_p, seed) and the step ends in the sample tick (csrc/sample.hip).  `pen`
         (llm/penalties.Rows of this generation, or None): a penalty plan; its rows are reset from the prompts when a new
-        generation begins.  `edit` (llm/logit_edits.Rows of this generation, or None): an edit plan, reset likewise.
+        generation begins.  `edit` (llm/logit_edits.Rows of this generation, or None): an edit plan, reset likewise; `fsm` (llm/token_fsm.Rows of this generation, or None): an FSM plan.
         `n_lp`: returns (ids, Logprobs of the step)."""
         from .. import hipnp as hp
         B = ids.shape[0]
@@ -266,13 +318,14 @@ class DecodeSteps:
                              f"(max_seq_len {cache.shape[1]}, {self.freqs_cos.shape[0]} RoPE rows)")
         if B > cache.shape[0]:
             raise ValueError(f"batch {B} exceeds the KV cache's max_batch_size {cache.shape[0]}")
-        st = self._decode_plan(B, sampling is not None, penalty=pen is not None, n_lp=n_lp, edit=edit is not None)
+        st = self._decode_plan(B, sampling is not None, penalty=pen is not None, n_lp=n_lp, edit=edit is not None,
+                               fsm=False if fsm is None else fsm.spec.caps)
         if st is None:
-            return self._decode_step_generic(ids, pos, sampling, pen, n_lp, edit)
+            return self._decode_step_generic(ids, pos, sampling, pen, n_lp, edit, fsm)
         ahead, st["ahead"] = st.get("ahead"), None
         if ahead is not None:
             if (ahead[0] == pos and ahead[1] is ids and st["params_val"] == sampling     # exactly this step, queued ahead
-                    and st.get("pen_run") is pen and st.get("edit_run") is edit):
+                    and st.get("pen_run") is pen and st.get("edit_run") is edit and st.get("fsm_run") is fsm):
                 out = st["last_out"] = ahead[2]
                 if more and pos + 1 < limit:
                     self._decode_ahead(st, pos + 1)
@@ -287,7 +340,7 @@ class DecodeSteps:
             # a new generation: its own history -- slots in mapped host memory the pick kernel stores into directly
             st["hist"] = hp.Mailbox(cache.shape[1], (B, 1))
             self._hist_begin(st, st["hist"])
-        self._run_values(st, sampling, pen, edit)
+        self._run_values(st, sampling, pen, edit, fsm)
         if ids is not st["ids"] and ids is not st.get("last_out"):
             st["ids"][...] = ids                                 # (not the array the previous step returned: that
             self._decode_gather(st)                              # one's embedding row is already in x)
@@ -352,10 +405,11 @@ class DecodeSteps:
         L.call("pdn_swiglu_fwd_f32", g, u, sw, B * F, st)
         gemv(sw, F, f.down.weight, x, D, beta=1.0)                    # x += swiglu @ Wdown
 
-    def _eager_tail(self, ws, gemv, fed, pos, pen, draw, n_lp, edit=None):
+    def _eager_tail(self, ws, gemv, fed, pos, pen, draw, n_lp, edit=None, fsm=None):
         """The end of an eager step: the final RMSNorm and the vocabulary projection; `pen` (llm/penalties.Rows): the
         statement of llm/penalties.py on the host counts, the tokens `fed` (device ids) at positions `pos` (host (B,), -1:
-        a stopped row) counted first; `edit` (llm/logit_edits.Rows): the rows' edits (`_edit_rows`); then the greedy
+        a stopped row) counted first; `fsm` (llm/token_fsm.Rows): the rows' machines advanced by `fed` and their masks
+        (`_fsm_step_host`); `edit` (llm/logit_edits.Rows): the rows' edits (`_edit_rows`); then the greedy
         pick, or `draw(out)`, which launches the draw into `out`.  Returns
         the ids, (B, 1) int64 (`n_lp`: and the rows' Logprobs, none for rows at -1)."""
         from .. import hipnp as hp, _lib
@@ -366,6 +420,8 @@ class DecodeSteps:
         if pen is not None:
             pen.feed(fed.get(), pos)
             ws["logits"][...] = pen.apply(ws["logits"].get())
+        if fsm is not None:
+            self._fsm_step_host(ws["logits"], fsm, fed, pos)     # (contiguous rows: in place)
         if edit is not None:
             self._edit_step_host(ws["logits"], edit, pos)        # (contiguous rows: in place)
         if draw is None:
@@ -379,7 +435,7 @@ class DecodeSteps:
         tok[pos < 0] = -1
         return out, self._logprobs_rows(ws["logits"], tok, n_lp)
 
-    def _decode_step_generic(self, ids, pos: int, sampling=None, pen=None, n_lp=None, edit=None):
+    def _decode_step_generic(self, ids, pos: int, sampling=None, pen=None, n_lp=None, edit=None, fsm=None):
         """The same step from the library's generic entry points (skinny `pdn_gemm_f32`, RMSNorm, RoPE, decode
         attention, SwiGLU), ~77 launches from preallocated buffers: for shapes / layouts the graph path does not take."""
         from .. import hipnp as hp, _lib
@@ -412,7 +468,7 @@ class DecodeSteps:
 
         def draw(out):                                # (the sampled form of the pick: counter (pos, b))
             L.call("pdn_sample_rows_f32", ws["logits"]._ptr, V, B, V, params_buffer(*sampling)._ptr, pos, out._ptr, st)
-        return self._eager_tail(ws, gemv, ids, np.full(B, pos), pen, None if sampling is None else draw, n_lp, edit)
+        return self._eager_tail(ws, gemv, ids, np.full(B, pos), pen, None if sampling is None else draw, n_lp, edit, fsm)
 
     # -- ragged decode (generate_ragged): every row at its own position ------------------------------
     def _decode_step_rows(self, ids, run, i: int, more: bool = False):
@@ -429,9 +485,11 @@ class DecodeSteps:
         pos = np.where(live, lens + i, -1).astype(np.int32)
         n_lp = run.get("lp")
         st = self._decode_plan(B, sampling is not None, ragged=True, penalty=run.get("pen") is not None, n_lp=n_lp,
-                               edit=run.get("edit") is not None, per_row=isinstance(sampling, Table))
+                               edit=run.get("edit") is not None, per_row=isinstance(sampling, Table),
+                               fsm=False if run.get("fsm") is None else run["fsm"].spec.caps)
         if st is None:
-            out = self._decode_step_generic_rows(ids, pos, sampling, pen=run.get("pen"), n_lp=n_lp, edit=run.get("edit"))
+            out = self._decode_step_generic_rows(ids, pos, sampling, pen=run.get("pen"), n_lp=n_lp, edit=run.get("edit"),
+                                                 fsm=run.get("fsm"))
             out, lp = out if n_lp is not None else (out, None)
             if pos.min() < 0:
                 tok = out.get().reshape(B, 1)
@@ -453,7 +511,7 @@ class DecodeSteps:
             st["step"][...] = np.int32(i)
             st["stop"][...] = run["stop_mask"]
             self._hist_begin(st, run["hist"])
-        self._run_values(st, sampling, run.get("pen"), run.get("edit"))
+        self._run_values(st, sampling, run.get("pen"), run.get("edit"), run.get("fsm"))
         if ids is not st["ids"] and ids is not st.get("last_out"):
             # (a stopped row's -1 is no token: any valid id stands in, its row computes nothing that is kept)
             st["ids"][...] = np.maximum(ids.get(), 0) if isinstance(ids, hp.readback_array) else ids
@@ -472,7 +530,7 @@ class DecodeSteps:
             st["host_step"] = i + 1
             st["ahead"] = ((id(run), i), st["last_out"], run["hist"].slot(i))
 
-    def _decode_step_generic_rows(self, ids, pos, sampling=None, req=None, pen=None, n_lp=None, edit=None):
+    def _decode_step_generic_rows(self, ids, pos, sampling=None, req=None, pen=None, n_lp=None, edit=None, fsm=None):
         """`_decode_step_generic` with a position per row (pos: host int32, -1 = a stopped row: computed at position 0,
         no cache slot written): k / v are projected into scratch rows and written to each row's own slot, RoPE takes
         each row's own cos / sin row, and the attention runs over each row's own key count (pdn_attention_decode_rows_f32).
@@ -532,4 +590,4 @@ class DecodeSteps:
             else:
                 L.call("pdn_decode_sample_tick_rows_f32", logits, V, B, V, params_buffer(*sampling)._ptr, out._ptr,
                        pd._ptr, step._ptr, None, None, None, 0, 0, None, st)
-        return self._eager_tail(ws, gemv, idc, pos, pen, None if sampling is None else draw, n_lp, edit)
+        return self._eager_tail(ws, gemv, idc, pos, pen, None if sampling is None else draw, n_lp, edit, fsm)

@@ -30,6 +30,7 @@ from . import logit_edits as edit_np
 from . import penalties as pen_np
 from . import prefix as prefix_np
 from . import speculative as spec_np
+from . import token_fsm as fsm_np
 from .decode_plan import DecodePlan
 from .decode_search import SearchEngine
 from .decode_serve import ServeEngine
@@ -397,7 +398,7 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
 
     def generate(self, input_ids, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0,
                  repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=None, logit_bias=None,
-                 allowed_token_ids=None):
+                 allowed_token_ids=None, token_fsm=None):
         """Yield the next ids, (B, 1) int64, for positions L .. max_new_tokens - 1.  temperature 0 (the default): the
         greedy pick of the reference (model.py:258-269); temperature > 0: drawn with top-k / top-p and the seeded
         counter-based generator of llm/sampling.py (token at position t of row b: Philox counter (t, b)).
@@ -407,13 +408,18 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         of the row the pick or the draw read -- token (B, 1), top_ids (B, n), top_logprobs (B, n).
         `logit_bias` ({token id: bias}; -inf bans the token) / `allowed_token_ids` (the only tokens a row may produce):
         the edits of llm/logit_edits.py, after the penalties and before the pick or the draw -- one value for every row,
-        or a sequence with one value (or None) per row.  The arguments are checked here, before anything runs."""
+        or a sequence with one value (or None) per row.
+        `token_fsm` (an llm/token_fsm.TokenFSM for every row, or a sequence with one or None per row): constrained
+        decoding -- a row may only produce tokens its machine allows in its current state, which starts at the machine's
+        start state and advances on every token the row produces; after the penalties, before the edits.
+        The arguments are checked here, before anything runs."""
         temperature, top_k, top_p, seed = check_sampling_args(temperature, top_k, top_p, seed)
         penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty)
         n_lp = lp_np.check_n(logprobs)
         edit = edit_np.check_args(logit_bias, allowed_token_ids, 0, self.vocab_size, input_ids.shape[0])
+        fsm = fsm_np.check_args(token_fsm, self.vocab_size, input_ids.shape[0])
         return self._generate(input_ids, max_new_tokens, (temperature, top_k, top_p, seed) if temperature > 0 else None,
-                              penalty, n_lp, edit)
+                              penalty, n_lp, edit, fsm)
 
     def score(self, input_ids, logprobs=0):
         """log p(x_t | x_<t) of given sequences: input_ids (B, L) int, L >= 2.  Returns llm/logprobs.Logprobs for
@@ -448,7 +454,8 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
 
     def generate_ragged(self, prompts, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
                         speculate=0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                        logprobs=None, logit_bias=None, allowed_token_ids=None, min_new_tokens=0, min_p=0.0):
+                        logprobs=None, logit_bias=None, allowed_token_ids=None, min_new_tokens=0, min_p=0.0,
+                        token_fsm=None):
         """Generation for B prompts of different lengths, every row at its own position.  Yields a (B, 1) int64 Tensor
         per step: step i holds, for row b, the token at position len_b + i.  `max_new_tokens` is the number of NEW tokens
         per row -- `generate`'s second argument is an end position instead: for equal lengths L,
@@ -474,6 +481,8 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         sequence with one value per row, mixed freely: row b is then drawn with its own values, key (seed_b, 0) and
         counter (t, b); a row with temperature 0 in a run that samples takes the first maximum of its logits, and a run
         whose temperatures are all 0 is the greedy run.  The penalties stay one set of values for every row.
+        `token_fsm`: as in `generate` (llm/token_fsm.py), one machine or one (or None) per prompt; a stopped row's state
+        stays.  Not with speculate > 0.
         Every argument is checked here (ValueError), before anything runs."""
         V = self.vocab_size
         if int(max_new_tokens) != max_new_tokens or max_new_tokens < 0:
@@ -505,11 +514,12 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         if stops.size and (stops.min() < 0 or stops.max() >= V):
             raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
         edit = edit_np.check_args(logit_bias, allowed_token_ids, min_new_tokens, V, len(rows), stops, k)
+        fsm = fsm_np.check_args(token_fsm, V, len(rows), k)
         self.last_speculation = None if k == 0 else spec_np.counts()
         if k:
             return self._speculate([r.astype(np.int64) for r in rows], max_new_tokens, k, sampling, stops)
         return self._generate_ragged([r.astype(np.int64) for r in rows], max_new_tokens, sampling, stops, penalty,
-                                     n_lp, edit)
+                                     n_lp, edit, fsm)
 
     # -- decode fast path -----------------------------------------------------------
     graph_decode = True     # class switch: False issues the step's launches one by one instead of replaying a hipGraph
@@ -521,7 +531,8 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
     # -- continuous batching (serve): a finished row takes the next waiting request -------------------------------
     def serve(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
               prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=None,
-              prefix_cache=False, logit_bias=None, allowed_token_ids=None, min_new_tokens=0, min_p=0.0):
+              prefix_cache=False, logit_bias=None, allowed_token_ids=None, min_new_tokens=0, min_p=0.0,
+              token_fsm=None):
         """Continuous batching: N requests (`prompts`, N may exceed max_batch_size) through `slots` decode rows
         (default min(N, max_batch_size)).  A row frees when its request yields a stop id or uses up its budget
         (`max_new_tokens`: one int, or one per request; 0 = the request yields nothing and never takes a row).  Before
@@ -559,7 +570,10 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         sampled ones, and two requests may differ in temperature or seed.  The promise above holds per request: request
         r's tokens are those of row r of `generate_ragged(prompts, max(budgets), <r's own values for every row>)`, drawn
         with key (seed_r, 0) and counter (t, r), whichever row it runs in and whatever the other requests' values are.
-        The penalties are not per request: they stay one set of values for the call."""
+        The penalties are not per request: they stay one set of values for the call.
+        `token_fsm` (llm/token_fsm.py): one machine for every request, or a sequence with one (or None) per request -- a
+        request's machine follows it into whichever row it runs in, from its start state, with plain and chunked prefill
+        and with the prefix cache."""
         penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty)
         n_lp = lp_np.check_n(logprobs)
         k_pre = prefix_np.check_arg(prefix_cache, prefill_chunk)
@@ -597,21 +611,23 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         if stops.size and (stops.min() < 0 or stops.max() >= V):
             raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
         edit = edit_np.check_args(logit_bias, allowed_token_ids, min_new_tokens, V, N, stops)
+        fsm = fsm_np.check_args(token_fsm, V, N)
         C = chunked.check_chunk(prefill_chunk, slots)
         if C is not None:
             return self._serve_chunked([p.astype(np.int64) for p in rows], budgets, int(slots), C, sampling, stops,
-                                       penalty, n_lp, k_pre, edit)
-        return self._serve([p.astype(np.int64) for p in rows], budgets, int(slots), sampling, stops, penalty, n_lp, edit)
+                                       penalty, n_lp, k_pre, edit, fsm)
+        return self._serve([p.astype(np.int64) for p in rows], budgets, int(slots), sampling, stops, penalty, n_lp, edit,
+                           fsm)
 
     def serve_all(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
                   prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
                   logprobs=None, prefix_cache=False, logit_bias=None, allowed_token_ids=None, min_new_tokens=0,
-                  min_p=0.0):
+                  min_p=0.0, token_fsm=None):
         """`serve` run to the end: a list of N int64 arrays, request r's generated tokens in order.  `logprobs` = n: a
         list of (tokens, Logprobs) instead, the arrays of length k / (k, n) for a request's k tokens."""
         it = self.serve(prompts, max_new_tokens, slots, temperature, top_k, top_p, seed, stop_ids, prefill_chunk,
                         repetition_penalty, presence_penalty, frequency_penalty, logprobs, prefix_cache, logit_bias,
-                        allowed_token_ids, min_new_tokens, min_p)
+                        allowed_token_ids, min_new_tokens, min_p, token_fsm)
         out = [[] for _ in range(len(prompts))]
         lps = [[] for _ in range(len(prompts))]
         for step in it:
