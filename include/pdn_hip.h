@@ -960,7 +960,8 @@ int64_t pdn_attention_bwd_lds_bytes(int L, int head_dim);
  * additive mask (the padding mask of examples/pydynet/transformer.py:120-128, the causal mask tensor of
  * llm/clip/model.py:8-13,54-55), q and k/v with their own strides (views into a packed QKV projection
  * or into a cache).  Key tiles stream through LDS with an online softmax; nothing of size Lq x Lk
- * touches HBM.  mask element (b, h, q, k) = mask[b*sb + h*sh + q*sq + k*sk] (stride 0 broadcasts). */
+ * touches HBM.  mask element (b, h, q, k) = mask[b*sb + h*sh + q*sq + k*sk] (stride 0 broadcasts).
+ * B * H is the grid's y extent: above 65535 both entries return PDN_EUNSUPPORTED before any launch. */
 int pdn_attention_stream_supported(int head_dim);
 int pdn_attention_stream_fwd_f32(const float* q, const float* k, const float* v, float* o, float* lse, int B,
                                  int H, int Lq, int Lk, int head_dim, int64_t q_row_stride,

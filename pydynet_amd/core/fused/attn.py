@@ -49,6 +49,9 @@ def _key_bias_of(mask, B, H, Lq, Lk):
     return _contig(m).reshape(shape[0], Lk)
 
 
+_STREAM_MAX_BH = 65535     # kMaxGridY of csrc/attention_stream.hip
+
+
 def _attn_kernel(B, H, hd, Lq, Lk, start_pos, mask, layouts):
     """'resident' (K/V of a head held in LDS 256 rows at a time: hd 48 / 64, L <= 1024 -- the benchmark shape is
     one chunk; masks that only depend on the key ride in as a key bias), 'stream' (general kernels: other masks, other
@@ -62,7 +65,8 @@ def _attn_kernel(B, H, hd, Lq, Lk, start_pos, mask, layouts):
         kb = _key_bias_of(mask, B, H, Lq, Lk) if mask is not None else None
         if (mask is None or kb is not None) and _L().query("pdn_attention_supported", Lq, hd):
             return "resident", kb
-    if _L().query("pdn_attention_stream_supported", hd) and kl == vl:
+    # (B * H is the grid's y extent of the streaming kernels: a larger batch takes the composition)
+    if _L().query("pdn_attention_stream_supported", hd) and kl == vl and B * H <= _STREAM_MAX_BH:
         return "stream", None
     return None, None
 

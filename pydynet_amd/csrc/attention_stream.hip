@@ -270,8 +270,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_stream_kernel(
     ld.issue(Kg, Vg, a.kv_rs, 0, a.Lk, a.rc, a.rs, true);
     ld.commit(Kbuf(0), Vbuf(0));
   }
+  // delta = dO . o comes from the SAME contraction as dP = dO . v below (same instruction, same order over the head
+  // dim: the diagonal of O dO^T), so that where a row is one key (o = v) dP - delta cancels to an exact zero instead of
+  // the round-off of two differently ordered sums
   float4 qf[NT8], gf[NT8];
-  float dpart = 0.f;
+  f32x16 dd;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) dd[r] = 0.f;
   {
     const float* qrow = Q + qbase + (int64_t)qc * a.q_rs + 4 * lh;
     const float* grow = dO + qbase + (int64_t)qc * a.q_rs + 4 * lh;
@@ -282,10 +287,19 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_stream_kernel(
       if (a.rc) qf[t] = as_rot(qf[t], a.rc, a.rs, qc + a.start_pos, 4 * t + 2 * lh, HD / 2, 1.f);
       gf[t] = *reinterpret_cast<const float4*>(grow + 8 * t);
       const float4 ov = *reinterpret_cast<const float4*>(orow + 8 * t);
-      dpart += (ov.x * gf[t].x + ov.y * gf[t].y) + (ov.z * gf[t].z + ov.w * gf[t].w);
+      dd = __builtin_amdgcn_mfma_f32_32x32x2f32(ov.x, gf[t].x, dd, 0, 0, 0);
+      dd = __builtin_amdgcn_mfma_f32_32x32x2f32(ov.y, gf[t].y, dd, 0, 0, 0);
+      dd = __builtin_amdgcn_mfma_f32_32x32x2f32(ov.z, gf[t].z, dd, 0, 0, 0);
+      dd = __builtin_amdgcn_mfma_f32_32x32x2f32(ov.w, gf[t].w, dd, 0, 0, 0);
     }
   }
-  const float delta_q = dpart + __shfl_xor(dpart, 32, 64);
+  // dd[r] of lane (li, lh) is o[as_krow(r, lh)] . dO[li]: the diagonal sits in the half-wave with lh = bit 2 of li
+  float dpart = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (r == (li & 3) + 4 * (li >> 3)) dpart = dd[r];
+  const float dother = __shfl_xor(dpart, 32, 64);
+  const float delta_q = lh == ((li >> 2) & 1) ? dpart : dother;
   const float lse_q = LSE[(int64_t)bh * a.Lq + qc];
   if (lh == 0 && qpos < a.Lq) Delta[(int64_t)bh * a.Lq + qpos] = delta_q;
   f32x16 dq[DT];
@@ -473,10 +487,18 @@ bool hd_ok(int hd) { return hd == 16 || hd == 24 || hd == 32 || hd == 48 || hd =
     default: { constexpr int HD = 128; BODY; } break; \
   }
 
-int check_common(const char* who, int head_dim, int64_t q_rs, int64_t q_bs, int64_t kv_rs, int64_t kv_bs,
+// B * H is the grid's y extent: HIP launches take at most 65535 there (hipDeviceProp_t::maxGridSize[1] of the MI355X
+// reports 65536; the library keeps to the 65535 every other entry holds its y extent to)
+constexpr int64_t kMaxGridY = 65535;
+
+int check_common(const char* who, int B, int H, int head_dim, int64_t q_rs, int64_t q_bs, int64_t kv_rs, int64_t kv_bs,
                  const float* rc, const float* rs, int start_pos, uintptr_t ptr_or) {
   if (!hd_ok(head_dim)) {
     pdn_set_error("%s: head_dim %d not in {16, 24, 32, 48, 64, 96, 128}", who, head_dim);
+    return PDN_EUNSUPPORTED;
+  }
+  if ((int64_t)B * H > kMaxGridY) {
+    pdn_set_error("%s: B * H = %lld exceeds the grid's y limit of %lld", who, (long long)B * H, (long long)kMaxGridY);
     return PDN_EUNSUPPORTED;
   }
   if ((q_rs % 4) || (q_bs % 4) || (kv_rs % 4) || (kv_bs % 4) || (ptr_or & 15)) {
@@ -513,7 +535,7 @@ int pdn_attention_stream_fwd_f32(const float* q, const float* k, const float* v,
                                  const float* rope_sin, void* stream) {
   if (B == 0 || H == 0 || Lq == 0) return PDN_OK;
   PDN_CHECK_ARG(q && k && v && o && lse && Lk > 0, "pdn_attention_stream_fwd_f32: bad operand");
-  int rc = check_common("pdn_attention_stream_fwd_f32", head_dim, q_row_stride, q_batch_stride, kv_row_stride,
+  int rc = check_common("pdn_attention_stream_fwd_f32", B, H, head_dim, q_row_stride, q_batch_stride, kv_row_stride,
                         kv_batch_stride, rope_cos, rope_sin, start_pos,
                         (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o);
   if (rc) return rc;
@@ -539,7 +561,7 @@ int pdn_attention_stream_bwd_f32(const float* q, const float* k, const float* v,
                                  int64_t workspace_bytes, void* stream) {
   if (B == 0 || H == 0 || Lq == 0) return PDN_OK;
   PDN_CHECK_ARG(q && k && v && o && d_o && lse && dq && dk && dv && Lk > 0, "pdn_attention_stream_bwd_f32: bad operand");
-  int rc = check_common("pdn_attention_stream_bwd_f32", head_dim, q_row_stride, q_batch_stride, kv_row_stride,
+  int rc = check_common("pdn_attention_stream_bwd_f32", B, H, head_dim, q_row_stride, q_batch_stride, kv_row_stride,
                         kv_batch_stride, rope_cos, rope_sin, start_pos,
                         (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o |
                             (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv);

@@ -148,6 +148,22 @@ class AttentionMixin:
     def pdn_attention_stream_supported(self, hd): return 1 if hd in (16, 24, 32, 48, 64, 96, 128) else 0
     def pdn_attention_stream_bwd_workspace_bytes(self, B, H, Lq): return 4 * B * H * Lq
 
+    def _stream_refusal(self, needed, aligned, B, H, Lk, hd, qrs, qbs, krs, kbs, start, rc, rsn):
+        """The host checks of csrc/attention_stream.hip, in its order: the status a refused call returns, else 0."""
+        if not all(needed) or Lk <= 0:
+            return -1
+        if not self.pdn_attention_stream_supported(hd):
+            return -2
+        if B * H > 65535:                                   # B * H is the grid's y extent
+            return -2
+        if qrs % 4 or qbs % 4 or krs % 4 or kbs % 4 or any(int(p) % 16 for p in aligned):
+            return -1
+        if bool(rc) != bool(rsn) or (rc and (int(rc) % 8 or int(rsn) % 8)):
+            return -1
+        if rc and start:
+            return -2
+        return 0
+
     def _stream_scores(self, Q, K, B, H, Lq, Lk, hd, causal, start, mask, sb, sh, sq, sk):
         s = np.matmul(Q, K.swapaxes(-1, -2)) / np.float32(math.sqrt(hd))
         if causal:
@@ -159,9 +175,12 @@ class AttentionMixin:
 
     def pdn_attention_stream_fwd_f32(self, q, k, v, o, lse, B, H, Lq, Lk, hd, qrs, qbs, krs, kbs, causal, start,
                                      mask, sb, sh, sq, sk, rc, rsn, stream):
+        if B == 0 or H == 0 or Lq == 0:
+            return 0
+        bad = self._stream_refusal((q, k, v, o, lse), (q, k, v, o), B, H, Lk, hd, qrs, qbs, krs, kbs, start, rc, rsn)
+        if bad:
+            return bad
         self._count(11)
-        if not self.pdn_attention_stream_supported(hd) or (rc and start):
-            return -2
         Q, O = [view(p, (B, H, Lq, hd), (qbs, hd, qrs, 1), np.float32) for p in (q, o)]
         K, V = [np.array(view(p, (B, H, Lk, hd), (kbs, hd, krs, 1), np.float32)) for p in (k, v)]
         Q, K = self._rot(np.array(Q), rc, rsn, Lq, hd, 1.0), self._rot(K, rc, rsn, Lk, hd, 1.0)
@@ -175,17 +194,27 @@ class AttentionMixin:
 
     def pdn_attention_stream_bwd_f32(self, q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk, hd, qrs, qbs, krs, kbs,
                                      causal, start, mask, sb, sh, sq, sk, rc, rsn, ws, wsb, stream):
+        if B == 0 or H == 0 or Lq == 0:
+            return 0
+        bad = self._stream_refusal((q, k, v, o, do, lse, dq, dk, dv), (q, k, v, o, do, dq, dk, dv), B, H, Lk, hd, qrs, qbs,
+                                   krs, kbs, start, rc, rsn)
+        if bad:
+            return bad
+        if not ws or wsb < self.pdn_attention_stream_bwd_workspace_bytes(B, H, Lq):
+            return -3
         self._count(11)
-        if not self.pdn_attention_stream_supported(hd) or (rc and start):
-            return -2
         qv = lambda p: view(p, (B, H, Lq, hd), (qbs, hd, qrs, 1), np.float32)
         kv = lambda p: view(p, (B, H, Lk, hd), (kbs, hd, krs, 1), np.float32)
         Q, O, DO, K, V = np.array(qv(q)), np.array(qv(o)), np.array(qv(do)), np.array(kv(k)), np.array(kv(v))
         Q, K = self._rot(Q, rc, rsn, Lq, hd, 1.0), self._rot(K, rc, rsn, Lk, hd, 1.0)
         s = self._stream_scores(Q, K, B, H, Lq, Lk, hd, causal, start, mask, sb, sh, sq, sk)
         p = np.exp(s - flat(lse, B * H * Lq).reshape(B, H, Lq, 1))
-        delta = (DO * O).sum(-1, keepdims=True)
-        dp = np.matmul(DO, V.swapaxes(-1, -2))
+        # as the kernel: delta = dO . o and dP = dO . v accumulate over the head dim in ONE order, so a row of one key
+        # (o = v) has dP - delta == 0 exactly
+        delta, dp = np.zeros((B, H, Lq, 1), np.float32), np.zeros((B, H, Lq, Lk), np.float32)
+        for d in range(hd):
+            delta += DO[..., d:d + 1] * O[..., d:d + 1]
+            dp += DO[..., d:d + 1] * V[..., None, :, d]
         ds = p * (dp - delta) / np.float32(math.sqrt(hd))
         kv(dv)[...] = np.matmul(p.swapaxes(-1, -2), DO)
         qv(dq)[...] = self._rot(np.matmul(ds, K), rc, rsn, Lq, hd, -1.0)

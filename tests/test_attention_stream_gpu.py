@@ -3,7 +3,10 @@ the reference's composition -- `q k^T / sqrt(hd) (+ mask) -> softmax(-1) -> @ v`
 (llm/llama/model.py:112-121, llm/clip/model.py:47-63, examples/pydynet/transformer.py:70-92) -- over
 every supported head dim, ragged lengths, Lq != Lk with a start position (KV-cache prefill), additive
 masks in the layouts the reference builds ((L, L) causal tensor, (B, 1, 1, L) padding mask), strided
-q / k / v views, and RoPE applied in the loads.  Tolerance 2e-5 of the tensor's largest entry."""
+q / k / v views, and RoPE applied in the loads.  Tolerance 2e-5 of the tensor's largest entry.
+
+The tile, workgroup, mask-stride, start-position and padded-stride edges of the same kernels, with guard elements, NaN-prefilled
+outputs and an exact (one-hot) pass, are in tests/test_attention_stream_variants.py."""
 import math
 
 import numpy as np
