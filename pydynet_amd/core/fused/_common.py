@@ -20,6 +20,11 @@ def _L():
     return _lib.lib()
 
 
+def _provides(name):
+    from ... import _lib
+    return _lib.provides(name)
+
+
 def _contig(a):
     return a if a.is_contiguous() else a.copy()
 
@@ -46,7 +51,7 @@ def _foldable(node, idx, t):
     """The gradient input `idx` already holds (handed over by the engine as `node._existing`) if
     this node can add it inside its own kernel; marks the input as folded."""
     ex = getattr(node, "_existing", None)
-    ex = ex[idx] if ex is not None else None
+    ex = _materialised(ex[idx]) if ex is not None else None
     if ex is None or isinstance(ex, np.ndarray) or ex.dtype != np.float32 \
             or ex.shape != tuple(t.shape) or not ex.is_contiguous():
         return None
@@ -136,21 +141,69 @@ def _pack_columns(hp, weights):
     return cat
 
 
-def _dx_of_shared_input(hp, node, x, dcat, weights, T, fin):
-    """dx = [d_1 | d_2 | ...] @ [W_1 | W_2 | ...]^T (+ the gradient x already holds) for projections that share their
-    input: ONE contraction over all of them.  With the weights equally spaced in memory (how `Attention.move` /
-    `FeedForward.move` pack them) and enough rows the product reads them where they live
-    (`pdn_gemm_outres_blocks_nt_f32`); otherwise against a column-packed copy made here."""
-    L = _L()
-    dx = hp.empty(x.shape, np.float32)
-    ex = _foldable(node, 0, x)
-    exr = ex.reshape(T, fin) if ex is not None else None
+def _weight_blocks(hp, L, dcat, weights, T, fin):
+    """(arrays, stacked view, kb) when the input-gradient product may read the weights where they live
+    (`pdn_gemm_outres_blocks_nt_f32`): equally spaced in memory, 288 input features, enough rows.  Else None."""
     ws = [_contig(w.data) for w in weights]
     stack = hp.stacked_view(ws)
     kb = ws[0].shape[1]
     if (fin == 288 and stack is not None and abs(stack._strides[0]) < (1 << 40) and dcat.is_contiguous()
             and os.environ.get("PDN_NO_DX_BLOCKS", "0") != "1"
             and L.query("pdn_gemm_outres_blocks_supported", T, kb, len(ws))):
+        return ws, stack, kb
+    return None
+
+
+class DeferredInputGrad:
+    """The input gradient dx = [d_1 | d_2 | ...] @ [W_1 | W_2 | ...]^T of projections that share their input, NOT YET
+    FORMED: what `qkv_attention` / `ffn_swiglu` hand an `rms_norm` input instead of the array when that node can run the
+    product itself with its own backward in the product's drain (`pdng_outres_blocks_nt_rmsnorm_bwd_f32`), so that the
+    (tokens x 288) gradient of the norm's output never passes through memory.  Carries the packed gradient, the weight
+    blocks and the shape; `materialise()` runs the product as `_dx_of_shared_input` would have (once: the array is kept).
+    Only a node with `takes_deferred_grad` ever sees one: the engine, `_accumulate` and `_foldable` materialise it for
+    everybody else."""
+
+    def __init__(self, hp, dcat, ws, stack, kb, shape, T):
+        self._hp, self.dcat, self.ws, self.stack, self.kb, self.T = hp, dcat, ws, stack, kb, T
+        self.shape, self.dtype, self._array = tuple(shape), np.dtype(np.float32), None
+
+    def materialise(self):
+        if self._array is None:
+            hp = self._hp
+            dx = hp.empty(self.shape, np.float32)
+            _L().call("pdn_gemm_outres_blocks_nt_f32", self.dcat._ptr, self.ws[0]._ptr, self.stack._strides[0], self.kb,
+                      len(self.ws), dx._ptr, None, self.T, self.dcat.shape[1], 288, hp.stream())
+            self._array, self.dcat, self.ws, self.stack = dx, None, None, None
+        return self._array
+
+
+def _materialised(g):
+    return g.materialise() if isinstance(g, DeferredInputGrad) else g
+
+
+def _dx_of_shared_input(hp, node, x, dcat, weights, T, fin, side=None):
+    """dx = [d_1 | d_2 | ...] @ [W_1 | W_2 | ...]^T (+ the gradient x already holds) for projections that share their
+    input: ONE contraction over all of them.  With the weights equally spaced in memory (how `Attention.move` /
+    `FeedForward.move` pack them) and enough rows the product reads them where they live
+    (`pdn_gemm_outres_blocks_nt_f32`); otherwise against a column-packed copy made here.
+    When x is an `rms_norm` node that can fold its backward into that product (`takes_deferred_grad`, 288 columns, rows >=
+    `fuse_bwd_min_rows`), nothing has reached x yet and no side stream (`side`) is in use, the product is left to that
+    node: a `DeferredInputGrad` is returned."""
+    L = _L()
+    blocks = _weight_blocks(hp, L, dcat, weights, T, fin)
+    existing = getattr(node, "_existing", None)
+    if (blocks is not None and side is None and not two_stream["enabled"] and type(x).__dict__.get("takes_deferred_grad", False)
+            and type(x).fuse_bwd and T >= type(x).fuse_bwd_min_rows and x.device.is_hip and x.shape[-1] == 288
+            and existing is not None and existing[0] is None and x.grad is None and x.last and x.requires_grad
+            and hp.capturing() is None
+            and _provides("pdng_outres_blocks_nt_rmsnorm_bwd_f32")):
+        ws, stack, kb = blocks
+        return DeferredInputGrad(hp, dcat, ws, stack, kb, x.shape, T)
+    dx = hp.empty(x.shape, np.float32)
+    ex = _foldable(node, 0, x)
+    exr = ex.reshape(T, fin) if ex is not None else None
+    if blocks is not None:
+        ws, stack, kb = blocks
         L.call("pdn_gemm_outres_blocks_nt_f32", dcat._ptr, ws[0]._ptr, stack._strides[0], kb, len(ws),
                dx._ptr, exr._ptr if exr is not None else None, T, dcat.shape[1], fin, hp.stream())
     else:

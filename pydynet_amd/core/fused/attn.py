@@ -497,7 +497,7 @@ class qkv_attention(_Operator):
                         hp.gemm(x2.T, dblocks[i], dws[i])
                         grads[1 + i] = dws[i]
         if x.requires_grad:
-            grads[0] = _dx_of_shared_input(hp, self, x, dqkv, (wq, wk, wv), T, D)
+            grads[0] = _dx_of_shared_input(hp, self, x, dqkv, (wq, wk, wv), T, D, side)
         if side is not None:
             side.join()
         return grads

@@ -8,7 +8,8 @@ import os
 
 from ...autograd import is_grad_enable
 from ..tensor import _Operator
-from ._common import _hip, _L, _contig, _require_f32, _foldable, _is_leaf_f32, _Deferred
+from ._common import (_hip, _L, _contig, _require_f32, _foldable, _is_leaf_f32, _Deferred, DeferredInputGrad, _materialised,
+                      _provides)
 
 
 class rms_norm(_Deferred, _Operator):
@@ -22,6 +23,11 @@ class rms_norm(_Deferred, _Operator):
     folds_existing = True
     fold = os.environ.get("PDN_NO_NORM_FOLD", "0") != "1"        # (same-box A/B switch)
     fold_min_rows = 4096
+    # Round 16: a `qkv_attention` / `ffn_swiglu` consumer hands this node its input gradient UNFORMED (`DeferredInputGrad`)
+    # and backward_all runs the product with the norm's backward in its drain (`pdng_outres_blocks_nt_rmsnorm_bwd_f32`)
+    takes_deferred_grad = True
+    fuse_bwd = os.environ.get("PDN_NO_NORM_BWD_FUSE", "0") != "1"     # (same-box A/B switch)
+    fuse_bwd_min_rows = 65536
 
     def __init__(self, x, weight, eps=1e-6):
         self.eps = float(eps)
@@ -63,12 +69,21 @@ class rms_norm(_Deferred, _Operator):
         hp, L = _hip(), _L()
         cols = x.shape[-1]
         rows = self._x.size // cols
-        g = _contig(g)
+        fused = (isinstance(g, DeferredInputGrad) and x.requires_grad and cols == 288 and g.T == rows
+                 and _provides("pdng_outres_blocks_nt_rmsnorm_bwd_f32"))
+        g = g if fused else _contig(_materialised(g))
         dx = hp.empty(x.shape, np.float32)
         direct = w.requires_grad and _is_leaf_f32(w)
         dw = w.grad if direct else (hp.empty((cols,), np.float32) if w.requires_grad else None)
-        ws, wsb = hp.workspace(L.query("pdn_rmsnorm_bwd_workspace_bytes", rows, cols))
         ex = _foldable(self, 0, x) if x.requires_grad else None
+        if fused:
+            kb, nb = g.kb, len(g.ws)
+            ws, wsb = hp.workspace(L.query("pdng_outres_blocks_nt_rmsnorm_bwd_workspace_bytes", rows, kb, nb))
+            L.call("pdng_outres_blocks_nt_rmsnorm_bwd_f32", g.dcat._ptr, g.ws[0]._ptr, g.stack._strides[0], kb, nb,
+                   self._x._ptr, w.data._ptr, self._rms._ptr, ex._ptr if ex is not None else None, dx._ptr,
+                   dw._ptr if dw is not None else None, 1 if direct else 0, rows, g.dcat.shape[1], ws, wsb, hp.stream())
+            return [dx, None if direct else dw]
+        ws, wsb = hp.workspace(L.query("pdn_rmsnorm_bwd_workspace_bytes", rows, cols))
         L.call("pdn_rmsnorm_bwd_f32", self._x._ptr, w.data._ptr, self._rms._ptr, g._ptr,
                ex._ptr if ex is not None else None, dx._ptr,
                dw._ptr if dw is not None else None, 1 if direct else 0, rows, cols, ws, wsb, hp.stream())

@@ -307,6 +307,11 @@ class Tensor:
                 if not inputs:
                     continue
                 if g is not None:
+                    if getattr(g, "materialise", None) is not None and (
+                            retain_graph or not type(node).__dict__.get("takes_deferred_grad", False)):
+                        # an input gradient its producer left unformed (core/fused/_common.py: DeferredInputGrad) for a
+                        # node that cannot form it itself, or whose gradient stays readable behind this walk
+                        g = node.grad = g.materialise()
                     folded = ()
                     if hasattr(node, "backward_all"):
                         if node.folds_existing:
@@ -372,6 +377,12 @@ def _unbroadcast(g, shape):
 
 
 def _accumulate(t, add_grad, xp):
+    # an unformed input gradient (core/fused/_common.py: DeferredInputGrad) is adopted as it is by an op node that holds
+    # nothing yet; anything that has to be added to, or that stops at a leaf, is formed first
+    if getattr(t.grad, "materialise", None) is not None:
+        t.grad = t.grad.materialise()
+    if getattr(add_grad, "materialise", None) is not None and (t.grad is not None or not t.last):
+        add_grad = add_grad.materialise()
     fresh = add_grad.shape != tuple(t.shape)
     if fresh:
         add_grad = _unbroadcast(add_grad, t.shape)
@@ -417,6 +428,7 @@ class _Operator(Tensor):
     backward_all and lists in `self._folded` the inputs whose returned gradient includes them."""
 
     folds_existing = False
+    takes_deferred_grad = False      # True IN THE CLASS'S OWN DICT: backward_all accepts a DeferredInputGrad (core/fused/_common.py)
 
     def _init_node(self, data, device, inputs):
         self.data = data

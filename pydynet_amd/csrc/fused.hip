@@ -14,6 +14,7 @@
 // RMSNorm, 256 for attention scores), loads are 16 B per lane, row reductions are wave
 // shuffles -- no LDS.  Everything is fp32; reductions are in a fixed order (deterministic).
 #include "common.h"
+#include "gemm_routes.h"
 
 // ======================================================================================
 // softmax over the last (contiguous) dim, optional attention prologue:
@@ -327,6 +328,14 @@ __global__ __launch_bounds__(1024) void colsum_partials_kernel(const float* __re
     for (int k = 1; k < 64; ++k) t += red[k][tx];
     out[c] = accumulate ? out[c] + t : t;
   }
+}
+
+// for the other files that leave partial rows (csrc/normgrad.hip; declared in gemm_routes.h)
+int pdn_colsum_partials_launch(const float* part, int nb, int cols, float* out, int accumulate, void* stream) {
+  hipLaunchKernelGGL(colsum_partials_kernel, dim3((cols + COLSUM_COLS - 1) / COLSUM_COLS), dim3(1024), 0, (hipStream_t)stream,
+                     part, nb, cols, out, accumulate);
+  PDN_LAUNCH_CHECK();
+  return PDN_OK;
 }
 
 extern "C" int64_t pdn_rmsnorm_bwd_workspace_bytes(int64_t rows, int cols) {

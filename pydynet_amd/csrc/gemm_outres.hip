@@ -501,6 +501,17 @@ extern "C" int pdn_gemm_outres_blocks_nt_f32(const float* A, const float* W, int
   pdn_gemm_prof_end(tk, stream);
   return rc;
 }
+// the same product at ANY row count (pdn_gemm_outres_blocks_supported is a statement about speed, not about what the kernel
+// can do): the two-launch route of csrc/normgrad.hip below the split kernel's 65536 rows
+int pdn_outres_blocks_nt_launch(const float* A, const float* W, int64_t b_block_stride, int kb, int nb, float* C, int M,
+                                int64_t lda, int64_t ldc, void* stream) {
+  const int K = kb * nb;
+  if (kb <= 0 || kb % OR_KP != 0 || nb < 1 || (b_block_stride & 3) || !pdn_gemm_outres_supported(M, OR_N, K, lda, K, ldc, 1)) {
+    pdn_set_error("pdn_outres_blocks_nt_launch: unsupported shape M=%d kb=%d nb=%d", M, kb, nb);
+    return PDN_EUNSUPPORTED;
+  }
+  return outres_launch(A, W, C, nullptr, nullptr, M, OR_N, K, lda, kb, ldc, 1, nullptr, 0, stream, kb, b_block_stride);
+}
 
 static int outres_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int N,
                          int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans, void* workspace,

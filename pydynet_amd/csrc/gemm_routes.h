@@ -23,6 +23,8 @@ extern "C" int pdn_gemm_outres_f32(const float* A, const float* B, float* C, con
 extern "C" int pdn_gemm_outres_ws_f32(const float* A, const float* B, float* C, const float* bias, const float* residual,
                                       int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans,
                                       void* workspace, int64_t workspace_bytes, void* stream);
+int pdn_outres_blocks_nt_launch(const float* A, const float* W, int64_t b_block_stride, int kb, int nb, float* C, int M,
+                                int64_t lda, int64_t ldc, void* stream);
 int pdn_gemm_outres_tn_plan(int N, int K, int* nw_out, int* k_per_split_out);
 int pdn_gemm_outres_tn_launch(const float* X, const float* G, float* C, int N, int K, int64_t ldx, int64_t ldg,
                               int64_t ldc, int64_t slab, int nw, int k_per_split, void* stream);
@@ -51,6 +53,14 @@ int pdn_outres_split_takes(const float* A, const float* B, const float* C, const
 int pdn_outres_split_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int K,
                             int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, void* stream,
                             int count_slot);
+// ... with the RMSNorm backward of the product formed in the drain (csrc/normgrad.hip, include/pdn_normgrad.h)
+int pdn_outres_split_norm_bwd_partial_rows(int M);
+int pdn_outres_split_norm_bwd_launch(const float* A, const float* W, int64_t b_bstride, int kb, int nb, const float* x,
+                                     const float* w, const float* rms, const float* ex, float* dx, float* dwpart, int M,
+                                     int64_t lda, void* stream);
+
+// ---- csrc/fused.hip: out[c] (+)= sum_b part[b][c] in a fixed order
+int pdn_colsum_partials_launch(const float* part, int nb, int cols, float* out, int accumulate, void* stream);
 
 // ---- csrc/gemm_rowres.hip: the row-resident / tile-piece kernels (K = 288)
 extern "C" int pdn_gemm_rowres_supported(int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans);

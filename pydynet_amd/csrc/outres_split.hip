@@ -129,7 +129,27 @@ struct OrsParams {
   float* C;
   int M, np, nblk;
   int64_t lda, ldc;
+  // epilogue 1 (the RMSNorm backward in the drain): C is dx; x, the held gradient and dx share the row stride ldc
+  const float* nx;                // the norm's raw input
+  const float* nw;                // its 288 weights
+  const float* nrms;              // M values
+  const float* nex;               // may be null: the gradient x already holds, added to dx
+  float* dwpart;                  // may be null: gridDim.x x 288 partial sums of the weight gradient
 };
+
+// the sum over the sixteen lanes r = lane & 15 of a row of the wave, in every one of them and with the same bits in each
+// (every step adds the same two numbers on both sides): two steps inside the quads, then the halves of eight and of sixteen
+// mirrored onto each other.  All 64 lanes must be active.
+template <int CTRL>
+__device__ __forceinline__ float ors_dpp_add(float v) {
+  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float ors_row16_sum(float v) {
+  v = ors_dpp_add<0xB1>(v);       // quad_perm [1, 0, 3, 2]
+  v = ors_dpp_add<0x4E>(v);       // quad_perm [2, 3, 0, 1]
+  v = ors_dpp_add<0x141>(v);      // row_half_mirror
+  return ors_dpp_add<0x140>(v);   // row_mirror
+}
 
 // the largest finite magnitude of eight values
 __device__ __forceinline__ float ors_max8(const float4& a, const float4& b) {
@@ -159,7 +179,16 @@ __device__ __forceinline__ void ors_form2(float x0, float x1, int S, unsigned& h
 
 // ABLATE (timing experiments, PDN_OUTRES_SPLIT_ABLATE; the results are WRONG): 1 = the planes of A are constants, A is
 // never read (MFMA + LDS only); 2 = A is fetched once, before the loop (no HBM stream in); 3 = nothing is stored.
-template <int ABLATE>
+//
+// EPI 1: the drain does not store C = dy but the RMSNorm backward of it (csrc/fused.hip: rmsnorm_bwd_kernel), per row t
+//   z = x[t] / rms[t],  dz = dy w,  dx[t] = (dz - z mean(z dz)) / rms[t] (+ held gradient),  dw += dy z
+// A row's 288 columns lie in the four lanes lane & 15, + 16, + 32, + 48.  Pass A forms dy tile by tile, reads x once (as
+// the residual is requested in epilogue 0), adds up the row's dot product and the weight-gradient sums, and leaves dz and z
+// IN THE TWO ACCUMULATOR SETS of the element, which are zeroed behind the drain anyway; pass B forms dx from them, so x is
+// read once and dy never leaves the registers.  dw: a tile's float4 summed over the wave's sixteen rows, the r == 0 lanes
+// add it into a row of LDS private to the wave, the eight rows are added in a fixed order into dwpart[workgroup] at the
+// end (no atomics; csrc/fused.hip's colsum_partials_kernel sums the workgroups).
+template <int ABLATE, int EPI = 0>
 __global__ __launch_bounds__(512, 1) void ors_main_kernel(OrsParams p) {
   __shared__ __attribute__((aligned(1024))) char smem[ORS_LDS];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -173,6 +202,12 @@ __global__ __launch_bounds__(512, 1) void ors_main_kernel(OrsParams p) {
   __shared__ __attribute__((aligned(16))) int col_sh[ORS_N];
   __shared__ __attribute__((aligned(16))) float col_bias[ORS_N];
   if (tid < ORS_N) { col_sh[tid] = p.wsh[tid]; col_bias[tid] = p.bias ? p.bias[tid] : -0.f; }
+  // EPI 1: [the norm's 288 weights | eight rows of weight-gradient sums]; read behind the same barriers
+  __shared__ __attribute__((aligned(16))) float norm_sh[EPI == 1 ? ORS_NORM_FLOATS : 1];
+  if constexpr (EPI == 1) {
+    if (tid < ORS_N) norm_sh[tid] = p.nw[tid];
+    for (int i = tid; i < ORS_DW_FLOATS; i += 512) norm_sh[ORS_N + i] = 0.f;
+  }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
   // W: the image of piece `piece` into slot `slot`, five instructions per wave
@@ -316,12 +351,120 @@ __global__ __launch_bounds__(512, 1) void ors_main_kernel(OrsParams p) {
     }
 
     // ---- the block's rows: the lane's row, columns 16 j + 4 q .. + 3 of tile j -------------------------------------------
-    const int64_t row = (int64_t)blk * ORS_WG_ROWS + wave * 16 + r;
+    const int64_t row = ors_lane_row(blk, wave, r);
     // The exponents and the bias come out of LDS (col_sh / col_bias), so the only memory operations of the drain are the
     // residual loads and the stores, and no load sits between two stores: a wait for a load would also wait for every store
     // issued before it (both count in vmcnt, in order), which made each of the 18 tiles two or three memory round trips.
     // The residual is requested ORS_DRAIN tiles at a time, one group ahead of the group being stored.
-    if ((ABLATE != 3 || p.M < 0) && row < p.M) {
+    if constexpr (EPI == 1) {
+      // Every lane walks pass A (the sums over the wave's rows need all 64, and a branch per load costs registers); a row
+      // >= M reads the last row like ors_a_row, adds zeros to dw and stores nothing.
+      const bool valid = row < p.M;
+      const int64_t rowc = ors_min_l(row, p.M - 1);
+      // (opaque: taken apart, its loop-invariant part 4 q would be added to every base pointer ahead of the stream of pieces
+      // and stay in registers through it)
+      int64_t ro = rowc * p.ldc + ors_out_col(0, q);
+      asm volatile("" : "+v"(ro));
+      auto dy_of = [&](int j) __attribute__((always_inline)) {
+        const int4 sv = *reinterpret_cast<const int4*>(__builtin_assume_aligned(col_sh + ors_out_col(j, q), 16));
+        float4 o;
+        o.x = stn_unscale(acc1[j][0], acc0[j][0], S + sv.x);
+        o.y = stn_unscale(acc1[j][1], acc0[j][1], S + sv.y);
+        o.z = stn_unscale(acc1[j][2], acc0[j][2], S + sv.z);
+        o.w = stn_unscale(acc1[j][3], acc0[j][3], S + sv.w);
+        return o;
+      };
+      const float* xs = p.nx + ro;
+      // tile j of the lane: columns ors_out_col(j, q) .. + 3, `cj` floats behind tile 0's, which `ro` holds
+      auto cj = [&](int j) __attribute__((always_inline)) { return ors_out_col(j, q) - ors_out_col(0, q); };
+      auto x_of = [&](int j) __attribute__((always_inline)) { return *reinterpret_cast<const float4*>(xs + cj(j)); };
+      float4 rq[2][ORS_NDRAIN];
+#pragma unroll
+      for (int i = 0; i < ORS_NDRAIN; ++i) rq[0][i] = x_of(i);
+      const float rinv = 1.0f / p.nrms[rowc];
+      const bool want_dw = p.dwpart != nullptr;
+      int dwo = ORS_N + ors_dw_lds(wave, ors_out_col(0, q));
+      asm volatile("" : "+v"(dwo));
+      float* dwrow = norm_sh + dwo;
+      float dot = 0.f;
+      // ---- pass A
+#pragma unroll
+      for (int g = 0; g < ORS_NT / ORS_NDRAIN; ++g) {
+        if (g + 1 < ORS_NT / ORS_NDRAIN) {
+#pragma unroll
+          for (int i = 0; i < ORS_NDRAIN; ++i) rq[(g + 1) & 1][i] = x_of((g + 1) * ORS_NDRAIN + i);
+        }
+#pragma unroll
+        for (int i = 0; i < ORS_NDRAIN; ++i) {
+          const int j = g * ORS_NDRAIN + i;
+          const float4 dy = dy_of(j);
+          const float4 x4 = rq[g & 1][i];
+          const float4 w4 = *reinterpret_cast<const float4*>(__builtin_assume_aligned(norm_sh + ors_out_col(j, q), 16));
+          float4 z, dz;
+          z.x = x4.x * rinv; z.y = x4.y * rinv; z.z = x4.z * rinv; z.w = x4.w * rinv;
+          dz.x = dy.x * w4.x; dz.y = dy.y * w4.y; dz.z = dy.z * w4.z; dz.w = dy.w * w4.w;
+          // (pinned: left free, the compiler keeps dy and the tile's weights for pass B and forms dz there, twelve registers per
+          // tile in place of the accumulators' eight, and the kernel spills)
+          asm volatile("" : "+v"(dz.x), "+v"(dz.y), "+v"(dz.z), "+v"(dz.w));
+          dot += (z.x * dz.x + z.y * dz.y) + (z.z * dz.z + z.w * dz.w);
+          if (want_dw) {
+            float4 c;
+            c.x = ors_row16_sum(valid ? dy.x * z.x : 0.f);
+            c.y = ors_row16_sum(valid ? dy.y * z.y : 0.f);
+            c.z = ors_row16_sum(valid ? dy.z * z.z : 0.f);
+            c.w = ors_row16_sum(valid ? dy.w * z.w : 0.f);
+            if (r == 0) {
+              float4* d = reinterpret_cast<float4*>(__builtin_assume_aligned(dwrow + cj(j), 16));
+              float4 s = *d;
+              s.x += c.x; s.y += c.y; s.z += c.z; s.w += c.w;
+              *d = s;
+            }
+          }
+          acc0[j][0] = dz.x; acc0[j][1] = dz.y; acc0[j][2] = dz.z; acc0[j][3] = dz.w;
+          acc1[j][0] = z.x; acc1[j][1] = z.y; acc1[j][2] = z.z; acc1[j][3] = z.w;
+          __builtin_amdgcn_sched_barrier(0);        // a tile at a time
+        }
+      }
+      dot += __shfl_xor(dot, 16, 64);               // the same bits in the row's four lanes: both sides add the same two
+      dot += __shfl_xor(dot, 32, 64);
+      dot = dot / (float)ORS_N;
+      // ---- pass B: dx out of the accumulators; the held gradient is requested one group ahead of the group being stored
+      // (the rule of the residual loop below)
+      if (valid) {
+        float* out = p.C + ro;
+        auto dx_of = [&](int j) __attribute__((always_inline)) {
+          float4 o;
+          o.x = (acc0[j][0] - acc1[j][0] * dot) * rinv;
+          o.y = (acc0[j][1] - acc1[j][1] * dot) * rinv;
+          o.z = (acc0[j][2] - acc1[j][2] * dot) * rinv;
+          o.w = (acc0[j][3] - acc1[j][3] * dot) * rinv;
+          return o;
+        };
+        if (p.nex) {
+          const float* res = p.nex + ro;
+#pragma unroll
+          for (int i = 0; i < ORS_NDRAIN; ++i) rq[0][i] = *reinterpret_cast<const float4*>(res + cj(i));
+#pragma unroll
+          for (int g = 0; g < ORS_NT / ORS_NDRAIN; ++g) {
+            if (g + 1 < ORS_NT / ORS_NDRAIN) {
+#pragma unroll
+              for (int i = 0; i < ORS_NDRAIN; ++i) rq[(g + 1) & 1][i] = *reinterpret_cast<const float4*>(res + cj((g + 1) * ORS_NDRAIN + i));
+            }
+#pragma unroll
+            for (int i = 0; i < ORS_NDRAIN; ++i) {
+              const int j = g * ORS_NDRAIN + i;
+              float4 o = dx_of(j);
+              const float4 r4 = rq[g & 1][i];
+              o.x += r4.x; o.y += r4.y; o.z += r4.z; o.w += r4.w;
+              *reinterpret_cast<float4*>(out + cj(j)) = o;
+            }
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < ORS_NT; ++j) *reinterpret_cast<float4*>(out + cj(j)) = dx_of(j);
+        }
+      }
+    } else if ((ABLATE != 3 || p.M < 0) && row < p.M) {
       float* out = p.C + row * p.ldc + 4 * q;
       auto tile_out = [&](int j) __attribute__((always_inline)) {
         const int4 sv = *reinterpret_cast<const int4*>(__builtin_assume_aligned(col_sh + 16 * j + 4 * q, 16));
@@ -372,6 +515,18 @@ __global__ __launch_bounds__(512, 1) void ors_main_kernel(OrsParams p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) { acc0[j][i] = 0.f; acc1[j][i] = 0.f; }
   }
+  // EPI 1: the eight waves' weight-gradient sums, added in a fixed order, are this workgroup's partial row
+  if constexpr (EPI == 1) {
+    if (p.dwpart) {
+      __syncthreads();
+      if (tid < ORS_N) {
+        const float* s = norm_sh + ORS_N + tid;
+        p.dwpart[(int64_t)blockIdx.x * ORS_N + tid] =
+            ((s[ors_dw_lds(0, 0)] + s[ors_dw_lds(1, 0)]) + (s[ors_dw_lds(2, 0)] + s[ors_dw_lds(3, 0)])) +
+            ((s[ors_dw_lds(4, 0)] + s[ors_dw_lds(5, 0)]) + (s[ors_dw_lds(6, 0)] + s[ors_dw_lds(7, 0)]));
+      }
+    }
+  }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
@@ -413,9 +568,16 @@ int pdn_outres_split_takes(const float* A, const float* B, const float* C, const
   return cs == hipStreamCaptureStatusNone ? 1 : 0;
 }
 
-int pdn_outres_split_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int K,
-                            int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, void* stream,
-                            int count_slot) {
+// `norm` (epilogue 1, csrc/normgrad.hip): the RMSNorm backward of the product in the drain; C is then dx
+namespace {
+struct OrsNorm {
+  const float *x, *w, *rms, *ex;
+  float* dwpart;                  // ors_grid(M) x 288 floats, or null
+};
+}
+static int ors_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int K,
+                      int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, void* stream,
+                      int count_slot, const OrsNorm* norm) {
   // both read on every call like PDN_OUTRES_SPLIT (tools/outres_split_probe.py alternates them in one process), the
   // ablation announced the first time it is seen
   const char* ea = getenv("PDN_OUTRES_SPLIT_ABLATE");
@@ -456,9 +618,31 @@ int pdn_outres_split_launch(const float* A, const float* B, float* C, const floa
   if (env_wgs == 0) wgs = p.nblk;
   else if (env_wgs > 0) wgs = ors_min_i(env_wgs, p.nblk);
   const dim3 grid((unsigned)wgs);
-  if (ablate == 3) hipLaunchKernelGGL(ors_main_kernel<3>, grid, dim3(512), 0, st, p);
+  if (norm) {
+    // the partial rows of dw are one per workgroup of ors_grid(M): neither the grid switch nor the ablations apply
+    p.nx = norm->x; p.nw = norm->w; p.nrms = norm->rms; p.nex = norm->ex; p.dwpart = norm->dwpart;
+    hipLaunchKernelGGL((ors_main_kernel<0, 1>), dim3((unsigned)ors_grid(M)), dim3(512), 0, st, p);
+  } else if (ablate == 3) hipLaunchKernelGGL(ors_main_kernel<3>, grid, dim3(512), 0, st, p);
   else STN_LAUNCH_ABLATE(ors_main_kernel, ablate, grid, stream, p);
   pdn_count(count_slot);            // 46 behind outres_launch, 47 for the 288 x 288 products of pdn_gemm_f32
   PDN_LAUNCH_CHECK();
   return PDN_OK;
+}
+
+int pdn_outres_split_launch(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int K,
+                            int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int kb, int64_t b_bstride, void* stream,
+                            int count_slot) {
+  return ors_launch(A, B, C, bias, residual, M, K, lda, ldb, ldc, b_trans, kb, b_bstride, stream, count_slot, nullptr);
+}
+
+int pdn_outres_split_norm_bwd_partial_rows(int M) { return ors_grid(M); }
+
+// dx = rmsnorm_bwd([d_1 | ... | d_nb] [W_1 | ... | W_nb]^T) (+ ex) in one launch of the product; dwpart (nullable) receives
+// pdn_outres_split_norm_bwd_partial_rows(M) rows of 288 partial sums of dw.  The caller has asked pdn_outres_split_takes.
+int pdn_outres_split_norm_bwd_launch(const float* A, const float* W, int64_t b_bstride, int kb, int nb, const float* x,
+                                     const float* w, const float* rms, const float* ex, float* dx, float* dwpart, int M,
+                                     int64_t lda, void* stream) {
+  const OrsNorm norm = {x, w, rms, ex, dwpart};
+  return ors_launch(A, W, dx, nullptr, nullptr, M, kb * nb, lda, kb, ORS_N, 1, kb, b_bstride, stream, PDN_CNT_OUTRES_SPLIT,
+                    &norm);
 }

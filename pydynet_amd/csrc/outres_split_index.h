@@ -30,6 +30,7 @@
 #define ORS_LDS (ORS_RING0 + 8 * ORS_RING * ORS_RAW)     // 136 KiB (the kernel adds 2 x 1152 bytes: column exponents and bias)
 #define ORS_IMG_WGS ((ORS_N * 4 + 255) / 256) // workgroups of 256 threads per piece in the image pass: one unit per thread
 #define ORS_DRAIN 6                         // tiles of the residual requested at a time by the drain (18 = 3 groups)
+#define ORS_NDRAIN 3                         // tiles of x requested at a time by pass A of the RMSNorm-backward drain (six groups)
 #define ORS_MAX_WGS 256                      // one workgroup per CU
 #define ORS_MIN_ROWS 65536
 #define ORS_MIN_K 256                        // eight pieces: more than the ring holds, so a fetch is never two blocks ahead
@@ -80,6 +81,16 @@ ORS_HD bool ors_ahead_next(int s, int np) { return s + ORS_RING >= np; }
 
 // ---- C: lane (r, q) stores columns 16 j + 4 q .. + 3 of row r for tile j ---------------------------------------------------
 ORS_HD int ors_out_col(int j, int q) { return 16 * j + 4 * q; }
+
+// ---- the RMSNorm-backward drain (epilogue 1): lane (r, q) of wave w owns row ors_lane_row(blk, w, r) and, for tile j, its
+// columns ors_out_col(j, q) .. + 3, of x, of the held gradient and of dx alike; a row >= M reads x and rms of the last row
+// (ors_min_l(row, M - 1), as ors_a_row does for A), adds zeros to the weight-gradient sums and stores nothing.
+// The weight-gradient sums of a wave's sixteen rows go into a row of LDS private to the wave, float ors_dw_lds(w, col)
+// of ORS_DW_FLOATS (behind the 288 norm weights in the same array); the r == 0 lanes add there, columns ors_out_col(j, q).
+#define ORS_DW_FLOATS (8 * ORS_N)
+#define ORS_NORM_FLOATS (ORS_N + ORS_DW_FLOATS)   // the epilogue's LDS: [288 weights | 8 waves x 288 sums]
+ORS_HD int64_t ors_lane_row(int blk, int wave, int r) { return (int64_t)blk * ORS_WG_ROWS + wave * 16 + r; }
+ORS_HD int ors_dw_lds(int wave, int col) { return wave * ORS_N + col; }
 
 // ---- the running exponent of a row --------------------------------------------------------------------------------------
 #define ORS_UNSET (1 << 20)                  // no finite non-zero value seen yet: every maximum moves it
