@@ -177,6 +177,23 @@ class DeferredInputGrad:
         return self._array
 
 
+def _norm_dw_blocks(hp, L, norm, dcat, gstack, T, nb_cols, nb):
+    """gstack[b] += rmsnorm(x)^T dcat[:, b * nb_cols:(b + 1) * nb_cols] from norm = (x, rms, w): the normalised rows were
+    never written (`pdnp_norm_dw_blocks_f32`, include/pdn_normplanes.h)."""
+    raw, rms, wn, eps = norm
+    ws, wsb = hp.workspace(L.query("pdnp_norm_dw_blocks_workspace_bytes", T, nb_cols, nb))
+    L.call("pdnp_norm_dw_blocks_f32", raw._ptr, wn._ptr, rms._ptr, dcat._ptr, dcat._strides[0], gstack._ptr, gstack._strides[0],
+           1.0, T, nb_cols, nb, ws, wsb, hp.stream())
+
+
+def _xn_of(hp, L, norm, T, cols):
+    """The normalised rows after all (a consumer that has no entry working from (x, rms, w)): the norm's own kernel."""
+    raw, rms, wn, eps = norm
+    xn = hp.empty((T, cols), np.float32)
+    L.call("pdn_rmsnorm_fwd_f32", raw._ptr, wn._ptr, xn._ptr, None, T, cols, eps, hp.stream())
+    return xn
+
+
 def _materialised(g):
     return g.materialise() if isinstance(g, DeferredInputGrad) else g
 

@@ -11,7 +11,8 @@ import numpy as np
 from . import segments as _seg
 from .norm import rms_norm
 from ..tensor import Tensor, _Operator
-from ._common import _hip, _L, _contig, _require_f32, _beside, _is_leaf_f32, _dx_of_shared_input
+from ._common import (_hip, _L, _contig, _require_f32, _beside, _is_leaf_f32, _dx_of_shared_input, _provides, _norm_dw_blocks,
+                      _xn_of)
 
 
 def _attn_layout(x):
@@ -334,6 +335,13 @@ class qkv_attention(_Operator):
     rope_epilogue = os.environ.get("PDN_NO_ROPE_EPILOGUE", "0") != "1"   # RoPE in the store of the q | k | v projection
     rope_min_rows = 4096
     prerotate = os.environ.get("PDN_NO_PREROTATE", "0") != "1"           # (same-box A/B switch)
+    # Round 17: a folded norm's output is not written; the weight gradient forms it from (x, rms, w) (include/pdn_normplanes.h)
+    norm_planes = os.environ.get("PDN_NO_NORM_PLANES", "0") != "1"       # (same-box A/B switch)
+    # ... from 65536 rows, where it was measured (a step at 65536 and at 131072 rows).  The entries take 16384 / 32768 rows, but
+    # the column maxima they save shrink with the rows (35 us at 131072, about 9 at 32768: not told from noise in a step), and
+    # below this the weight gradient stays a pdn_gemm_f32 call, whose workspace is the in-process switch between the split
+    # and the fp32 kernel (include/pdn_hip.h)
+    norm_planes_min_rows = 65536
     _rope_tables = {}       # (cos ptr, sin ptr, L, hd) -> expanded (L, hd, 2) table for the projection's epilogue
 
     @staticmethod
@@ -394,15 +402,25 @@ class qkv_attention(_Operator):
         # a still-deferred RMSNorm in front (fused.rms_norm): its rows are normalised in this projection's A load
         self.norm_folded = bool(self.rotated and isinstance(x, rms_norm) and x._pending is not None
                                 and L.query("pdn_qkv_rope_norm_supported", T, D, D, Lq, hd))
+        self._norm = None
         if self.norm_folded:
             raw_t, wn = x._pending
             raw = _contig(raw_t.data)
-            xn, rms = hp.empty(x.shape, np.float32), hp.empty((T,), np.float32)
+            rms = hp.empty((T,), np.float32)
             tab = self._rope_table(cos, sin, Lq, hd)
-            L.call("pdn_qkv_rope_norm_fwd_f32", raw._ptr, _contig(wn.data)._ptr, x.eps, xn._ptr, rms._ptr, ws[0]._ptr,
-                   (ws[1]._ptr - ws[0]._ptr) // 4, qkv._ptr, tab._ptr, T, D, D, Lq, hd, D, hp.stream())
-            x._adopt(raw, rms, xn)
-        x2 = _contig(x.data).reshape(T, D)
+            if (qkv_attention.norm_planes and T >= qkv_attention.norm_planes_min_rows and _provides("pdnp_norm_dw_blocks_f32") and hp.capturing() is None
+                    and L.query("pdnp_qkv_rope_norm_supported", T, D, D, Lq, hd)):
+                wnd = _contig(wn.data)
+                L.call("pdnp_qkv_rope_norm_fwd_f32", raw._ptr, wnd._ptr, x.eps, rms._ptr, ws[0]._ptr,
+                       (ws[1]._ptr - ws[0]._ptr) // 4, qkv._ptr, tab._ptr, T, D, D, Lq, hd, D, hp.stream())
+                x._adopt_stats(raw, rms)
+                self._norm = (raw, rms, wnd, x.eps)
+            else:
+                xn = hp.empty(x.shape, np.float32)
+                L.call("pdn_qkv_rope_norm_fwd_f32", raw._ptr, _contig(wn.data)._ptr, x.eps, xn._ptr, rms._ptr, ws[0]._ptr,
+                       (ws[1]._ptr - ws[0]._ptr) // 4, qkv._ptr, tab._ptr, T, D, D, Lq, hd, D, hp.stream())
+                x._adopt(raw, rms, xn)
+        x2 = _contig(x.data).reshape(T, D) if self._norm is None else None
         if self.norm_folded:
             pass
         elif self.rotated:
@@ -485,9 +503,13 @@ class qkv_attention(_Operator):
         dws = [hp.empty(w.shape, np.float32) if gstack is None and w.requires_grad and not _is_leaf_f32(w) else None
                for w in weights]
         with side or contextlib.nullcontext():
-            if gstack is not None:
+            if gstack is not None and self._norm is not None:
+                _norm_dw_blocks(hp, L, self._norm, dqkv, gstack, T, D, 3)
+            elif gstack is not None:
                 hp.gemm(x2.T, dblocks, gstack, beta=1.0)              # three x^T @ d_i in one launch
             else:
+                if x2 is None:              # (unstacked / non-leaf weights: rare, the normalised rows are written after all)
+                    x2 = _xn_of(hp, L, self._norm, T, D)
                 for i, w in enumerate(weights):
                     if not w.requires_grad:
                         continue

@@ -9,7 +9,8 @@ import numpy as np
 
 from .norm import rms_norm
 from ..tensor import _Operator
-from ._common import (_hip, _L, _contig, _require_f32, _foldable, _beside, _is_leaf_f32, _pack_columns, _dx_of_shared_input)
+from ._common import (_hip, _L, _contig, _require_f32, _foldable, _beside, _is_leaf_f32, _pack_columns, _dx_of_shared_input,
+                      _provides, _norm_dw_blocks, _xn_of)
 
 
 class gate_up_swiglu(_Operator):
@@ -110,6 +111,13 @@ class ffn_swiglu(_Operator):
     enabled = os.environ.get("PDN_NO_FFN_NODE", "0") != "1"            # (same-box A/B switches)
     epilogues = os.environ.get("PDN_NO_SWIGLU_EPILOGUE", "0") != "1"
     epilogue_min_rows = 4096         # below this the projections are launch-sized: the separate kernels are as good
+    # Round 17: a folded norm's output is not written; the weight gradient forms it from (x, rms, w) (include/pdn_normplanes.h)
+    norm_planes = os.environ.get("PDN_NO_NORM_PLANES", "0") != "1"       # (same-box A/B switch)
+    # ... from 65536 rows, where it was measured (a step at 65536 and at 131072 rows).  The entries take 16384 / 32768 rows, but
+    # the column maxima they save shrink with the rows (35 us at 131072, about 9 at 32768: not told from noise in a step), and
+    # below this the weight gradient stays a pdn_gemm_f32 call, whose workspace is the in-process switch between the split
+    # and the fp32 kernel (include/pdn_hip.h)
+    norm_planes_min_rows = 65536
 
     @staticmethod
     def applicable(x, wg, wu, wd):
@@ -144,14 +152,24 @@ class ffn_swiglu(_Operator):
         # a still-deferred RMSNorm in front (fused.rms_norm): its rows are normalised in the gate | up projection's A load
         self.norm_folded = bool(self.used_epilogue and isinstance(x, rms_norm) and x._pending is not None
                                 and L.query("pdn_gateup_swiglu_norm_supported", T, F, fin))
+        self._norm = None
         if self.norm_folded:
             raw_t, wn = x._pending
             raw = _contig(raw_t.data)
-            xn, rms = hp.empty(x.shape, np.float32), hp.empty((T,), np.float32)
-            L.call("pdn_gateup_swiglu_norm_fwd_f32", raw._ptr, _contig(wn.data)._ptr, x.eps, xn._ptr, rms._ptr, ws[0]._ptr,
-                   (ws[1]._ptr - ws[0]._ptr) // 4, gu._ptr, h._ptr, T, F, fin, fin, hp.stream())
-            x._adopt(raw, rms, xn)
-        x2 = _contig(x.data).reshape(-1, fin)
+            rms = hp.empty((T,), np.float32)
+            if (ffn_swiglu.norm_planes and T >= ffn_swiglu.norm_planes_min_rows and _provides("pdnp_norm_dw_blocks_f32") and hp.capturing() is None
+                    and L.query("pdnp_gateup_swiglu_norm_supported", T, F, fin)):
+                wnd = _contig(wn.data)
+                L.call("pdnp_gateup_swiglu_norm_fwd_f32", raw._ptr, wnd._ptr, x.eps, rms._ptr, ws[0]._ptr,
+                       (ws[1]._ptr - ws[0]._ptr) // 4, gu._ptr, h._ptr, T, F, fin, fin, hp.stream())
+                x._adopt_stats(raw, rms)
+                self._norm = (raw, rms, wnd, x.eps)
+            else:
+                xn = hp.empty(x.shape, np.float32)
+                L.call("pdn_gateup_swiglu_norm_fwd_f32", raw._ptr, _contig(wn.data)._ptr, x.eps, xn._ptr, rms._ptr, ws[0]._ptr,
+                       (ws[1]._ptr - ws[0]._ptr) // 4, gu._ptr, h._ptr, T, F, fin, fin, hp.stream())
+                x._adopt(raw, rms, xn)
+        x2 = _contig(x.data).reshape(-1, fin) if self._norm is None else None
         if self.norm_folded:
             pass
         elif self.used_epilogue:
@@ -180,7 +198,7 @@ class ffn_swiglu(_Operator):
         x, wg, wu, wd = self.last[:4]
         fin, F = wg.shape
         x2, gu, h = self._saved
-        T = x2.shape[0]
+        T = h.shape[0]
         grads = [None] * len(self.last)
         if self.has_res and self.last[4].requires_grad:
             grads[4] = g
@@ -210,9 +228,13 @@ class ffn_swiglu(_Operator):
         gstack = None
         if all(w.requires_grad and _is_leaf_f32(w) for w in weights):
             gstack = hp.stacked_view([w.grad for w in weights])
-        if gstack is not None:
+        if gstack is not None and self._norm is not None:
+            _norm_dw_blocks(hp, L, self._norm, dgu, gstack, T, F, 2)
+        elif gstack is not None:
             hp.gemm(x2.T, dhalves, gstack, beta=1.0)
         else:
+            if x2 is None:                  # (unstacked / non-leaf weights: rare, the normalised rows are written after all)
+                x2 = _xn_of(hp, L, self._norm, T, fin)
             for i, w in enumerate(weights):
                 if not w.requires_grad:
                     continue

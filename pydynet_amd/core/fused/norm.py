@@ -18,7 +18,9 @@ class rms_norm(_Deferred, _Operator):
     Round 5: on the HIP device, at the model width the row-resident projection kernels hold in registers (288) and with
     enough rows for them, the node is DEFERRED (`_Deferred`): a `qkv_attention` / `ffn_swiglu` node that consumes it
     normalises the rows inside its projection's A load (`pdn_*_norm_fwd_f32`) and hands this node its output and the rows'
-    rms (`_adopt`); any other consumer reads `.data`, which runs the node's own kernel then.  Backward is unchanged."""
+    rms (`_adopt`); any other consumer reads `.data`, which runs the node's own kernel then.  Backward is unchanged.
+    Round 17: from 65536 rows (`norm_planes_min_rows` of the consumer) the consumer's kernel does not write the output at
+    all and hands over the rms alone (`_adopt_stats`); its weight gradient forms the normalised rows from (x, rms, w) on the way into its operand planes."""
 
     folds_existing = True
     fold = os.environ.get("PDN_NO_NORM_FOLD", "0") != "1"        # (same-box A/B switch)
@@ -43,6 +45,15 @@ class rms_norm(_Deferred, _Operator):
         self._x, self._rms = raw, rms
         self.data = out                     # (no longer pending: an ordinary node from here on)
 
+    def _adopt_stats(self, raw, rms):
+        """Round 17: the consumer's kernel normalised the rows but did NOT write them (`pdnp_*_norm_fwd_f32`); it and this
+        node's backward work from `raw`, `rms` and the weight.  The node stays pending: any other reader of `.data` runs the
+        node's own kernel then, which leaves the adopted `_x` / `_rms` alone (`forward_`)."""
+        self._x, self._rms = raw, rms
+        self._stats_adopted = True
+
+    _stats_adopted = False
+
     def forward_(self, x, w):
         if self.xp is np:
             self._rms = np.sqrt((x.data * x.data).mean(-1, keepdims=True) + np.asarray(self.eps, x.dtype))
@@ -50,12 +61,13 @@ class rms_norm(_Deferred, _Operator):
         _require_f32(self, x, w)
         hp, L = _hip(), _L()
         cols = x.shape[-1]
-        self._x = _contig(x.data)
-        rows = self._x.size // cols
+        xc = _contig(x.data)
+        rows = xc.size // cols
         out = hp.empty(x.shape, np.float32)
-        self._rms = hp.empty((rows,), np.float32)
-        L.call("pdn_rmsnorm_fwd_f32", self._x._ptr, w.data._ptr, out._ptr, self._rms._ptr, rows, cols,
-               self.eps, hp.stream())
+        rms = hp.empty((rows,), np.float32)
+        L.call("pdn_rmsnorm_fwd_f32", xc._ptr, w.data._ptr, out._ptr, rms._ptr, rows, cols, self.eps, hp.stream())
+        if not self._stats_adopted:         # (adopted: backward keeps the statistics the consumer's projection used)
+            self._x, self._rms = xc, rms
         return out
 
     def backward_all(self, g):

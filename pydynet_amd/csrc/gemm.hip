@@ -187,6 +187,10 @@ struct GemmCall {
   int64_t ws_bytes, ws_floats;   // its capacity: 0 without a workspace
   void* stream;
   hipStream_t st;
+  // pdn_gemm_outres_tn_blocks_norm (csrc/normplanes.hip): A^T holds the rows BEFORE an RMSNorm with this weight and these
+  // row statistics, and the operand is the norm's output, which exists nowhere.  Only route 7's split-fp16 form takes it.
+  const float* norm_w = nullptr;
+  const float* norm_rms = nullptr;
 };
 // what a route returns when the call is not its own: the next route is tried
 constexpr int kNotTaken = -0x7fffffff - 1;
@@ -373,6 +377,7 @@ static int route_outres_tn_blocks(GemmCall& c) {
   const int64_t xoff = (((int64_t)64 * M * n_all * 4 + 255) & ~(int64_t)255);
   const bool split16 = pdn_outres_tn_split_supported(M, N, nbatch, K) && pdn_outres_tn_split_enabled() && c.workspace &&
                        c.workspace_bytes >= xoff + pdn_outres_tn_split_extra_bytes(K) && al16(c.workspace);
+  if (c.norm_w && !split16) return kNotTaken;        // (no fp32 kernel forms the norm: the caller materialises its output)
   if (split16) {
     kps = ((K / 32 + pdn_outres_tn_split_ranges((int)n_all, K, splits) - 1) / pdn_outres_tn_split_ranges((int)n_all, K, splits)) * 32;
     splits = (K + kps - 1) / kps;
@@ -382,7 +387,9 @@ static int route_outres_tn_blocks(GemmCall& c) {
   if (getenv("PDN_GEMM_DEBUG"))
     fprintf(stderr, "pdn_gemm_f32 M=%d N=%lld K=%d -> output-resident TN%s (%d blocks, splits %d)\n", M,
             (long long)n_all, K, split16 ? ", split-fp16" : "", nbatch, splits);
-  const int rc = split16 ? pdn_outres_tn_split_launch(p.A, p.B, (float*)c.workspace, (int)n_all, K, p.a_cs, p.b_rs, N, kps,
+  const int rc = c.norm_w ? pdn_outres_tn_split_norm_launch(p.A, c.norm_w, c.norm_rms, p.B, (float*)c.workspace, (int)n_all, K,
+                                                            p.a_cs, p.b_rs, N, kps, (char*)c.workspace + xoff, c.stream)
+                 : split16 ? pdn_outres_tn_split_launch(p.A, p.B, (float*)c.workspace, (int)n_all, K, p.a_cs, p.b_rs, N, kps,
                                                       (char*)c.workspace + xoff, c.stream)
                          : pdn_gemm_outres_tn_blocks_launch(p.A, p.B, (float*)c.workspace, (int)n_all, K, p.a_cs, p.b_rs, N, nw, kps,
                                                             c.stream);
@@ -499,7 +506,7 @@ static int gemm_f32_impl(int M, int N, int K, float alpha, const float* A, int64
                          int64_t c_bs1, int64_t c_bs2, const float* residual,
                          float* b_colsum, int colsum_accumulate, void* workspace,
                          int64_t workspace_bytes, void* stream, uint32_t* relu_mask, const uint32_t* grad_mask,
-                         float* mask_colsum = nullptr) {
+                         float* mask_colsum = nullptr, const float* norm_w = nullptr, const float* norm_rms = nullptr) {
   const bool ext_on = relu_mask || grad_mask;
   PDN_CHECK_ARG(!ext_on || (nb1 == 1 && nb2 == 1 && N % 32 == 0 && !b_colsum),
                 "pdn_gemm_f32: the mask epilogues need one batch and N a multiple of 32 (N = %d)", N);
@@ -509,6 +516,7 @@ static int gemm_f32_impl(int M, int N, int K, float alpha, const float* A, int64
   PDN_CHECK_ARG(ldc >= N, "pdn_gemm_f32: ldc (%lld) < N (%d)", (long long)ldc, N);
 
   GemmCall c;
+  c.norm_w = norm_w; c.norm_rms = norm_rms;
   GemmParams& p = c.p;
   p.A = A; p.B = B; p.C = C; p.bias = bias; p.ws = (float*)workspace;
   p.residual = residual; p.colsum = b_colsum; p.colsum_acc = colsum_accumulate;
@@ -538,6 +546,7 @@ static int gemm_f32_impl(int M, int N, int K, float alpha, const float* A, int64
   }
   // the routes in their order: the first that takes the call launches it
   int rc;
+  if (c.norm_w) return route_outres_tn_blocks(c);
   if ((rc = route_skinny(c)) != kNotTaken) return rc;
   if ((rc = route_narrow(c)) != kNotTaken) return rc;
   if ((rc = route_outres(c)) != kNotTaken) return rc;
@@ -558,6 +567,17 @@ extern "C" int pdn_gemm_f32(int M, int N, int K, float alpha, const float* A, in
                             int64_t workspace_bytes, void* stream) {
   return gemm_f32_impl(M, N, K, alpha, A, a_rs, a_cs, B, b_rs, b_cs, beta, C, ldc, bias, nb1, nb2, a_bs1, a_bs2, b_bs1, b_bs2,
                        c_bs1, c_bs2, residual, b_colsum, colsum_accumulate, workspace, workspace_bytes, stream, nullptr, nullptr);
+}
+
+// dW_b (288 x nb_cols, rows ldc apart, blocks c_bs apart) = beta dW_b + xn^T G_b over the nb column blocks of G (K x nb *
+// nb_cols, rows ldg apart), xn = x * (1 / rms) * norm_w never written: route 7 alone, with its bracket, counters and slab
+// reduce.  PDN_NORMPLANES_NOT_TAKEN where its split-fp16 form does not take the call; the caller then forms xn itself.
+int pdn_gemm_outres_tn_blocks_norm(const float* x, const float* norm_w, const float* rms, const float* G, int64_t ldg, float* dW,
+                                   int64_t ldc, int64_t c_bs, float beta, int K, int nb_cols, int nb, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+  const int rc = gemm_f32_impl(288, nb_cols, K, 1.f, x, 1, 288, G, ldg, 1, beta, dW, ldc, nullptr, 1, nb, 0, 0, 0, nb_cols, 0, c_bs,
+                               nullptr, nullptr, 0, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, norm_w, rms);
+  return rc == kNotTaken ? PDN_NORMPLANES_NOT_TAKEN : rc;
 }
 
 // ======================================================================================

@@ -72,3 +72,11 @@ int pdn_gemm_rowres_blocks(const float* A, const float* B, float* C, int M, int 
                            int64_t ldc, int b_trans, int nblocks, int64_t b_block_stride, void* stream);
 // ---- csrc/gemm_rowtile.hip
 extern "C" int pdn_gemm_rowtile_mode(int mode);                 // a negative mode only asks
+
+// ---- csrc/gemm.hip: route 7 (the packed layer weight gradients) with the A operand given as the rows before an RMSNorm, its
+// weight and its row statistics, for csrc/normplanes.hip.  PDN_NORMPLANES_NOT_TAKEN: the split-fp16 form does not take the
+// call (shape, switch, workspace, alignment) and nothing was launched.
+#define PDN_NORMPLANES_NOT_TAKEN (-0x7fffffff)
+int pdn_gemm_outres_tn_blocks_norm(const float* x, const float* norm_w, const float* rms, const float* G, int64_t ldg, float* dW,
+                                   int64_t ldc, int64_t c_bs, float beta, int K, int nb_cols, int nb, void* workspace,
+                                   int64_t workspace_bytes, void* stream);

@@ -27,6 +27,7 @@
 #include "gemm_rowtile.h"
 #include "gemm_prof.h"
 #include "gemm_routes.h"
+#include "rowtile_split_index.h"   // RTS_MIN_ROWS: from where the split-fp16 projections run
 #include <stdlib.h>
 
 // Timing-ablation switches (tools/*_probe.py): read ONCE per process; a non-zero value makes kernels skip work and return
@@ -829,14 +830,13 @@ static int rowtile_would_take(int M, int N, int epi, int F) {
 extern "C" int pdn_gateup_swiglu_norm_supported(int M, int F, int K) {
   return (pdn_gateup_swiglu_supported(M, F, K) && rowtile_would_take(M, 2 * F, 1, F)) ? 1 : 0;
 }
-extern "C" int pdn_gateup_swiglu_norm_fwd_f32(const float* x, const float* norm_w, float eps, float* xn, float* rms,
-                                              const float* w_gate, int64_t w_stride, float* gu, float* h, int M, int F,
-                                              int K, int64_t ldx, void* stream) {
-  if (M == 0 || F == 0) return PDN_OK;
-  PDN_CHECK_ARG(x && norm_w && xn && rms && w_gate && gu && h, "pdn_gateup_swiglu_norm_fwd_f32: null operand");
+// (xn null: the entry of include/pdn_normplanes.h, which the split-fp16 kernel alone serves)
+static int gateup_norm_fwd(const char* name, const float* x, const float* norm_w, float eps, float* xn, float* rms,
+                           const float* w_gate, int64_t w_stride, float* gu, float* h, int M, int F, int K, int64_t ldx,
+                           void* stream) {
   const int64_t ws = w_stride < 0 ? -w_stride : w_stride;
   if (!pdn_gateup_swiglu_norm_supported(M, F, K) || ws % 4 != 0 || ws < (int64_t)K * F || ws + (int64_t)K * F >= (1ll << 30)) {
-    pdn_set_error("pdn_gateup_swiglu_norm_fwd_f32: unsupported shape M=%d F=%d K=%d", M, F, K);
+    pdn_set_error("%s: unsupported shape M=%d F=%d K=%d", name, M, F, K);
     return PDN_EUNSUPPORTED;
   }
   RowResEpi e{1, h, F, nullptr, F, nullptr, 1, 1, 0};
@@ -848,6 +848,29 @@ extern "C" int pdn_gateup_swiglu_norm_fwd_f32(const float* x, const float* norm_
   const int rc = rowres_launch(x, wbase, gu, nullptr, nullptr, M, 2 * F, K, ldx, F, 2 * F, 0, 2, ws, stream, &e);
   pdn_gemm_prof_end(tk, stream);
   return rc;
+}
+extern "C" int pdn_gateup_swiglu_norm_fwd_f32(const float* x, const float* norm_w, float eps, float* xn, float* rms,
+                                              const float* w_gate, int64_t w_stride, float* gu, float* h, int M, int F,
+                                              int K, int64_t ldx, void* stream) {
+  if (M == 0 || F == 0) return PDN_OK;
+  PDN_CHECK_ARG(x && norm_w && xn && rms && w_gate && gu && h, "pdn_gateup_swiglu_norm_fwd_f32: null operand");
+  return gateup_norm_fwd("pdn_gateup_swiglu_norm_fwd_f32", x, norm_w, eps, xn, rms, w_gate, w_stride, gu, h, M, F, K, ldx, stream);
+}
+// The same without xn (include/pdn_normplanes.h): where the split-fp16 kernel takes the launch, which alone can leave xn out
+static bool rowtile_split_open() { return pdn_rowtile_split_enabled() && pdn_gemm_rowtile_mode(-1) != 3; }
+extern "C" int pdnp_gateup_swiglu_norm_supported(int M, int F, int K) {
+  return (pdn_gateup_swiglu_norm_supported(M, F, K) && M >= RTS_MIN_ROWS && 2 * (int64_t)F < (1 << 24) && rowtile_split_open()) ? 1 : 0;
+}
+extern "C" int pdnp_gateup_swiglu_norm_fwd_f32(const float* x, const float* norm_w, float eps, float* rms, const float* w_gate,
+                                               int64_t w_stride, float* gu, float* h, int M, int F, int K, int64_t ldx,
+                                               void* stream) {
+  if (M == 0 || F == 0) return PDN_OK;
+  PDN_CHECK_ARG(x && norm_w && rms && w_gate && gu && h, "pdnp_gateup_swiglu_norm_fwd_f32: null operand");
+  if (!pdnp_gateup_swiglu_norm_supported(M, F, K)) {
+    pdn_set_error("pdnp_gateup_swiglu_norm_fwd_f32: unsupported shape M=%d F=%d K=%d, or the split-fp16 kernel is switched off", M, F, K);
+    return PDN_EUNSUPPORTED;
+  }
+  return gateup_norm_fwd("pdnp_gateup_swiglu_norm_fwd_f32", x, norm_w, eps, nullptr, rms, w_gate, w_stride, gu, h, M, F, K, ldx, stream);
 }
 // dgu (M x 2F) = SwiGLU'(gu) applied to dh = dy (M x 288) W_down^T, W_down (F x 288) row-major; dh is never written.
 extern "C" int pdn_swiglu_bwd_gemm_f32(const float* dy, const float* w_down, const float* gu, float* dgu, int M, int F, int K,
@@ -888,14 +911,11 @@ extern "C" int pdn_qkv_rope_fwd_f32(const float* x, const float* wq, int64_t w_s
 extern "C" int pdn_qkv_rope_norm_supported(int M, int D, int K, int L, int hd) {
   return (pdn_qkv_rope_supported(M, D, K, L, hd) && rowtile_would_take(M, 3 * D, 3, 0)) ? 1 : 0;
 }
-extern "C" int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, float* xn, float* rms, const float* wq,
-                                         int64_t w_stride, float* qkv, const float* rope, int M, int D, int K, int L, int hd,
-                                         int64_t ldx, void* stream) {
-  if (M == 0 || D == 0) return PDN_OK;
-  PDN_CHECK_ARG(x && norm_w && xn && rms && wq && qkv && rope && (((uintptr_t)rope & 7) == 0),
-                "pdn_qkv_rope_norm_fwd_f32: null / misaligned operand");
+static int qkv_norm_fwd(const char* name, const float* x, const float* norm_w, float eps, float* xn, float* rms, const float* wq,
+                        int64_t w_stride, float* qkv, const float* rope, int M, int D, int K, int L, int hd, int64_t ldx,
+                        void* stream) {
   if (!pdn_qkv_rope_norm_supported(M, D, K, L, hd) || w_stride % 4 != 0) {
-    pdn_set_error("pdn_qkv_rope_norm_fwd_f32: unsupported shape M=%d D=%d K=%d L=%d hd=%d", M, D, K, L, hd);
+    pdn_set_error("%s: unsupported shape M=%d D=%d K=%d L=%d hd=%d", name, M, D, K, L, hd);
     return PDN_EUNSUPPORTED;
   }
   RowResEpi e{3, nullptr, 0, nullptr, 0, rope, L, hd, 2 * D};
@@ -904,6 +924,31 @@ extern "C" int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, fl
   const int rc = rowres_launch(x, wq, qkv, nullptr, nullptr, M, 3 * D, K, ldx, D, 3 * D, 0, 3, w_stride, stream, &e);
   pdn_gemm_prof_end(tk, stream);
   return rc;
+}
+extern "C" int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, float* xn, float* rms, const float* wq,
+                                         int64_t w_stride, float* qkv, const float* rope, int M, int D, int K, int L, int hd,
+                                         int64_t ldx, void* stream) {
+  if (M == 0 || D == 0) return PDN_OK;
+  PDN_CHECK_ARG(x && norm_w && xn && rms && wq && qkv && rope && (((uintptr_t)rope & 7) == 0),
+                "pdn_qkv_rope_norm_fwd_f32: null / misaligned operand");
+  return qkv_norm_fwd("pdn_qkv_rope_norm_fwd_f32", x, norm_w, eps, xn, rms, wq, w_stride, qkv, rope, M, D, K, L, hd, ldx, stream);
+}
+// The same without xn (include/pdn_normplanes.h)
+extern "C" int pdnp_qkv_rope_norm_supported(int M, int D, int K, int L, int hd) {
+  return (pdn_qkv_rope_norm_supported(M, D, K, L, hd) && M >= RTS_MIN_ROWS && hd % 4 == 0 && (int64_t)L * hd < (1 << 27) &&
+          3 * (int64_t)D < (1 << 24) && rowtile_split_open()) ? 1 : 0;
+}
+extern "C" int pdnp_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, float* rms, const float* wq,
+                                          int64_t w_stride, float* qkv, const float* rope, int M, int D, int K, int L, int hd,
+                                          int64_t ldx, void* stream) {
+  if (M == 0 || D == 0) return PDN_OK;
+  PDN_CHECK_ARG(x && norm_w && rms && wq && qkv && rope && (((uintptr_t)rope & 7) == 0),
+                "pdnp_qkv_rope_norm_fwd_f32: null / misaligned operand");
+  if (!pdnp_qkv_rope_norm_supported(M, D, K, L, hd)) {
+    pdn_set_error("pdnp_qkv_rope_norm_fwd_f32: unsupported shape M=%d D=%d K=%d L=%d hd=%d, or the split-fp16 kernel is switched off", M, D, K, L, hd);
+    return PDN_EUNSUPPORTED;
+  }
+  return qkv_norm_fwd("pdnp_qkv_rope_norm_fwd_f32", x, norm_w, eps, nullptr, rms, wq, w_stride, qkv, rope, M, D, K, L, hd, ldx, stream);
 }
 
 // logits (M x V) = x (M x 288) W (288 x V) + bias and lse[m] = log sum_v exp(logits[m][v]) in ONE launch (EPI 4).

@@ -34,5 +34,7 @@ int pdn_rowtile_launch(const RowTileArgs& a, void* stream);
 // The split-fp16 form of epilogues 1, 2 and 3 for 16384 rows and more (csrc/rowtile_split.hip), which pdn_rowtile_launch
 // takes unless the mode is 3, PDN_ROWTILE_SPLIT is 0, the shape is not its own or the stream is being captured (it
 // allocates).  Epilogue 2 (b_trans, N = F, ldc >= 2F): F a multiple of 32, ldb >= 288, C apart from GU and A.
+// With norm_w, xn may be null HERE (not in the fp32 kernel): the rows' rms is still written, the normalised rows are not.
+int pdn_rowtile_split_enabled();
 int pdn_rowtile_split_takes(const RowTileArgs& a, void* stream);
 int pdn_rowtile_split_launch(const RowTileArgs& a, void* stream);

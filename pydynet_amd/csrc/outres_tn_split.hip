@@ -11,7 +11,8 @@
 // gemm_splitk_reduce_kernel launch of the caller combines (with beta).
 //
 //   x[:, d] 2^s(d) = xh + xl / 2048     three passes per call (csrc/split_tn_planes.hip): column maxima, exponents, 36 KiB
-//                                       plane images in LDS order
+//                                       plane images in LDS order; ONE pass where x is an RMSNorm output given as
+//                                       (rows, weight, rms): its exponents follow from the weight (stn_split_xn_kernel)
 //   g 2^S = gh + gl / 2048              formed in registers from raw fp32 g, which is read exactly ONCE by LDS-DMA into a
 //                                       swizzled ring of four pieces and read back transposed between the MFMAs
 //   dW 2^(S + s(d)) = xh gh + (xh gl + xl gh) / 2048
@@ -233,8 +234,9 @@ int pdn_outres_tn_split_ranges(int n_all, int K, int plan) { return ots_ranges(n
 
 // slabs as pdn_gemm_outres_tn_blocks_launch leaves them for `ranges` = ceil(K / k_per_split) K ranges: range s of block b at
 // C + (b * ranges + s) * 288 * nb_cols.  `extra`: stn_extra_bytes(K, OTS_XKIB) bytes, 16-byte aligned.
-int pdn_outres_tn_split_launch(const float* X, const float* G, float* C, int n_all, int K, int64_t ldx, int64_t ldg,
-                               int nb_cols, int k_per_split, void* extra, void* stream) {
+// (norm_w, rms) given: X holds the rows BEFORE an RMSNorm whose output is the operand (one plane launch instead of three)
+static int ots_launch(const float* X, const float* norm_w, const float* rms, const float* G, float* C, int n_all, int K,
+                      int64_t ldx, int64_t ldg, int nb_cols, int k_per_split, void* extra, void* stream) {
   PDN_CHECK_ARG(n_all % nb_cols == 0 && pdn_outres_tn_split_supported(STN_N, nb_cols, n_all / nb_cols, K) && k_per_split > 0 &&
                     k_per_split % STN_KP == 0 && ((((uintptr_t)X | (uintptr_t)G | (uintptr_t)extra | (uintptr_t)C) & 15) == 0) &&
                     (ldx & 3) == 0 && (ldg & 3) == 0 && ldx >= STN_N && ldg >= n_all,
@@ -245,7 +247,8 @@ int pdn_outres_tn_split_launch(const float* X, const float* G, float* C, int n_a
   PDN_CHECK_ARG(ranges <= 65535, "pdn_outres_tn_split_launch: %d K ranges", ranges);
   OtsParams p;
   memset(&p, 0, sizeof(p));
-  p.g = G; p.ximg = static_cast<const char*>(extra); p.xsh = stn_x_planes_launch(X, ldx, K, extra, nullptr, nullptr, stream);
+  p.g = G; p.ximg = static_cast<const char*>(extra);
+  p.xsh = norm_w ? stn_xn_planes_launch(X, ldx, norm_w, rms, K, extra, stream) : stn_x_planes_launch(X, ldx, K, extra, nullptr, nullptr, stream);
   p.C = C;
   p.n_all = n_all; p.nb_cols = nb_cols; p.K = K; p.k_per_split = k_per_split;
   p.ldg = ldg; p.slab = (int64_t)STN_N * nb_cols; p.blk_stride = (int64_t)ranges * STN_N * nb_cols;
@@ -255,6 +258,15 @@ int pdn_outres_tn_split_launch(const float* X, const float* G, float* C, int n_a
   pdn_count(PDN_CNT_OUTRES_TN_SPLIT);
   PDN_LAUNCH_CHECK();
   return PDN_OK;
+}
+int pdn_outres_tn_split_launch(const float* X, const float* G, float* C, int n_all, int K, int64_t ldx, int64_t ldg,
+                               int nb_cols, int k_per_split, void* extra, void* stream) {
+  return ots_launch(X, nullptr, nullptr, G, C, n_all, K, ldx, ldg, nb_cols, k_per_split, extra, stream);
+}
+int pdn_outres_tn_split_norm_launch(const float* x, const float* norm_w, const float* rms, const float* G, float* C, int n_all,
+                                    int K, int64_t ldx, int64_t ldg, int nb_cols, int k_per_split, void* extra, void* stream) {
+  PDN_CHECK_ARG(norm_w && rms && (((uintptr_t)norm_w | (uintptr_t)rms) & 3) == 0, "pdn_outres_tn_split_norm_launch: norm operands");
+  return ots_launch(x, norm_w, rms, G, C, n_all, K, ldx, ldg, nb_cols, k_per_split, extra, stream);
 }
 
 // ---- the down-projection weight gradient: dW_down (M x 288) = h^T g2 as (g2^T h)^T, one block, transposed store ----------

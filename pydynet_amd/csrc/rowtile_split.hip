@@ -17,7 +17,7 @@
 //     kernel (x * (1 / r) * w), stores xn as whole lines, passes the 32 x 32 chunk through its staging area and reads it
 //     back as the B fragments of two k-steps, which are split: 16 fp32 registers die as 16 plane registers are born, so
 //     the 144 fp32 values and the 144 plane registers are never alive together.  Only the workgroups of the first column
-//     range (blockIdx.y == 0) write xn / rms.
+//     range (blockIdx.y == 0) write xn / rms; with a null xn (include/pdn_normplanes.h) rms alone, under the same predicate.
 //   * the epilogues run in the drain, AFTER the scale is removed (one ldexp with the sum of the two integer exponents):
 //     RoPE rotates the pairs inside a lane's four columns with the table entries of its own row (the two EVEN columns'
 //     entries serve both members of a pair), requested three or four slots ahead into four registers; SwiGLU meets
@@ -225,6 +225,7 @@ __global__ __launch_bounds__(512, 1) void rts_main_kernel(RtsParams p) {
     nexv = -sh;
     const bool wr_on = blockIdx.y == 0 && !(p.ablate & 1);
     if (NORM && lh == 0 && wr_on && (!GUARD || m0 + li < p.M)) p.rms[m0 + li] = st.x;
+    const bool xn_on = wr_on && p.xn != nullptr;    // (no xn: the caller's backward works from x, norm_w and rms)
     char* xrow[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -242,7 +243,7 @@ __global__ __launch_bounds__(512, 1) void rts_main_kernel(RtsParams p) {
         float4 v = xa[c][i];
         if (NORM) {
           v.x = v.x * inv[i] * w.x; v.y = v.y * inv[i] * w.y; v.z = v.z * inv[i] * w.z; v.w = v.w * inv[i] * w.w;
-          if (wr_on && (!GUARD || m0 + rts_pl_row(lane, i) < p.M)) *reinterpret_cast<float4*>(xrow[i] + 128 * c) = v;
+          if (xn_on && (!GUARD || m0 + rts_pl_row(lane, i) < p.M)) *reinterpret_cast<float4*>(xrow[i] + 128 * c) = v;
         }
         *reinterpret_cast<float4*>(__builtin_assume_aligned(pw + i * (8 * 144), 16)) = v;
       }
@@ -505,9 +506,12 @@ struct RtsTemp {
 static int rts_tiles(const RowTileArgs& a) { return a.epi == 1 ? a.F / 16 : a.N / 32; }
 
 // PDN_ROWTILE_SPLIT=0: the fp32 kernel at every size (A/B switch; read once, announced)
-int pdn_rowtile_split_takes(const RowTileArgs& a, void* stream) {
+int pdn_rowtile_split_enabled() {
   static const int s_on = ls_env_switch("PDN_ROWTILE_SPLIT", 1, "the q | k | v and gate | up projections and dh + SwiGLU backward stay on the fp32 MFMA kernel");
-  if (!s_on || (a.epi != 1 && a.epi != 2 && a.epi != 3) || a.M < RTS_MIN_ROWS || a.bias || a.residual) return 0;
+  return s_on;
+}
+int pdn_rowtile_split_takes(const RowTileArgs& a, void* stream) {
+  if (!pdn_rowtile_split_enabled() ||(a.epi != 1 && a.epi != 2 && a.epi != 3) || a.M < RTS_MIN_ROWS || a.bias || a.residual) return 0;
   if ((a.epi == 2) != (a.b_trans != 0)) return 0;
   if (a.N < 32 || a.N % 32 != 0 || a.nblocks < 1 || (a.N / a.nblocks) * a.nblocks != a.N || (a.N / a.nblocks) % 32 != 0) return 0;
   if ((a.lda & 3) || (a.ldc & 3) || a.lda < RTS_K || a.ldc < a.N || a.ldc >= (1 << 24) || a.ldb < (a.b_trans ? RTS_K : a.N / a.nblocks)) return 0;
@@ -526,7 +530,8 @@ int pdn_rowtile_split_takes(const RowTileArgs& a, void* stream) {
   if (a.epi == 3 && (!a.rope || a.hd < 4 || a.hd % 4 != 0 || a.L < 1 || a.rope_cols % 32 != 0 || a.rope_cols > a.N ||
                      (int64_t)a.L * a.hd >= (1 << 27) || ((uintptr_t)a.rope & 7)))
     return 0;
-  if (a.norm_w && !(a.xn && a.rms && (a.ldxn & 3) == 0 && a.ldxn >= RTS_K && (((uintptr_t)a.xn | (uintptr_t)a.norm_w) & 15) == 0)) return 0;
+  // (xn may be null: rms alone is left for the backward)
+  if (a.norm_w && !(a.rms && (!a.xn || ((a.ldxn & 3) == 0 && a.ldxn >= RTS_K)) && (((uintptr_t)a.xn | (uintptr_t)a.norm_w) & 15) == 0)) return 0;
   // the W images come from the library's allocator, which a stream that is being captured must not call
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) { (void)hipGetLastError(); return 0; }
@@ -550,7 +555,7 @@ int pdn_rowtile_split_launch(const RowTileArgs& a, void* stream) {
   p.A = a.A; p.lda = a.lda; p.wimg = w.wimg; p.C = a.C; p.H = a.H; p.GU = a.GU ? a.GU : a.A; p.ldc = (unsigned)a.ldc; p.ldh = (unsigned)a.ldh;
   p.rope = a.rope ? a.rope : a.A; p.L = a.L > 0 ? a.L : 1; p.hd = a.hd > 0 ? a.hd : 32; p.rope_tiles = a.rope_cols / 32;
   p.hd_magic = rts_rope_magic(p.hd);
-  p.F = a.F; p.norm_w = a.norm_w ? a.norm_w : a.A; p.xn = a.xn ? a.xn : a.C; p.rms = a.rms; p.ldxn = a.ldxn; p.norm_eps = a.norm_eps;
+  p.F = a.F; p.norm_w = a.norm_w ? a.norm_w : a.A; p.xn = a.norm_w ? a.xn : a.C; p.rms = a.rms; p.ldxn = a.ldxn; p.norm_eps = a.norm_eps;
   p.M = a.M; p.ntiles = nt; p.ablate = s_ablate;
   int parts;
   rts_plan(a.M, nt, &p.tpw, &parts);

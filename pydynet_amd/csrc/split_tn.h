@@ -11,6 +11,9 @@
 // = [images: rows / 32 pieces | 288 exponents]; returns the exponents.  lse and targets given: 37 KiB images whose tails
 // hold the row statistics of the next piece; both null: 36 KiB images.
 int* stn_x_planes_launch(const float* x, int64_t ldx, int rows, void* extra, const float* lse, const int64_t* targets, void* stream);
+// ... the same 36 KiB images and exponents of xn = x * (1 / rms) * w, which is never written, in one launch: the exponents
+// follow from w (rms[t] >= sqrt(mean_d x[t][d]^2) is the caller's contract)
+int* stn_xn_planes_launch(const float* x, int64_t ldx, const float* w, const float* rms, int rows, void* extra, void* stream);
 // csrc/outres_tn_split.hip: the packed layer weight gradients on split-fp16 MFMA
 int pdn_outres_tn_split_enabled();
 int pdn_outres_tn_split_supported(int M, int nb_cols, int nbatch, int K);
@@ -18,6 +21,9 @@ int64_t pdn_outres_tn_split_extra_bytes(int K);
 int pdn_outres_tn_split_ranges(int n_all, int K, int plan);
 int pdn_outres_tn_split_launch(const float* X, const float* G, float* C, int n_all, int K, int64_t ldx, int64_t ldg,
                                int nb_cols, int k_per_split, void* extra, void* stream);
+// ... with X = the RMSNorm output of (x, norm_w, rms), formed by the plane pass (csrc/normplanes.hip, include/pdn_normplanes.h)
+int pdn_outres_tn_split_norm_launch(const float* x, const float* norm_w, const float* rms, const float* G, float* C, int n_all,
+                                    int K, int64_t ldx, int64_t ldg, int nb_cols, int k_per_split, void* extra, void* stream);
 // ... and the down-projection weight gradient dW_down (M x 288) = h^T g2 on the same kernel with the roles swapped and a
 // transposed store (one block; slabs M x 288 row-major)
 int pdn_down_dw_split_supported(int M, int N, int K);

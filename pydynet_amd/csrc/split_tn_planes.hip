@@ -4,7 +4,9 @@
 //
 // in three launches: partial column maxima over ranges of rows, the exponent of every column, then the plane images, one per
 // piece of 32 tokens, transposed, in LDS order (csrc/split_tn_index.h).  With lse and targets the images are 37 KiB and
-// their tails carry the row statistics of the NEXT piece (the lm_head weight gradient), without 36 KiB.
+// their tails carry the row statistics of the NEXT piece (the lm_head weight gradient), without 36 KiB.  Where x is the output
+// of an RMSNorm that was never written, ONE launch forms it from the rows before the norm and takes the exponents from the
+// norm weight (stn_split_xn_kernel below).
 #include "split_tn.h"
 
 #define STN_L2E 1.4426950408889634f
@@ -104,6 +106,61 @@ __global__ __launch_bounds__(256) void stn_split_x_tail_kernel(const float* __re
                                                                 const float* __restrict__ lse, const int64_t* __restrict__ targets,
                                                                 int rows, char* __restrict__ ximg) {
   stn_split_x<LDW_XKIB, true>(x, ldx, xsh, lse, targets, rows, ximg);
+}
+
+// ---- the plane images of an RMSNorm OUTPUT that is never written: xn[t][d] = x[t][d] * (1 / rms[t]) * w[d], formed here with
+// the arithmetic of the projection kernels (csrc/rowtile_split.hip, csrc/gemm_rowtile.hip), in ONE launch.  No pass for the
+// column maxima: with rms[t] >= sqrt(mean_d x[t][d]^2) every |x[t][d]| <= sqrt(288) rms[t], so |xn[t][d]| < 17 |w[d]| and
+// the exponent of column d follows from w[d] alone (ls_shift puts the BOUND into [2^8, 2^9); a zero or non-finite w[d]: 0).
+// The same loads, staging and image as stn_split_x; workgroup 0 leaves the 288 exponents for the main kernel's drain.
+__global__ __launch_bounds__(256) void stn_split_xn_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w,
+                                                            const float* __restrict__ rms, int* __restrict__ xsh,
+                                                            char* __restrict__ ximg) {
+  __shared__ __attribute__((aligned(16))) float raw[STN_KP * STN_N];
+  __shared__ float inv[STN_KP];
+  char* img = ximg + (int64_t)blockIdx.x * stn_xpiece(OTS_XKIB);
+  const float* xp = x + (int64_t)blockIdx.x * STN_KP * ldx;
+  float4 v[STN_PASS_LOADS];
+#pragma unroll
+  for (int e = 0; e < STN_PASS_LOADS; ++e) {
+    const int i = threadIdx.x + STN_PASS_THREADS * e;
+    v[e] = *reinterpret_cast<const float4*>(xp + (int64_t)stn_pass_row(i) * ldx + 4 * stn_pass_chunk(i));
+  }
+  if (threadIdx.x < STN_KP) inv[threadIdx.x] = 1.f / rms[(int64_t)blockIdx.x * STN_KP + threadIdx.x];
+  if (blockIdx.x == 0)
+    for (int d = threadIdx.x; d < STN_N; d += STN_PASS_THREADS) xsh[d] = ls_shift(17.f * fabsf(w[d]));
+#pragma unroll
+  for (int e = 0; e < STN_PASS_LOADS; ++e) {
+    const int i = threadIdx.x + STN_PASS_THREADS * e;
+    *reinterpret_cast<float4*>(raw + stn_pass_lds(stn_pass_row(i), 4 * stn_pass_chunk(i))) = v[e];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < (STN_N * 4 + STN_PASS_THREADS - 1) / STN_PASS_THREADS; ++e) {
+    const int u = threadIdx.x + STN_PASS_THREADS * e;
+    if (u < STN_N * 4) {
+      const int d = stn_pass_unit_d(u), q = stn_pass_unit_q(u);
+      const float wd = w[d];
+      const int sh = ls_shift(17.f * fabsf(wd));
+      f16x8 hv, lv;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        _Float16 h, l;
+        ls_split(raw[stn_pass_lds(8 * q + k, d)] * inv[8 * q + k] * wd, sh, h, l);
+        hv[k] = h; lv[k] = l;
+      }
+      *reinterpret_cast<f16x8*>(img + 16 * u) = hv;
+      *reinterpret_cast<f16x8*>(img + STN_PLANE + 16 * u) = lv;
+    }
+  }
+}
+
+int* stn_xn_planes_launch(const float* x, int64_t ldx, const float* w, const float* rms, int rows, void* extra, void* stream) {
+  const int npieces = rows / STN_KP;
+  char* ximg = static_cast<char*>(extra);
+  int* xsh = reinterpret_cast<int*>(ximg + (int64_t)npieces * stn_xpiece(OTS_XKIB));
+  hipLaunchKernelGGL(stn_split_xn_kernel, dim3(npieces), dim3(256), 0, (hipStream_t)stream, x, ldx, w, rms, xsh, ximg);
+  return xsh;
 }
 
 int* stn_x_planes_launch(const float* x, int64_t ldx, int rows, void* extra, const float* lse, const int64_t* targets, void* stream) {
