@@ -572,13 +572,13 @@ int pdn_attention_decode_f32(const float* q, const float* k_cache, const float* 
  *                            blk_max / blk_arg (optional, B x pdn_decode_gemv_blocks(N)): per row and workgroup the
  *                            first maximum of the workgroup's columns + its column: first half of a greedy pick.
  *                            act = 2: x rows are the partials of pdn_decode_attention_f32 (act_ns key ranges,
- *                            heads of act_hd) and f is their softmax-weighted merge.
+ *                            heads of act_hd) and f is their softmax-weighted merge (K / act_hd <= 256 heads).
  *   pdn_decode_attention_f32 qkv (B, 3 D) rows [q | k | v] of the new token: q, k rotated by the angle of position
  *                            *pos (model.py:23-44), k / v appended to cache row *pos (model.py:105-110), then the
  *                            query attends to cache positions [0, *pos] (model.py:112-121, L = 1: no mask), the keys
  *                            cut into n_splits ranges: partials (B, n_splits, H, 4 + hd)
  *                            = [max, sum of exp, -, - | sum of exp(s - max) v] per range, merged by the output
- *                            projection's loads (act = 2).
+ *                            projection's loads (act = 2).  A range without keys: [-inf, 0, -, - | zeros].
  *   pdn_decode_pick_tick_f32 next_ids[b] = column of the first maximum over the candidates (model.py:262-268:
  *                            argmax(-1)), also stored (system scope) at (*history)[*pos * B + b] when a history (a
  *                            device-resident pointer to a (max_len, B) int64 buffer, possibly mapped host memory:

@@ -56,7 +56,8 @@ __global__ __launch_bounds__(256) void decode_gemv_kernel(
   //      without waiting, the first P k-steps of this thread's column quad: the weights do not depend on the
   //      activation, so they travel while the row is summed and normalised (these kernels are latency chains:
   //      a token is ~20 dependent launches of a few microseconds each).  No load sits behind a branch: rows past K
-  //      re-read row `slice` and are masked where they are used (32-bit offsets, two instructions per load) ----
+  //      re-read row `slice` (K < S: the last row) and are masked where they are used (32-bit offsets, two
+  //      instructions per load) ----
   DecStage stg;
   const bool staged = sum.base != nullptr;
   if (staged) dec_stage_issue(sum, K, 0, norm_w, stg);
@@ -64,12 +65,13 @@ __global__ __launch_bounds__(256) void decode_gemv_kernel(
   //  waves x a few dozen loads is most of a microsecond -- so steps past K are skipped by a uniform branch; they are
   //  the LAST loads, where the compiler's then conservative wait counts cost nothing)
   const int nsteps = (K + S - 1) / S;
+  const int kslice = min(slice, K - 1);    // (K < S: the slices past K have no row of their own -- W has no row `slice`)
   float4 wreg[P];
 #pragma unroll
   for (int i = 0; i < P; ++i) {
     const int k = slice + i * S;
     if (!EXACT) wreg[i] = make_float4(0.f, 0.f, 0.f, 0.f);        // (EXACT: K needs exactly P k-steps)
-    if (EXACT || i < nsteps) wreg[i] = *reinterpret_cast<const float4*>(wp + (unsigned)((k < K ? k : slice) * w_rs));
+    if (EXACT || i < nsteps) wreg[i] = *reinterpret_cast<const float4*>(wp + (unsigned)((k < K ? k : kslice) * w_rs));
   }
   // epilogue operands of the finishing threads, likewise
   const int fq = tid % Q, fj = tid / Q, fn = blockIdx.x * TN + 4 * fq;
@@ -173,7 +175,7 @@ __global__ __launch_bounds__(256) void decode_gemv_kernel(
     {
 #pragma unroll
       for (int i = 0; i < P; ++i) {
-        const int k = slice + i * S, kc = k < K ? k : slice;
+        const int k = slice + i * S, kc = k < K ? k : kslice;
         const float4 w = wreg[i];          // (zeros where the step was skipped)
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
@@ -303,6 +305,7 @@ static int decode_gemv_impl(const float* x, int64_t x_row_stride, const float* n
                     (int64_t)B * res_row_stride < lim,
                 "pdn_decode_gemv_f32: strides out of the 32-bit range of the kernel");
   PDN_CHECK_ARG(act != 2 || (act_ns > 0 && act_hd > 0 && K % act_hd == 0), "pdn_decode_gemv_f32: act 2 needs splits / head_dim");
+  PDN_CHECK_ARG(act != 2 || K / act_hd <= 256, "pdn_decode_gemv_f32: act 2 merges at most 256 heads (a thread per head)");
   const int nb = B == 1 ? 1 : (B == 2 ? 2 : 4);
   DecSum sum = sum_in;
   if (act == 0 && !sum.base && K % 4 == 0 && K <= 1024 && x_row_stride % 4 == 0 && (((uintptr_t)x | (uintptr_t)norm_w) & 15) == 0)
@@ -402,9 +405,11 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(const int* __rest
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
   const int Dc = D / C, nqd = Dc / 4;                              // this workgroup's columns of the projected row
   float* out = part_out + (((int64_t)b * NS + sp) * H + h) * rec;
-  if (t0 >= t1) {                        // no keys in this range (uniform over the workgroup)
+  if (t0 >= t1) {                        // no keys in this range (uniform over the workgroup): m = -inf, l = 0, sums 0
     if (tid == 0 && ci == 0) { out[0] = -INFINITY; out[1] = 0.f; }
+    // (the consumers weigh these sums by 0, they do not skip them: 0 * whatever the buffer held is NaN)
     if (OPROJ) for (int i = tid; i < nqd; i += 256) reinterpret_cast<float4*>(out + 4 + ci * Dc)[i] = z4;
+    else if (tid < f4) reinterpret_cast<float4*>(out + 4)[tid] = z4;
     return;
   }
   float* kb = kc + (int64_t)b * cbs + (int64_t)h * hd;

@@ -13,8 +13,16 @@ class DecodeMixin:
     # -- graph-replayable decode step (csrc/decode.hip) -----------------------------------------------
     def pdn_decode_gemv_f32(self, x, x_rs, norm_w, eps, W, w_rs, blk_cols, w_bs, bias, residual, r_rs, y, y_rs,
                             B, K, N, act, act_ns, act_hd, blk_max, blk_arg, stream):
-        if B > 8 or B * K > 16384 or N % blk_cols or blk_cols % 4:
+        if B == 0 or N == 0:
+            return 0
+        if B > 8 or B * K > 16384 or blk_cols <= 0 or N % blk_cols or blk_cols % 4:
             return -1
+        if w_rs % 4 or w_bs % 4 or y_rs % 4 or r_rs % 4 or ((W | y | (bias or 0) | (residual or 0)) & 15):
+            return -1                           # (columns in multiples of 4, 16-byte aligned operands)
+        if act and norm_w:
+            return -1
+        if act == 2 and (act_ns <= 0 or act_hd <= 0 or K % act_hd or K // act_hd > 256):
+            return -1                           # (one thread per head merges: at most 256 heads)
         if act == 2:
             H = K // act_hd
             R = np.array(view(x, (B, act_ns, H, 4 + act_hd), (x_rs, H * (4 + act_hd), 4 + act_hd, 1), np.float32))
@@ -29,7 +37,8 @@ class DecodeMixin:
             pass
         elif act:
             g, u = X[:, :K], X[:, K:]
-            a = g / (np.float32(1) + np.exp(-g)) * u
+            with np.errstate(over="ignore"):    # (expf(-g) = inf for g < -88.7: the quotient is -0, as in the kernel)
+                a = g / (np.float32(1) + np.exp(-g)) * u
         elif norm_w:
             a = X / np.sqrt((X * X).mean(-1, keepdims=True) + np.float32(eps)) * flat(norm_w, K)
         else:
@@ -81,8 +90,9 @@ class DecodeMixin:
         chunk = -(-T // NS)
         for sp in range(NS):
             t0, t1 = sp * chunk, min(T, (sp + 1) * chunk)
-            if t0 >= t1:
+            if t0 >= t1:                        # a range without keys: m = -inf, l = 0, sums 0 (the merge weighs them by 0)
                 out[:, sp, :, 0], out[:, sp, :, 1] = -np.inf, 0.0
+                out[:, sp, :, 4:] = 0.0
                 continue
             ss = s[:, :, t0:t1]
             m = ss.max(-1)

@@ -108,10 +108,11 @@ def test_rows_entries(hip, entry, hd, B, kind):
                 assert np.array_equal(kr[b], kc[b]) and np.array_equal(vr[b], vc[b]), (entry, ns, b)
                 continue
             assert np.array_equal(kr[b], ks[b]) and np.array_equal(vr[b], vs[b]), (entry, ns, b, "cache slot")
-            # [m, l, -, - | sum]: fields 2, 3 are never written, nor the sums of a range without keys (l = 0)
+            # [m, l, -, - | sum]: fields 2, 3 are never written; a range without keys is [-inf, 0 | zeros] in every entry
             assert np.array_equal(got[b][..., :2], one[b][..., :2]), (entry, ns, b, "records")
-            full = one[b][..., 1] > 0
-            assert np.array_equal(got[b][full][:, 4:], one[b][full][:, 4:]), (entry, ns, b, "records")
+            assert np.array_equal(got[b][..., 4:], one[b][..., 4:]), (entry, ns, b, "records")
+            empty = one[b][..., 1] == 0
+            assert np.all(got[b][empty][:, 0] == -np.inf) and not got[b][empty][:, 4:].any(), (entry, ns, b, "empty ranges")
             # float64 statement: q (| k | v) of the row, RoPE at its own position, attention over [0, p]
             if entry == "block":
                 x = base[b].astype(np.float64)
