@@ -530,11 +530,13 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(const int* __rest
   if (tg < groups) part[tg * f4 + vc4] = acc;
   lds_barrier();
   // combine in a fixed order: 8 threads per column quad add every 8th group, then one thread adds those 8
-  if (tid < 8 * f4) {
-    const int g0 = dec_div(tid, f4);
+  // (8 f4 slots: one trip up to head_dim 128; above it 8 f4 > 256 and a thread fills a second slot -- a slot left
+  //  unwritten is what the score buffer held there, and the pass below adds all 8 f4)
+  for (int s = tid; s < 8 * f4; s += 256) {
+    const int g0 = s < 256 ? tg : s / f4, c4 = s - g0 * f4;        // (dec_div is exact up to 256 only)
     float4 r = z4;
-    for (int g = g0; g < groups; g += 8) { const float4 t = part[g * f4 + vc4]; r.x += t.x; r.y += t.y; r.z += t.z; r.w += t.w; }
-    part[groups * f4 + tid] = r;
+    for (int g = g0; g < groups; g += 8) { const float4 t = part[g * f4 + c4]; r.x += t.x; r.y += t.y; r.z += t.z; r.w += t.w; }
+    part[groups * f4 + s] = r;
   }
   lds_barrier();
   if (tid < f4) {

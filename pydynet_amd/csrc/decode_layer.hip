@@ -43,12 +43,13 @@ __global__ __launch_bounds__(256) void decode_mlp_kernel(const float* __restrict
   // (a load instruction costs its 16 clocks of the CU's address path whether its lanes are useful or not, so steps
   //  past the end are skipped by uniform branches; they are the LAST loads of their group)
   const int nsteps = (D + S - 1) / S;
+  const int kslice = min(slice, D - 1);    // (D < S: the slices past D have no row of their own -- Wg / Wu have no row `slice`)
   float4 wreg[P];
 #pragma unroll
   for (int i = 0; i < P; ++i) {
     const int k = slice + i * S;
     if (!EXACT) wreg[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (EXACT || i < nsteps) wreg[i] = *reinterpret_cast<const float4*>(wp + (unsigned)((k < D ? k : slice) * w_rs));
+    if (EXACT || i < nsteps) wreg[i] = *reinterpret_cast<const float4*>(wp + (unsigned)((k < D ? k : kslice) * w_rs));
   }
   const int nq = D >> 2, G = dec_div(256, nq), dsl = dec_div(tid, nq), dq = tid - dsl * nq;
   const float* wdp = Wd + (unsigned)(j * MLP_SL * wd_rs + 4 * dq);
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(256) void decode_mlp_kernel(const float* __restrict
     for (int r = 0; r < NB; ++r) acc[r] = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int i = 0; i < P; ++i) {
-      const int k = slice + i * S, kc = k < D ? k : slice;
+      const int k = slice + i * S, kc = k < D ? k : kslice;
       const float4 w = wreg[i];            // (zeros where the step was skipped)
 #pragma unroll
       for (int r = 0; r < NB; ++r) {

@@ -65,7 +65,22 @@ class DecodeMixin:
     def pdn_decode_gemv_blocks(self, N):
         return (N + 15) // 16 if N <= 4096 else ((N + 31) // 32 if N <= 16384 else (N + 63) // 64)
 
+    @staticmethod
+    def _attention_refused(qkv, rs, cos, sin, kc, vc, parts, hd, NS, cbs, pos, max_len):
+        """The PDN_CHECK_ARGs of csrc/decode.hip decode_attention_impl, in its order."""
+        if not (qkv and cos and sin and kc and vc and parts and pos and max_len > 0):
+            return True
+        if hd <= 0 or hd % 4 or hd > 256 or cbs % 4 or rs % 4 or ((qkv | kc | vc | parts) & 15):
+            return True
+        if not 1 <= NS <= 64:
+            return True
+        return 4 * max(-(-max_len // NS), (256 // (hd // 4) + 8) * hd) > 60 * 1024    # (scores | partial sums in LDS)
+
     def pdn_decode_attention_f32(self, qkv, rs, cos, sin, kc, vc, parts, B, H, hd, NS, cbs, pos, max_len, stream):
+        if B == 0 or H == 0:
+            return 0
+        if self._attention_refused(qkv, rs, cos, sin, kc, vc, parts, hd, NS, cbs, pos, max_len):
+            return -1
         D, half = H * hd, hd // 2
         p = int(flat(pos, 1, np.int32)[0])
         assert 0 <= p < max_len
@@ -104,9 +119,14 @@ class DecodeMixin:
     def pdn_decode_attention_oproj_f32(self, qkv, rs, cos, sin, kc, vc, Wo, wo_rs, recs, B, H, hd, NS, cbs, pos,
                                        max_len, stream):
         D = H * hd
-        if D > 1024 or NS * H > 256:
+        if B == 0 or H == 0:
+            return 0
+        if self._attention_refused(qkv, rs, cos, sin, kc, vc, recs, hd, NS, cbs, pos, max_len):
             return -1
-        tmp = np.zeros(B * NS * H * (4 + hd), np.float32)
+        if not Wo or D > 1024 or NS * H > 256 or wo_rs % 4 or wo_rs < 0 or (Wo & 15):
+            return -1
+        tmp = np.zeros(B * NS * H * (4 + hd) + 4, np.float32)
+        tmp = tmp[(-tmp.ctypes.data // 4) % 4:][:B * NS * H * (4 + hd)]                 # (16-byte aligned, as the entry asks)
         rc = self.pdn_decode_attention_f32(qkv, rs, cos, sin, kc, vc, tmp.ctypes.data, B, H, hd, NS, cbs, pos, max_len,
                                            stream)
         if rc:
@@ -161,7 +181,7 @@ class DecodeMixin:
             view(vc + 4 * (b * cbs + p * D), (D,), (1,), np.float32)[...] = Vn[b].reshape(D)
         Wov = view(Wo, (H, hd, D), (hd * wo_rs, wo_rs, 1), np.float32)
         out = flat(recs, B * (NS + 1) * H * (4 + D)).reshape(B, NS + 1, H, 4 + D)
-        out[...] = 0
+        out[..., :2], out[..., 4:] = 0, 0       # (the two pad slots of a record are never written)
         Kc = view(kc, (B, max(p, 1), H, hd), (cbs, D, hd, 1), np.float32)
         Vc = view(vc, (B, max(p, 1), H, hd), (cbs, D, hd, 1), np.float32)
         sc = np.float32(1 / math.sqrt(hd))
@@ -201,12 +221,13 @@ class DecodeMixin:
         if recs:
             h = h + self._merge_records(np.array(view(recs, (B, ns, H, 4 + D), (recs_rs, H * (4 + D), 4 + D, 1),
                                                       np.float32)), ns, H, D)
-            if x_out:
-                view(x_out, (B, D), (x_out_rs, 1), np.float32)[...] = h
+        if x_out:                               # (with or without records: decode_stage.h leaves the staged row there)
+            view(x_out, (B, D), (x_out_rs, 1), np.float32)[...] = h
         n = h / np.sqrt((h * h).mean(-1, keepdims=True) + np.float32(eps)) * flat(norm_w, D)
         g = n @ view(Wg, (D, F), (w_rs, 1), np.float32)
         u = n @ view(Wu, (D, F), (w_rs, 1), np.float32)
-        a = (g / (np.float32(1) + np.exp(-g)) * u).astype(np.float32)
+        with np.errstate(over="ignore"):        # (expf(-g) = inf for g < -88.7: the quotient is -0, as in the kernel)
+            a = (g / (np.float32(1) + np.exp(-g)) * u).astype(np.float32)
         Wdv = view(Wd, (F, D), (wd_rs, 1), np.float32)
         J = F // 32
         out = view(parts, (B, J, D), (parts_rs, D, 1), np.float32)
