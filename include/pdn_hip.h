@@ -244,7 +244,9 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  51 dh + SwiGLU backward on split-fp16 MFMA (csrc/rowtile_split.hip): no entry of its own, the form
  *     pdn_swiglu_bwd_gemm_f32 takes at 16384 rows and more; counts in 3 as well, not in 41
  *  52 token-FSM constrained decoding of a decode step (csrc/token_fsm.hip): once per launch of pdnf_fsm_reset,
- *     pdnf_fsm_step_f32 and pdnf_fsm_rows_f32 of include/pdn_fsm.h */
+ *     pdnf_fsm_step_f32 and pdnf_fsm_rows_f32 of include/pdn_fsm.h
+ *  53 multi-token stop sequences of a decode step (csrc/stop_seq.hip): once per launch of pdnh_stop_reset and
+ *     pdnh_stop_step of include/pdn_stopseq.h */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores

@@ -89,7 +89,9 @@ enum {
                                   // NOT in 41
   PDN_CNT_TOKEN_FSM = 52,         // token-FSM constrained decoding of a decode step (csrc/token_fsm.hip, include/pdn_fsm.h): once
                                   // per launching pdnf_* entry
-  PDN_CNT_SLOTS = 53
+  PDN_CNT_STOP_SEQ = 53,          // multi-token stop sequences of a decode step (csrc/stop_seq.hip, include/pdn_stopseq.h): once
+                                  // per launching pdnh_* entry
+  PDN_CNT_SLOTS = 54
 };
 void pdn_count(int slot);
 

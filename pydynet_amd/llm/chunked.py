@@ -10,7 +10,8 @@ Per step:
      token is fed in this step yields its first token (Philox counter (len, req) when sampled); a row still mid-prompt
      yields -1.
   4. `finish`: every row that yielded a token moves one position on and has one token less to go; a request ends at its
-     budget or at a stop id, and its row is free for the next step's admission.
+     budget, at a stop id or at the end of a stop sequence (llm/stop_sequences.py), and its row is free for the next
+     step's admission.
 With C at least the number of prompt tokens admitted at every step, every admitted prompt completes in its admission
 step, and the steps are exactly those of `serve`."""
 import numpy as np
@@ -83,9 +84,10 @@ class Schedule:
         complete = (n > 0) & (self.fed + n == lens)
         return n, decode, complete
 
-    def finish(self, n, toks, stops=()):
+    def finish(self, n, toks, stops=(), stopped=None):
         """Step 4, after the step's tokens `toks` (S,) (-1 where a row yielded none): returns the requests shown for the
-        step, (S,) int64 (the request in each row during the step)."""
+        step, (S,) int64 (the request in each row during the step).  `stopped` (S,) bool: the rows whose token ends a stop
+        sequence; they end as at a stop id."""
         lens = self.row_lens()
         shown = self.req.copy()
         done_prompt = (n > 0) & (self.fed + n == lens)
@@ -96,5 +98,7 @@ class Schedule:
         self.pos[has] += 1
         self.last[has] = toks[has]
         done = has & ((self.left <= 0) | np.isin(toks, np.asarray(stops, np.int64)))
+        if stopped is not None:
+            done |= has & np.asarray(stopped, bool)
         self.req[done], self.pos[done], self.left[done], self.fed[done] = -1, -1, 0, 0
         return shown

@@ -11,6 +11,7 @@ import numpy as np
 from . import logit_edits as edit_np
 from . import logprobs as lp_np
 from . import penalties as pen_np
+from . import stop_sequences as ss_np
 from . import token_fsm as fsm_np
 from .sampling import Table, params_bytes
 
@@ -31,6 +32,9 @@ _EDIT_ENTRIES = ("pdne_logit_edit_chunks", "pdne_logit_edit_reset", "pdne_logit_
 # the entry points of the token FSM (csrc/token_fsm.hip, include/pdn_fsm.h): without them every path applies the statement of
 # llm/token_fsm.py
 _FSM_ENTRIES = ("pdnf_fsm_chunks", "pdnf_fsm_reset", "pdnf_fsm_step_f32", "pdnf_fsm_rows_f32")
+# the entry points of the stop sequences (csrc/stop_seq.hip, include/pdn_stopseq.h): without them the plan refuses and every
+# path stops its rows by the host matcher of llm/stop_sequences.py
+_STOPSEQ_ENTRIES = ("pdnh_stop_reset", "pdnh_stop_step")
 # the per-row sampled launches (include/pdn_persample.h): without them a run with a parameter table leaves the graph path and
 # every draw applies the statement of llm/sampling.py row by row
 _PERSAMPLE_ENTRIES = ("pdnq_sample_rows_f32", "pdnq_decode_sample_tick_rows_f32", "pdnq_decode_sample_tick_slots_f32",
@@ -59,7 +63,7 @@ class DecodePlan:
         return mask.view(np.int32)
 
     def _decode_plan(self, B, sampling=False, ragged=False, serve=False, beam=0, n_stops=0, penalty=False, n_lp=None,
-                     edit=False, per_row=False, fsm=False):
+                     edit=False, per_row=False, fsm=False, stopseq=False):
         """Buffers and weight views of the graph-replayable decode step (csrc/decode.hip), or None when the
         model's shapes / layout are outside what those kernels take (then the generic launches below run).
         `sampling`: the step ends in the sample tick (csrc/sample.hip) instead of the greedy pick; its parameters live in
@@ -94,7 +98,13 @@ class DecodePlan:
         live in the plan at that capacity (`fsm_off`, `fsm_tok`, `fsm_next`, `fsm_dflt`: a later call's machines of similar
         size are uploaded into the same arrays), the rows' state words, start states and prompt lengths in `fsm_state`,
         `fsm_start_state`, `fsm_start`.  A greedy plan's `cand_v` / `cand_i` then hold the candidates of the last of the
-        three kernels.  None when the library lacks the entries."""
+        three kernels.  None when the library lacks the entries.
+        `stopseq` (generate_ragged / serve with stop_sequences, csrc/stop_seq.hip; False, or the (sets, sequences, tokens)
+        capacity of the call's tables, llm/stop_sequences.StopSeqs.caps; with `ragged`): pdnh_stop_step is the last launch
+        of a step, behind the tick and the logprobs tick -- it appends the token the tick stored to the row's tail ring
+        and stops the row (pos = -1) when one of its sequences ends there; the tables live in the plan at that capacity
+        (`ss_set_off`, `ss_seq_off`, `ss_toks`), the rows' set ids, prompt lengths and tails in `ss_set`, `ss_start`,
+        `ss_tail`, min_new_tokens in `ss_min`.  None when the library lacks the entries."""
         from .. import hipnp as hp, _lib
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
         st = getattr(self, "_decode_st", None)
@@ -109,6 +119,7 @@ class DecodePlan:
         key += ("edit",) if edit else ()
         key += ("per_row",) if per_row else ()
         key += ("fsm",) + tuple(int(c) for c in fsm) if fsm else ()
+        key += ("stopseq",) + tuple(int(c) for c in stopseq) if stopseq else ()
         if st is not None and st["key"] == key:
             return st if st["ok"] else None
         if st is not None:
@@ -127,6 +138,8 @@ class DecodePlan:
             ok = False
         if fsm and not all(_lib.provides(n) for n in _FSM_ENTRIES):
             ok = False
+        if stopseq and not (ragged and all(_lib.provides(n) for n in _STOPSEQ_ENTRIES)):
+            ok = False
         packs = []
         if ok:
             for layer in self.layers:
@@ -142,7 +155,8 @@ class DecodePlan:
         st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged), "serve": bool(serve),
               "wide": wide, "rows": bool(ragged or wide), "beam": int(beam),
               "full": bool(sampling or beam or penalty or edit or fsm),
-              "pen": bool(penalty), "lp_n": n_lp, "edit": bool(edit), "per_row": bool(per_row), "fsm": bool(fsm)}
+              "pen": bool(penalty), "lp_n": n_lp, "edit": bool(edit), "per_row": bool(per_row), "fsm": bool(fsm),
+              "stopseq": bool(stopseq)}
         if ok:
             nblk = _lib.lib().query("pdn_decode_wide_blocks" if wide else "pdn_decode_gemv_blocks", V)
             # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
@@ -226,6 +240,12 @@ class DecodePlan:
                 if not sampling and not edit:
                     nc = _lib.lib().query("pdnf_fsm_chunks", V)
                     st.update(cand_v=hp.empty((B, nc), np.float32), cand_i=hp.empty((B, nc), np.int32))
+            if stopseq:
+                caps = tuple(int(c) for c in stopseq)
+                st.update(ss_set_off=hp.zeros((caps[0] + 1,), np.int32), ss_seq_off=hp.zeros((caps[1] + 1,), np.int32),
+                          ss_toks=hp.zeros((caps[2],), np.int32), ss_set=hp.asarray(np.full(B, -1, np.int32)),
+                          ss_start=hp.zeros((B,), np.int32), ss_tail=hp.asarray(np.full((B, ss_np.MAX_LEN), -1, np.int32)),
+                          ss_min=hp.zeros((1,), np.int32), ss_caps=caps, ss_val=None, ss_run=None)
             if n_lp is not None:
                 st.update(lp_ptr=hp.zeros((1,), np.int64), lp_box=None, lp_work=hp.zeros(
                     (_lib.lib().query("pdn_logprobs_work_bytes", B, V, n_lp) // 8 + 2,), np.int64))
@@ -328,6 +348,7 @@ class DecodePlan:
             self._edit_step(st, s)
             self._decode_tick(st, s)
             self._lp_tick(st, s)
+            self._stop_step(st, s)
             return
         for layer, (wqkv, wgu) in zip(self.layers, st["packs"]):
             a, f = layer.attention, layer.ffn
@@ -358,6 +379,7 @@ class DecodePlan:
         self._edit_step(st, s)
         self._decode_tick(st, s)
         self._lp_tick(st, s)
+        self._stop_step(st, s)
 
     def _decode_launches_wide(self, st, s):
         """The wide step (9 .. 256 rows, csrc/decode_wide.hip): 5 launches per layer -- q | k | v with RMSNorm in the load,
@@ -393,6 +415,7 @@ class DecodePlan:
         self._edit_step(st, s)
         self._decode_tick(st, s)
         self._lp_tick(st, s)
+        self._stop_step(st, s)
 
     def _lp_tick(self, st, s):
         """Plans with logprobs: after the tick, each row's record (csrc/logprobs.hip) of the step the tick just finished
@@ -414,12 +437,15 @@ class DecodePlan:
             st["lp_box"] = hp.Mailbox(_LP_RING, (st["B"], lp_np.record_words(st["lp_n"])), unset=lp_np.UNSET)
             st["lp_ptr"][...] = np.int64(st["lp_box"]._ptr)
 
-    def _run_values(self, st, sampling, pen=None, edit=None, fsm=None):
+    def _run_values(self, st, sampling, pen=None, edit=None, fsm=None, stopseq=None, lens=None):
         """The values of a run, uploaded when they differ from those in the plan (stream ordered: earlier steps read the
         old ones): the sampling parameters (a llm/sampling.Table: row b takes request b's block; a served plan's rows take
         theirs at admission, `_params_rows`), and for a run with penalties (`pen`: its llm/penalties.Rows) every row's
         prompt with zero counts; for a run with logit edits (`edit`: its llm/logit_edits.Rows) every row's request; for a
-        run with machines (`fsm`: its llm/token_fsm.Rows) the tables and every row's start state."""
+        run with machines (`fsm`: its llm/token_fsm.Rows) the tables and every row's start state; for a run with stop
+        sequences (`stopseq`: its llm/stop_sequences.Rows, fed the rows' first tokens) the tables and every row's set,
+        prompt length and first token (`lens`: the prompt lengths) -- and, for a run that comes back mid-stream, the rings of
+        its matcher."""
         if st["params_val"] != sampling:
             if isinstance(sampling, Table):
                 if not st.get("serve"):
@@ -436,6 +462,13 @@ class DecodePlan:
         if fsm is not None and st["fsm_run"] is not fsm:
             self._fsm_reset(st, np.arange(st["B"]), fsm.req, fsm.start, fsm.spec)
             st["fsm_run"] = fsm
+        if stopseq is not None and st["ss_run"] is not stopseq:
+            self._stop_reset(st, np.arange(st["B"]), stopseq.set, lens, stopseq.first, stopseq.spec)
+            if (stopseq.count > 1).any():
+                # (a run that comes back to the plan mid-stream, after another generation used it: the rings as the
+                #  host matcher holds them, slot for slot the device's)
+                st["ss_tail"][...] = stopseq.tail
+            st["ss_run"] = stopseq
 
     @staticmethod
     def _params_rows(st, table, reqs):
@@ -494,6 +527,38 @@ class DecodePlan:
         d_len = hp.asarray(np.asarray(lens, np.int32).reshape(-1))
         _lib.lib().call("pdnf_fsm_reset", st["fsm_state"]._ptr, st["fsm_start_state"]._ptr, st["fsm_start"]._ptr, st["B"],
                         d_rows._ptr, int(rows.size), d_state._ptr, d_len._ptr, hp.stream())
+
+    def _stop_step(self, st, s):
+        """Plans with stop sequences: the last launch of a step, behind the tick (and the logprobs tick) -- each row the
+        tick left running appends the token it stored to its tail ring and stops (pos = -1) when one of its sequences
+        ends there (csrc/stop_seq.hip)."""
+        if not st["stopseq"]:
+            return
+        from .. import _lib
+        _lib.lib().call("pdnh_stop_step", st["ids"]._ptr, st["pos"]._ptr, st["B"], st["ss_set_off"]._ptr,
+                        st["ss_seq_off"]._ptr, st["ss_toks"]._ptr, *st["ss_caps"], st["ss_set"]._ptr, st["ss_start"]._ptr,
+                        st["ss_tail"]._ptr, st["ss_min"]._ptr, s)
+
+    def _stop_reset(self, st, rows, sets, lens, first, spec):
+        """Rows `rows` of a plan with stop sequences take the set ids `sets` of `spec` (llm/stop_sequences.StopSeqs) with
+        prompt lengths `lens`, a cleared tail and their first tokens `first` (-1, or None for all: it will come out of a
+        replayed step); one launch, stream ordered after every step queued before.  The plan's tables and min_new_tokens
+        become the call's (stream ordered too)."""
+        from .. import hipnp as hp, _lib
+        if st["ss_val"] is not spec:
+            for name, a in zip(("ss_set_off", "ss_seq_off", "ss_toks"), ss_np.padded(spec.tables, st["ss_caps"])):
+                st[name][...] = a
+            st["ss_min"][...] = np.int32(spec.m)
+            st["ss_val"] = spec
+        rows = np.asarray(rows, np.int32).reshape(-1)
+        if not rows.size:
+            return
+        first = np.full(rows.size, -1, np.int32) if first is None else np.asarray(first, np.int32).reshape(-1)
+        # (device copies held until the call has been issued; the allocator orders their reuse on the stream)
+        d_rows, d_set, d_first = hp.asarray(rows), hp.asarray(np.asarray(sets, np.int32).reshape(-1)), hp.asarray(first)
+        d_len = hp.asarray(np.asarray(lens, np.int32).reshape(-1))
+        _lib.lib().call("pdnh_stop_reset", st["ss_set"]._ptr, st["ss_start"]._ptr, st["ss_tail"]._ptr, st["B"],
+                        d_rows._ptr, int(rows.size), d_set._ptr, d_len._ptr, d_first._ptr, hp.stream())
 
     def _edit_step(self, st, s):
         """Edit plans: between the vocabulary projection (or the penalty kernel) and the tick, each live row's logits are
@@ -596,7 +661,8 @@ class DecodePlan:
         runs write the KV cache slots of the next two steps with exactly what the real steps will write there, and they
         advance ids, positions and counters.  `keep` maps the plan arrays to put back afterwards to their values: a host
         value, or None for a device copy taken before the capture.  A penalty plan's `counts` are always kept (the runs
-        count their fed tokens too), and an FSM plan's state words (the runs advance them).
+        count their fed tokens too), an FSM plan's state words (the runs advance them) and the tails of a plan with stop
+        sequences (the runs append to them and may stop rows: `pos` is kept by every caller).
         `redirect` = (name, mailbox[, slots]): the runs' tick stores its tokens through the device pointer st[name],
         which points at a SCRATCH twin of `mailbox` meanwhile, so that the real one's slots stay "not written" until the
         real steps store there (a later step with other ids would otherwise read the capture's token as its own).  The
@@ -615,6 +681,8 @@ class DecodePlan:
                 keep = dict(keep, counts=None)
             if st.get("fsm"):
                 keep = dict(keep, fsm_state=None)
+            if st.get("stopseq"):
+                keep = dict(keep, ss_tail=None)
             saved = {n: st[n].copy() if v is None else v for n, v in keep.items()}
             moved = [redirect] if redirect else []
             if st.get("lp_n") is not None:

@@ -10,20 +10,24 @@ from . import logit_edits as edit_np
 from . import logprobs as lp_np
 from . import penalties as pen_np
 from . import prefix as prefix_np
+from . import stop_sequences as ss_np
 from . import token_fsm as fsm_np
 from .decode_plan import _MIXED_ENTRIES
 from .sampling import Table, draw_rows
 
 
 class ServeEngine:
-    def _serve(self, rows, budgets, S, sampling, stops, penalty=None, n_lp=None, edit=None, fsm=None):
+    def _serve(self, rows, budgets, S, sampling, stops, penalty=None, n_lp=None, edit=None, fsm=None, stopseq=None):
         """The scheduler of `serve`.  Per step: the rows holding a request decode one token, then the rows freed by the
         previous step take the waiting requests in order through one prompt pass (`_serve_prefill`), then the step is
         yielded.  The host keeps, per row, the request, the position of its next decode step, the tokens it may still
         produce and its last token; on the graph path the device keeps the same in the served plan (`_serve_begin`) and
         the host writes it only after an admission, when every queued step has been read.  `edit` (llm/logit_edits.Edits):
         request r's edits follow it into the row that takes it, as its prompt set and counts do with penalties; `fsm`
-        (llm/token_fsm.Machines): likewise request r's machine, from its start state."""
+        (llm/token_fsm.Machines): likewise request r's machine, from its start state.  `stopseq`
+        (llm/stop_sequences.StopSeqs): a request also ends at the end of one of its stop sequences -- the host matcher
+        (`srows`) reports it on every path, from the tokens it reads, and on the graph path the device stops the row in
+        the same step (csrc/stop_seq.hip), so a step queued ahead computes nothing for it."""
         lens = np.array([r.size for r in rows], np.int64)
         queue = [r for r in range(len(rows)) if budgets[r] > 0]   # FIFO by index; a budget of 0 never takes a row
         req = np.full(S, -1, np.int64)
@@ -31,10 +35,11 @@ class ServeEngine:
         left = np.zeros(S, np.int64)
         last = np.zeros(S, np.int64)
         hip = self._fast_path(self.tok_embedding.weight.device)
-        st = self._serve_begin(S, sampling, stops, penalty, n_lp, edit, fsm) if hip else None  # None: the plan refuses -> generic
+        st = self._serve_begin(S, sampling, stops, penalty, n_lp, edit, fsm, stopseq) if hip else None  # None: the plan refuses -> generic
         pen = None if penalty is None or st is not None else pen_np.Rows(S, self.vocab_size, penalty)   # (host counts)
         erows = None if edit is None or st is not None else edit_np.Rows(S, edit)                        # (host state)
         frows = None if fsm is None or st is not None else fsm_np.Rows(S, fsm)                           # (host state)
+        srows = None if stopseq is None else ss_np.Rows(S, stopseq)                                      # (every path)
         q = 0
         try:
             while True:
@@ -75,6 +80,8 @@ class ServeEngine:
                         toks[run] = d[run]
                     toks[adm], shown[adm] = first, new
                     req[adm], pos[adm], left[adm] = new, lens[new], budgets[new]
+                    if srows is not None:
+                        srows.reset(adm, new)
                 # every row that produced a token: one position further, one token less; a request ends at its budget
                 # or at a stop id, and its row is free for the next step
                 has = shown >= 0
@@ -82,6 +89,8 @@ class ServeEngine:
                 pos[has] += 1
                 last[has] = toks[has]
                 done = has & ((left <= 0) | np.isin(toks, stops))
+                if srows is not None:                            # (the admitted rows' first tokens included)
+                    done |= has & srows.feed(toks)
                 req[done], pos[done], left[done] = -1, -1, 0
                 if st is not None and adm.size:
                     self._serve_write(st, req, pos, left, last)
@@ -91,6 +100,8 @@ class ServeEngine:
                         self._edit_reset(st, adm, new, lens[new], edit)
                     if st["fsm"]:
                         self._fsm_reset(st, adm, new, lens[new], fsm)
+                    if st["stopseq"]:
+                        self._stop_reset(st, adm, stopseq.sets_of(new), lens[new], first, stopseq)
                     if (req >= 0).any():
                         self._serve_ahead(st, int(np.where(req >= 0, pos, -1).max()))
                 yield (shown, toks) if n_lp is None else (shown, toks, lpv)
@@ -190,11 +201,12 @@ class ServeEngine:
 
     # (graph path of `serve`: the served plan holds the rows' state on the device; steps are issued, queued ahead and
     #  read in order, through a ring of `ring` history slots)
-    def _serve_begin(self, S, sampling, stops, penalty=None, n_lp=None, edit=None, fsm=None):
+    def _serve_begin(self, S, sampling, stops, penalty=None, n_lp=None, edit=None, fsm=None, stopseq=None):
         from .. import hipnp as hp
         st = self._decode_plan(S, sampling is not None, ragged=True, serve=True, penalty=penalty is not None, n_lp=n_lp,
                                edit=edit is not None, per_row=isinstance(sampling, Table),
-                               fsm=False if fsm is None else fsm.caps)
+                               fsm=False if fsm is None else fsm.caps,
+                               stopseq=False if stopseq is None else stopseq.caps)
         if st is None:
             return None
         st["table"] = sampling if st["per_row"] else None        # (the rows' blocks: written with their requests)
@@ -216,6 +228,9 @@ class ServeEngine:
         if fsm is not None:                                      # (likewise: here only the tables are uploaded)
             self._fsm_reset(st, [], [], [], fsm)
             st["fsm_run"] = None
+        if stopseq is not None:                                  # (likewise: the tables and min_new_tokens)
+            self._stop_reset(st, [], [], [], None, stopseq)
+            st["ss_run"] = None
         st["pending"], st["read"] = 0, 0
         return st
 
@@ -265,7 +280,7 @@ class ServeEngine:
 
     # -- chunked prefill (serve(prefill_chunk=C)): prompts fed C tokens per step (statement: llm/chunked.py) -----------
     def _serve_chunked(self, rows, budgets, S, C, sampling, stops, penalty=None, n_lp=None, prefix=None, edit=None,
-                       fsm=None):
+                       fsm=None, stopseq=None):
         """The scheduler of `serve` with a chunk: llm/chunked.Schedule decides, per step, which rows decode and which
         prompt tokens are fed.  Graph path (`_mixed_begin`): a step with prompt tokens runs the mixed step (the decode
         rows and the chunks as query rows of the wide product, csrc/extend.hip), a step without runs the served step.
@@ -273,10 +288,12 @@ class ServeEngine:
         `_serve_prefill` for the requests whose prompts complete in that step.
         `prefix` = k (the prefix cache, llm/prefix.Schedule): on the graph path the rows admitted in a step that reuse
         another row's tokens take them through one copy launch, issued eagerly before the step (`_prefix_copy`), and
-        their prefill starts at fed = n; every other path starts every prompt at 0 (the schedule with reuse forced off)."""
+        their prefill starts at fed = n; every other path starts every prompt at 0 (the schedule with reuse forced off).
+        `stopseq` (llm/stop_sequences.StopSeqs): as in `_serve`; an admitted row's first token comes out of a replayed
+        step, so its device tail starts empty."""
         lens = np.array([r.size for r in rows], np.int64)
         hip = self._fast_path(self.tok_embedding.weight.device)
-        st = self._mixed_begin(S, C, sampling, stops, penalty, n_lp, edit, fsm) if hip else None
+        st = self._mixed_begin(S, C, sampling, stops, penalty, n_lp, edit, fsm, stopseq) if hip else None
         if prefix is None:
             sch = chunked.Schedule(lens, budgets, S, C)
         else:
@@ -287,6 +304,7 @@ class ServeEngine:
         pen = None if penalty is None or st is not None else pen_np.Rows(S, self.vocab_size, penalty)   # (host counts)
         erows = None if edit is None or st is not None else edit_np.Rows(S, edit)                        # (host state)
         frows = None if fsm is None or st is not None else fsm_np.Rows(S, fsm)                           # (host state)
+        srows = None if stopseq is None else ss_np.Rows(S, stopseq)                                      # (every path)
         dirty = False                                           # (the device's row state differs from the host's)
         try:
             while True:
@@ -311,6 +329,10 @@ class ServeEngine:
                         self._fsm_reset(st, adm, new, lens[new], fsm)
                     else:
                         frows.reset(adm, new, lens[new])
+                if adm.size and stopseq is not None:            # (likewise; the first token: out of a later step)
+                    if st is not None:
+                        self._stop_reset(st, adm, stopseq.sets_of(new), lens[new], None, stopseq)
+                    srows.reset(adm, new)
                 if not sch.busy():
                     return
                 n, dec, comp = sch.plan()
@@ -352,7 +374,7 @@ class ServeEngine:
                             first, lpf = first
                             lp_np.merge(lpv, b, lpf)
                         toks[b] = first
-                shown = sch.finish(n, toks, stops)
+                shown = sch.finish(n, toks, stops, None if srows is None else srows.feed(toks))
                 yield (shown, toks) if n_lp is None else (shown, toks, lpv)
         finally:
             if st is not None and st["pending"]:
@@ -392,12 +414,12 @@ class ServeEngine:
         return bool(type(self).wide_decode and S + C <= 256 and all(_lib.provides(n) for n in _MIXED_ENTRIES)
                     and L.query("pdn_decode_mixed_supported", D, H, D // H, F, V, cache_len))
 
-    def _mixed_begin(self, S, C, sampling, stops, penalty=None, n_lp=None, edit=None, fsm=None):
+    def _mixed_begin(self, S, C, sampling, stops, penalty=None, n_lp=None, edit=None, fsm=None, stopseq=None):
         """The served plan (`_serve_begin`) plus the buffers of the mixed step (`mixed`), or None when either refuses."""
         from .. import hipnp as hp, _lib
         if not self._mixed_ok(S, C):
             return None
-        st = self._serve_begin(S, sampling, stops, penalty, n_lp, edit, fsm)
+        st = self._serve_begin(S, sampling, stops, penalty, n_lp, edit, fsm, stopseq)
         if st is None or st["ns"] > 8:
             return None
         M = st.get("mixed")
@@ -487,12 +509,14 @@ class ServeEngine:
         # (penalty plans: a row completing its prompt here is at position len = start and counts nothing; greedy: the
         #  plan's candidates are those of the penalty kernel.  Edit plans: that row has generated no token; the
         #  candidates are those of the edit kernel.  FSM plans: that row is in its start state, which the kernel takes at
-        #  g = 0 whatever the row's word holds)
+        #  g = 0 whatever the row's word holds.  Stop sequences: the tick leaves that row at position len + 1, behind its
+        #  first generated token, as it leaves a decode row at start + g)
         self._pen_step(st, s)
         self._fsm_step(st, s)
         self._edit_step(st, s)
         self._decode_tick(st, s, mixed=M)
         self._lp_tick(st, s)
+        self._stop_step(st, s)
 
     def _mixed_layers(self, M, packs, n_runs, max_run, R, ns, s):
         """The layers of the mixed step on R query rows (M["x"] in, M["x"] out): q | k | v with RMSNorm in the load, the KV

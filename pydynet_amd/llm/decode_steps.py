@@ -9,6 +9,7 @@ from ..core import Tensor
 from . import logit_edits as edit_np
 from . import logprobs as lp_np
 from . import penalties as pen_np
+from . import stop_sequences as ss_np
 from . import token_fsm as fsm_np
 from .decode_plan import _EDIT_ENTRIES, _FSM_ENTRIES, _PEN_ENTRIES
 from .sampling import Table, draw_rows, params_buffer, sample_next, sample_next_table
@@ -187,7 +188,7 @@ class DecodeSteps:
         pos = np.asarray(pos, np.int64).reshape(-1)
         return self._edit_rows(logits, erows.spec, erows.req, np.maximum(pos - erows.start, 0), pos)
 
-    def _generate_ragged(self, rows, n, sampling, stops, penalty=None, n_lp=None, edit=None, fsm=None):
+    def _generate_ragged(self, rows, n, sampling, stops, penalty=None, n_lp=None, edit=None, fsm=None, stopseq=None):
         B = len(rows)
         lens = np.array([r.size for r in rows], np.int64)
         if n == 0:
@@ -195,12 +196,17 @@ class DecodeSteps:
         pen = None if penalty is None else pen_np.Rows(B, self.vocab_size, penalty, rows)
         erows = None if edit is None else edit_np.Rows(B, edit, np.arange(B), lens)
         frows = None if fsm is None else fsm_np.Rows(B, fsm, np.arange(B), lens)
+        # (the rows' matcher: llm/stop_sequences.py -- every path drops the rows it reports from `live`; the graph path's
+        #  device state stops them at the same step, csrc/stop_seq.hip)
+        srows = None if stopseq is None else ss_np.Rows(B, stopseq, np.arange(B))
         nxt = self._prompt_rows(rows, lens, sampling, penalty, n_lp, edit, fsm)
         if n_lp is not None:
             nxt, lp = nxt
         live = np.ones(B, bool)
         if stops.size:
             live = ~np.isin(nxt.numpy().reshape(-1), stops)
+        if srows is not None:
+            live = live & ~srows.feed(nxt.numpy().reshape(-1))
         yield nxt if n_lp is None else (nxt, lp_np.as_step(lp))
         fast = self._fast_path(nxt.device)
         if fast:
@@ -208,7 +214,7 @@ class DecodeSteps:
             # tokens by STEP: slot i holds step i of every row (-1 for a stopped row), so "not written yet" is its own
             # value; two slots beyond the last step for the runs of a graph capture
             run = {"lens": lens, "live": live, "sampling": sampling, "stop_mask": self._stop_mask(stops), "pen": pen,
-                   "edit": erows, "fsm": frows,
+                   "edit": erows, "fsm": frows, "stopseq": srows,
                    "hist": hp.Mailbox(n + 2, (B, 1), unset=np.iinfo(np.int64).min), "lp": n_lp}
         ids = nxt.data
         for i in range(1, n):
@@ -223,10 +229,12 @@ class DecodeSteps:
                 nxt = self._step_module_rows(nxt, np.where(live, lens + i, -1), sampling, pen=pen, n_lp=n_lp,
                                              edit=erows, fsm=frows)
                 nxt, lp = nxt if n_lp is not None else (nxt, None)
-            if stops.size:
+            if stops.size or srows is not None:
                 yield nxt if n_lp is None else (nxt, lp_np.as_step(lp))
                 tok = nxt.numpy().reshape(-1)                    # (fast path: a poll of the mapped history slot)
                 live = live & (tok >= 0) & ~np.isin(tok, stops)
+                if srows is not None:
+                    live = live & ~srows.feed(tok)
                 continue
             yield nxt if n_lp is None else (nxt, lp_np.as_step(lp))
 
@@ -486,7 +494,8 @@ class DecodeSteps:
         n_lp = run.get("lp")
         st = self._decode_plan(B, sampling is not None, ragged=True, penalty=run.get("pen") is not None, n_lp=n_lp,
                                edit=run.get("edit") is not None, per_row=isinstance(sampling, Table),
-                               fsm=False if run.get("fsm") is None else run["fsm"].spec.caps)
+                               fsm=False if run.get("fsm") is None else run["fsm"].spec.caps,
+                               stopseq=False if run.get("stopseq") is None else run["stopseq"].spec.caps)
         if st is None:
             out = self._decode_step_generic_rows(ids, pos, sampling, pen=run.get("pen"), n_lp=n_lp, edit=run.get("edit"),
                                                  fsm=run.get("fsm"))
@@ -511,7 +520,7 @@ class DecodeSteps:
             st["step"][...] = np.int32(i)
             st["stop"][...] = run["stop_mask"]
             self._hist_begin(st, run["hist"])
-        self._run_values(st, sampling, run.get("pen"), run.get("edit"), run.get("fsm"))
+        self._run_values(st, sampling, run.get("pen"), run.get("edit"), run.get("fsm"), run.get("stopseq"), lens)
         if ids is not st["ids"] and ids is not st.get("last_out"):
             # (a stopped row's -1 is no token: any valid id stands in, its row computes nothing that is kept)
             st["ids"][...] = np.maximum(ids.get(), 0) if isinstance(ids, hp.readback_array) else ids

@@ -30,6 +30,7 @@ from . import logit_edits as edit_np
 from . import penalties as pen_np
 from . import prefix as prefix_np
 from . import speculative as spec_np
+from . import stop_sequences as ss_np
 from . import token_fsm as fsm_np
 from .decode_plan import DecodePlan
 from .decode_search import SearchEngine
@@ -455,7 +456,7 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
     def generate_ragged(self, prompts, max_new_tokens: int, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
                         speculate=0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
                         logprobs=None, logit_bias=None, allowed_token_ids=None, min_new_tokens=0, min_p=0.0,
-                        token_fsm=None):
+                        token_fsm=None, stop_sequences=None):
         """Generation for B prompts of different lengths, every row at its own position.  Yields a (B, 1) int64 Tensor
         per step: step i holds, for row b, the token at position len_b + i.  `max_new_tokens` is the number of NEW tokens
         per row -- `generate`'s second argument is an end position instead: for equal lengths L,
@@ -483,6 +484,11 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         whose temperatures are all 0 is the greedy run.  The penalties stay one set of values for every row.
         `token_fsm`: as in `generate` (llm/token_fsm.py), one machine or one (or None) per prompt; a stopped row's state
         stays.  Not with speculate > 0.
+        `stop_sequences` (llm/stop_sequences.py): a sequence of token-id sequences for every row, or a sequence with one
+        such (or None) per prompt.  A row stops like at a stop id once the tokens it generated end in one of its
+        sequences -- the token that completes the match is yielded, the row yields -1 from then on; prompt tokens never
+        take part.  With `min_new_tokens` = m a match counts from the step at which a stop id could first be yielded.  The
+        other rows' tokens do not change.  Not with speculate > 0.
         Every argument is checked here (ValueError), before anything runs."""
         V = self.vocab_size
         if int(max_new_tokens) != max_new_tokens or max_new_tokens < 0:
@@ -513,13 +519,15 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         stops = np.asarray(sorted({int(t) for t in stop_ids}), np.int64)
         if stops.size and (stops.min() < 0 or stops.max() >= V):
             raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
-        edit = edit_np.check_args(logit_bias, allowed_token_ids, min_new_tokens, V, len(rows), stops, k)
+        stopseq = ss_np.check_args(stop_sequences, V, len(rows), min_new_tokens, k)
+        edit = edit_np.check_args(logit_bias, allowed_token_ids, min_new_tokens, V, len(rows), stops, k,
+                                  stop_sequences=stopseq is not None)
         fsm = fsm_np.check_args(token_fsm, V, len(rows), k)
         self.last_speculation = None if k == 0 else spec_np.counts()
         if k:
             return self._speculate([r.astype(np.int64) for r in rows], max_new_tokens, k, sampling, stops)
         return self._generate_ragged([r.astype(np.int64) for r in rows], max_new_tokens, sampling, stops, penalty,
-                                     n_lp, edit, fsm)
+                                     n_lp, edit, fsm, stopseq)
 
     # -- decode fast path -----------------------------------------------------------
     graph_decode = True     # class switch: False issues the step's launches one by one instead of replaying a hipGraph
@@ -532,7 +540,7 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
     def serve(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
               prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=None,
               prefix_cache=False, logit_bias=None, allowed_token_ids=None, min_new_tokens=0, min_p=0.0,
-              token_fsm=None):
+              token_fsm=None, stop_sequences=None):
         """Continuous batching: N requests (`prompts`, N may exceed max_batch_size) through `slots` decode rows
         (default min(N, max_batch_size)).  A row frees when its request yields a stop id or uses up its budget
         (`max_new_tokens`: one int, or one per request; 0 = the request yields nothing and never takes a row).  Before
@@ -573,7 +581,12 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         The penalties are not per request: they stay one set of values for the call.
         `token_fsm` (llm/token_fsm.py): one machine for every request, or a sequence with one (or None) per request -- a
         request's machine follows it into whichever row it runs in, from its start state, with plain and chunked prefill
-        and with the prefix cache."""
+        and with the prefix cache.
+        `stop_sequences` (llm/stop_sequences.py): a sequence of token-id sequences for every request, or a sequence with
+        one such (or None) per request.  A request also ends, and frees its row for the next admission, once the tokens it
+        generated end in one of its sequences (the matching tokens are yielded; prompt tokens never take part; with
+        `min_new_tokens` = m a match counts from the step at which a stop id could first be yielded).  The match is made
+        inside the replayed step, so a step queued ahead computes nothing for the row and writes nothing to its cache."""
         penalty = pen_np.check_args(repetition_penalty, presence_penalty, frequency_penalty)
         n_lp = lp_np.check_n(logprobs)
         k_pre = prefix_np.check_arg(prefix_cache, prefill_chunk)
@@ -610,24 +623,27 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         stops = np.asarray(sorted({int(t) for t in stop_ids}), np.int64)
         if stops.size and (stops.min() < 0 or stops.max() >= V):
             raise ValueError(f"stop ids must lie in [0, {V}), got {stops.tolist()}")
-        edit = edit_np.check_args(logit_bias, allowed_token_ids, min_new_tokens, V, N, stops)
+        stopseq = ss_np.check_args(stop_sequences, V, N, min_new_tokens)
+        edit = edit_np.check_args(logit_bias, allowed_token_ids, min_new_tokens, V, N, stops,
+                                  stop_sequences=stopseq is not None)
         fsm = fsm_np.check_args(token_fsm, V, N)
         C = chunked.check_chunk(prefill_chunk, slots)
         if C is not None:
             return self._serve_chunked([p.astype(np.int64) for p in rows], budgets, int(slots), C, sampling, stops,
-                                       penalty, n_lp, k_pre, edit, fsm)
+                                       penalty, n_lp, k_pre, edit, fsm, stopseq)
         return self._serve([p.astype(np.int64) for p in rows], budgets, int(slots), sampling, stops, penalty, n_lp, edit,
-                           fsm)
+                           fsm, stopseq)
 
     def serve_all(self, prompts, max_new_tokens, slots=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, stop_ids=(),
                   prefill_chunk=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
                   logprobs=None, prefix_cache=False, logit_bias=None, allowed_token_ids=None, min_new_tokens=0,
-                  min_p=0.0, token_fsm=None):
-        """`serve` run to the end: a list of N int64 arrays, request r's generated tokens in order.  `logprobs` = n: a
+                  min_p=0.0, token_fsm=None, stop_sequences=None):
+        """`serve` run to the end: a list of N int64 arrays, request r's generated tokens in order -- cut after its first
+        stop id or at the end of its first matching stop sequence, the matching tokens included.  `logprobs` = n: a
         list of (tokens, Logprobs) instead, the arrays of length k / (k, n) for a request's k tokens."""
         it = self.serve(prompts, max_new_tokens, slots, temperature, top_k, top_p, seed, stop_ids, prefill_chunk,
                         repetition_penalty, presence_penalty, frequency_penalty, logprobs, prefix_cache, logit_bias,
-                        allowed_token_ids, min_new_tokens, min_p, token_fsm)
+                        allowed_token_ids, min_new_tokens, min_p, token_fsm, stop_sequences)
         out = [[] for _ in range(len(prompts))]
         lps = [[] for _ in range(len(prompts))]
         for step in it:

@@ -118,16 +118,21 @@ class Edits:
         return bits, on, ids, vals, cnt
 
 
-def check_args(logit_bias=None, allowed_token_ids=None, min_new_tokens=0, V=0, n=1, stop_ids=(), speculate=0):
+def check_args(logit_bias=None, allowed_token_ids=None, min_new_tokens=0, V=0, n=1, stop_ids=(), speculate=0,
+               stop_sequences=False):
     """Validate the edit arguments of a call with `n` prompts / requests over a vocabulary of `V` tokens; returns an `Edits`,
-    or None when nothing is to be edited (all three at their defaults).  ValueError: see the tests."""
+    or None when nothing is to be edited (all three at their defaults).  `stop_sequences`: the call has stop sequences
+    (llm/stop_sequences.py) -- min_new_tokens then needs no stop id, and without one it edits nothing (the sequences are
+    held back by their own matcher, no logit is touched for them).  ValueError: see the tests."""
     m = min_new_tokens
     if isinstance(m, (bool, np.bool_)) or not isinstance(m, _INT) or m < 0:
         raise ValueError(f"min_new_tokens must be a non-negative integer, got {m!r}")
     m = int(m)
     stops = np.unique(np.asarray(list(stop_ids), np.int64).reshape(-1))
     if m > 0 and not stops.size:
-        raise ValueError("min_new_tokens > 0 needs stop_ids (it keeps a request from stopping)")
+        if not stop_sequences:
+            raise ValueError("min_new_tokens > 0 needs stop_ids (it keeps a request from stopping)")
+        m = 0                                    # (no stop id to mask)
     biases = _per_request("logit_bias", logit_bias, n, lambda v: isinstance(v, Mapping))
     allows = _per_request("allowed_token_ids", allowed_token_ids, n, _one_allowed)
     reqs = []

@@ -100,8 +100,8 @@ class Schedule(chunked.Schedule):
         st["copies"] += int(((n > 0) & (donors != rows)).sum())
         return rows, new, donors, n
 
-    def finish(self, n, toks, stops=()):
-        shown = super().finish(n, toks, stops)
+    def finish(self, n, toks, stops=(), stopped=None):
+        shown = super().finish(n, toks, stops, stopped)
         freed = shown != self.req                                     # (a row ends only after its whole prompt was fed)
         if freed.any():
             self._valid[freed] = self.lens[shown[freed]]
