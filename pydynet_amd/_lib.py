@@ -47,6 +47,9 @@ NORMPLANES_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "pdn_
 # multi-token stop sequences of a decode step (prefix pdnh_, include/pdn_stopseq.h): likewise, held to the rule by
 # tests/test_stopseq_abi_cpu.py
 STOPSEQ_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "pdn_stopseq.h"),)
+# all weight plane images of a training pass in one launch (prefix pdnw_, include/pdn_wimages.h): likewise, held to the
+# rule by tests/test_wimages_abi_cpu.py
+WIMAGES_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "pdn_wimages.h"),)
 
 _CTYPE = {
     "int": ctypes.c_int,
@@ -62,7 +65,7 @@ def parse_header(path: str = HEADER_PATH):
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     text = re.sub(r"//[^\n]*", "", text)
     protos = {}
-    for m in re.finditer(r"(const\s+char\s*\*|int64_t|int)\s+(pdn[xlsrzeqfgph]?_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
+    for m in re.finditer(r"(const\s+char\s*\*|int64_t|int)\s+(pdn[xlsrzeqfgphw]?_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
         ret, name, args = m.group(1), m.group(2), m.group(3)
         restype = ctypes.c_char_p if "char" in ret else _CTYPE[ret]
         argtypes = []
@@ -100,7 +103,7 @@ class _Lib:
         self.protos = parse_header()
         for path in (EXT_HEADER_PATHS + LOSS_HEADER_PATHS + SEG_HEADER_PATHS + ROWLOSS_HEADER_PATHS + SMOOTH_HEADER_PATHS
                      + EDIT_HEADER_PATHS + PERSAMPLE_HEADER_PATHS + FSM_HEADER_PATHS + NORMGRAD_HEADER_PATHS
-                     + NORMPLANES_HEADER_PATHS + STOPSEQ_HEADER_PATHS):
+                     + NORMPLANES_HEADER_PATHS + STOPSEQ_HEADER_PATHS + WIMAGES_HEADER_PATHS):
             self.protos.update(parse_header(path))
         self.fn = {}
         for name, (restype, argtypes) in self.protos.items():

@@ -33,6 +33,7 @@ from .ffn import gate_up_swiglu, ffn_swiglu
 from .conv import relu, conv2d, conv2d_relu_pool, pool2d
 from .recurrent import _cell_grads, rnn_cell, lstm_cell, gru_cell, gru_sequence
 from .vision import patch_project, patch_embed, clip_logits
+from . import wimages
 from . import chain as _chain_mod
 from .chain import attn_link
 from .. import tensor as _tensor

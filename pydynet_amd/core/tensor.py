@@ -301,47 +301,59 @@ class Tensor:
             self.grad = xp.ones(self.shape, dtype=self.dtype)
             self._grad_owned = True
             order, pending = _ancestors(self)
-            for node in order:
-                g = node.grad
-                inputs = node.last
-                if not inputs:
-                    continue
-                if g is not None:
-                    if getattr(g, "materialise", None) is not None and (
-                            retain_graph or not type(node).__dict__.get("takes_deferred_grad", False)):
-                        # an input gradient its producer left unformed (core/fused/_common.py: DeferredInputGrad) for a
-                        # node that cannot form it itself, or whose gradient stays readable behind this walk
-                        g = node.grad = g.materialise()
-                    folded = ()
-                    if hasattr(node, "backward_all"):
-                        if node.folds_existing:
-                            # hand the node the gradients its non-leaf inputs already hold: it may
-                            # add them inside its own kernel (GEMM / norm epilogue) instead of the
-                            # engine running a separate accumulation pass afterwards
-                            node._existing = [inp.grad if (inp.requires_grad and inp.last) else None
-                                              for inp in inputs]
-                            folded = node._folded = set()
-                        grads = node.backward_all(g)
-                        if node.folds_existing:
-                            node._existing = None
-                    else:
-                        grads = [node.grad_fn(inp, g) if inp.requires_grad else None for inp in inputs]
-                    for i, (inp, add_grad) in enumerate(zip(inputs, grads)):
-                        if inp.requires_grad and add_grad is not None:
-                            if i in folded:
-                                inp.grad, inp._grad_owned = add_grad, True
-                            else:
-                                _accumulate(inp, add_grad, xp)
-                for inp in inputs:
-                    if inp.requires_grad and not inp.last:       # a leaf: count down its edges
-                        left = pending.get(inp._gid, 0) - 1
-                        pending[inp._gid] = left
-                        if left == 0 and inp._grad_hook is not None:
-                            inp._grad_hook(inp)
-                if not retain_graph:
-                    Graph._free_node(node)
-                    if node is not self:
-                        node.grad = None
+            # a pass that left the weight forms of its backward on one of its nodes (Llama._forward_hidden): all their fp16
+            # plane images in one launch, bound for this walk only (core/fused/wimages.py)
+            images = next((im for im in (n.__dict__.get("_backward_images") for n in order) if im is not None), None)
+            if images is not None and images.bind():
+                try:
+                    self._backward_walk(order, pending, retain_graph, xp)
+                finally:
+                    images.release()
+            else:
+                self._backward_walk(order, pending, retain_graph, xp)
+
+    def _backward_walk(self, order, pending, retain_graph, xp):
+        for node in order:
+            g = node.grad
+            inputs = node.last
+            if not inputs:
+                continue
+            if g is not None:
+                if getattr(g, "materialise", None) is not None and (
+                        retain_graph or not type(node).__dict__.get("takes_deferred_grad", False)):
+                    # an input gradient its producer left unformed (core/fused/_common.py: DeferredInputGrad) for a
+                    # node that cannot form it itself, or whose gradient stays readable behind this walk
+                    g = node.grad = g.materialise()
+                folded = ()
+                if hasattr(node, "backward_all"):
+                    if node.folds_existing:
+                        # hand the node the gradients its non-leaf inputs already hold: it may
+                        # add them inside its own kernel (GEMM / norm epilogue) instead of the
+                        # engine running a separate accumulation pass afterwards
+                        node._existing = [inp.grad if (inp.requires_grad and inp.last) else None
+                                          for inp in inputs]
+                        folded = node._folded = set()
+                    grads = node.backward_all(g)
+                    if node.folds_existing:
+                        node._existing = None
+                else:
+                    grads = [node.grad_fn(inp, g) if inp.requires_grad else None for inp in inputs]
+                for i, (inp, add_grad) in enumerate(zip(inputs, grads)):
+                    if inp.requires_grad and add_grad is not None:
+                        if i in folded:
+                            inp.grad, inp._grad_owned = add_grad, True
+                        else:
+                            _accumulate(inp, add_grad, xp)
+            for inp in inputs:
+                if inp.requires_grad and not inp.last:       # a leaf: count down its edges
+                    left = pending.get(inp._gid, 0) - 1
+                    pending[inp._gid] = left
+                    if left == 0 and inp._grad_hook is not None:
+                        inp._grad_hook(inp)
+            if not retain_graph:
+                Graph._free_node(node)
+                if node is not self:
+                    node.grad = None
 
 
 def _ancestors(root):

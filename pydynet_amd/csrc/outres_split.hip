@@ -33,56 +33,22 @@
 #include "split_tn.h"
 #include "outres_split_index.h"
 #include "gemm_routes.h"
+#include "weight_images.h"
 
 extern "C" int pdn_malloc(void** ptr, int64_t bytes);
 extern "C" int pdn_free(void* ptr);
 
-// ---- W: the largest magnitude per output column of every piece (Inf for a non-finite one) --------------------------------
-struct OrsWParams {
-  const float* B;
-  float* pmax;                    // np x 288
-  int* wsh;                       // 288 exponents
-  char* wimg;                     // np images
-  int np, ppb;
-  int64_t ldb, bstride;
-};
-
-__device__ __forceinline__ float ors_finite_or_inf(float a) { return a < INFINITY ? a : INFINITY; }   // |NaN| -> Inf
-
-// the eight values of unit q of column d of this workgroup's piece
-template <bool NN>
-__device__ __forceinline__ void ors_w_unit(const OrsWParams& p, const float* tile, int d, int q, float (&v)[8]) {
-  if (NN) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = tile[ors_nn_lds(8 * q + j, d)];
-  } else {
-    const float* src = p.B + ors_w_src_nt(blockIdx.x, d, q, p.ppb, p.ldb, p.bstride);
-    const float4 a = *reinterpret_cast<const float4*>(src);
-    const float4 b = *reinterpret_cast<const float4*>(src + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-}
-// NN: the piece's 32 rows of B into the LDS tile, whole rows at a time
-__device__ __forceinline__ void ors_w_stage_nn(const OrsWParams& p, float* tile) {
-  for (int i = threadIdx.x; i < ORS_KP * (ORS_N / 4); i += 256) {
-    const float4 a = *reinterpret_cast<const float4*>(p.B + ors_w_src_nn(blockIdx.x, i, p.ldb));
-    float* t = tile + ors_nn_lds(i / 72, 4 * (i % 72));
-    t[0] = a.x; t[1] = a.y; t[2] = a.z; t[3] = a.w;
-  }
-  __syncthreads();
-}
-
+// ---- W: the largest magnitude per output column of every piece (Inf for a non-finite one).  The bodies are those of
+// csrc/weight_images.h, shared with the batched builder. -----------------------------------------------------------------
 template <bool NN>
 __global__ __launch_bounds__(256) void ors_w_max_kernel(OrsWParams p) {
-  __shared__ float tile[NN ? ORS_KP * ORS_NN_LD : 1];
-  if (NN) ors_w_stage_nn(p, tile);
+  __shared__ float tile[NN ? ORS_W_TILE : 1];
+  if (NN) ors_w_stage_nn(p, tile, blockIdx.x, 0, ORS_N / 4);
   for (int i = threadIdx.x; i < ORS_N * 4; i += 256) {
     const int d = i >> 2, q = i & 3;
     float v[8];
-    ors_w_unit<NN>(p, tile, d, q, v);
-    float m = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) m = fmaxf(m, ors_finite_or_inf(fabsf(v[j])));
+    ors_w_unit<NN>(p, tile, blockIdx.x, d, q, v);
+    float m = ors_w_max8(v);
     m = fmaxf(m, __shfl_xor(m, 1, 64));                     // the four units of a column lie in four adjacent lanes
     m = fmaxf(m, __shfl_xor(m, 2, 64));
     if (q == 0) p.pmax[(int64_t)blockIdx.x * ORS_N + d] = m;
@@ -92,8 +58,8 @@ __global__ __launch_bounds__(256) void ors_w_max_kernel(OrsWParams p) {
 // ---- W: the plane images, ORS_IMG_WGS workgroups per piece -------------------------------------------------------------------------
 template <bool NN>
 __global__ __launch_bounds__(256) void ors_w_img_kernel(OrsWParams p) {
-  __shared__ float tile[NN ? ORS_KP * ORS_NN_LD : 1];
-  if (NN) ors_w_stage_nn(p, tile);
+  __shared__ float tile[NN ? ORS_W_TILE : 1];
+  if (NN) ors_w_stage_nn(p, tile, blockIdx.x, 0, ORS_N / 4);
   char* img = p.wimg + (int64_t)blockIdx.x * ORS_PIECE;
   // ONE unit per thread, the 1152 units of a piece over ORS_IMG_WGS workgroups (grid.y): with np workgroups of 4.5 units per
   // thread the pass was a chain of five memory round trips on a tenth of the chip (NN: every workgroup stages the whole tile)
@@ -105,17 +71,8 @@ __global__ __launch_bounds__(256) void ors_w_img_kernel(OrsWParams p) {
     const int sh = ls_shift(amax);
     if (blockIdx.x == 0 && q == 0) p.wsh[d] = sh;
     float v[8];
-    ors_w_unit<NN>(p, tile, d, q, v);
-    f16x8 hv, lv;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      _Float16 h, l;
-      ls_split(v[j], sh, h, l);
-      hv[j] = h; lv[j] = l;
-    }
-    char* dst = img + ors_img_unit(d, q);
-    *reinterpret_cast<f16x8*>(dst) = hv;
-    *reinterpret_cast<f16x8*>(dst + ORS_PLANE) = lv;
+    ors_w_unit<NN>(p, tile, blockIdx.x, d, q, v);
+    ors_w_put(img, d, q, sh, v);
   }
 }
 
@@ -593,22 +550,24 @@ static int ors_launch(const float* A, const float* B, float* C, const float* bia
   const char* eg = getenv("PDN_OUTRES_SPLIT_WGS");
   const int env_wgs = eg ? atoi(eg) : -1;
   const int np = K / ORS_KP;
-  // [images: np pieces | per-piece column maxima: np x 288 | 288 exponents]
-  OrsTemp tmp;
-  const int rc = tmp.get((int64_t)np * ORS_PIECE + (int64_t)np * ORS_N * 4 + ORS_N * 4, stream);
-  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  OrsWParams w;
-  memset(&w, 0, sizeof(w));
-  w.B = B; w.wimg = static_cast<char*>(tmp.p); w.pmax = reinterpret_cast<float*>(w.wimg + (int64_t)np * ORS_PIECE);
-  w.wsh = reinterpret_cast<int*>(w.pmax + (int64_t)np * ORS_N);
-  w.np = np; w.ppb = kb > 0 ? kb / ORS_KP : np; w.ldb = ldb; w.bstride = kb > 0 ? b_bstride : 0;
-  if (b_trans) {
-    hipLaunchKernelGGL(ors_w_max_kernel<false>, dim3(np), dim3(256), 0, st, w);
-    hipLaunchKernelGGL(ors_w_img_kernel<false>, dim3(np, ORS_IMG_WGS), dim3(256), 0, st, w);
-  } else {
-    hipLaunchKernelGGL(ors_w_max_kernel<true>, dim3(np), dim3(256), 0, st, w);
-    hipLaunchKernelGGL(ors_w_img_kernel<true>, dim3(np, ORS_IMG_WGS), dim3(256), 0, st, w);
+  // the images and exponents: from the set bound to this thread when it holds exactly this weight in this form
+  // (csrc/weight_images.hip), else built here into [images: np pieces | per-piece column maxima: np x 288 | 288 exponents]
+  const PdnwDesc key = pdnw_key_ors(B, K, ldb, b_trans, kb, b_bstride);
+  OrsWParams w = ors_w_params(key);
+  OrsTemp tmp;
+  if (!pdnw_lookup(key, stream, &w.wimg, &w.wsh)) {
+    const int rc = tmp.get((int64_t)np * ORS_PIECE + (int64_t)np * ORS_N * 4 + ORS_N * 4, stream);
+    if (rc) return rc;
+    w.wimg = static_cast<char*>(tmp.p); w.pmax = reinterpret_cast<float*>(w.wimg + (int64_t)np * ORS_PIECE);
+    w.wsh = reinterpret_cast<int*>(w.pmax + (int64_t)np * ORS_N);
+    if (b_trans) {
+      hipLaunchKernelGGL(ors_w_max_kernel<false>, dim3(np), dim3(256), 0, st, w);
+      hipLaunchKernelGGL(ors_w_img_kernel<false>, dim3(np, ORS_IMG_WGS), dim3(256), 0, st, w);
+    } else {
+      hipLaunchKernelGGL(ors_w_max_kernel<true>, dim3(np), dim3(256), 0, st, w);
+      hipLaunchKernelGGL(ors_w_img_kernel<true>, dim3(np, ORS_IMG_WGS), dim3(256), 0, st, w);
+    }
   }
   OrsParams p;
   memset(&p, 0, sizeof(p));

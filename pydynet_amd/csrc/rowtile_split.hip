@@ -29,80 +29,29 @@
 //     row-wise store step meets, per lane, the 16 bytes of gate and of up at its row and columns of gu and writes dgate
 //     and dup there: whole 128-byte lines in all four streams.  The gu values of two row steps are held at a time (16
 //     registers), requested behind the staging loads of the tile before or in front of those of slot 6 (run_tile).
-// One small launch per call (rts_w_kernel) builds the tile images from the weights where they live; the optimiser changes
-// them every step.  Every address comes from rowtile_split_index.h, which tests/rowtile_split_check.cpp walks on the host.
+// The tile images are built from the weights where they live; the optimiser changes them every step.  One small launch per
+// call (rts_w_kernel) does it, unless the caller has bound a set that was built for the whole pass in one launch
+// (include/pdn_wimages.h) and holds this weight in this form.  Every address comes from rowtile_split_index.h, which
+// tests/rowtile_split_check.cpp walks on the host.
 // Deterministic: fixed order, no atomics.
 #include "common.h"
 #include "lm_head_split.h"
 #include "gemm_rowtile.h"
 #include "rowtile_split_index.h"
+#include "weight_images.h"
 #include <stdlib.h>
 #include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 extern "C" int pdn_malloc(void** ptr, int64_t bytes);
 extern "C" int pdn_free(void* ptr);
 
-// ---- W: one workgroup per tile --------------------------------------------------------------------------------------
-struct RtsWParams {
-  const float* B;
-  char* wimg;
-  int kind, nper;
-  int64_t ldb, bstride;
-  unsigned g_off, u_off;
-};
+// ---- W: one workgroup per tile (the body: csrc/weight_images.h, shared with the batched builder) -------------------------
 __global__ __launch_bounds__(256) void rts_w_kernel(RtsWParams p) {
-  __shared__ float sm[RTS_K * 33];
-  __shared__ float smax[8 * 32];
-  const int tid = threadIdx.x, c = tid & 31, kq = tid >> 5, tile = blockIdx.x;
-  float amax = 0.f;
-  bool bad = false;
-  if (p.kind == 2) {
-    // transposed source (the rows of W_down are the tile's columns): read along k, 288 contiguous floats per column
-    for (int i = tid; i < 32 * RTS_K; i += 256) {
-      const int n = rts_w_t_n(i), k = rts_w_t_k(i);
-      sm[k * 33 + n] = p.B[rts_w_src_t(tile, n, k, p.ldb)];
-    }
-    __syncthreads();
-    for (int k = kq; k < RTS_K; k += 8) {
-      const float f = sm[k * 33 + c];
-      amax = fmaxf(amax, fabsf(f));
-      bad |= !(fabsf(f) < INFINITY);
-    }
-  } else {
-    for (int k = kq; k < RTS_K; k += 8) {
-      const float f = p.B[rts_w_src(p.kind, tile, c, k, p.nper, p.ldb, p.bstride, p.g_off, p.u_off)];
-      sm[k * 33 + c] = f;
-      amax = fmaxf(amax, fabsf(f));
-      bad |= !(fabsf(f) < INFINITY);
-    }
-  }
-  smax[kq * 32 + c] = bad ? INFINITY : amax;
-  __syncthreads();
-  char* img = p.wimg + (int64_t)tile * RTS_TILE;
-  float cm = smax[c];
-#pragma unroll
-  for (int i = 1; i < 8; ++i) cm = fmaxf(cm, smax[i * 32 + c]);
-  const int sh = ls_shift(cm);                      // (column c: the same for every unit this thread writes)
-  for (int u = tid; u < 32 * 36; u += 256) {        // u = 32 ku + n: n == c
-    const int ku = u >> 5;
-    f16x8 hv, lv;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      _Float16 h, l;
-      ls_split(sm[(8 * ku + j) * 33 + c], sh, h, l);
-      hv[j] = h; lv[j] = l;
-    }
-    char* dst = img + rts_img_unit(c, ku);
-    *reinterpret_cast<f16x8*>(dst) = hv;
-    *reinterpret_cast<f16x8*>(dst + RTS_PLANE) = lv;
-  }
-  if (tid < 32) {
-    reinterpret_cast<int*>(img + RTS_TAIL)[tid] = -sh;
-    reinterpret_cast<float*>(img + RTS_TAIL + 128)[tid] = 0.f;
-  }
+  __shared__ float sm[RTS_W_SM];
+  __shared__ float smax[RTS_W_SMAX];
+  rts_w_tile(p, blockIdx.x, sm, smax);
 }
 
 // ---- the product ------------------------------------------------------------------------------------------------
@@ -541,15 +490,18 @@ int pdn_rowtile_split_takes(const RowTileArgs& a, void* stream) {
 int pdn_rowtile_split_launch(const RowTileArgs& a, void* stream) {
   static const int s_ablate = ls_env_switch("PDN_ROWTILE_SPLIT_ABLATE", 0, "timing ablation active, the results of the split q | k | v, gate | up and dh + SwiGLU backward kernels are WRONG");
   const int nt = rts_tiles(a);
-  RtsTemp img;
-  const int rc = img.get((int64_t)nt * RTS_TILE, stream);
-  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  RtsWParams w;
-  memset(&w, 0, sizeof(w));
-  w.B = a.B; w.wimg = static_cast<char*>(img.p); w.kind = a.epi; w.nper = a.N / a.nblocks; w.ldb = a.ldb;
-  w.bstride = a.nblocks > 1 ? a.b_block_stride : 0; w.g_off = a.g_off; w.u_off = a.u_off;
-  hipLaunchKernelGGL(rts_w_kernel, dim3(nt), dim3(256), 0, st, w);
+  // the image: from the set bound to this thread when it holds exactly this weight in this form (csrc/weight_images.hip),
+  // else built here
+  const PdnwDesc key = pdnw_key_rts(a.epi, a.B, a.N, a.nblocks, a.ldb, a.b_block_stride, a.g_off, a.u_off, a.F);
+  RtsWParams w = rts_w_params(key);
+  RtsTemp img;
+  if (!pdnw_lookup(key, stream, &w.wimg, nullptr)) {
+    const int rc = img.get((int64_t)nt * RTS_TILE, stream);
+    if (rc) return rc;
+    w.wimg = static_cast<char*>(img.p);
+    hipLaunchKernelGGL(rts_w_kernel, dim3(nt), dim3(256), 0, st, w);
+  }
   RtsParams p;
   memset(&p, 0, sizeof(p));
   p.A = a.A; p.lda = a.lda; p.wimg = w.wimg; p.C = a.C; p.H = a.H; p.GU = a.GU ? a.GU : a.A; p.ldc = (unsigned)a.ldc; p.ldh = (unsigned)a.ldh;

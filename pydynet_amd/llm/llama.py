@@ -254,10 +254,38 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         # the reference rebuilds an additive -inf mask on the host every call (model.py:199-203);
         # here causality is a flag of the fused attention node and nothing is uploaded.
         mask = True if L > 1 else None
+        # a training pass: the fp16 plane images of all layers' weights in one launch, bound around the layer loop; the
+        # backward forms are left on the pass's last node, where Tensor.backward finds them (core/fused/wimages.py)
+        fwd_images, bwd_images = self._pass_images(h, L) if start_pos == 0 and mask is not None else (None, None)
+        bound = fwd_images is not None and fwd_images.bind()
+        try:
+            for layer in self.layers:
+                h = layer(h, start_pos, mask, cos, sin) if segment_ids is None else \
+                    layer(h, start_pos, mask, cos, sin, segment_ids=segment_ids)
+        finally:
+            if bound:
+                fwd_images.release()
+        out = self.norm(h)
+        if bwd_images is not None and out.requires_grad:
+            out._backward_images = bwd_images
+        return out
+
+    def _pass_images(self, h, L):
+        """(forward, backward) `fused.wimages.ImageSet`s of this training forward over the hidden state `h`, or (None, None)"""
+        wim = fused.wimages
+        T = h.size // h.shape[-1]
+        if not (self._train and is_grad_enable() and h.device.is_hip and h.dtype == np.float32 and T >= wim.min_rows
+                and wim.enabled()):
+            return None, None
+        fwd, bwd, keep = [], [], []
         for layer in self.layers:
-            h = layer(h, start_pos, mask, cos, sin) if segment_ids is None else \
-                layer(h, start_pos, mask, cos, sin, segment_ids=segment_ids)
-        return self.norm(h)
+            att, ffn = layer.attention, layer.ffn
+            ws = [m.weight.data for m in (att.Q, att.K, att.V, att.O, ffn.gate, ffn.up, ffn.down)]
+            f, b = wim.layer_forms(*ws, T, L, att.head_dim)
+            fwd += f
+            bwd += b
+            keep += ws
+        return (wim.ImageSet(fwd, keep) if fwd else None), (wim.ImageSet(bwd, keep) if bwd else None)
 
     def forward_logits(self, input_ids, start_pos: int = 0):
         return self.lm_head(self._forward_hidden(input_ids, start_pos))
