@@ -12,6 +12,7 @@ from .core import (Tensor, add, sub, mul, div, pow, matmul, abs, sum, mean, min,
                    sigmoid, tanh, sqrt, square, vsplit, hsplit, dsplit, split, unsqueeze, squeeze)
 from .special import zeros, ones, rand, randn, empty, uniform
 from .cuda import Device
+from .core.fused.dropout import Generator
 from .autograd import enable_grad, no_grad
 from . import autograd, core, cuda, special, nn, optim  # noqa: F401
 
@@ -19,4 +20,4 @@ __all__ = ["Tensor", "add", "sub", "mul", "div", "pow", "matmul", "abs", "sum", 
            "argmax", "argmin", "maximum", "minimum", "exp", "log", "sign", "reshape", "transpose",
            "swapaxes", "concat", "sigmoid", "tanh", "sqrt", "square", "vsplit", "hsplit", "dsplit",
            "split", "unsqueeze", "squeeze", "zeros", "ones", "rand", "randn", "empty", "uniform",
-           "Device", "enable_grad", "no_grad"]
+           "Device", "Generator", "enable_grad", "no_grad"]

@@ -123,7 +123,8 @@ class Graph:
             g.replay()                  # `loss` (and anything else `step` returned) is overwritten in place
 
     Rules for `step`: everything on the device (no `.item()`, no host arrays turned into device tensors,
-    no dropout drawing host random numbers); tensors it allocates live in a pool private to the graph,
+    no dropout drawing host random numbers: a `Dropout` with a `Generator` is allowed, its mask is drawn on the device and
+    every replay claims a fresh one); tensors it allocates live in a pool private to the graph,
     so the arrays it returns stay valid -- and are rewritten -- across replays.  Optimizers that keep a
     host-side step counter (Adam) switch to a device-side counter while capturing."""
 

@@ -91,7 +91,9 @@ enum {
                                   // per launching pdnf_* entry
   PDN_CNT_STOP_SEQ = 53,          // multi-token stop sequences of a decode step (csrc/stop_seq.hip, include/pdn_stopseq.h): once
                                   // per launching pdnh_* entry
-  PDN_CNT_SLOTS = 54
+  PDN_CNT_DROPOUT = 54,           // dropout with the mask drawn on the device (csrc/dropout.hip, include/pdn_dropout.h): once per
+                                  // launching pdnd_* entry, the set and the claim included
+  PDN_CNT_SLOTS = 55
 };
 void pdn_count(int slot);
 

@@ -208,8 +208,14 @@ class TransformerBlock(nn.Module):
         self.input_norm = nn.RMSNorm(dim, dtype=dtype)
         self.post_attn_norm = nn.RMSNorm(dim, dtype=dtype)
 
-    def forward(self, x, start_pos, mask, freqs_cos, freqs_sin, segment_ids=None):
+    def forward(self, x, start_pos, mask, freqs_cos, freqs_sin, segment_ids=None, drop=None):
         # z = x + attn(norm(x)); out = z + ffn(norm(z)) -- both adds ride in the GEMM epilogues
+        if drop is not None:
+            # residual dropout, drop = (p, generator): z = x + dropout(attn(norm(x))); out = z + dropout(ffn(norm(z))).  The O
+            # and down projections run without the residual epilogue; the add rides in the dropout kernel (fused.dropout_add)
+            kw = {} if segment_ids is None else {"segment_ids": segment_ids}
+            z = fused.dropout_add(self.attention(self.input_norm(x), start_pos, mask, freqs_cos, freqs_sin, **kw), x, *drop)
+            return fused.dropout_add(self.ffn(self.post_attn_norm(z)), z, *drop)
         if segment_ids is None:
             z = self.attention(self.input_norm(x), start_pos, mask, freqs_cos, freqs_sin, residual=x)
         else:
@@ -223,8 +229,18 @@ class TransformerBlock(nn.Module):
 
 class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
     def __init__(self, vocab_size, embed_dim, n_heads, ffn_dim, max_seq_len, max_batch_size=None,
-                 n_layers=6, dtype=None):
+                 n_layers=6, dtype=None, *, dropout=0.0, generator=None):
         super().__init__()
+        # embedding and residual dropout, in training mode only, the masks drawn on the device from `generator`
+        # (core/fused/dropout.py; no counterpart in the reference).  Without one the model keeps a Generator(0) of its own on
+        # whichever device it is moved to: a move starts that generator at (0, 0) again, and replicas built this way (data
+        # parallel) all draw the same masks -- give each its own `generator` where that matters.  `score` runs without dropout
+        # and claims nothing.  dropout == 0.0: the model is the reference's, launch for launch
+        if not 0 <= dropout < 1:
+            raise ValueError(f"dropout must lie in [0, 1), got {dropout}")
+        self.dropout, self.generator, self._own_generator = float(dropout), generator, generator is None
+        if self._own_generator and self.dropout > 0:
+            self.generator = fused.Generator(0)
         self.vocab_size, self.embed_dim, self.n_heads, self.ffn_dim = vocab_size, embed_dim, n_heads, ffn_dim
         self.max_seq_len, self.max_batch_size, self.n_layers = max_seq_len, max_batch_size, n_layers
         self.tok_embedding = nn.Embedding(vocab_size, embed_dim, dtype=dtype)
@@ -237,9 +253,20 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         self.norm = nn.RMSNorm(embed_dim, dtype=dtype)
         self.lm_head = nn.Linear(embed_dim, vocab_size, dtype=dtype)      # bias=True, as the reference
 
+    _inference_pass = False           # set by `score` around its pass: training mode without dropout
+
+    def move(self, device):
+        super().move(device)
+        if self._own_generator and self.dropout > 0:
+            self.generator = fused.Generator(0, device)
+        return self
+
     def _forward_hidden(self, input_ids, start_pos: int, segment_ids=None):
         L = input_ids.shape[-1]
         h = self.tok_embedding(input_ids)
+        drop = (self.dropout, self.generator) if self.dropout > 0 and self._train and not self._inference_pass else None
+        if drop is not None:
+            h = fused.dropout(h, *drop)
         if segment_ids is not None:
             # packed rows: the documents' bounds once per step, shared by every layer (core/fused/segments.py)
             if not self._train or start_pos != 0:
@@ -260,6 +287,9 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         bound = fwd_images is not None and fwd_images.bind()
         try:
             for layer in self.layers:
+                if drop is not None:
+                    h = layer(h, start_pos, mask, cos, sin, segment_ids=segment_ids, drop=drop)
+                    continue
                 h = layer(h, start_pos, mask, cos, sin) if segment_ids is None else \
                     layer(h, start_pos, mask, cos, sin, segment_ids=segment_ids)
         finally:
@@ -473,10 +503,12 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         dev = self.tok_embedding.weight.device
         try:
             self.train(True)
+            self._inference_pass = True           # (training mode borrowed for an inference pass: no dropout, nothing claimed)
             with no_grad():
                 logits = self.forward_logits(Tensor(ids[:, :-1], dtype=np.int64, device=dev), 0)
                 lp = self._logprobs_rows(logits.reshape(B * (L - 1), self.vocab_size), ids[:, 1:].reshape(-1), n)
         finally:
+            self._inference_pass = False
             self.train(mode)
         return lp_np.Logprobs(lp.token.reshape(B, L - 1), lp.top_ids.reshape(B, L - 1, n),
                               lp.top_logprobs.reshape(B, L - 1, n))
