@@ -8,6 +8,7 @@ import os
 
 import numpy as np
 
+from . import gqa as _gqa
 from . import segments as _seg
 from .norm import rms_norm
 from ..tensor import Tensor, _Operator
@@ -51,6 +52,19 @@ def _key_bias_of(mask, B, H, Lq, Lk):
 
 
 _STREAM_MAX_BH = 65535     # kMaxGridY of csrc/attention_stream.hip
+
+
+def _expand_heads(x, G):
+    """(B, L, Hkv, hd) device array -> a contiguous (B, L, Hkv * G, hd) copy, head j repeated G times (gqa.expand)."""
+    hp = _hip()
+    B, Lx, Hkv, hd = x.shape
+    return hp.broadcast_to(x.reshape(B, Lx, Hkv, 1, hd), (B, Lx, Hkv, G, hd)).copy().reshape(B, Lx, Hkv * G, hd)
+
+
+def _reduce_heads(dx, G):
+    """The transpose of `_expand_heads`: summed over each group (gqa.reduce_groups)."""
+    B, Lx, H, hd = dx.shape
+    return _contig(dx).reshape(B, Lx, H // G, G, hd).sum(3)
 
 
 def _attn_kernel(B, H, hd, Lq, Lk, start_pos, mask, layouts):
@@ -122,7 +136,9 @@ def _segment_mask(seg, Lq):
 class attention(_Operator):
     """softmax(q k^T / sqrt(hd) + causal_mask + mask) v  per (batch, head).
 
-    q: (B, L, H, hd); k, v: (B, Lk, H, hd) -- the layout the Q/K/V projections produce, consumed
+    q: (B, L, H, hd); k, v: (B, Lk, Hkv, hd), Hkv == H or a divisor of it (grouped-query attention: query head h reads
+    key/value head h // (H // Hkv), core/fused/gqa.py; on a HIP device the shared-K/V kernels of include/pdn_gqattn.h for
+    group sizes 2 .. 8, any other grouped call on the multi-head paths over a repeated copy) -- the layout the Q/K/V projections produce, consumed
     through strides (no transposes, no copies; views into a packed QKV projection or a KV cache are
     fine).  Output (B, L, H, hd).  `causal` applies the additive -inf upper-triangular mask of
     llm/llama/model.py:199-203 with `start_pos`; `mask` is an optional constant additive mask
@@ -134,12 +150,17 @@ class attention(_Operator):
 
     use_flash = True      # class switch: False forces the GEMM + softmax path (A/B and tests)
     use_resident = True   # class switch: False sends the benchmark shape through the streaming kernels too
+    use_gqa = True        # class switch: False runs grouped-query calls on the multi-head paths over repeated K / V (A/B)
 
     def __init__(self, q, k, v, causal=True, start_pos=0, mask=None, segment_ids=None):
         self.causal, self.start_pos = bool(causal), int(start_pos)
         self._mask = mask.data if isinstance(mask, Tensor) else mask
         self._kind = None
+        self._kv_x = None                 # K / V repeated along the head axis, where a grouped call runs on the multi-head paths
         self._segments = segment_ids
+        G = _gqa.group_size(q.shape[2], k.shape[2])
+        if G > 1 and segment_ids is not None:
+            raise ValueError("attention: segment_ids are not supported with fewer key/value heads than query heads")
         if segment_ids is not None and (not self.causal or self.start_pos != 0 or q.shape[1] != k.shape[1]):
             raise ValueError("attention: segment_ids need causal=True, start_pos=0 and as many keys as queries")
         super().__init__(q, k, v)
@@ -165,19 +186,33 @@ class attention(_Operator):
 
     def forward_(self, q, k, v):
         B, Lq, H, hd = q.shape
-        Lk = k.shape[1]
+        kd, vd = k.data, v.data
+        G = H // kd.shape[2]
+        self._kv_x = None
+        if G > 1 and self.xp is not np:
+            out = self._gqa_forward(q, k, v)
+            if out is not None:
+                return out
+        if G > 1:
+            # grouped heads on the paths below: K / V repeated along the head axis, dk / dv summed over the group in backward
+            if self.xp is np:
+                kd, vd = _gqa.expand(kd, G), _gqa.expand(vd, G)
+            else:
+                kd, vd = _expand_heads(kd, G), _expand_heads(vd, G)
+            self._kv_x = (kd, vd)
+        Lk = kd.shape[1]
         if self.xp is np:
-            s = np.matmul(q.data.transpose(0, 2, 1, 3), k.data.transpose(0, 2, 3, 1)) / np.asarray(math.sqrt(hd), q.dtype)
+            s = np.matmul(q.data.transpose(0, 2, 1, 3), kd.transpose(0, 2, 3, 1)) / np.asarray(math.sqrt(hd), q.dtype)
             add = self._np_mask(Lq, Lk, q.dtype, B)
             if add is not None:
                 s = s + add
             e = np.exp(s - s.max(-1, keepdims=True))
             self._p = e / e.sum(-1, keepdims=True)
-            return np.ascontiguousarray(np.matmul(self._p, v.data.transpose(0, 2, 1, 3)).transpose(0, 2, 1, 3))
+            return np.ascontiguousarray(np.matmul(self._p, vd.transpose(0, 2, 1, 3)).transpose(0, 2, 1, 3))
         _require_f32(self, q, k, v)
         hp, L = _hip(), _L()
         causal = 1 if (self.causal and Lq > 1) else 0
-        layouts = (_attn_layout(q.data), _attn_layout(k.data), _attn_layout(v.data))
+        layouts = (_attn_layout(q.data), _attn_layout(kd), _attn_layout(vd))
         mask_dev = hp.asarray(self._mask) if self._mask is not None else None
         if self._segments is not None:
             seg = self._bounds(B, Lq, True)
@@ -187,8 +222,8 @@ class attention(_Operator):
                 rs, bs = layouts[0]
                 out = hp.empty((B, Lq, H, hd), np.float32)
                 self._lse = hp.empty((B, H, Lq), np.float32)
-                self._res = (q.data, k.data, v.data, seg, rs, bs)
-                L.call("pdns_attention_fwd_f32", q.data._ptr, k.data._ptr, v.data._ptr, out._ptr, self._lse._ptr,
+                self._res = (q.data, kd, vd, seg, rs, bs)
+                L.call("pdns_attention_fwd_f32", q.data._ptr, kd._ptr, vd._ptr, out._ptr, self._lse._ptr,
                        B, H, Lq, hd, rs, bs, H * hd, Lq * H * hd, None, None, seg.start._ptr, hp.stream())
                 return out
             # any other shape: the block mask as an additive mask of the existing paths
@@ -198,7 +233,7 @@ class attention(_Operator):
         self._kind, kb = _attn_kernel(B, H, hd, Lq, Lk, self.start_pos, mask_dev, layouts)
         if self._kind == "resident":
             # scores stay in registers: one kernel, nothing of size L x L in HBM; lse kept for backward
-            qd, kd, vd = q.data, k.data, v.data
+            qd = q.data
             rs, bs = layouts[0]
             out = hp.empty((B, Lq, H, hd), np.float32)
             self._lse = hp.empty((B, H, Lq), np.float32)
@@ -223,12 +258,12 @@ class attention(_Operator):
             else:
                 self._q_used = q.data
             self._lay = layouts
-            L.call("pdn_attention_stream_fwd_f32", self._q_used._ptr, k.data._ptr, v.data._ptr, out._ptr,
+            L.call("pdn_attention_stream_fwd_f32", self._q_used._ptr, kd._ptr, vd._ptr, out._ptr,
                    self._lse._ptr, B, H, Lq, Lk, hd, layouts[0][0], layouts[0][1], layouts[1][0], layouts[1][1],
                    causal, self.start_pos, mp, sb, sh, sq, sk, None, None, hp.stream())
             return out
         p = hp.empty((B, H, Lq, Lk), np.float32)
-        hp.gemm(q.data.transpose(0, 2, 1, 3), k.data.transpose(0, 2, 3, 1), p)
+        hp.gemm(q.data.transpose(0, 2, 1, 3), kd.transpose(0, 2, 3, 1), p)
         div = math.sqrt(hd)
         if mask_dev is not None:
             p = p / np.float32(div) + mask_dev.astype(np.float32)
@@ -237,13 +272,70 @@ class attention(_Operator):
                Lq if causal else 0, self.start_pos, hp.stream())
         self._p = p
         out = hp.empty((B, Lq, H, hd), np.float32)
-        hp.gemm(p, v.data.transpose(0, 2, 1, 3), out.transpose(0, 2, 1, 3))
+        hp.gemm(p, vd.transpose(0, 2, 1, 3), out.transpose(0, 2, 1, 3))
         return out
 
     def backward_all(self, do):
         q, k, v = self.last
+        if self.xp is not np and self._kind == "gqa":
+            return self._gqa_backward(do, q, k.data, v.data)
+        if self._kv_x is None:
+            return self._backward(do, q, k.data, v.data)
+        G = q.shape[2] // k.shape[2]
+        kd, vd = self._kv_x
+        self._kv_x = None
+        dq, dk, dv = self._backward(do, q, kd, vd)
+        if self.xp is np:
+            return [dq, _gqa.reduce_groups(dk, G), _gqa.reduce_groups(dv, G)]
+        return [dq, _reduce_heads(dk, G), _reduce_heads(dv, G)]
+
+    def _gqa_forward(self, q, k, v):
+        """The shared-K/V kernels of include/pdn_gqattn.h where they take the call (`_kind` "gqa"), else None."""
+        _require_f32(self, q, k, v)
+        kd, vd = k.data, v.data
         B, Lq, H, hd = q.shape
-        Lk = k.shape[1]
+        Lk, Hkv = kd.shape[1], kd.shape[2]
+        hp, L = _hip(), _L()
+        lays = (_attn_layout(q.data), _attn_layout(kd), _attn_layout(vd))
+        if not (attention.use_flash and attention.use_gqa and None not in lays and lays[1] == lays[2] and B * Hkv <= _STREAM_MAX_BH
+                and _provides("pdnk_attention_supported")
+                and L.query("pdnk_attention_supported", hd, H, Hkv)):
+            return None
+        self._kind = "gqa"
+        mask_dev = hp.asarray(self._mask) if self._mask is not None else None
+        self._mask_eff = mask_dev
+        causal = 1 if (self.causal and Lq > 1) else 0
+        out = hp.empty((B, Lq, H, hd), np.float32)
+        self._lse = hp.empty((B, H, Lq), np.float32)
+        mp, sb, sh, sq, sk, self._mask_dev = _attn_mask_args(mask_dev, B, H, Lq, Lk)
+        # the output is written with the QUERY strides: give the kernel a q-shaped contiguous view
+        self._q_used = q.data if lays[0] == (H * hd, Lq * H * hd if B > 1 else 0) else q.data.copy()
+        qlay = _attn_layout(self._q_used)
+        L.call("pdnk_attention_fwd_f32", self._q_used._ptr, kd._ptr, vd._ptr, out._ptr, self._lse._ptr, B, H, Hkv, Lq, Lk,
+               hd, qlay[0], qlay[1], lays[1][0], lays[1][1], causal, self.start_pos, mp, sb, sh, sq, sk, hp.stream())
+        return out
+
+    def _gqa_backward(self, do, q, kd, vd):
+        B, Lq, H, hd = q.shape
+        Lk, Hkv = kd.shape[1], kd.shape[2]
+        hp, L = _hip(), _L()
+        causal = 1 if (self.causal and Lq > 1) else 0
+        do = _contig(do)
+        dq = hp.empty(q.shape, np.float32)
+        # dk / dv are written with the key strides: contiguous gradients need contiguous k / v
+        ksrc, vsrc = _contig(kd), _contig(vd)
+        dk, dv = hp.empty(kd.shape, np.float32), hp.empty(vd.shape, np.float32)
+        mp, sb, sh, sq, sk, keep = _attn_mask_args(self._mask_dev, B, H, Lq, Lk) \
+            if self._mask_eff is not None else (None, 0, 0, 0, 0, None)
+        ws, wsb = hp.workspace(L.query("pdnk_attention_bwd_workspace_bytes", B, H, Lq))
+        L.call("pdnk_attention_bwd_f32", self._q_used._ptr, ksrc._ptr, vsrc._ptr, self.data._ptr, do._ptr, self._lse._ptr,
+               dq._ptr, dk._ptr, dv._ptr, B, H, Hkv, Lq, Lk, hd, H * hd, Lq * H * hd if B > 1 else 0, Hkv * hd,
+               Lk * Hkv * hd if B > 1 else 0, causal, self.start_pos, mp, sb, sh, sq, sk, ws, wsb, hp.stream())
+        return [dq, dk, dv]
+
+    def _backward(self, do, q, kd, vd):
+        B, Lq, H, hd = q.shape
+        Lk = kd.shape[1]
         causal = 1 if (self.causal and Lq > 1) else 0
         if self.xp is not np and self._kind == "segmented":
             hp, L = _hip(), _L()
@@ -286,8 +378,8 @@ class attention(_Operator):
             do = _contig(do)
             dq = hp.empty(q.shape, np.float32)
             # dk / dv are written with the key strides: contiguous gradients need contiguous k / v
-            ksrc, vsrc = _contig(k.data), _contig(v.data)
-            dk, dv = hp.empty(k.shape, np.float32), hp.empty(v.shape, np.float32)
+            ksrc, vsrc = _contig(kd), _contig(vd)
+            dk, dv = hp.empty(kd.shape, np.float32), hp.empty(vd.shape, np.float32)
             klay = (H * hd, Lk * H * hd if B > 1 else 0)
             mp, sb, sh, sq, sk, keep = _attn_mask_args(self._mask_dev, B, H, Lq, Lk) \
                 if self._mask_eff is not None else (None, 0, 0, 0, 0, None)
@@ -302,20 +394,20 @@ class attention(_Operator):
         if self.xp is np:
             doT = do.transpose(0, 2, 1, 3)
             dv = np.matmul(p.swapaxes(-1, -2), doT).transpose(0, 2, 1, 3)
-            dp = np.matmul(doT, v.data.transpose(0, 2, 3, 1))
+            dp = np.matmul(doT, vd.transpose(0, 2, 3, 1))
             ds = (dp - (dp * p).sum(-1, keepdims=True)) * p / np.asarray(math.sqrt(hd), q.dtype)
-            dq = np.matmul(ds, k.data.transpose(0, 2, 1, 3)).transpose(0, 2, 1, 3)
+            dq = np.matmul(ds, kd.transpose(0, 2, 1, 3)).transpose(0, 2, 1, 3)
             dk = np.matmul(ds.swapaxes(-1, -2), q.data.transpose(0, 2, 1, 3)).transpose(0, 2, 1, 3)
             return [dq, dk, dv]
         hp, L = _hip(), _L()
         doT = do.transpose(0, 2, 1, 3)
-        dv = hp.empty(v.shape, np.float32)
+        dv = hp.empty(vd.shape, np.float32)
         hp.gemm(p.swapaxes(-1, -2), doT, dv.transpose(0, 2, 1, 3))                  # P^T dO
         dp = hp.empty(p.shape, np.float32)
-        hp.gemm(doT, v.data.transpose(0, 2, 3, 1), dp)                              # dO V^T
+        hp.gemm(doT, vd.transpose(0, 2, 3, 1), dp)                              # dO V^T
         L.call("pdn_softmax_bwd_f32", p._ptr, dp._ptr, dp._ptr, B * H * Lq, Lk, math.sqrt(hd), hp.stream())
-        dq, dk = hp.empty(q.shape, np.float32), hp.empty(k.shape, np.float32)
-        hp.gemm(dp, k.data.transpose(0, 2, 1, 3), dq.transpose(0, 2, 1, 3))         # dS K
+        dq, dk = hp.empty(q.shape, np.float32), hp.empty(kd.shape, np.float32)
+        hp.gemm(dp, kd.transpose(0, 2, 1, 3), dq.transpose(0, 2, 1, 3))         # dS K
         hp.gemm(dp.swapaxes(-1, -2), q.data.transpose(0, 2, 1, 3), dk.transpose(0, 2, 1, 3))  # dS^T Q
         return [dq, dk, dv]
 

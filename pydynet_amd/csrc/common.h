@@ -93,7 +93,9 @@ enum {
                                   // per launching pdnh_* entry
   PDN_CNT_DROPOUT = 54,           // dropout with the mask drawn on the device (csrc/dropout.hip, include/pdn_dropout.h): once per
                                   // launching pdnd_* entry, the set and the claim included
-  PDN_CNT_SLOTS = 55
+  PDN_CNT_ATT_GQA = 55,           // grouped-query attention (csrc/attention_gqa.hip, include/pdn_gqattn.h): once per launching
+                                  // pdnk_* entry, either direction
+  PDN_CNT_SLOTS = 56
 };
 void pdn_count(int slot);
 

@@ -47,8 +47,9 @@ _LP_RING = 8
 class DecodePlan:
     def _fast_path(self, dev):
         """Whether generation on device `dev` takes the HIP decode fast path: fast_decode on, a HIP device, inference
-        mode, float32 weights and a head dimension the kernels' float4 loads take."""
-        return bool(type(self).fast_decode and dev.is_hip and not self._train
+        mode, float32 weights, a head dimension the kernels' float4 loads take and as many key/value heads as query heads
+        (a grouped-query model decodes on the tape-node path)."""
+        return bool(type(self).fast_decode and dev.is_hip and not self._train and self.n_kv_heads == self.n_heads
                     and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
 
     def _head_bias(self):

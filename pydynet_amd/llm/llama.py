@@ -51,6 +51,16 @@ def apply_rotary_emb(xq, xk, freqs_cos, freqs_sin):
     return fused.rope(xq, freqs_cos, freqs_sin), fused.rope(xk, freqs_cos, freqs_sin)
 
 
+def check_kv_heads(n_heads, n_kv_heads):
+    """The key/value head count of a model with `n_heads` query heads: `n_kv_heads`, or n_heads for None; ValueError
+    unless it is a positive divisor of n_heads."""
+    if n_kv_heads is None:
+        return n_heads
+    if not isinstance(n_kv_heads, (int, np.integer)) or n_kv_heads < 1 or n_heads % n_kv_heads:
+        raise ValueError(f"n_kv_heads must be a positive divisor of n_heads = {n_heads}, got {n_kv_heads!r}")
+    return int(n_kv_heads)
+
+
 class FeedForward(nn.Module):
     def __init__(self, dim, up_dim, dtype=None):
         super().__init__()
@@ -92,17 +102,21 @@ class FeedForward(nn.Module):
 
 
 class Attention(nn.Module):
-    def __init__(self, dim, n_heads, max_seq_len, max_batch_size=None, dtype=None):
+    def __init__(self, dim, n_heads, max_seq_len, max_batch_size=None, dtype=None, *, n_kv_heads=None):
         super().__init__()
         assert dim % n_heads == 0
         self.dim, self.n_heads, self.head_dim = dim, n_heads, dim // n_heads
+        # grouped-query attention: n_kv_heads < n_heads key/value heads, query head h reads head h // (n_heads // n_kv_heads)
+        # (core/fused/gqa.py).  K, V and the caches shrink with it; the default is multi-head attention, the reference's
+        self.n_kv_heads = check_kv_heads(n_heads, n_kv_heads)
+        kv_dim = self.n_kv_heads * self.head_dim
         self.Q = nn.Linear(dim, dim, bias=False, dtype=dtype)
-        self.K = nn.Linear(dim, dim, bias=False, dtype=dtype)
-        self.V = nn.Linear(dim, dim, bias=False, dtype=dtype)
+        self.K = nn.Linear(dim, kv_dim, bias=False, dtype=dtype)
+        self.V = nn.Linear(dim, kv_dim, bias=False, dtype=dtype)
         self.O = nn.Linear(dim, dim, bias=False, dtype=dtype)
         self.max_seq_len = max_seq_len
         self.max_batch_size = max_batch_size if max_batch_size is not None else 1
-        shape = (self.max_batch_size, max_seq_len, n_heads, self.head_dim)
+        shape = (self.max_batch_size, max_seq_len, self.n_kv_heads, self.head_dim)
         self.cache_k = nn.Parameter(zeros(shape, dtype=dtype), requires_grad=False)
         self.cache_v = nn.Parameter(zeros(shape, dtype=dtype), requires_grad=False)
 
@@ -116,6 +130,8 @@ class Attention(nn.Module):
         """Re-home the Q/K/V weights in one (3, dim, dim) buffer: each stays a contiguous Parameter,
         and being equally spaced lets the three projections run as one batched GEMM."""
         from .. import hipnp as hp
+        if self.n_kv_heads != self.n_heads:       # K / V are narrower than Q: nothing to stack
+            return
         ws = [self.Q.weight, self.K.weight, self.V.weight]
         st = hp.stacked_view([w.data for w in ws])
         if st is not None and st._strides[0] == ws[0].data.size:      # already adjacent, in order
@@ -127,10 +143,10 @@ class Attention(nn.Module):
 
     def __call__(self, x, start_pos, mask, freqs_cos, freqs_sin, residual=None, segment_ids=None):
         B, L, _ = x.shape
-        H, hd = self.n_heads, self.head_dim
+        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
         if segment_ids is not None:
             return self._segmented(x, start_pos, mask, freqs_cos, freqs_sin, residual, segment_ids)
-        if (self._train and start_pos == 0 and mask is not None and is_grad_enable()
+        if (self._train and start_pos == 0 and mask is not None and is_grad_enable() and Hkv == H
                 and fused.qkv_attention.applicable(x, L, hd)):
             out = fused.qkv_attention(x, self.Q.weight, self.K.weight, self.V.weight, freqs_cos, freqs_sin, H)
             out = out.reshape(B, L, -1)
@@ -138,8 +154,8 @@ class Attention(nn.Module):
                 return self.O(out)
             return fused.linear(out, self.O.weight, None, residual)
         xq = self.Q(x).reshape(B, L, H, hd)
-        xk = self.K(x).reshape(B, L, H, hd)
-        xv = self.V(x).reshape(B, L, H, hd)
+        xk = self.K(x).reshape(B, L, Hkv, hd)
+        xv = self.V(x).reshape(B, L, Hkv, hd)
         xq, xk = apply_rotary_emb(xq, xk, freqs_cos, freqs_sin)
         if not self._train:                       # KV cache: inference only (model.py:105-110)
             self.cache_k[:B, start_pos:start_pos + L] = xk
@@ -158,6 +174,8 @@ class Attention(nn.Module):
         mask."""
         B, L, _ = x.shape
         H, hd = self.n_heads, self.head_dim
+        if self.n_kv_heads != H:
+            raise ValueError("segment_ids (packed rows) are not supported with n_kv_heads < n_heads")
         if not self._train or start_pos != 0 or mask is None:
             raise ValueError("segment_ids are for training passes over whole rows (train mode, start_pos 0, more than one position)")
         if is_grad_enable() and fused.qkv_attention.applicable(x, L, hd, segment_ids):
@@ -179,15 +197,15 @@ class Attention(nn.Module):
         computed at position 0 and its cache left alone).  Built from the operators above: RoPE with the cos / sin row of
         each row's position, the cache written at (b, pos[b]), attention over the cache with -inf for keys j > pos[b]."""
         B = x.shape[0]
-        H, hd = self.n_heads, self.head_dim
+        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
         p = np.maximum(pos, 0)
         xq = self.Q(x).reshape(B, 1, H, hd)
-        xk = self.K(x).reshape(B, 1, H, hd)
-        xv = self.V(x).reshape(B, 1, H, hd)
+        xk = self.K(x).reshape(B, 1, Hkv, hd)
+        xv = self.V(x).reshape(B, 1, Hkv, hd)
         # the B rows as one sequence of B positions: RoPE takes one (cos, sin) row per position
         cos, sin = freqs_cos[p], freqs_sin[p]
         xq = fused.rope(xq.reshape(1, B, H, hd), cos, sin).reshape(B, 1, H, hd)
-        xk = fused.rope(xk.reshape(1, B, H, hd), cos, sin).reshape(B, 1, H, hd)
+        xk = fused.rope(xk.reshape(1, B, Hkv, hd), cos, sin).reshape(B, 1, Hkv, hd)
         for b in np.flatnonzero(pos >= 0):
             self.cache_k[int(b), int(p[b])] = xk[int(b), 0]
             self.cache_v[int(b), int(p[b])] = xv[int(b), 0]
@@ -201,9 +219,9 @@ class Attention(nn.Module):
 
 
 class TransformerBlock(nn.Module):
-    def __init__(self, dim, n_heads, ffn_dim, max_seq_len, max_batch_size=None, dtype=None):
+    def __init__(self, dim, n_heads, ffn_dim, max_seq_len, max_batch_size=None, dtype=None, *, n_kv_heads=None):
         super().__init__()
-        self.attention = Attention(dim, n_heads, max_seq_len, max_batch_size, dtype)
+        self.attention = Attention(dim, n_heads, max_seq_len, max_batch_size, dtype, n_kv_heads=n_kv_heads)
         self.ffn = FeedForward(dim, ffn_dim, dtype)
         self.input_norm = nn.RMSNorm(dim, dtype=dtype)
         self.post_attn_norm = nn.RMSNorm(dim, dtype=dtype)
@@ -229,8 +247,12 @@ class TransformerBlock(nn.Module):
 
 class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
     def __init__(self, vocab_size, embed_dim, n_heads, ffn_dim, max_seq_len, max_batch_size=None,
-                 n_layers=6, dtype=None, *, dropout=0.0, generator=None):
+                 n_layers=6, dtype=None, *, dropout=0.0, generator=None, n_kv_heads=None):
         super().__init__()
+        # n_kv_heads (a divisor of n_heads; default n_heads): grouped-query attention, as every Llama since Llama 2-70B
+        # (`Attention`).  Training, scoring and every generation entry take such a model; its decode steps run on the
+        # tape-node path, not in the graph-replayed step.  Left at its default the model is the reference's, launch for launch
+        self.n_kv_heads = check_kv_heads(n_heads, n_kv_heads)
         # embedding and residual dropout, in training mode only, the masks drawn on the device from `generator`
         # (core/fused/dropout.py; no counterpart in the reference).  Without one the model keeps a Generator(0) of its own on
         # whichever device it is moved to: a move starts that generator at (0, 0) again, and replicas built this way (data
@@ -248,7 +270,7 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         self.freqs_cos = nn.Parameter(cos, False)
         self.freqs_sin = nn.Parameter(sin, False)
         self.layers = nn.ModuleList([
-            TransformerBlock(embed_dim, n_heads, ffn_dim, max_seq_len, max_batch_size, dtype)
+            TransformerBlock(embed_dim, n_heads, ffn_dim, max_seq_len, max_batch_size, dtype, n_kv_heads=self.n_kv_heads)
             for _ in range(n_layers)])
         self.norm = nn.RMSNorm(embed_dim, dtype=dtype)
         self.lm_head = nn.Linear(embed_dim, vocab_size, dtype=dtype)      # bias=True, as the reference
@@ -305,7 +327,7 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         wim = fused.wimages
         T = h.size // h.shape[-1]
         if not (self._train and is_grad_enable() and h.device.is_hip and h.dtype == np.float32 and T >= wim.min_rows
-                and wim.enabled()):
+                and wim.enabled() and self.n_kv_heads == self.n_heads):     # (the image forms take square K / V weights)
             return None, None
         fwd, bwd, keep = [], [], []
         for layer in self.layers:
