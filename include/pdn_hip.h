@@ -250,7 +250,9 @@ int pdn_qkv_rope_norm_fwd_f32(const float* x, const float* norm_w, float eps, fl
  *  54 dropout with the mask drawn on the device (csrc/dropout.hip): once per launch of pdnd_rng_set, pdnd_rng_claim and
  *     the three pdnd_dropout_* entries of include/pdn_dropout.h
  *  55 grouped-query attention (csrc/attention_gqa.hip): once per pdnk_attention_fwd_f32 and pdnk_attention_bwd_f32 of
- *     include/pdn_gqattn.h */
+ *     include/pdn_gqattn.h
+ *  56 decode attention of a grouped-query model (csrc/decode_gqa.hip): once per pdnj_decode_attention_f32 of
+ *     include/pdn_gqdecode.h */
 int pdn_kernel_counters(int64_t* out, int n, int reset);
 /* Round 5: which kernel the row-resident entry points below and above launch.  The tile-piece kernel
  * (csrc/gemm_rowtile.hip: one 32-column tile of B over the whole contraction per piece, rotating accumulator sets, stores

@@ -95,7 +95,9 @@ enum {
                                   // launching pdnd_* entry, the set and the claim included
   PDN_CNT_ATT_GQA = 55,           // grouped-query attention (csrc/attention_gqa.hip, include/pdn_gqattn.h): once per launching
                                   // pdnk_* entry, either direction
-  PDN_CNT_SLOTS = 56
+  PDN_CNT_DECODE_GQA = 56,        // decode attention of a grouped-query model (csrc/decode_gqa.hip, include/pdn_gqdecode.h):
+                                  // once per pdnj_decode_attention_f32 launch
+  PDN_CNT_SLOTS = 57
 };
 void pdn_count(int slot);
 

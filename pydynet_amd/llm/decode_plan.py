@@ -40,6 +40,9 @@ _STOPSEQ_ENTRIES = ("pdnh_stop_reset", "pdnh_stop_step")
 _PERSAMPLE_ENTRIES = ("pdnq_sample_rows_f32", "pdnq_decode_sample_tick_rows_f32", "pdnq_decode_sample_tick_slots_f32",
                       "pdnq_decode_wide_sample_tick_rows_f32", "pdnq_decode_wide_sample_tick_slots_f32",
                       "pdnq_spec_verify_sample_tick_f32")
+# the entry points of a grouped-query model's decode attention (csrc/decode_gqa.hip, include/pdn_gqdecode.h): without them
+# the plan refuses a grouped model, which then decodes on the tape-node path
+_GQA_ENTRIES = ("pdnj_decode_attention_supported", "pdnj_decode_attention_f32")
 # ring slots of the log-probability records of a decode plan (csrc/logprobs.hip): more than the steps ever in flight
 _LP_RING = 8
 
@@ -51,6 +54,19 @@ class DecodePlan:
         (a grouped-query model decodes on the tape-node path)."""
         return bool(type(self).fast_decode and dev.is_hip and not self._train and self.n_kv_heads == self.n_heads
                     and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
+
+    def _grouped_path(self, dev, B, **plan):
+        """Whether a grouped-query model (n_kv_heads < n_heads) takes the graph-replayed step for `B` rows on `dev`: the
+        conditions of `_fast_path` but the head counts, and a plan that accepts -- `plan`: the arguments the step will
+        hand to `_decode_plan`, which is asked itself (and keeps the plan it built), so this is True exactly when the step
+        finds a plan.  The plan's fallback, the generic launches, is multi-head only: where this is False the model takes
+        the tape-node step.  `generate` and `generate_ragged` alone ask; serve, chunked prefill, speculative decoding,
+        beam search and the prefix cache assume key/value rows as wide as the model and stay behind `_fast_path`."""
+        if not (type(self).fast_decode and dev.is_hip and not self._train and self.n_kv_heads != self.n_heads
+                and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0):
+            return False
+        cache = self.layers[0].attention.cache_k
+        return B <= cache.shape[0] and self._decode_plan(B, **plan) is not None
 
     def _head_bias(self):
         """The address of the lm_head bias, or None for a head without one."""
@@ -108,6 +124,10 @@ class DecodePlan:
         `ss_tail`, min_new_tokens in `ss_min`.  None when the library lacks the entries."""
         from .. import hipnp as hp, _lib
         D, H, F, V = self.embed_dim, self.n_heads, self.ffn_dim, self.vocab_size
+        # a grouped-query model (Hkv < H key/value heads): q | k | v rows of D + 2 KVD floats, projected in two launches
+        # (Q and K | V have different row strides), the attention of csrc/decode_gqa.hip, never the fused / block forms
+        Hkv, gqa = self.n_kv_heads, self.n_kv_heads != self.n_heads
+        KVD = Hkv * (D // H)
         st = getattr(self, "_decode_st", None)
         # a captured step (and the stacked weight views) hold the address of EVERY array the launches read: the key
         # covers them all -- rebinding `.data` of any parameter / cache re-plans -- and the switches that shape the plan
@@ -131,6 +151,11 @@ class DecodePlan:
         if wide:
             # (the merge of the key-range partials happens in the output projection's load: at most 8 ranges)
             ok = int(os.environ.get("PDN_DECODE_SPLITS", "0") or 0) <= 8
+        # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
+        ns = int(os.environ.get("PDN_DECODE_SPLITS", "0")) or (1 if cache_len <= 256 else 4)
+        if gqa and not (all(_lib.provides(n) for n in _GQA_ENTRIES) and not beam and not serve
+                        and _lib.lib().query("pdnj_decode_attention_supported", H, Hkv, D // H, ns, cache_len)):
+            ok = False
         if penalty and not all(_lib.provides(n) for n in _PEN_ENTRIES):
             ok = False
         if edit and not all(_lib.provides(n) for n in _EDIT_ENTRIES):
@@ -145,23 +170,25 @@ class DecodePlan:
         if ok:
             for layer in self.layers:
                 a, f = layer.attention, layer.ffn
-                qkv = hp.stacked_view([a.Q.weight.data, a.K.weight.data, a.V.weight.data])
+                # (a grouped model: the stacked K | V alone, Attention._pack_qkv; Q is read where it lies)
+                qkv = hp.stacked_view([a.K.weight.data, a.V.weight.data] if gqa else
+                                      [a.Q.weight.data, a.K.weight.data, a.V.weight.data])
                 gu = hp.stacked_view([f.gate.weight.data, f.up.weight.data])
-                mats = (a.O.weight.data, f.down.weight.data)
+                mats = (a.O.weight.data, f.down.weight.data) + ((a.Q.weight.data,) if gqa else ())
+                if gqa and qkv is not None and qkv._strides[0] < 0:
+                    qkv = None
                 if qkv is None or gu is None or not all(m.is_contiguous() for m in mats):    # (block strides may be < 0)
                     ok = False
                     break
                 packs.append((qkv, gu))
             ok = ok and self.lm_head.weight.data.is_contiguous() and self.tok_embedding.weight.data.is_contiguous()
         st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged), "serve": bool(serve),
-              "wide": wide, "rows": bool(ragged or wide), "beam": int(beam),
+              "wide": wide, "rows": bool(ragged or wide), "beam": int(beam), "gqa": gqa,
               "full": bool(sampling or beam or penalty or edit or fsm),
               "pen": bool(penalty), "lp_n": n_lp, "edit": bool(edit), "per_row": bool(per_row), "fsm": bool(fsm),
               "stopseq": bool(stopseq)}
         if ok:
             nblk = _lib.lib().query("pdn_decode_wide_blocks" if wide else "pdn_decode_gemv_blocks", V)
-            # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
-            ns = int(os.environ.get("PDN_DECODE_SPLITS", "0")) or (1 if self.layers[0].attention.cache_k.shape[1] <= 256 else 4)
             st.update(packs=packs, graphs={}, nograph=False, host_pos=None, ns=ns,
                       ids=hp.zeros((B, 1), np.int64), pos=hp.zeros((1,), np.int32),
                       cand_v=hp.empty((B, nblk), np.float32), cand_i=hp.empty((B, nblk), np.int32),
@@ -173,11 +200,11 @@ class DecodePlan:
                       # (a plan with a parameter table: a block per row)
                       params=hp.zeros((B, 3) if per_row else (3,), np.int64) if sampling else None, params_val=None,
                       **{n: hp.empty((B, w), np.float32) for n, w in
-                         (("x", D), ("qkv", 3 * D), ("att", ns * H * (4 + D // H)), ("gu", 2 * F), ("logits", V))})
+                         (("x", D), ("qkv", D + 2 * KVD), ("att", ns * H * (4 + D // H)), ("gu", 2 * F), ("logits", V))})
             # three launches per layer (csrc/decode_layer.hip): the output / down projections leave per-head /
             # per-32-hidden-unit records that the next kernel's staging adds to the residual row
             J = _lib.lib().query("pdn_decode_mlp_slices", F)
-            st["fused"] = bool(not wide and type(self).fused_decode and J and D <= 1024 and ns * H <= 256 and len(self.layers) > 0 and all(
+            st["fused"] = bool(not wide and not gqa and type(self).fused_decode and J and D <= 1024 and ns * H <= 256 and len(self.layers) > 0 and all(
                 l.ffn.gate.weight.data.is_contiguous() and l.ffn.up.weight.data.is_contiguous() for l in self.layers))
             # two launches per layer (csrc/decode_block.hip): the q | k | v projection inside the attention kernel, one
             # more record per head for the new key
@@ -210,7 +237,7 @@ class DecodePlan:
                 # the wide ticks count their rows in at `arrive`; the split products keep partial tiles and arrival
                 # counters in `work` (both zero between launches)
                 work = max(_lib.lib().query("pdn_decode_wide_work_floats", B, k, n)
-                           for k, n in ((D, 3 * D), (D, D), (F, D), (D, 2 * F), (D, V)))
+                           for k, n in ((D, 3 * D), (D, D), (F, D), (D, 2 * F), (D, V)) + (((D, 2 * KVD),) if gqa else ()))
                 st.update(arrive=hp.zeros((1,), np.int32), work=hp.zeros((max(work, 4),), np.float32))
             if serve:
                 st.update(req=hp.zeros((B,), np.int32), left=hp.zeros((B,), np.int32), ring=4, pending=0, issued=0)
@@ -355,12 +382,23 @@ class DecodePlan:
             a, f = layer.attention, layer.ffn
             ck, cv = a.cache_k.data, a.cache_v.data
             cbs = ck._strides[0]
-            # h = RMSNorm(x); [q | k | v] = h @ [Wq | Wk | Wv]
-            L.call("pdn_decode_gemv_f32", x, D, layer.input_norm.weight.data._ptr, layer.input_norm.eps, wqkv._ptr, D, D,
-                   wqkv._strides[0], None, None, 0, qkv, 3 * D, B, D, 3 * D, 0, 0, 0, None, None, s)
-            # RoPE of q / k, cache append, attention over positions [0, pos]
-            L.call(f"pdn_decode_attention_{rows}f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, att, B, H, hd, st["ns"], cbs, pos,
-                   ck.shape[1], s)
+            if st["gqa"]:
+                # a grouped model, six launches per layer: q = h @ Wq and [k | v] = h @ [Wk | Wv] (RMSNorm in both loads),
+                # then RoPE, cache append and the attention of the G query heads per key/value head (csrc/decode_gqa.hip)
+                nrm, wq, KVD = layer.input_norm, a.Q.weight.data, a.n_kv_heads * hd
+                L.call("pdn_decode_gemv_f32", x, D, nrm.weight.data._ptr, nrm.eps, wq._ptr, D, D, 0, None, None, 0, qkv,
+                       D + 2 * KVD, B, D, D, 0, 0, 0, None, None, s)
+                L.call("pdn_decode_gemv_f32", x, D, nrm.weight.data._ptr, nrm.eps, wqkv._ptr, KVD, KVD, wqkv._strides[0],
+                       None, None, 0, qkv + 4 * D, D + 2 * KVD, B, D, 2 * KVD, 0, 0, 0, None, None, s)
+                L.call("pdnj_decode_attention_f32", qkv, D + 2 * KVD, cos, sin, ck._ptr, cv._ptr, att, B, H, a.n_kv_heads,
+                       hd, st["ns"], cbs, pos, ck.shape[1], int(st["rows"]), s)
+            else:
+                # h = RMSNorm(x); [q | k | v] = h @ [Wq | Wk | Wv]
+                L.call("pdn_decode_gemv_f32", x, D, layer.input_norm.weight.data._ptr, layer.input_norm.eps, wqkv._ptr, D, D,
+                       wqkv._strides[0], None, None, 0, qkv, 3 * D, B, D, 3 * D, 0, 0, 0, None, None, s)
+                # RoPE of q / k, cache append, attention over positions [0, pos]
+                L.call(f"pdn_decode_attention_{rows}f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, att, B, H, hd, st["ns"], cbs,
+                       pos, ck.shape[1], s)
             wo, wd = a.O.weight.data, f.down.weight.data
             # x += merge(att partials) @ Wo: the key-range partials are merged while the row is staged
             L.call("pdn_decode_gemv_f32", att, st["att"].shape[1], None, 0.0, wo._ptr, D, D, 0, None, x, D, x, D, B, D, D,
@@ -396,10 +434,20 @@ class DecodePlan:
             a, f = layer.attention, layer.ffn
             ck, cv = a.cache_k.data, a.cache_v.data
             nrm = layer.input_norm
-            L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wqkv._ptr, D, D,
-                   wqkv._strides[0], None, qkv, 3 * D, 0, None, None, pos, B, D, 3 * D, work, s)
-            L.call("pdn_decode_attention_rows_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, att, B, H, hd, ns,
-                   ck._strides[0], pos, ck.shape[1], s)
+            if st["gqa"]:
+                # (a grouped model: Q and K | V in two products, the attention of csrc/decode_gqa.hip -- six launches)
+                wq, KVD = a.Q.weight.data, a.n_kv_heads * hd
+                L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wq._ptr, D, D, 0, None,
+                       qkv, D + 2 * KVD, 0, None, None, pos, B, D, D, work, s)
+                L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wqkv._ptr, KVD, KVD,
+                       wqkv._strides[0], None, qkv + 4 * D, D + 2 * KVD, 0, None, None, pos, B, D, 2 * KVD, work, s)
+                L.call("pdnj_decode_attention_f32", qkv, D + 2 * KVD, cos, sin, ck._ptr, cv._ptr, att, B, H, a.n_kv_heads,
+                       hd, ns, ck._strides[0], pos, ck.shape[1], 1, s)
+            else:
+                L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wqkv._ptr, D, D,
+                       wqkv._strides[0], None, qkv, 3 * D, 0, None, None, pos, B, D, 3 * D, work, s)
+                L.call("pdn_decode_attention_rows_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, att, B, H, hd, ns,
+                       ck._strides[0], pos, ck.shape[1], s)
             L.call("pdn_decode_wide_gemm_f32", att, st["att"].shape[1], 3, None, 0.0, ns, hd, a.O.weight.data._ptr, D, D,
                    0, None, x, D, 1, None, None, pos, B, D, D, work, s)
             nrm = layer.post_attn_norm

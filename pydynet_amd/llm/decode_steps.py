@@ -38,7 +38,10 @@ class DecodeSteps:
                     logits = self._edit_rows(logits, edit, erows.req, np.zeros(B, np.int64))
                 next_id = logits.argmax(-1, True) if sampling is None else sample_next(logits, pos, *sampling)
                 lp = None if n_lp is None else self._logprobs_rows(logits, next_id.numpy(), n_lp)
-            elif self._fast_path(next_id.device):
+            elif self._fast_path(next_id.device) or self._grouped_path(
+                    next_id.device, B, sampling=sampling is not None, penalty=pen is not None, n_lp=n_lp,
+                    edit=erows is not None, fsm=False if frows is None else frows.spec.caps):
+                # (a grouped-query model: the same step where its plan accepts, llm/decode_plan.py)
                 # (`more`: another token will be asked for -- the step after this one may be queued ahead)
                 out = self._decode_step_hip(next_id.data, pos, more=pos + 1 < max_new_tokens, sampling=sampling,
                                             pen=pen, n_lp=n_lp, edit=erows, fsm=frows)
@@ -208,7 +211,10 @@ class DecodeSteps:
         if srows is not None:
             live = live & ~srows.feed(nxt.numpy().reshape(-1))
         yield nxt if n_lp is None else (nxt, lp_np.as_step(lp))
-        fast = self._fast_path(nxt.device)
+        fast = self._fast_path(nxt.device) or self._grouped_path(
+            nxt.device, B, sampling=sampling is not None, ragged=True, penalty=pen is not None, n_lp=n_lp,
+            edit=erows is not None, per_row=isinstance(sampling, Table), fsm=False if frows is None else frows.spec.caps,
+            stopseq=False if srows is None else srows.spec.caps)
         if fast:
             from .. import hipnp as hp
             # tokens by STEP: slot i holds step i of every row (-1 for a stopped row), so "not written yet" is its own
@@ -329,6 +335,8 @@ class DecodeSteps:
         st = self._decode_plan(B, sampling is not None, penalty=pen is not None, n_lp=n_lp, edit=edit is not None,
                                fsm=False if fsm is None else fsm.spec.caps)
         if st is None:
+            if self.n_kv_heads != self.n_heads:                  # (never: `_grouped_path` asked this very plan)
+                raise RuntimeError("the decode plan refused a grouped-query model; the generic step is multi-head only")
             return self._decode_step_generic(ids, pos, sampling, pen, n_lp, edit, fsm)
         ahead, st["ahead"] = st.get("ahead"), None
         if ahead is not None:
@@ -497,6 +505,8 @@ class DecodeSteps:
                                fsm=False if run.get("fsm") is None else run["fsm"].spec.caps,
                                stopseq=False if run.get("stopseq") is None else run["stopseq"].spec.caps)
         if st is None:
+            if self.n_kv_heads != self.n_heads:                  # (never: `_grouped_path` asked this very plan)
+                raise RuntimeError("the decode plan refused a grouped-query model; the generic step is multi-head only")
             out = self._decode_step_generic_rows(ids, pos, sampling, pen=run.get("pen"), n_lp=n_lp, edit=run.get("edit"),
                                                  fsm=run.get("fsm"))
             out, lp = out if n_lp is not None else (out, None)

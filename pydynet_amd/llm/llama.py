@@ -128,15 +128,17 @@ class Attention(nn.Module):
 
     def _pack_qkv(self):
         """Re-home the Q/K/V weights in one (3, dim, dim) buffer: each stays a contiguous Parameter,
-        and being equally spaced lets the three projections run as one batched GEMM."""
+        and being equally spaced lets the three projections run as one batched GEMM.  A grouped-query model's K / V are
+        narrower than Q: those two alone share a (2, dim, kv_dim) buffer, the second launch of its decode step's
+        projection (llm/decode_plan.py)."""
         from .. import hipnp as hp
-        if self.n_kv_heads != self.n_heads:       # K / V are narrower than Q: nothing to stack
-            return
         ws = [self.Q.weight, self.K.weight, self.V.weight]
+        if self.n_kv_heads != self.n_heads:
+            ws = ws[1:]
         st = hp.stacked_view([w.data for w in ws])
         if st is not None and st._strides[0] == ws[0].data.size:      # already adjacent, in order
             return
-        buf = hp.empty((3,) + tuple(ws[0].shape), ws[0].dtype)
+        buf = hp.empty((len(ws),) + tuple(ws[0].shape), ws[0].dtype)
         for i, w in enumerate(ws):
             buf[i] = w.data
             w.data = buf[i]
