@@ -8,6 +8,7 @@ import os
 
 import numpy as np
 
+from . import band as _band
 from . import gqa as _gqa
 from . import segments as _seg
 from .norm import rms_norm
@@ -86,6 +87,19 @@ def _attn_kernel(B, H, hd, Lq, Lk, start_pos, mask, layouts):
     return None, None
 
 
+_BAND_BLOCKS = {}           # (Lq, Lk, start_pos, W) -> the (Lq, Lk) float32 band of a window that runs on the masked paths
+
+
+def _band_block(Lq, Lk, start_pos, W):
+    key = (Lq, Lk, start_pos, W)
+    blk = _BAND_BLOCKS.get(key)
+    if blk is None:
+        if len(_BAND_BLOCKS) > 16:
+            _BAND_BLOCKS.clear()
+        blk = _BAND_BLOCKS[key] = _band.band_mask(Lq, Lk, start_pos, W, np.float32)
+    return blk
+
+
 class SegmentBounds:
     """`start` / `end` of every position's document ((B, L) each; core/fused/segments.py), made once per step from the
     `segment_ids` and handed to every attention node of the step.  On a HIP device both are int32 device arrays written
@@ -146,14 +160,22 @@ class attention(_Operator):
     non-decreasing along a row, or a `SegmentBounds`): the documents of a packed row -- a query sees the keys of its own
     document only (core/fused/segments.py); needs `causal`, `start_pos` 0 and L == Lk.  Resident shapes (hd 48 / 64, L a
     multiple of 32 up to 1024) run the segmented kernels of include/pdn_segattn.h, any other shape the masked path with
-    the block mask formed on the device."""
+    the block mask formed on the device.  `window` (a positive integer; needs `causal` and Lk >= start_pos + L): sliding-
+    window attention, a query sees the last `window` keys up to its own (core/fused/band.py).  On a HIP device, without a
+    `mask` and with as many key/value heads as query heads, the band kernels of include/pdn_bandattn.h, whose work is
+    O(L * window); every other call with a window (an extra `mask`, grouped heads, a head dim outside those kernels) adds
+    the band as a constant (L, Lk) mask, built on the host once per shape, to the paths above: correct, and O(L * Lk)."""
 
     use_flash = True      # class switch: False forces the GEMM + softmax path (A/B and tests)
     use_resident = True   # class switch: False sends the benchmark shape through the streaming kernels too
     use_gqa = True        # class switch: False runs grouped-query calls on the multi-head paths over repeated K / V (A/B)
+    use_band = True       # class switch: False runs a window as an additive mask on the streaming kernels (A/B)
 
-    def __init__(self, q, k, v, causal=True, start_pos=0, mask=None, segment_ids=None):
+    def __init__(self, q, k, v, causal=True, start_pos=0, mask=None, segment_ids=None, window=None):
         self.causal, self.start_pos = bool(causal), int(start_pos)
+        self.window = _band.check(window, self.causal, q.shape[1], k.shape[1], self.start_pos)
+        if self.window is not None and segment_ids is not None:
+            raise ValueError("attention: window is not supported with segment_ids")
         self._mask = mask.data if isinstance(mask, Tensor) else mask
         self._kind = None
         self._kv_x = None                 # K / V repeated along the head axis, where a grouped call runs on the multi-head paths
@@ -167,7 +189,9 @@ class attention(_Operator):
 
     def _np_mask(self, Lq, Lk, dtype, B=None):
         add = None
-        if self.causal and Lq > 1:
+        if self.window is not None:       # (the band holds the causal edge, and a single query keeps its lower edge)
+            add = _band.band_mask(Lq, Lk, self.start_pos, self.window, dtype)
+        elif self.causal and Lq > 1:
             m = np.triu(np.full((Lq, Lq), float("-inf")), k=1)
             add = np.concatenate([np.zeros((Lq, self.start_pos)), m], axis=1).astype(dtype)
         if self._mask is not None:
@@ -177,6 +201,15 @@ class attention(_Operator):
             mk = _seg.block_mask(self._bounds(B, Lq, False).start, dtype)
             add = mk if add is None else add + mk
         return add
+
+    def _dev_mask(self, Lq, Lk):
+        """The caller's mask on the device; a window that runs on the masked paths adds its band."""
+        hp = _hip()
+        m = hp.asarray(self._mask) if self._mask is not None else None
+        if self.window is None:
+            return m
+        band = hp.asarray(_band_block(Lq, Lk, self.start_pos, self.window))
+        return band if m is None else band + m.astype(np.float32)
 
     def _bounds(self, B, Lq, on_hip):
         seg = segment_bounds(self._segments, on_hip)
@@ -189,6 +222,10 @@ class attention(_Operator):
         kd, vd = k.data, v.data
         G = H // kd.shape[2]
         self._kv_x = None
+        if self.window is not None and G == 1 and self._mask is None and self.xp is not np:
+            out = self._band_forward(q, k, v)
+            if out is not None:
+                return out
         if G > 1 and self.xp is not np:
             out = self._gqa_forward(q, k, v)
             if out is not None:
@@ -213,7 +250,7 @@ class attention(_Operator):
         hp, L = _hip(), _L()
         causal = 1 if (self.causal and Lq > 1) else 0
         layouts = (_attn_layout(q.data), _attn_layout(kd), _attn_layout(vd))
-        mask_dev = hp.asarray(self._mask) if self._mask is not None else None
+        mask_dev = self._dev_mask(Lq, Lk)
         if self._segments is not None:
             seg = self._bounds(B, Lq, True)
             if (mask_dev is None and attention.use_flash and attention.use_resident and None not in layouts
@@ -279,6 +316,8 @@ class attention(_Operator):
         q, k, v = self.last
         if self.xp is not np and self._kind == "gqa":
             return self._gqa_backward(do, q, k.data, v.data)
+        if self.xp is not np and self._kind == "band":
+            return self._band_backward(do, q, k.data, v.data)
         if self._kv_x is None:
             return self._backward(do, q, k.data, v.data)
         G = q.shape[2] // k.shape[2]
@@ -302,7 +341,7 @@ class attention(_Operator):
                 and L.query("pdnk_attention_supported", hd, H, Hkv)):
             return None
         self._kind = "gqa"
-        mask_dev = hp.asarray(self._mask) if self._mask is not None else None
+        mask_dev = self._dev_mask(Lq, Lk)
         self._mask_eff = mask_dev
         causal = 1 if (self.causal and Lq > 1) else 0
         out = hp.empty((B, Lq, H, hd), np.float32)
@@ -331,6 +370,43 @@ class attention(_Operator):
         L.call("pdnk_attention_bwd_f32", self._q_used._ptr, ksrc._ptr, vsrc._ptr, self.data._ptr, do._ptr, self._lse._ptr,
                dq._ptr, dk._ptr, dv._ptr, B, H, Hkv, Lq, Lk, hd, H * hd, Lq * H * hd if B > 1 else 0, Hkv * hd,
                Lk * Hkv * hd if B > 1 else 0, causal, self.start_pos, mp, sb, sh, sq, sk, ws, wsb, hp.stream())
+        return [dq, dk, dv]
+
+    def _band_forward(self, q, k, v):
+        """The band kernels of include/pdn_bandattn.h where they take the call (`_kind` "band"), else None.  No `causal`
+        flag goes down: the band holds the causal edge, and a single query behind a cache keeps its lower edge."""
+        _require_f32(self, q, k, v)
+        kd, vd = k.data, v.data
+        B, Lq, H, hd = q.shape
+        Lk = kd.shape[1]
+        hp, L = _hip(), _L()
+        lays = (_attn_layout(q.data), _attn_layout(kd), _attn_layout(vd))
+        if not (attention.use_flash and attention.use_band and None not in lays and lays[1] == lays[2] and B * H <= _STREAM_MAX_BH
+                and _provides("pdnb_attention_supported") and L.query("pdnb_attention_supported", hd)):
+            return None
+        self._kind = "band"
+        out = hp.empty((B, Lq, H, hd), np.float32)
+        self._lse = hp.empty((B, H, Lq), np.float32)
+        # the output is written with the QUERY strides: give the kernel a q-shaped contiguous view
+        self._q_used = q.data if lays[0] == (H * hd, Lq * H * hd if B > 1 else 0) else q.data.copy()
+        qlay = _attn_layout(self._q_used)
+        L.call("pdnb_attention_fwd_f32", self._q_used._ptr, kd._ptr, vd._ptr, out._ptr, self._lse._ptr, B, H, Lq, Lk, hd,
+               qlay[0], qlay[1], lays[1][0], lays[1][1], self.start_pos, self.window, hp.stream())
+        return out
+
+    def _band_backward(self, do, q, kd, vd):
+        B, Lq, H, hd = q.shape
+        Lk = kd.shape[1]
+        hp, L = _hip(), _L()
+        do = _contig(do)
+        dq = hp.empty(q.shape, np.float32)
+        # dk / dv are written with the key strides: contiguous gradients need contiguous k / v
+        ksrc, vsrc = _contig(kd), _contig(vd)
+        dk, dv = hp.empty(kd.shape, np.float32), hp.empty(vd.shape, np.float32)
+        ws, wsb = hp.workspace(L.query("pdnb_attention_bwd_workspace_bytes", B, H, Lq))
+        L.call("pdnb_attention_bwd_f32", self._q_used._ptr, ksrc._ptr, vsrc._ptr, self.data._ptr, do._ptr, self._lse._ptr,
+               dq._ptr, dk._ptr, dv._ptr, B, H, Lq, Lk, hd, H * hd, Lq * H * hd if B > 1 else 0, H * hd,
+               Lk * H * hd if B > 1 else 0, self.start_pos, self.window, ws, wsb, hp.stream())
         return [dq, dk, dv]
 
     def _backward(self, do, q, kd, vd):

@@ -97,7 +97,9 @@ enum {
                                   // pdnk_* entry, either direction
   PDN_CNT_DECODE_GQA = 56,        // decode attention of a grouped-query model (csrc/decode_gqa.hip, include/pdn_gqdecode.h):
                                   // once per pdnj_decode_attention_f32 launch
-  PDN_CNT_SLOTS = 57
+  PDN_CNT_ATT_BAND = 57,          // sliding-window attention (csrc/attention_band.hip, include/pdn_bandattn.h): once per launching
+                                  // pdnb_* entry, either direction
+  PDN_CNT_SLOTS = 58
 };
 void pdn_count(int slot);
 

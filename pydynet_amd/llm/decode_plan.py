@@ -51,8 +51,10 @@ class DecodePlan:
     def _fast_path(self, dev):
         """Whether generation on device `dev` takes the HIP decode fast path: fast_decode on, a HIP device, inference
         mode, float32 weights, a head dimension the kernels' float4 loads take and as many key/value heads as query heads
-        (a grouped-query model decodes on the tape-node path)."""
+        (a grouped-query model decodes on the tape-node path) and no sliding window (the decode kernels attend to every
+        cached key: a windowed model decodes on the tape-node path too)."""
         return bool(type(self).fast_decode and dev.is_hip and not self._train and self.n_kv_heads == self.n_heads
+                    and self.sliding_window is None
                     and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
 
     def _grouped_path(self, dev, B, **plan):
@@ -63,7 +65,7 @@ class DecodePlan:
         the tape-node step.  `generate` and `generate_ragged` alone ask; serve, chunked prefill, speculative decoding,
         beam search and the prefix cache assume key/value rows as wide as the model and stay behind `_fast_path`."""
         if not (type(self).fast_decode and dev.is_hip and not self._train and self.n_kv_heads != self.n_heads
-                and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0):
+                and self.sliding_window is None and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0):
             return False
         cache = self.layers[0].attention.cache_k
         return B <= cache.shape[0] and self._decode_plan(B, **plan) is not None

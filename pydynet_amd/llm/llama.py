@@ -61,6 +61,16 @@ def check_kv_heads(n_heads, n_kv_heads):
     return int(n_kv_heads)
 
 
+def check_window(sliding_window, max_seq_len):
+    """The attention window of a model: None (every earlier key), or a positive int; ValueError otherwise.  A window of
+    max_seq_len or more hides no key and is normalised to None."""
+    if sliding_window is None:
+        return None
+    if isinstance(sliding_window, (bool, np.bool_)) or not isinstance(sliding_window, (int, np.integer)) or sliding_window < 1:
+        raise ValueError(f"sliding_window must be a positive integer or None, got {sliding_window!r}")
+    return None if sliding_window >= max_seq_len else int(sliding_window)
+
+
 class FeedForward(nn.Module):
     def __init__(self, dim, up_dim, dtype=None):
         super().__init__()
@@ -102,10 +112,12 @@ class FeedForward(nn.Module):
 
 
 class Attention(nn.Module):
-    def __init__(self, dim, n_heads, max_seq_len, max_batch_size=None, dtype=None, *, n_kv_heads=None):
+    def __init__(self, dim, n_heads, max_seq_len, max_batch_size=None, dtype=None, *, n_kv_heads=None, sliding_window=None):
         super().__init__()
         assert dim % n_heads == 0
         self.dim, self.n_heads, self.head_dim = dim, n_heads, dim // n_heads
+        # sliding-window attention: a query sees the last `sliding_window` keys up to its own (core/fused/band.py)
+        self.sliding_window = check_window(sliding_window, max_seq_len)
         # grouped-query attention: n_kv_heads < n_heads key/value heads, query head h reads head h // (n_heads // n_kv_heads)
         # (core/fused/gqa.py).  K, V and the caches shrink with it; the default is multi-head attention, the reference's
         self.n_kv_heads = check_kv_heads(n_heads, n_kv_heads)
@@ -148,7 +160,8 @@ class Attention(nn.Module):
         H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
         if segment_ids is not None:
             return self._segmented(x, start_pos, mask, freqs_cos, freqs_sin, residual, segment_ids)
-        if (self._train and start_pos == 0 and mask is not None and is_grad_enable() and Hkv == H
+        W = self.sliding_window           # (a windowed model: the separate nodes below, never the one-node form)
+        if (self._train and start_pos == 0 and mask is not None and is_grad_enable() and Hkv == H and W is None
                 and fused.qkv_attention.applicable(x, L, hd)):
             out = fused.qkv_attention(x, self.Q.weight, self.K.weight, self.V.weight, freqs_cos, freqs_sin, H)
             out = out.reshape(B, L, -1)
@@ -164,7 +177,10 @@ class Attention(nn.Module):
             self.cache_v[:B, start_pos:start_pos + L] = xv
             xk = self.cache_k[:B, :start_pos + L]
             xv = self.cache_v[:B, :start_pos + L]
-        out = fused.attention(xq, xk, xv, causal=mask is not None, start_pos=start_pos)
+        if W is None:
+            out = fused.attention(xq, xk, xv, causal=mask is not None, start_pos=start_pos)
+        else:                                     # (causal for a one-token step too: it still has a lower edge)
+            out = fused.attention(xq, xk, xv, causal=True, start_pos=start_pos, window=W)
         out = out.reshape(B, L, -1)
         if residual is None:
             return self.O(out)
@@ -178,6 +194,8 @@ class Attention(nn.Module):
         H, hd = self.n_heads, self.head_dim
         if self.n_kv_heads != H:
             raise ValueError("segment_ids (packed rows) are not supported with n_kv_heads < n_heads")
+        if self.sliding_window is not None:
+            raise ValueError("segment_ids (packed rows) are not supported with sliding_window")
         if not self._train or start_pos != 0 or mask is None:
             raise ValueError("segment_ids are for training passes over whole rows (train mode, start_pos 0, more than one position)")
         if is_grad_enable() and fused.qkv_attention.applicable(x, L, hd, segment_ids):
@@ -212,7 +230,11 @@ class Attention(nn.Module):
             self.cache_k[int(b), int(p[b])] = xk[int(b), 0]
             self.cache_v[int(b), int(p[b])] = xv[int(b), 0]
         T = int(p.max()) + 1
-        mask = np.where(np.arange(T)[None, :] > p[:, None], -np.inf, 0.0).astype(xq.dtype).reshape(B, 1, 1, T)
+        keys = np.arange(T)[None, :]
+        hidden = keys > p[:, None]
+        if self.sliding_window is not None:       # ... and for the keys that have left row b's window
+            hidden |= keys < p[:, None] - self.sliding_window + 1
+        mask = np.where(hidden, -np.inf, 0.0).astype(xq.dtype).reshape(B, 1, 1, T)
         out = fused.attention(xq, self.cache_k[:B, :T], self.cache_v[:B, :T], causal=False, mask=mask)
         out = out.reshape(B, 1, -1)
         if residual is None:
@@ -221,9 +243,11 @@ class Attention(nn.Module):
 
 
 class TransformerBlock(nn.Module):
-    def __init__(self, dim, n_heads, ffn_dim, max_seq_len, max_batch_size=None, dtype=None, *, n_kv_heads=None):
+    def __init__(self, dim, n_heads, ffn_dim, max_seq_len, max_batch_size=None, dtype=None, *, n_kv_heads=None,
+                 sliding_window=None):
         super().__init__()
-        self.attention = Attention(dim, n_heads, max_seq_len, max_batch_size, dtype, n_kv_heads=n_kv_heads)
+        self.attention = Attention(dim, n_heads, max_seq_len, max_batch_size, dtype, n_kv_heads=n_kv_heads,
+                                   sliding_window=sliding_window)
         self.ffn = FeedForward(dim, ffn_dim, dtype)
         self.input_norm = nn.RMSNorm(dim, dtype=dtype)
         self.post_attn_norm = nn.RMSNorm(dim, dtype=dtype)
@@ -249,8 +273,13 @@ class TransformerBlock(nn.Module):
 
 class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
     def __init__(self, vocab_size, embed_dim, n_heads, ffn_dim, max_seq_len, max_batch_size=None,
-                 n_layers=6, dtype=None, *, dropout=0.0, generator=None, n_kv_heads=None):
+                 n_layers=6, dtype=None, *, dropout=0.0, generator=None, n_kv_heads=None, sliding_window=None):
         super().__init__()
+        # sliding_window (a positive int; default None): every layer's queries see the last `sliding_window` keys up to their
+        # own, as in Mistral (`Attention`, core/fused/band.py).  Training, scoring and every generation entry take such a
+        # model; its decode steps run on the tape-node path over the full-length KV cache, not in the graph-replayed step.
+        # None, or a window of max_seq_len or more, is the reference's model, launch for launch
+        self.sliding_window = check_window(sliding_window, max_seq_len)
         # n_kv_heads (a divisor of n_heads; default n_heads): grouped-query attention, as every Llama since Llama 2-70B
         # (`Attention`).  Training, scoring and every generation entry take such a model; its decode steps run on the
         # tape-node path, not in the graph-replayed step.  Left at its default the model is the reference's, launch for launch
@@ -272,7 +301,8 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         self.freqs_cos = nn.Parameter(cos, False)
         self.freqs_sin = nn.Parameter(sin, False)
         self.layers = nn.ModuleList([
-            TransformerBlock(embed_dim, n_heads, ffn_dim, max_seq_len, max_batch_size, dtype, n_kv_heads=self.n_kv_heads)
+            TransformerBlock(embed_dim, n_heads, ffn_dim, max_seq_len, max_batch_size, dtype, n_kv_heads=self.n_kv_heads,
+                             sliding_window=self.sliding_window)
             for _ in range(n_layers)])
         self.norm = nn.RMSNorm(embed_dim, dtype=dtype)
         self.lm_head = nn.Linear(embed_dim, vocab_size, dtype=dtype)      # bias=True, as the reference
@@ -329,7 +359,8 @@ class Llama(DecodePlan, DecodeSteps, ServeEngine, SearchEngine, nn.Module):
         wim = fused.wimages
         T = h.size // h.shape[-1]
         if not (self._train and is_grad_enable() and h.device.is_hip and h.dtype == np.float32 and T >= wim.min_rows
-                and wim.enabled() and self.n_kv_heads == self.n_heads):     # (the image forms take square K / V weights)
+                and wim.enabled() and self.n_kv_heads == self.n_heads      # (the image forms take square K / V weights)
+                and self.sliding_window is None):                           # (... and belong to the one-node attention)
             return None, None
         fwd, bwd, keep = [], [], []
         for layer in self.layers:
