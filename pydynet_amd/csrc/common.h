@@ -99,7 +99,9 @@ enum {
                                   // once per pdnj_decode_attention_f32 launch
   PDN_CNT_ATT_BAND = 57,          // sliding-window attention (csrc/attention_band.hip, include/pdn_bandattn.h): once per launching
                                   // pdnb_* entry, either direction
-  PDN_CNT_SLOTS = 58
+  PDN_CNT_DECODE_BAND = 58,       // decode attention of a sliding-window model (csrc/decode_band.hip, include/pdn_banddecode.h):
+                                  // once per pdnv_decode_attention_f32 launch
+  PDN_CNT_SLOTS = 59
 };
 void pdn_count(int slot);
 

@@ -43,6 +43,9 @@ _PERSAMPLE_ENTRIES = ("pdnq_sample_rows_f32", "pdnq_decode_sample_tick_rows_f32"
 # the entry points of a grouped-query model's decode attention (csrc/decode_gqa.hip, include/pdn_gqdecode.h): without them
 # the plan refuses a grouped model, which then decodes on the tape-node path
 _GQA_ENTRIES = ("pdnj_decode_attention_supported", "pdnj_decode_attention_f32")
+# the entry points of a sliding-window model's decode attention (csrc/decode_band.hip, include/pdn_banddecode.h), grouped
+# heads or not: without them the plan refuses a windowed model, which then decodes on the tape-node path
+_BAND_ENTRIES = ("pdnv_decode_attention_supported", "pdnv_decode_attention_f32")
 # ring slots of the log-probability records of a decode plan (csrc/logprobs.hip): more than the steps ever in flight
 _LP_RING = 8
 
@@ -58,14 +61,17 @@ class DecodePlan:
                     and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0)
 
     def _grouped_path(self, dev, B, **plan):
-        """Whether a grouped-query model (n_kv_heads < n_heads) takes the graph-replayed step for `B` rows on `dev`: the
-        conditions of `_fast_path` but the head counts, and a plan that accepts -- `plan`: the arguments the step will
-        hand to `_decode_plan`, which is asked itself (and keeps the plan it built), so this is True exactly when the step
-        finds a plan.  The plan's fallback, the generic launches, is multi-head only: where this is False the model takes
-        the tape-node step.  `generate` and `generate_ragged` alone ask; serve, chunked prefill, speculative decoding,
-        beam search and the prefix cache assume key/value rows as wide as the model and stay behind `_fast_path`."""
-        if not (type(self).fast_decode and dev.is_hip and not self._train and self.n_kv_heads != self.n_heads
-                and self.sliding_window is None and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0):
+        """Whether a model that `_fast_path` refuses for its attention alone -- grouped-query (n_kv_heads < n_heads),
+        sliding-window (sliding_window set), or both -- takes the graph-replayed step for `B` rows on `dev`: the
+        conditions of `_fast_path` but the head counts and the window, and a plan that accepts -- `plan`: the arguments the
+        step will hand to `_decode_plan`, which is asked itself (and keeps the plan it built), so this is True exactly when
+        the step finds a plan.  The plan's fallback, the generic launches, is multi-head and unwindowed only: where this is
+        False the model takes the tape-node step.  `generate` and `generate_ragged` alone ask; serve, chunked prefill,
+        speculative decoding, beam search and the prefix cache assume key/value rows as wide as the model and attention to
+        every cached key, and stay behind `_fast_path`."""
+        if not (type(self).fast_decode and dev.is_hip and not self._train
+                and (self.n_kv_heads != self.n_heads or self.sliding_window is not None)
+                and self.lm_head.weight.dtype == np.float32 and (self.embed_dim // self.n_heads) % 4 == 0):
             return False
         cache = self.layers[0].attention.cache_k
         return B <= cache.shape[0] and self._decode_plan(B, **plan) is not None
@@ -130,6 +136,10 @@ class DecodePlan:
         # (Q and K | V have different row strides), the attention of csrc/decode_gqa.hip, never the fused / block forms
         Hkv, gqa = self.n_kv_heads, self.n_kv_heads != self.n_heads
         KVD = Hkv * (D // H)
+        # a sliding-window model (`band`): the attention of csrc/decode_band.hip over the last W keys, grouped heads or not
+        # (a grouped one keeps its two projections), the key ranges and the LDS bound by W, never the fused / block forms
+        W = self.sliding_window
+        band = W is not None
         st = getattr(self, "_decode_st", None)
         # a captured step (and the stacked weight views) hold the address of EVERY array the launches read: the key
         # covers them all -- rebinding `.data` of any parameter / cache re-plans -- and the switches that shape the plan
@@ -139,6 +149,7 @@ class DecodePlan:
         key = (B, hp._state["device"], int(type(self).fused_decode or 0), os.environ.get("PDN_DECODE_SPLITS", ""),
                cache_len, tuple(ptrs), bool(sampling), wide,   # (the addresses: no hash to collide)
                (int(beam), int(n_stops), bool(penalty)), bool(ragged), bool(serve)) + (() if n_lp is None else (int(n_lp),))
+        key += ("window", int(W)) if band else ()
         key += ("edit",) if edit else ()
         key += ("per_row",) if per_row else ()
         key += ("fsm",) + tuple(int(c) for c in fsm) if fsm else ()
@@ -149,13 +160,19 @@ class DecodePlan:
             for g in st.get("graphs", {}).values():
                 g.destroy()
         ok = (B <= 8 and B * max(D, F) <= 16384 and D % 4 == 0 and F % 4 == 0 and V % 4 == 0 and (D // H) % 4 == 0
-              and self.layers[0].attention.cache_k.shape[1] * 4 <= 60 * 1024 and D // H <= 256)
+              # (the multi-head decode attention holds cache_len scores in LDS; a windowed plan's attention holds the
+              #  window's, asked of pdnv_decode_attention_supported below, and no other launch of the five sees the cache)
+              and (band or self.layers[0].attention.cache_k.shape[1] * 4 <= 60 * 1024) and D // H <= 256)
         if wide:
             # (the merge of the key-range partials happens in the output projection's load: at most 8 ranges)
             ok = int(os.environ.get("PDN_DECODE_SPLITS", "0") or 0) <= 8
         # key ranges per head in the decode attention: one CU pulls ~11 B/clk, so long caches are cut up
-        ns = int(os.environ.get("PDN_DECODE_SPLITS", "0")) or (1 if cache_len <= 256 else 4)
-        if gqa and not (all(_lib.provides(n) for n in _GQA_ENTRIES) and not beam and not serve
+        # (a windowed step reads at most W keys: the rule is applied to W)
+        ns = int(os.environ.get("PDN_DECODE_SPLITS", "0")) or (1 if (W if band else cache_len) <= 256 else 4)
+        if band and not (all(_lib.provides(n) for n in _BAND_ENTRIES) and not beam and not serve
+                         and _lib.lib().query("pdnv_decode_attention_supported", H, Hkv, D // H, ns, W, cache_len)):
+            ok = False
+        if gqa and not band and not (all(_lib.provides(n) for n in _GQA_ENTRIES) and not beam and not serve
                         and _lib.lib().query("pdnj_decode_attention_supported", H, Hkv, D // H, ns, cache_len)):
             ok = False
         if penalty and not all(_lib.provides(n) for n in _PEN_ENTRIES):
@@ -185,7 +202,7 @@ class DecodePlan:
                 packs.append((qkv, gu))
             ok = ok and self.lm_head.weight.data.is_contiguous() and self.tok_embedding.weight.data.is_contiguous()
         st = {"B": B, "key": key, "ok": ok, "sampling": bool(sampling), "ragged": bool(ragged), "serve": bool(serve),
-              "wide": wide, "rows": bool(ragged or wide), "beam": int(beam), "gqa": gqa,
+              "wide": wide, "rows": bool(ragged or wide), "beam": int(beam), "gqa": gqa, "window": W,
               "full": bool(sampling or beam or penalty or edit or fsm),
               "pen": bool(penalty), "lp_n": n_lp, "edit": bool(edit), "per_row": bool(per_row), "fsm": bool(fsm),
               "stopseq": bool(stopseq)}
@@ -206,7 +223,7 @@ class DecodePlan:
             # three launches per layer (csrc/decode_layer.hip): the output / down projections leave per-head /
             # per-32-hidden-unit records that the next kernel's staging adds to the residual row
             J = _lib.lib().query("pdn_decode_mlp_slices", F)
-            st["fused"] = bool(not wide and not gqa and type(self).fused_decode and J and D <= 1024 and ns * H <= 256 and len(self.layers) > 0 and all(
+            st["fused"] = bool(not wide and not gqa and not band and type(self).fused_decode and J and D <= 1024 and ns * H <= 256 and len(self.layers) > 0 and all(
                 l.ffn.gate.weight.data.is_contiguous() and l.ffn.up.weight.data.is_contiguous() for l in self.layers))
             # two launches per layer (csrc/decode_block.hip): the q | k | v projection inside the attention kernel, one
             # more record per head for the new key
@@ -392,15 +409,22 @@ class DecodePlan:
                        D + 2 * KVD, B, D, D, 0, 0, 0, None, None, s)
                 L.call("pdn_decode_gemv_f32", x, D, nrm.weight.data._ptr, nrm.eps, wqkv._ptr, KVD, KVD, wqkv._strides[0],
                        None, None, 0, qkv + 4 * D, D + 2 * KVD, B, D, 2 * KVD, 0, 0, 0, None, None, s)
-                L.call("pdnj_decode_attention_f32", qkv, D + 2 * KVD, cos, sin, ck._ptr, cv._ptr, att, B, H, a.n_kv_heads,
-                       hd, st["ns"], cbs, pos, ck.shape[1], int(st["rows"]), s)
+                if st["window"] is None:
+                    L.call("pdnj_decode_attention_f32", qkv, D + 2 * KVD, cos, sin, ck._ptr, cv._ptr, att, B, H,
+                           a.n_kv_heads, hd, st["ns"], cbs, pos, ck.shape[1], int(st["rows"]), s)
             else:
                 # h = RMSNorm(x); [q | k | v] = h @ [Wq | Wk | Wv]
                 L.call("pdn_decode_gemv_f32", x, D, layer.input_norm.weight.data._ptr, layer.input_norm.eps, wqkv._ptr, D, D,
                        wqkv._strides[0], None, None, 0, qkv, 3 * D, B, D, 3 * D, 0, 0, 0, None, None, s)
                 # RoPE of q / k, cache append, attention over positions [0, pos]
-                L.call(f"pdn_decode_attention_{rows}f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, att, B, H, hd, st["ns"], cbs,
-                       pos, ck.shape[1], s)
+                if st["window"] is None:
+                    L.call(f"pdn_decode_attention_{rows}f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, att, B, H, hd, st["ns"],
+                           cbs, pos, ck.shape[1], s)
+            if st["window"] is not None:
+                # a windowed model: the keys [max(0, pos - W + 1), pos] of the linear cache (csrc/decode_band.hip); the
+                # qkv rows are those of the projections above, D + 2 KVD floats (3 D for a multi-head model)
+                L.call("pdnv_decode_attention_f32", qkv, D + 2 * a.n_kv_heads * hd, cos, sin, ck._ptr, cv._ptr, att, B, H,
+                       a.n_kv_heads, hd, st["ns"], cbs, pos, ck.shape[1], st["window"], int(st["rows"]), s)
             wo, wd = a.O.weight.data, f.down.weight.data
             # x += merge(att partials) @ Wo: the key-range partials are merged while the row is staged
             L.call("pdn_decode_gemv_f32", att, st["att"].shape[1], None, 0.0, wo._ptr, D, D, 0, None, x, D, x, D, B, D, D,
@@ -443,13 +467,19 @@ class DecodePlan:
                        qkv, D + 2 * KVD, 0, None, None, pos, B, D, D, work, s)
                 L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wqkv._ptr, KVD, KVD,
                        wqkv._strides[0], None, qkv + 4 * D, D + 2 * KVD, 0, None, None, pos, B, D, 2 * KVD, work, s)
-                L.call("pdnj_decode_attention_f32", qkv, D + 2 * KVD, cos, sin, ck._ptr, cv._ptr, att, B, H, a.n_kv_heads,
-                       hd, ns, ck._strides[0], pos, ck.shape[1], 1, s)
+                if st["window"] is None:
+                    L.call("pdnj_decode_attention_f32", qkv, D + 2 * KVD, cos, sin, ck._ptr, cv._ptr, att, B, H,
+                           a.n_kv_heads, hd, ns, ck._strides[0], pos, ck.shape[1], 1, s)
             else:
                 L.call("pdn_decode_wide_gemm_f32", x, D, 1, nrm.weight.data._ptr, nrm.eps, 0, 0, wqkv._ptr, D, D,
                        wqkv._strides[0], None, qkv, 3 * D, 0, None, None, pos, B, D, 3 * D, work, s)
-                L.call("pdn_decode_attention_rows_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, att, B, H, hd, ns,
-                       ck._strides[0], pos, ck.shape[1], s)
+                if st["window"] is None:
+                    L.call("pdn_decode_attention_rows_f32", qkv, 3 * D, cos, sin, ck._ptr, cv._ptr, att, B, H, hd, ns,
+                           ck._strides[0], pos, ck.shape[1], s)
+            if st["window"] is not None:
+                # (a windowed model: the window's keys alone, csrc/decode_band.hip; always the per-row form here)
+                L.call("pdnv_decode_attention_f32", qkv, D + 2 * a.n_kv_heads * hd, cos, sin, ck._ptr, cv._ptr, att, B, H,
+                       a.n_kv_heads, hd, ns, ck._strides[0], pos, ck.shape[1], st["window"], 1, s)
             L.call("pdn_decode_wide_gemm_f32", att, st["att"].shape[1], 3, None, 0.0, ns, hd, a.O.weight.data._ptr, D, D,
                    0, None, x, D, 1, None, None, pos, B, D, D, work, s)
             nrm = layer.post_attn_norm

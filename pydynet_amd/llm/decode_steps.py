@@ -335,8 +335,9 @@ class DecodeSteps:
         st = self._decode_plan(B, sampling is not None, penalty=pen is not None, n_lp=n_lp, edit=edit is not None,
                                fsm=False if fsm is None else fsm.spec.caps)
         if st is None:
-            if self.n_kv_heads != self.n_heads:                  # (never: `_grouped_path` asked this very plan)
-                raise RuntimeError("the decode plan refused a grouped-query model; the generic step is multi-head only")
+            if self.n_kv_heads != self.n_heads or self.sliding_window is not None:   # (never: `_grouped_path` asked this very plan)
+                raise RuntimeError("the decode plan refused a grouped-query or sliding-window model; the generic step is "
+                                   "multi-head and unwindowed only")
             return self._decode_step_generic(ids, pos, sampling, pen, n_lp, edit, fsm)
         ahead, st["ahead"] = st.get("ahead"), None
         if ahead is not None:
@@ -505,8 +506,9 @@ class DecodeSteps:
                                fsm=False if run.get("fsm") is None else run["fsm"].spec.caps,
                                stopseq=False if run.get("stopseq") is None else run["stopseq"].spec.caps)
         if st is None:
-            if self.n_kv_heads != self.n_heads:                  # (never: `_grouped_path` asked this very plan)
-                raise RuntimeError("the decode plan refused a grouped-query model; the generic step is multi-head only")
+            if self.n_kv_heads != self.n_heads or self.sliding_window is not None:   # (never: `_grouped_path` asked this very plan)
+                raise RuntimeError("the decode plan refused a grouped-query or sliding-window model; the generic step is "
+                                   "multi-head and unwindowed only")
             out = self._decode_step_generic_rows(ids, pos, sampling, pen=run.get("pen"), n_lp=n_lp, edit=run.get("edit"),
                                                  fsm=run.get("fsm"))
             out, lp = out if n_lp is not None else (out, None)
