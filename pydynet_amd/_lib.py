@@ -64,6 +64,9 @@ BAND_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "pdn_bandat
 # decode attention of a sliding-window model (prefix pdnv_, include/pdn_banddecode.h): likewise, held to the rule by
 # tests/test_band_decode_llama.py
 BANDDECODE_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "pdn_banddecode.h"),)
+# sliding-window attention over grouped heads (prefix pdnm_, include/pdn_gqbandattn.h): likewise, held to the rule by
+# tests/test_gqband_attention_gpu.py
+GQBAND_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "pdn_gqbandattn.h"),)
 
 _CTYPE = {
     "int": ctypes.c_int,
@@ -79,7 +82,7 @@ def parse_header(path: str = HEADER_PATH):
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     text = re.sub(r"//[^\n]*", "", text)
     protos = {}
-    for m in re.finditer(r"(const\s+char\s*\*|int64_t|int)\s+(pdn[xlsrzeqfgphwdkjbv]?_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
+    for m in re.finditer(r"(const\s+char\s*\*|int64_t|int)\s+(pdn[xlsrzeqfgphwdkjbvm]?_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
         ret, name, args = m.group(1), m.group(2), m.group(3)
         restype = ctypes.c_char_p if "char" in ret else _CTYPE[ret]
         argtypes = []
@@ -118,7 +121,8 @@ class _Lib:
         for path in (EXT_HEADER_PATHS + LOSS_HEADER_PATHS + SEG_HEADER_PATHS + ROWLOSS_HEADER_PATHS + SMOOTH_HEADER_PATHS
                      + EDIT_HEADER_PATHS + PERSAMPLE_HEADER_PATHS + FSM_HEADER_PATHS + NORMGRAD_HEADER_PATHS
                      + NORMPLANES_HEADER_PATHS + STOPSEQ_HEADER_PATHS + WIMAGES_HEADER_PATHS + DROPOUT_HEADER_PATHS
-                     + GQA_HEADER_PATHS + GQDECODE_HEADER_PATHS + BAND_HEADER_PATHS + BANDDECODE_HEADER_PATHS):
+                     + GQA_HEADER_PATHS + GQDECODE_HEADER_PATHS + BAND_HEADER_PATHS + BANDDECODE_HEADER_PATHS
+                     + GQBAND_HEADER_PATHS):
             self.protos.update(parse_header(path))
         self.fn = {}
         for name, (restype, argtypes) in self.protos.items():

@@ -163,8 +163,10 @@ class attention(_Operator):
     the block mask formed on the device.  `window` (a positive integer; needs `causal` and Lk >= start_pos + L): sliding-
     window attention, a query sees the last `window` keys up to its own (core/fused/band.py).  On a HIP device, without a
     `mask` and with as many key/value heads as query heads, the band kernels of include/pdn_bandattn.h, whose work is
-    O(L * window); every other call with a window (an extra `mask`, grouped heads, a head dim outside those kernels) adds
-    the band as a constant (L, Lk) mask, built on the host once per shape, to the paths above: correct, and O(L * Lk)."""
+    O(L * window), and with fewer key/value heads (group sizes 2 .. 8) the windowed shared-K/V kernels of
+    include/pdn_gqbandattn.h, O(L * window) as well; every other call with a window (an extra `mask`, a larger group, a head
+    dim outside those kernels) adds the band as a constant (L, Lk) mask, built on the host once per shape, to the paths
+    above: correct, and O(L * Lk)."""
 
     use_flash = True      # class switch: False forces the GEMM + softmax path (A/B and tests)
     use_resident = True   # class switch: False sends the benchmark shape through the streaming kernels too
@@ -224,6 +226,10 @@ class attention(_Operator):
         self._kv_x = None
         if self.window is not None and G == 1 and self._mask is None and self.xp is not np:
             out = self._band_forward(q, k, v)
+            if out is not None:
+                return out
+        if self.window is not None and G > 1 and self._mask is None and self.xp is not np:
+            out = self._gqband_forward(q, k, v)
             if out is not None:
                 return out
         if G > 1 and self.xp is not np:
@@ -318,6 +324,8 @@ class attention(_Operator):
             return self._gqa_backward(do, q, k.data, v.data)
         if self.xp is not np and self._kind == "band":
             return self._band_backward(do, q, k.data, v.data)
+        if self.xp is not np and self._kind == "gqband":
+            return self._gqband_backward(do, q, k.data, v.data)
         if self._kv_x is None:
             return self._backward(do, q, k.data, v.data)
         G = q.shape[2] // k.shape[2]
@@ -407,6 +415,45 @@ class attention(_Operator):
         L.call("pdnb_attention_bwd_f32", self._q_used._ptr, ksrc._ptr, vsrc._ptr, self.data._ptr, do._ptr, self._lse._ptr,
                dq._ptr, dk._ptr, dv._ptr, B, H, Lq, Lk, hd, H * hd, Lq * H * hd if B > 1 else 0, H * hd,
                Lk * H * hd if B > 1 else 0, self.start_pos, self.window, ws, wsb, hp.stream())
+        return [dq, dk, dv]
+
+    def _gqband_forward(self, q, k, v):
+        """The windowed shared-K/V kernels of include/pdn_gqbandattn.h where they take the call (`_kind` "gqband"), else
+        None.  No `causal` flag goes down, as in `_band_forward`.  `use_band = False` leaves the call to `_gqa_forward`, which
+        runs the window as an additive mask (A/B)."""
+        _require_f32(self, q, k, v)
+        kd, vd = k.data, v.data
+        B, Lq, H, hd = q.shape
+        Lk, Hkv = kd.shape[1], kd.shape[2]
+        hp, L = _hip(), _L()
+        lays = (_attn_layout(q.data), _attn_layout(kd), _attn_layout(vd))
+        if not (attention.use_flash and attention.use_band and attention.use_gqa and None not in lays and lays[1] == lays[2]
+                and B * Hkv <= _STREAM_MAX_BH and _provides("pdnm_attention_supported")
+                and L.query("pdnm_attention_supported", hd, H, Hkv)):
+            return None
+        self._kind = "gqband"
+        out = hp.empty((B, Lq, H, hd), np.float32)
+        self._lse = hp.empty((B, H, Lq), np.float32)
+        # the output is written with the QUERY strides: give the kernel a q-shaped contiguous view
+        self._q_used = q.data if lays[0] == (H * hd, Lq * H * hd if B > 1 else 0) else q.data.copy()
+        qlay = _attn_layout(self._q_used)
+        L.call("pdnm_attention_fwd_f32", self._q_used._ptr, kd._ptr, vd._ptr, out._ptr, self._lse._ptr, B, H, Hkv, Lq, Lk,
+               hd, qlay[0], qlay[1], lays[1][0], lays[1][1], self.start_pos, self.window, hp.stream())
+        return out
+
+    def _gqband_backward(self, do, q, kd, vd):
+        B, Lq, H, hd = q.shape
+        Lk, Hkv = kd.shape[1], kd.shape[2]
+        hp, L = _hip(), _L()
+        do = _contig(do)
+        dq = hp.empty(q.shape, np.float32)
+        # dk / dv are written with the key strides: contiguous gradients need contiguous k / v
+        ksrc, vsrc = _contig(kd), _contig(vd)
+        dk, dv = hp.empty(kd.shape, np.float32), hp.empty(vd.shape, np.float32)
+        ws, wsb = hp.workspace(L.query("pdnm_attention_bwd_workspace_bytes", B, H, Lq))
+        L.call("pdnm_attention_bwd_f32", self._q_used._ptr, ksrc._ptr, vsrc._ptr, self.data._ptr, do._ptr, self._lse._ptr,
+               dq._ptr, dk._ptr, dv._ptr, B, H, Hkv, Lq, Lk, hd, H * hd, Lq * H * hd if B > 1 else 0, Hkv * hd,
+               Lk * Hkv * hd if B > 1 else 0, self.start_pos, self.window, ws, wsb, hp.stream())
         return [dq, dk, dv]
 
     def _backward(self, do, q, kd, vd):

@@ -101,7 +101,9 @@ enum {
                                   // pdnb_* entry, either direction
   PDN_CNT_DECODE_BAND = 58,       // decode attention of a sliding-window model (csrc/decode_band.hip, include/pdn_banddecode.h):
                                   // once per pdnv_decode_attention_f32 launch
-  PDN_CNT_SLOTS = 59
+  PDN_CNT_ATT_GQBAND = 59,        // sliding-window attention over grouped heads (csrc/attention_gqband.hip, include/pdn_gqbandattn.h):
+                                  // once per launching pdnm_* entry, either direction
+  PDN_CNT_SLOTS = 60
 };
 void pdn_count(int slot);
 
